@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput benchmark of the Point-SAM hot path (encode + 1-prompt decode) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = one full pass (FPS -> kNN grouping -> mini-PointNet -> ViT-L -> two-way decoder -> per-point mask logits)
@@ -11,10 +11,14 @@ group_size=64, batch=8 per GPU, 1 point prompt, multimask output.  With N>1 ever
 `python bench.py --gpus N` without a launcher spawns the N ranks itself (one process per GPU, 127.0.0.1 rendezvous).
 Prints ONE JSON line on rank 0.
 
-Besides the contract fields the line carries: `roofline` (dominant GEMM kernel, live HIP-event durations), `cpu_baseline` (the oracle on
-cloud 0 of the SAME batch, host cores), `parity` (the timed configuration's own output for cloud 0 against that oracle run), `sustained`
-(a second, much longer timed region), `tokenizer` (FPS us/iteration, distance evaluations per second against the VALU peak), `rccl`
-(N > 1: ranks seen and the time of the per-step all_gather).
+A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`, per-step and per-rank times,
+start-up times).  --dump-outputs DIR also writes what the last timed step returned (masks.npy [B*N_GPUS,3,N] logits, iou.npy [B*N_GPUS,3],
+float32; seeded inputs and weights, so two builds compare output for output).  --full adds the measurements that take runs of their own:
+`roofline` (dominant GEMM kernel, live HIP-event durations, package power, the MFMA ceiling probe), `cpu_baseline` (the oracle on
+cloud 0 of the SAME batch, host cores), `parity` (the timed configuration's own output for every cloud against the oracle), `sustained`
+(a second, much longer timed region), `stage_ms` / `tokenizer` (FPS us/iteration, distance evaluations per second against the VALU peak),
+`rccl` (N > 1: ranks seen and the time of the per-step all_gather) and `other_workloads` (cfg3 / cfg5 as in-process legs of a cfg2 run);
+the --no-* switches and --sustained-steps / --other-* options below shape what --full runs.
 """
 import argparse
 import json
@@ -81,6 +85,11 @@ def parse_args(argv=None):
     ap.add_argument("--other-steps", type=int, default=20, help="timed steps of each extra leg (after 3 warm-ups, as a default run of that workload)")
     ap.add_argument("--data", default="synthetic", choices=["synthetic", "ply"],
                     help="synthetic: uniform clouds in the unit ball; ply: the reference's six demo clouds tiled / jittered to N points (SURVEY.md 8(d))")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra measurements and checks (roofline, cpu_baseline + parity, sustained, stage times, "
+                         "rccl, other_workloads); a plain run reports the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the (masks, iou) the last timed step returned as DIR/masks.npy and DIR/iou.npy (float32, at most 64 MB)")
     args = ap.parse_args(argv)
     given = {a.split("=")[0] for a in (argv if argv is not None else sys.argv[1:]) if a.startswith("--")}
     for key, val in WORKLOADS[args.workload].items():      # the workload's geometry, unless the flag was given explicitly
@@ -510,6 +519,8 @@ def worker(args):
     rank_times = list(timed.per_rank)
     H.finalize()
     assert torch.isfinite(out[0]).all()
+    if args.dump_outputs and rank == 0:      # before anything else replays the slots whose static buffers `out` may be
+        dump_outputs(args.dump_outputs, {"masks": out[0], "iou": out[1]})
     keep = (out[0][:B].clone(), out[1][:B].clone()) if world == 1 else (out[0][rank * B:(rank + 1) * B].clone(), out[1][rank * B:(rank + 1) * B].clone())
 
     if args.stub:
@@ -522,7 +533,7 @@ def worker(args):
 
     # second, long timed region: the same passes, enough of them that clock / power state is the sustained one
     sustained = None
-    if args.sustained_steps > 0:
+    if args.full and args.sustained_steps > 0:
         clocks, power, sampler = [], None, None
         if not args.stub and rank == 0:
             from point_sam_amd.profiling import PowerSampler
@@ -540,7 +551,7 @@ def worker(args):
 
     # the collective on its own: ranks seen + time of the per-step gather of the logits
     rccl = None
-    if world > 1:
+    if args.full and world > 1:
         ids = psdist.gather_results(torch.full((1,), float(rank), device=H.dev), world)
         fence()
         t0 = time.perf_counter()
@@ -571,7 +582,7 @@ def worker(args):
             return
 
     prof = stage_ms = tok = None
-    if not args.stub:
+    if args.full and not args.stub:
         if not args.no_gemm_profile:
             prof = H.gemm_profile()
         if not args.no_stage_times:
@@ -609,10 +620,10 @@ def worker(args):
         if args.stub:
             res["config"]["stub"] = dict(checks, taken=H.taken)
             res["data"] = "stub"
-        elif world == 1 and not a.no_cpu_baseline:
+        elif a.full and world == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"], res["parity"] = H.cpu_baseline(keep, iters=a.cpu_baseline_iters)
-        if not args.stub and world == 1 and a.workload == "cfg2" and a.other_workloads:
-            # BASELINE configs #3 / #5 as short legs of the SAME run AND PROCESS, so that whoever runs the default command sees them (each is also a
+        if a.full and not args.stub and world == 1 and a.workload == "cfg2" and a.other_workloads:
+            # BASELINE configs #3 / #5 as short legs of the SAME run AND PROCESS, so that whoever runs the --full command sees them (each is also a
             # full contract line of its own under --workload)
             import gc
             H.pipe = H.gpipe = H.model = None      # the main workload's graphs and weights are not needed any more
@@ -621,6 +632,24 @@ def worker(args):
             res["other_workloads"] = {w: other_leg(w, a, local, (roofline or {}).get("measured_mfma_ceiling_tflops")) for w in a.other_workloads.split(",")
                                       if w in WORKLOADS and w != a.workload}
         print(json.dumps(res), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """Writes each output as `path/<name>.npy` (float32).  An output that would take the files past DUMP_LIMIT_BYTES keeps a fixed, seeded
+    sample of its last axis (the points of a mask), the same columns in every run of the same shape."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v.detach().float().cpu() for k, v in arrays.items()}
+    small = sum(v.numel() * 4 for v in arrays.values() if v.dim() < 3)
+    for name, v in arrays.items():
+        if v.dim() >= 3 and small + v.numel() * 4 > DUMP_LIMIT_BYTES:
+            keep = max(1, (DUMP_LIMIT_BYTES - small) // (4 * (v.numel() // v.shape[-1])))
+            cols = torch.randperm(v.shape[-1], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            v = v[..., cols]
+        np.save(os.path.join(path, name + ".npy"), v.contiguous().numpy())
 
 
 def streams_report(args):

@@ -9,8 +9,9 @@ def per_kernel(path):
         acc[k][0] += float(r["Counter_Value"]); acc[k][1] += 1
     return acc
 tag = sys.argv[1]
-fetch = per_kernel(glob.glob(f"gpurun_out/pmc_fetch_{tag}/**/*counter_collection.csv", recursive=True)[0])
-write = per_kernel(glob.glob(f"gpurun_out/pmc_write_{tag}/**/*counter_collection.csv", recursive=True)[0])
+base = os.path.dirname(sys.argv[2]) or "."      # the PMC passes sit beside the output (scripts/gpu_round_evidence.sh: $OUT/pmc_{fetch,write}_TAG)
+fetch = per_kernel(glob.glob(f"{base}/pmc_fetch_{tag}/**/*counter_collection.csv", recursive=True)[0])
+write = per_kernel(glob.glob(f"{base}/pmc_write_{tag}/**/*counter_collection.csv", recursive=True)[0])
 out = {}
 for k, (v, n) in sorted(fetch.items(), key=lambda kv: -kv[1][0]):
     if k not in write or n < 2 or not ("gemm" in k or "attn" in k or "fps" in k or "knn" in k or "layernorm" in k): continue

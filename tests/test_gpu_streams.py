@@ -22,7 +22,7 @@ def _bench(*argv, timeout=900):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "PSAM_PRIVATE_STREAMS"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-stage-times", "--no-gemm-profile", "--no-mfma-probe",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-stage-times", "--no-gemm-profile", "--no-mfma-probe",
                         "--sustained-steps", "0", *argv], capture_output=True, text=True, env=env, timeout=timeout)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert r.returncode == 0 and lines, r.stderr[-2000:]

@@ -144,6 +144,10 @@ int32_t psam_gemm_f16x3p(const void* A, int64_t lda, const float* scaleA, const 
                          const float* bias, const float* residual, int64_t ldr, const float* rowbias, int64_t ldrb, int32_t rowgroup, int32_t M,
                          int32_t N, int32_t K, float alpha, int32_t act, psam_stream_t stream);
 void psam_gemm_f16x3p_force_config(int32_t cfg); /* tuning hook: tile / ring configuration index, -1 = auto */
+/* Test hooks: the configuration index (ping-pong kernel: 50 ..; the full-row tile of the row epilogues: 40) and the split-K factor (1: unsplit) of the
+ * calling thread's last psam_gemm_f16x3p(_ex) call; -1 and 0 when that call was refused.  A forced configuration runs as forced or is refused. */
+int32_t psam_gemm_f16x3p_last_config(void);
+int32_t psam_gemm_f16x3p_last_splitk(void);
 /* Epilogue of the packed-operand GEMMs: 1 = register-only epilogue on transposed accumulator tiles (csrc/gemm_epilogue_t.h) wherever the
  * launch's options allow it, 0 = always the LDS-transposition epilogue (csrc/gemm_epilogue.h), -1 = default (environment PSAM_GEMM_TR, else 1).
  * Both give the same bits; the hook exists for A/B measurements and the bitwise test. */

@@ -45,6 +45,8 @@ SIGNATURES = {
     "psam_pack_rows_f16x2_g8": (i32, [ptr, i64, ptr, i32, i32, ptr, i64, ptr]),
     "psam_gemm_f16x3p": (i32, [ptr, i64, ptr, ptr, i64, ptr, ptr, i64, ptr, ptr, i64, ptr, i64, i32, i32, i32, i32, f32, i32, ptr]),
     "psam_gemm_f16x3p_force_config": (None, [i32]),
+    "psam_gemm_f16x3p_last_config": (i32, []),
+    "psam_gemm_f16x3p_last_splitk": (i32, []),
     "psam_gemm_f16x3p_force_epilogue": (None, [i32]),
     "psam_gemm_f16x3p_force_splitk_fixup": (None, [i32]),
     "psam_gemm_f16x3p_force_continuous": (None, [i32]),

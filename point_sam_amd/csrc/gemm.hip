@@ -211,15 +211,21 @@ PSAM_API int32_t psam_gemm_f32(const float* A, int64_t lda, int64_t sA1, int64_t
     }
     if (act == 3) {
         PSAM_REQUIRE((N & 63) == 0 && !residual && !rowbias, PSAM_EINVAL, "psam_gemm_f32: SwiGLU epilogue needs N % 64 == 0, no residual/rowbias");
-        if (cfg == 2) cfg = 1;  // needs paired accumulator tiles (TN even)
+        if (cfg == 2) {   // needs paired accumulator tiles (TN even): the automatic choice moves to 128x64, a forced 64x64 is refused
+            PSAM_REQUIRE(g_force_cfg < 0, PSAM_EINVAL, "psam_gemm_f32: the forced 64x64 configuration cannot apply the SwiGLU epilogue");
+            cfg = 1;
+        }
     }
+    PSAM_REQUIRE(cfg >= 0 && cfg <= 2, PSAM_EINVAL, "psam_gemm_f32: unknown config");
     const int bm = cfg == 2 ? 64 : 128, bn = cfg == 0 ? 128 : 64;
     p.tiles_m = (int)psam_cdiv(M, bm);
     p.tiles_n = (int)psam_cdiv(N, bn);
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)batch);
-    if (cfg == 0) hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 2, 2>), grid, dim3(256), 0, stream, p);       // 128x128
-    else if (cfg == 1) hipLaunchKernelGGL((gemm_nt_kernel<4, 1, 1, 2>), grid, dim3(256), 0, stream, p);  // 128x64, wave = 32x64
-    else hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 1, 1>), grid, dim3(256), 0, stream, p);                // 64x64
+    switch (cfg) {
+        case 0: hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 2, 2>), grid, dim3(256), 0, stream, p); break;      // 128x128
+        case 1: hipLaunchKernelGGL((gemm_nt_kernel<4, 1, 1, 2>), grid, dim3(256), 0, stream, p); break;      // 128x64, wave = 32x64
+        case 2: hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 1, 1>), grid, dim3(256), 0, stream, p); break;      // 64x64
+    }
     return psam_launch_status("psam_gemm_f32: launch failed");
 }
 

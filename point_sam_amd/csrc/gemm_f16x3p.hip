@@ -517,6 +517,14 @@ PSAM_API int32_t psam_scale_pack_rows_g8_add_dual(const float* X, int64_t ldx, c
 // ---------------------------------------------------------------------------------------------- host
 static int g_f16x3p_cfg = -1;
 PSAM_API void psam_gemm_f16x3p_force_config(int32_t cfg) { g_f16x3p_cfg = cfg; }
+// Test hook: the configuration index (ping-pong: 50 ..) and split-K factor of the calling thread's last psam_gemm_f16x3p(_ex) launch; -1 / 0 when it was refused.
+static thread_local int32_t t_f16x3p_last_cfg = -1, t_f16x3p_last_splitk = 0;
+PSAM_API int32_t psam_gemm_f16x3p_last_config(void) { return t_f16x3p_last_cfg; }
+PSAM_API int32_t psam_gemm_f16x3p_last_splitk(void) { return t_f16x3p_last_splitk; }
+static int32_t f16x3p_ran(int32_t rc, int cfg, int ksplit) {
+    if (rc == PSAM_OK) { t_f16x3p_last_cfg = cfg; t_f16x3p_last_splitk = ksplit; }
+    return rc;
+}
 #ifdef PSAM_BUILD_EXPERIMENTS
 // Persistent form of the 128x128 register-epilogue configuration (gemm_f16x3c.hip: whole tiles from a queue, one continuous slab stream per workgroup)
 // for batch-sized launches: -1 = default (environment PSAM_GEMM_CONTINUOUS, else OFF: measured neutral), 0 = never, 1 = wherever it applies.
@@ -746,11 +754,40 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     *reinterpret_cast<sk_f32x4*>(C + (int64_t)r * ldc + c) = a;
 }
 
+// The lock-step configurations of psam_gemm_f16x3p_ex (every index here is listed in tests/test_gpu_gemm_configs.py, which checks it on the GPU).
+static int32_t launch_f16x3p_config(int cfg, F16PArgs& p, hipStream_t stream) {
+    switch (cfg) {   // the configurations that won somewhere in the sweeps (profiles/r02/r02_gemm_p_sweep_*.log); numbering kept from the sweeps
+        case 0: return launch_f16x3p<2, 2, 2, 2, 2, 0>(p, stream);            // 128x128, 4 waves of 64x64, 2 stages (64 KiB): 2 workgroups per CU
+        case 4: return launch_f16x3p<4, 2, 2, 2, 3, 0>(p, stream);            // 256x128, 8 waves, 3 stages (144 KiB)
+        case 9: return launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream);            // 128x128, 8 waves of 32x64, 4 stages + look-ahead fragments (128 KiB)
+        case 12: return launch_f16x3p<4, 2, 2, 3, 2, 0>(p, stream);           // 256x192, 8 waves of 64x96, 2 stages (112 KiB); no SwiGLU epilogue
+        case 14: return launch_f16x3p<4, 2, 2, 4, 2, 0>(p, stream);           // 256x256, 8 waves of 64x128, 2 stages (128 KiB)
+        case 21: return f16x3p_use_register_epilogue(p) ? launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2, 1>(p, stream)
+                                                        : launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2>(p, stream);     // 128x128, 4 waves, mid-slab stage release
+        case 23: return launch_f16x3p<4, 2, 2, 3, 2, 0, 0, 2>(p, stream);     // 256x192, mid-slab stage release
+        case 28: return launch_f16x3p<4, 2, 1, 2, 2, 0, 0, 2>(p, stream);     // 128x128, 8 waves of 32x64, 2 stages, mid-slab release (70 KiB): 2 per CU
+        case 29: return f16x3p_use_register_epilogue(p) ? launch_f16x3p<4, 2, 1, 2, 4, 1, 0, 0, 1>(p, stream)      // cfg 9 with the register epilogue (round 6)
+                                                        : launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream);
+        // deeper rings for single-cloud shapes, whose K loop is bound by the LDS-DMA round trip / slabs in flight (round 6, profiles/r06/r06_small_m.txt)
+        case 41: return launch_f16x3p<4, 2, 1, 2, 5, 1>(p, stream);           // cfg 9 with FIVE stages (exactly 160 KiB): four slabs in flight instead of three
+        case 42: return launch_f16x3p<4, 1, 1, 3, 5, 1>(p, stream);           // 128x96, 4 waves of 32x96, five stages (140 KiB); no SwiGLU epilogue
+        // 30 / 31: three workgroups per CU.  Alone they win on the short launches (proj 38.4 -> 32.3 us, up.3 233 -> 205 us), in the pipelined
+        // bench (two batches' kernels co-scheduled) they lose 1.5 % (profiles/r02/r02_gemm_tri_tile.txt): reachable through force_config only
+        case 30: return launch_f16x3p<2, 2, 2, 1, 2, 0, 0, 2>(p, stream);     // 128x64, 4 waves of 64x32, 48 KiB (no SwiGLU / fused extras)
+        case 31: return launch_f16x3p<2, 2, 1, 2, 2, 0, 0, 2>(p, stream);     // 64x128, 4 waves of 32x64, 48 KiB: 3 workgroups per CU
+        case 40: return launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>(p, stream);     // 128x256, 4 waves of 32x256 (whole rows per wave: row epilogues), 133 KiB
+        default: break;
+    }
+    psam_set_error("psam_gemm_f16x3p: unknown config");
+    return PSAM_EINVAL;
+}
+
 // A [M, K] and W [N, K]: g8-packed, row-scaled (scaleA[M], scaleW[N] powers of two); K % 32 == 0 (pad with zeros), K >= 128.
 PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* scaleA, const void* W, int64_t ldw, const float* scaleW, float* C,
                                      int64_t ldc, const float* bias, const float* residual, int64_t ldr, const float* rowbias, int64_t ldrb,
                                      int32_t rowgroup, int32_t M, int32_t N, int32_t K, float alpha, int32_t act, const psam_gemm_fuse_t* fuse,
                                      hipStream_t stream) {
+    t_f16x3p_last_cfg = -1; t_f16x3p_last_splitk = 0;
     PSAM_REQUIRE(A && W && C && scaleA && scaleW, PSAM_EINVAL, "psam_gemm_f16x3p: null pointer");
     PSAM_REQUIRE(M > 0 && N > 0 && K >= 128 && (K & 31) == 0, PSAM_EINVAL, "psam_gemm_f16x3p: bad shape (K % 32 == 0, K >= 128)");
     PSAM_REQUIRE(act >= 0 && act <= 3, PSAM_EINVAL, "psam_gemm_f16x3p: bad activation code");
@@ -808,10 +845,10 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
             case 42: rc = launch_f16x3p<4, 1, 1, 3, 5, 1>(p, stream); break;
             default: psam_set_error("psam_gemm_f16x3p_ex: split-K has no such tile configuration"); return PSAM_EINVAL;
         }
-        if (rc != PSAM_OK || counters) return rc;
+        if (rc != PSAM_OK || counters) return f16x3p_ran(rc, cfg, ks);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)psam_cdiv((int64_t)M * (N / 4), 256)), dim3(256), 0, stream, (const float*)fuse->splitk_ws,
                            fuse->splitk_plane, ks, M, N, bias, residual, ldr, alpha, act, C, ldc);
-        return psam_launch_status("psam_gemm_f16x3p_ex: split-K reduction launch failed");
+        return f16x3p_ran(psam_launch_status("psam_gemm_f16x3p_ex: split-K reduction launch failed"), cfg, ks);
     }
     if (fuse && fuse->hyper && !fuse->row_ln_g) {
         // hyper products from the 64-column wave tiles of the 128x128 / 256x128 configurations: N / 64 partial planes, added by psam_sum_planes
@@ -841,7 +878,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
                      "psam_gemm_f16x3p_ex: 16-byte alignment");
         p.row_ln_g = fuse->row_ln_g; p.row_ln_b = fuse->row_ln_b; p.row_ln_eps = fuse->row_ln_eps;
         p.pack_out = fuse->pack_out; p.out_scale = fuse->out_scale; p.out_k1 = 0.f; p.out_k2 = fuse->out_k2;
-        return launch_f16x3pp(70, p, stream);
+        return f16x3p_ran(launch_f16x3pp(70, p, stream), 70, 1);
 #endif
     } else if (fuse && (fuse->row_ln_g || fuse->hyper)) {
         // full-row epilogues: a wave owns whole rows of N == 256 columns (128x256 tiles, four waves of 32 rows)
@@ -858,7 +895,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         p.row_ln_g = fuse->row_ln_g; p.row_ln_b = fuse->row_ln_b; p.row_ln_eps = fuse->row_ln_eps;
         p.hyper = fuse->hyper; p.masks = fuse->masks; p.hyper_c = fuse->hyper_c; p.hyper_rows = fuse->hyper_rows;
         p.pack_out = fuse->pack_out; p.out_scale = fuse->out_scale; p.out_k1 = fuse->out_k1; p.out_k2 = fuse->out_k2; p.no_store = fuse->no_store;
-        return launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>(p, stream);
+        return f16x3p_ran(launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>(p, stream), 40, 1);      // = cfg 40
     }
     if (fuse && !fuse->hyper && (fuse->pack_out || fuse->stats || fuse->ln_c || fuse->gmax_out)) {
         // The fused epilogue paths exist for interior tiles of the two-tile-wide wave tiles only: whole 256-row / 128-column tiles.
@@ -881,16 +918,30 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         p.gmax_out = fuse->gmax_out; p.gmax_ld = fuse->gmax_ld; p.gmax_k = fuse->gmax_k; p.no_store = fuse->no_store;
         // group maximum: wave tiles of 64 rows (two stripes): 256x128 (cfg 4), 256x256 (cfg 14, N % 256 == 0), 128x128 of four waves (cfg 21);
         // row statistics / everything else: wave tiles two 32-column tiles wide (cfg 4, 9, 21, 28)
-        if (fuse->gmax_out) { if (cfg != 4 && cfg != 14 && cfg != 21) cfg = (N % 256 == 0 && !fuse->stats) ? 14 : 4; }
-        else if (cfg != 4 && cfg != 9 && cfg != 41 && cfg != 21 && cfg != 28) cfg = f16x3p_pick(M, N, K, act, true);
+        // (a forced lock-step configuration without the wave tiles for the requested extras is refused, not replaced)
+        const bool forced_ls = g_f16x3p_cfg >= 0 && g_f16x3p_cfg < 50;
+        if (fuse->gmax_out) {
+            if (cfg != 4 && cfg != 14 && cfg != 21) {
+                PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the group maximum (cfg 4, 14, 21)");
+                cfg = (N % 256 == 0 && !fuse->stats) ? 14 : 4;
+            }
+        } else if (cfg != 4 && cfg != 9 && cfg != 41 && cfg != 21 && cfg != 28) {
+            PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the fused extras (cfg 4, 9, 21, 28, 41)");
+            cfg = f16x3p_pick(M, N, K, act, true);
+        }
     }
     {   // ping-pong kernel (gemm_f16x3pp.hip) where it measured faster (f16x3pp_pick), or where a forced configuration names it
         const bool w_stats = p.stats != nullptr, w_gmax = p.gmax_out != nullptr, w_hyper = p.hyper != nullptr;
         const bool fused_any = w_stats || w_gmax || w_hyper || p.pack_out || p.ln_c;
         const bool shape_ok = !fused_any || ((M & 255) == 0 && (N & 127) == 0);
         const int forced = g_f16x3p_cfg;
-        if (forced >= 50 && forced < 100) { if (shape_ok && f16x3pp_supports(forced, act, w_stats, w_gmax, w_hyper)) cfg = forced; }
-        else if (forced < 0) {
+        if (forced >= 50 && forced < 80) {      // a forced ping-pong configuration runs as forced or is refused (no silent lock-step replacement)
+            PSAM_REQUIRE(shape_ok && f16x3pp_supports(forced, act, w_stats, w_gmax, w_hyper), PSAM_EINVAL,
+                         "psam_gemm_f16x3p_ex: the forced ping-pong configuration does not exist or cannot apply this epilogue / these extras");
+            cfg = forced;
+        } else if (forced >= 80 && forced < 100) {
+            if (shape_ok && f16x3pp_supports(forced, act, w_stats, w_gmax, w_hyper)) cfg = forced;
+        } else if (forced < 0) {
             const int pp = f16x3pp_pick(M, N, K, act);
             if (pp >= 0 && shape_ok && f16x3pp_supports(pp, act, w_stats, w_gmax, w_hyper)) cfg = pp;
         }
@@ -903,7 +954,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
             if (envq < 0) { const char* e = getenv("PSAM_GEMM_Q"); envq = e ? atoi(e) : 0; }
             if (envq >= 80 && M >= 2048 && N >= 1024 && K >= 512) q = (envq == 84 && (act == 3 || N % 192 != 0)) ? 80 : envq;
         }
-        if (q && f16x3q_supports(q, p)) return launch_f16x3q(q, p, stream);
+        if (q && f16x3q_supports(q, p)) return f16x3p_ran(launch_f16x3q(q, p, stream), q, 1);
     }
 #endif
     if (cfg >= 80 && cfg < 90) cfg = f16x3p_pick(M, N, K, act, true);      // (unit-ring configurations: experiments builds only)
@@ -913,12 +964,12 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
     // switches it in for the batch-sized launches), 90 .. 93 = even shares of the K slabs (stream-K, gemm_f16x3s.hip: slower)
     if (cfg == 94 || cfg == 95 || (cfg == 21 && g_f16x3p_cfg < 0 && M >= 2048 && f16x3p_continuous_enabled())) {
         int32_t rc = PSAM_OK;
-        if (f16x3p_use_register_epilogue(p) && launch_f16x3c(p, stream, rc, cfg == 95 ? 1 : 2)) return rc;
+        if (f16x3p_use_register_epilogue(p) && launch_f16x3c(p, stream, rc, cfg == 95 ? 1 : 2)) return f16x3p_ran(rc, cfg == 95 ? 95 : 94, 1);
         if (cfg >= 90) cfg = 21;
     }
     if (cfg >= 90 && cfg <= 93) {
         int32_t rc = PSAM_OK;
-        if (f16x3p_use_register_epilogue(p) && launch_f16x3s(p, stream, rc, cfg - 90)) return rc;
+        if (f16x3p_use_register_epilogue(p) && launch_f16x3s(p, stream, rc, cfg - 90)) return f16x3p_ran(rc, cfg, 1);
         cfg = 21;
     }
 #endif
@@ -937,7 +988,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         }
     }
 #endif
-    if (cfg >= 50 && (cfg < 100 || cfg >= 200)) return launch_f16x3pp(cfg, p, stream);
+    if (cfg >= 50 && (cfg < 100 || cfg >= 200)) return f16x3p_ran(launch_f16x3pp(cfg, p, stream), cfg, 1);
 #ifdef PSAM_GEMM_ABLATE
     if (cfg >= 100) {   // 100 + 32 * which + ablation bits; which: 0 = 128x128 4 waves S2, 1 = 256x128 8 waves S3, 2 = 256x192 S2, 3 = 256x256 S2
         const int which = (cfg - 100) / 32, abl = (cfg - 100) % 32;
@@ -951,30 +1002,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
 #undef ABL_CASE
     }
 #endif
-    switch (cfg) {   // the configurations that won somewhere in the sweeps (profiles/r02/r02_gemm_p_sweep_*.log); numbering kept from the sweeps
-        case 0: return launch_f16x3p<2, 2, 2, 2, 2, 0>(p, stream);            // 128x128, 4 waves of 64x64, 2 stages (64 KiB): 2 workgroups per CU
-        case 4: return launch_f16x3p<4, 2, 2, 2, 3, 0>(p, stream);            // 256x128, 8 waves, 3 stages (144 KiB)
-        case 9: return launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream);            // 128x128, 8 waves of 32x64, 4 stages + look-ahead fragments (128 KiB)
-        case 12: return launch_f16x3p<4, 2, 2, 3, 2, 0>(p, stream);           // 256x192, 8 waves of 64x96, 2 stages (112 KiB); no SwiGLU epilogue
-        case 14: return launch_f16x3p<4, 2, 2, 4, 2, 0>(p, stream);           // 256x256, 8 waves of 64x128, 2 stages (128 KiB)
-        case 21: return f16x3p_use_register_epilogue(p) ? launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2, 1>(p, stream)
-                                                        : launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2>(p, stream);     // 128x128, 4 waves, mid-slab stage release
-        case 23: return launch_f16x3p<4, 2, 2, 3, 2, 0, 0, 2>(p, stream);     // 256x192, mid-slab stage release
-        case 28: return launch_f16x3p<4, 2, 1, 2, 2, 0, 0, 2>(p, stream);     // 128x128, 8 waves of 32x64, 2 stages, mid-slab release (70 KiB): 2 per CU
-        case 29: return f16x3p_use_register_epilogue(p) ? launch_f16x3p<4, 2, 1, 2, 4, 1, 0, 0, 1>(p, stream)      // cfg 9 with the register epilogue (round 6)
-                                                        : launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream);
-        // deeper rings for single-cloud shapes, whose K loop is bound by the LDS-DMA round trip / slabs in flight (round 6, profiles/r06/r06_small_m.txt)
-        case 41: return launch_f16x3p<4, 2, 1, 2, 5, 1>(p, stream);           // cfg 9 with FIVE stages (exactly 160 KiB): four slabs in flight instead of three
-        case 42: return launch_f16x3p<4, 1, 1, 3, 5, 1>(p, stream);           // 128x96, 4 waves of 32x96, five stages (140 KiB); no SwiGLU epilogue
-        // 30 / 31: three workgroups per CU.  Alone they win on the short launches (proj 38.4 -> 32.3 us, up.3 233 -> 205 us), in the pipelined
-        // bench (two batches' kernels co-scheduled) they lose 1.5 % (profiles/r02/r02_gemm_tri_tile.txt): reachable through force_config only
-        case 30: return launch_f16x3p<2, 2, 2, 1, 2, 0, 0, 2>(p, stream);     // 128x64, 4 waves of 64x32, 48 KiB (no SwiGLU / fused extras)
-        case 31: return launch_f16x3p<2, 2, 1, 2, 2, 0, 0, 2>(p, stream);     // 64x128, 4 waves of 32x64, 48 KiB: 3 workgroups per CU
-        case 40: return launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>(p, stream);     // 128x256, 4 waves of 32x256 (whole rows per wave: row epilogues), 133 KiB
-        default: break;
-    }
-    psam_set_error("psam_gemm_f16x3p: unknown config");
-    return PSAM_EINVAL;
+    return f16x3p_ran(launch_f16x3p_config(cfg, p, stream), cfg, 1);
 }
 
 PSAM_API int32_t psam_gemm_f16x3p(const void* A, int64_t lda, const float* scaleA, const void* W, int64_t ldw, const float* scaleW, float* C,

@@ -247,11 +247,14 @@ PSAM_API int32_t psam_gemm_bf16x6(const float* A, int64_t lda, int64_t sA1, int6
     // measured (scripts/gemm_split_bench.py): both shapes saturate near 158 TFLOP/s fp32-equivalent once >= 2 workgroups
     // share a CU; with fewer than 512 128x128 tiles (N = 1024 GEMMs at M = 4096) the 128x64 shape keeps 2+ per CU.
     if (cfg < 0) cfg = (psam_cdiv(M, 128) * psam_cdiv(N, 128) * (int64_t)batch1 * batch2 >= 512 && K > 256) ? 0 : 1;
+    PSAM_REQUIRE(cfg == 0 || cfg == 1, PSAM_EINVAL, "psam_gemm_bf16x6: unknown config");
     const int bn = cfg == 0 ? 128 : 64;
     p.tiles_m = (int)psam_cdiv(M, 128);
     p.tiles_n = (int)psam_cdiv(N, bn);
     const dim3 grid((unsigned)(p.tiles_m * p.tiles_n), 1, (unsigned)((int64_t)batch1 * batch2));
-    if (cfg == 0) hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 2, 2, 2, true>), grid, dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_bf16x6_kernel<4, 1, 1, 2, false>), grid, dim3(256), 0, stream, p);
+    switch (cfg) {
+        case 0: hipLaunchKernelGGL((gemm_bf16x6_kernel<2, 2, 2, 2, true>), grid, dim3(256), 0, stream, p); break;       // 128x128
+        case 1: hipLaunchKernelGGL((gemm_bf16x6_kernel<4, 1, 1, 2, false>), grid, dim3(256), 0, stream, p); break;      // 128x64
+    }
     return psam_launch_status("psam_gemm_bf16x6: launch failed");
 }

@@ -129,6 +129,17 @@ __device__ __forceinline__ float dist2_exact(float ax, float ay, float az, float
     return s;
 }
 
+// An environment switch: its value (atoi / atof), dflt when it is unset.  Read once per process and thread-safely as the initialiser of a function-local
+// static: `static const int x = psam_env_int("NAME", dflt);`.
+static inline int psam_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static inline double psam_env_double(const char* name, double dflt) {
+    const char* e = getenv(name);
+    return e ? atof(e) : dflt;
+}
+
 // Experiments builds only: PSAM_ABLATE_REPEAT (bit mask, environment, read once) makes an idempotent kernel launch TWICE -- the throughput lost to the second
 // launch is the kernel's exposed time in the pipeline (profiles/r06/r06_refill.txt): 1 = psam_attention_packed, 2 = psam_layernorm (out of place),
 // 4 = psam_ln_stats_finalize.

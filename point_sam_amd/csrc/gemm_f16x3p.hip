@@ -532,8 +532,7 @@ static int g_f16x3p_continuous = -1;
 PSAM_API void psam_gemm_f16x3p_force_continuous(int32_t mode) { g_f16x3p_continuous = mode; }
 static bool f16x3p_continuous_enabled() {
     if (g_f16x3p_continuous >= 0) return g_f16x3p_continuous != 0;
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PSAM_GEMM_CONTINUOUS"); on = e ? (atoi(e) != 0) : 0; }
+    static const int on = psam_env_int("PSAM_GEMM_CONTINUOUS", 0);
     return on != 0;
 }
 #endif
@@ -546,13 +545,8 @@ extern "C" __attribute__((visibility("default"))) void psam_gemm_f16x3p_set_timi
 static int g_f16x3p_tr = -1;
 PSAM_API void psam_gemm_f16x3p_force_epilogue(int32_t mode) { g_f16x3p_tr = mode; }
 static int f16x3p_epilogue_mode() {
-    int mode = g_f16x3p_tr;
-    if (mode < 0) {
-        static int env = -2;
-        if (env == -2) { const char* e = getenv("PSAM_GEMM_TR"); env = e ? atoi(e) : 1; }
-        mode = env;
-    }
-    return mode;
+    static const int env = psam_env_int("PSAM_GEMM_TR", 1);
+    return g_f16x3p_tr >= 0 ? g_f16x3p_tr : env;
 }
 // Whether psam_gemm_f16x3p_ex takes psam_gemm_fuse_t.row_ln_* (Linear -> LayerNorm -> activation in one GEMM) for N output columns: 256 always
 // (full-row wave tiles, LDS epilogue), 512 with the register epilogue (128x512 workgroup tiles).
@@ -565,18 +559,11 @@ PSAM_API int32_t psam_gemm_f16x3p_fused_row_ln(int32_t N) {
 #ifndef PSAM_BUILD_EXPERIMENTS
     return 0;      // the 128x512 full-row tile is an experiments-build configuration (measured slower, see above)
 #endif
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PSAM_GEMM_ROWLN512"); on = e ? atoi(e) : 0; }
+    static const int on = psam_env_int("PSAM_GEMM_ROWLN512", 0);
     return N == 512 && on > 0 && f16x3p_epilogue_mode() > 0 ? 1 : 0;
 }
 bool f16x3p_use_register_epilogue(const F16PArgs& p) {
-    int mode = g_f16x3p_tr;
-    if (mode < 0) {
-        static int env = -2;
-        if (env == -2) { const char* e = getenv("PSAM_GEMM_TR"); env = e ? atoi(e) : 1; }
-        mode = env;
-    }
-    if (mode <= 0) return false;
+    if (f16x3p_epilogue_mode() <= 0) return false;
     if (p.gmax_out || p.row_ln_g || (p.no_store && !p.hyper)) return false;      // options only gemm_epilogue.h implements
     // per-group row bias: implemented, bitwise equal, but only when forced -- its one user (PatchEncoder conv2.0, K = 128, 512 MB of fp32 output)
     // is bound by the stores, and one-row-per-lane 16-byte stores lose against the LDS epilogue's full rows (247 vs 235 us,
@@ -585,68 +572,6 @@ bool f16x3p_use_register_epilogue(const F16PArgs& p) {
     if (p.hyper && (p.hyper_rows % 32 != 0 || (((uintptr_t)p.hyper) & 15) != 0 || (p.N & 3) != 0)) return false;
     if ((((uintptr_t)p.scaleW | (uintptr_t)p.bias | (uintptr_t)p.ln_c) & 15) != 0) return false;      // float4 loads of the column constants
     return true;
-}
-
-// Tile configuration for a shape.  Measured per-CU rates of the configurations are within ~15 % of each other once a CU is busy
-// (profiles/r02/r02_gemm_p_sweep_*.log; the kernel is power-limited, profiles/r02/r02_gemm_power_limit.txt); what differs is how many rounds
-// of workgroups a launch needs, how full the last one is -- and how a launch behaves when a few CUs are NOT available: the tokenizer
-// of the next batch (FPS: one 1024-thread workgroup per cloud, a whole CU each, ~2 ms per step) runs beside the dense stage, and a
-// launch of exactly #CU one-per-CU workgroups then needs a second round for the last few tiles (twice the time).  So the rounds are
-// counted on #CU - 8 and configurations with two workgroups per CU (64-70 KiB of LDS) are candidates for the shapes that would
-// otherwise sit exactly at one round.
-//   cost = rounds x tile area x (K + 300) x penalty x share
-// (300 ~ the epilogue of a tile in k-steps; penalty: operand bytes per flop of the smaller tiles, LDS-DMA path ~32 B/clk/CU; share: two
-// resident tiles on a CU each progress at ~60 % of a lone tile's speed).
-static int f16x3p_pick(int M, int N, int K, int act, bool two_wide_only) {
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
-    static int reserve = -1;
-    static double share2 = 0.0, pen9 = 0.0;
-    if (reserve < 0) {      // tuning hooks (environment, read once): CUs assumed busy elsewhere; slowdown of two co-resident tiles
-        const char* e = getenv("PSAM_GEMM_RESERVE_CUS");
-        reserve = e ? atoi(e) : 8;
-        const char* f = getenv("PSAM_GEMM_SHARE");
-        share2 = f ? atof(f) : 1.6;
-        const char* g = getenv("PSAM_GEMM_PEN9");
-        pen9 = g ? atof(g) : 1.15;
-    }
-    const int ncu_eff = ncu > 2 * reserve ? ncu - reserve : ncu;
-    struct Cand { int cfg, bm, bn, per_cu; bool swiglu, two_wide; double pen; };
-    // 41 = the eight-wave 128x128 tile on a FIVE-stage ring (exactly 160 KiB), 42 = 128x96 on five stages (140 KiB; single-cloud launches of one round): the same
-    // bits as cfg 9, and ALONE on the chip faster where the K loop is bound by the slabs in flight (giant qkv at one cloud 28.1 -> 25.5 -> 23.8 us, ViT-L fc2 at
-    // M = 2048 42.7 -> 41.0 us; profiles/r06/r06_small_m.txt) -- but in the two-stream pipelines they LOSE 4 % (cfg #5 146.3 -> 140.4 sessions/s, cfg #3 102.8 ->
-    // 98.6 clouds/s, profiles/r06/r06_small_m_ring.txt): a workgroup that holds all of a CU's LDS keeps the other stream's kernels off that CU.  OFF by default
-    // (PSAM_GEMM_SMALL_M_RING=1 / force_config 41, 42 switch them in: a single stream of work, e.g. an interactive predictor, gains).
-    static const Cand cands[] = {{14, 256, 256, 1, true, false, 1.0}, {23, 256, 192, 1, false, false, 1.0}, {4, 256, 128, 1, true, true, 1.05},
-                                 {41, 128, 128, 1, true, true, 1.15}, {21, 128, 128, 2, true, true, 1.15},  {28, 128, 128, 2, true, true, 1.2},
-                                 {42, 128, 96, 1, false, false, 1.15}};
-    static int small_ring = -1;
-    if (small_ring < 0) { const char* e = getenv("PSAM_GEMM_SMALL_M_RING"); small_ring = e ? atoi(e) : 0; }
-    int best = 41;
-    double best_cost = 1e300;
-    for (const Cand& c : cands) {
-        if (act == 3 && !c.swiglu) continue;
-        if (two_wide_only && !c.two_wide) continue;
-        const int64_t tiles = psam_cdiv(M, c.bm) * psam_cdiv(N, c.bn);
-        const double rounds = (double)psam_cdiv(tiles, (int64_t)ncu_eff * c.per_cu);
-        if (c.cfg == 42 && (!small_ring || M > 1024 || rounds > 1.0)) continue;
-        const double share = (c.per_cu == 2 && tiles * 2 > (int64_t)ncu_eff * 3) ? share2 : 1.0;
-        const double cost = rounds * c.bm * c.bn * (K + 300.0) * (c.cfg == 41 ? pen9 : c.pen) * share;
-        if (cost < best_cost) { best_cost = cost; best = c.cfg; }
-    }
-    if (best == 41 && !small_ring) best = 9;
-    // The eight-wave 128x128 tile comes as cfg 9 (four stages, 128 KiB: one workgroup per CU) and cfg 28 (two stages with the mid-slab release, 70 KiB: two
-    // per CU) -- the same wave tiles, the same bits.  Alone cfg 9 is 5-10 % faster on every single-cloud shape; in the two-stream pipelines the answer depends on
-    // the rows (profiles/r06/r06_sub9.txt): at M = 512 (giant, one cloud) cfg 9 wins (145.9 vs 138.4 sessions/s), at M = 2048 (ViT-L, N = 131072) cfg 28 wins
-    // (106.1 vs 103.2 clouds/s: with several rounds of tiles the LDS it leaves free lets the other stream's workgroups onto the CU).  PSAM_GEMM_SUB9=<cfg>
-    // overrides (A/B; 9 = always cfg 9).
-    static int sub9 = -1;
-    if (sub9 < 0) { const char* e = getenv("PSAM_GEMM_SUB9"); sub9 = e ? atoi(e) : 0; }
-    if (best == 9) best = sub9 > 0 ? sub9 : (M >= 2048 ? 28 : 9);
-    return best;
 }
 
 template <int WM, int WN, int TM, int TN, int S, int LA, int ABL = 0, int PF = 0, int TR = 0>
@@ -671,6 +596,94 @@ static int32_t launch_f16x3p(F16PArgs& p, hipStream_t stream) {
     return psam_launch_status("psam_gemm_f16x3p: launch failed");
 }
 
+// The lock-step configurations (psam_gemm_f16x3p_force_config 0 .. 49; every one is checked on the GPU by tests/test_gpu_gemm_configs.py): the ones that won
+// somewhere in the sweeps (profiles/r02/r02_gemm_p_sweep_*.log), numbering kept from the sweeps.  Group maximum: wave tiles of 64 rows (two stripes); every
+// other fused extra: wave tiles two 32-column tiles wide.  The split-K form of 21 is its LDS-epilogue instance, that of 29 its register-epilogue one.
+constexpr unsigned LS_ALL = F16P_SWIGLU | F16P_TWO_WIDE | F16P_GMAX, LS_TWO_WIDE = F16P_SWIGLU | F16P_TWO_WIDE;
+static const F16PConfig k_f16x3p_configs[] = {
+    // 128x128, 4 waves of 64x64, 2 stages (64 KiB): 2 workgroups per CU
+    {0, 128, 128, 2, 2, F16P_SWIGLU, &launch_f16x3p<2, 2, 2, 2, 2, 0>, nullptr, &launch_f16x3p<2, 2, 2, 2, 2, 0>},
+    // 256x128, 8 waves, 3 stages (144 KiB)
+    {4, 256, 128, 1, 2, LS_ALL, &launch_f16x3p<4, 2, 2, 2, 3, 0>, nullptr, &launch_f16x3p<4, 2, 2, 2, 3, 0>},
+    // 128x128, 8 waves of 32x64, 4 stages + look-ahead fragments (128 KiB)
+    {9, 128, 128, 1, 2, LS_TWO_WIDE, &launch_f16x3p<4, 2, 1, 2, 4, 1>, nullptr, &launch_f16x3p<4, 2, 1, 2, 4, 1>},
+    // 256x192, 8 waves of 64x96, 2 stages (112 KiB); no SwiGLU epilogue
+    {12, 256, 192, 1, 3, 0, &launch_f16x3p<4, 2, 2, 3, 2, 0>, nullptr, &launch_f16x3p<4, 2, 2, 3, 2, 0>},
+    // 256x256, 8 waves of 64x128, 2 stages (128 KiB)
+    {14, 256, 256, 1, 4, F16P_SWIGLU | F16P_GMAX, &launch_f16x3p<4, 2, 2, 4, 2, 0>, nullptr, &launch_f16x3p<4, 2, 2, 4, 2, 0>},
+    // 128x128, 4 waves, mid-slab stage release: the production configuration
+    {21, 128, 128, 2, 2, LS_ALL, &launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2>, &launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2, 1>, &launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2>},
+    // 256x192, mid-slab stage release
+    {23, 256, 192, 1, 3, 0, &launch_f16x3p<4, 2, 2, 3, 2, 0, 0, 2>, nullptr, &launch_f16x3p<4, 2, 2, 3, 2, 0, 0, 2>},
+    // 128x128, 8 waves of 32x64, 2 stages, mid-slab release (70 KiB): 2 per CU
+    {28, 128, 128, 2, 2, LS_TWO_WIDE, &launch_f16x3p<4, 2, 1, 2, 2, 0, 0, 2>, nullptr, &launch_f16x3p<4, 2, 1, 2, 2, 0, 0, 2>},
+    // cfg 9 with the register epilogue (round 6)
+    {29, 128, 128, 1, 2, F16P_SWIGLU, &launch_f16x3p<4, 2, 1, 2, 4, 1>, &launch_f16x3p<4, 2, 1, 2, 4, 1, 0, 0, 1>, &launch_f16x3p<4, 2, 1, 2, 4, 1, 0, 0, 1>},
+    // deeper rings for single-cloud shapes, whose K loop is bound by the LDS-DMA round trip / slabs in flight (round 6, profiles/r06/r06_small_m.txt):
+    // cfg 9 with FIVE stages (exactly 160 KiB): four slabs in flight instead of three; 128x96, 4 waves of 32x96, five stages (140 KiB), no SwiGLU epilogue
+    {41, 128, 128, 1, 2, LS_TWO_WIDE, &launch_f16x3p<4, 2, 1, 2, 5, 1>, nullptr, &launch_f16x3p<4, 2, 1, 2, 5, 1>},
+    {42, 128, 96, 1, 3, 0, &launch_f16x3p<4, 1, 1, 3, 5, 1>, nullptr, &launch_f16x3p<4, 1, 1, 3, 5, 1>},
+    // 30 / 31: three workgroups per CU.  Alone they win on the short launches (proj 38.4 -> 32.3 us, up.3 233 -> 205 us), in the pipelined bench (two
+    // batches' kernels co-scheduled) they lose 1.5 % (profiles/r02/r02_gemm_tri_tile.txt): reachable through force_config only.  128x64, 4 waves of
+    // 64x32, 48 KiB; 64x128, 4 waves of 32x64, 48 KiB
+    {30, 128, 64, 3, 1, F16P_SK_PICK, &launch_f16x3p<2, 2, 2, 1, 2, 0, 0, 2>, nullptr, nullptr},
+    {31, 64, 128, 3, 2, F16P_SWIGLU | F16P_SK_PICK, &launch_f16x3p<2, 2, 1, 2, 2, 0, 0, 2>, nullptr, nullptr},
+    // 128x256, 4 waves of 32x256 (whole rows per wave: the row epilogues of psam_gemm_f16x3p_ex), 133 KiB
+    {40, 128, 256, 1, 8, F16P_SWIGLU, &launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>, nullptr, nullptr},
+};
+static const F16PConfig* f16x3p_config(int cfg) { return f16p_find(k_f16x3p_configs, cfg); }
+static bool f16x3p_has(int cfg, unsigned caps) {
+    const F16PConfig* c = f16x3p_config(cfg);
+    return c && (c->caps & caps) == caps;
+}
+
+// Tile configuration for a shape.  Measured per-CU rates of the configurations are within ~15 % of each other once a CU is busy
+// (profiles/r02/r02_gemm_p_sweep_*.log; the kernel is power-limited, profiles/r02/r02_gemm_power_limit.txt); what differs is how many rounds
+// of workgroups a launch needs, how full the last one is -- and how a launch behaves when a few CUs are NOT available: the tokenizer
+// of the next batch (FPS: one 1024-thread workgroup per cloud, a whole CU each, ~2 ms per step) runs beside the dense stage, and a
+// launch of exactly #CU one-per-CU workgroups then needs a second round for the last few tiles (twice the time).  So the rounds are
+// counted on #CU - 8 and configurations with two workgroups per CU (64-70 KiB of LDS) are candidates for the shapes that would
+// otherwise sit exactly at one round.
+//   cost = rounds x tile area x (K + 300) x penalty x share
+// (300 ~ the epilogue of a tile in k-steps; penalty: operand bytes per flop of the smaller tiles, LDS-DMA path ~32 B/clk/CU; share: two
+// resident tiles on a CU each progress at ~60 % of a lone tile's speed).
+static int f16x3p_pick(int M, int N, int K, int act, bool two_wide_only) {
+    static const int ncu = f16x3p_cu_count();
+    // tuning hooks (environment, read once): CUs assumed busy elsewhere; slowdown of two co-resident tiles; penalty of the eight-wave 128x128 tile
+    static const int reserve = psam_env_int("PSAM_GEMM_RESERVE_CUS", 8);
+    static const double share2 = psam_env_double("PSAM_GEMM_SHARE", 1.6), pen9 = psam_env_double("PSAM_GEMM_PEN9", 1.15);
+    static const int small_ring = psam_env_int("PSAM_GEMM_SMALL_M_RING", 0), sub9 = psam_env_int("PSAM_GEMM_SUB9", 0);
+    const int ncu_eff = ncu > 2 * reserve ? ncu - reserve : ncu;
+    struct Cand { int cfg; double pen; };
+    // 41 = the eight-wave 128x128 tile on a FIVE-stage ring (exactly 160 KiB), 42 = 128x96 on five stages (140 KiB; single-cloud launches of one round): the same
+    // bits as cfg 9, and ALONE on the chip faster where the K loop is bound by the slabs in flight (giant qkv at one cloud 28.1 -> 25.5 -> 23.8 us, ViT-L fc2 at
+    // M = 2048 42.7 -> 41.0 us; profiles/r06/r06_small_m.txt) -- but in the two-stream pipelines they LOSE 4 % (cfg #5 146.3 -> 140.4 sessions/s, cfg #3 102.8 ->
+    // 98.6 clouds/s, profiles/r06/r06_small_m_ring.txt): a workgroup that holds all of a CU's LDS keeps the other stream's kernels off that CU.  OFF by default
+    // (PSAM_GEMM_SMALL_M_RING=1 / force_config 41, 42 switch them in: a single stream of work, e.g. an interactive predictor, gains).
+    static const Cand cands[] = {{14, 1.0}, {23, 1.0}, {4, 1.05}, {41, 1.15}, {21, 1.15}, {28, 1.2}, {42, 1.15}};
+    int best = 41;
+    double best_cost = 1e300;
+    for (const Cand& cand : cands) {
+        const F16PConfig& c = *f16x3p_config(cand.cfg);
+        if (act == 3 && !(c.caps & F16P_SWIGLU)) continue;
+        if (two_wide_only && !(c.caps & F16P_TWO_WIDE)) continue;
+        const int64_t tiles = psam_cdiv(M, c.bm) * psam_cdiv(N, c.bn);
+        const double rounds = (double)psam_cdiv(tiles, (int64_t)ncu_eff * c.per_cu);
+        if (c.cfg == 42 && (!small_ring || M > 1024 || rounds > 1.0)) continue;
+        const double share = (c.per_cu == 2 && tiles * 2 > (int64_t)ncu_eff * 3) ? share2 : 1.0;
+        const double cost = rounds * c.bm * c.bn * (K + 300.0) * (c.cfg == 41 ? pen9 : cand.pen) * share;
+        if (cost < best_cost) { best_cost = cost; best = c.cfg; }
+    }
+    if (best == 41 && !small_ring) best = 9;
+    // The eight-wave 128x128 tile comes as cfg 9 (four stages, 128 KiB: one workgroup per CU) and cfg 28 (two stages with the mid-slab release, 70 KiB: two
+    // per CU) -- the same wave tiles, the same bits.  Alone cfg 9 is 5-10 % faster on every single-cloud shape; in the two-stream pipelines the answer depends on
+    // the rows (profiles/r06/r06_sub9.txt): at M = 512 (giant, one cloud) cfg 9 wins (145.9 vs 138.4 sessions/s), at M = 2048 (ViT-L, N = 131072) cfg 28 wins
+    // (106.1 vs 103.2 clouds/s: with several rounds of tiles the LDS it leaves free lets the other stream's workgroups onto the CU).  PSAM_GEMM_SUB9=<cfg>
+    // overrides (A/B; 9 = always cfg 9).
+    if (best == 9) best = sub9 > 0 ? sub9 : (M >= 2048 ? 28 : 9);
+    return best;
+}
+
 // Optional fused extras of psam_gemm_f16x3p_ex: psam_gemm_fuse_t, include/pointsam_hip.h (part of this translation unit through common.h).
 
 // partial planes the hyper products of an N-column GEMM are delivered in: 1 with the row-LayerNorm (full-row) epilogue, N / 64 otherwise
@@ -678,17 +691,6 @@ PSAM_API int32_t psam_gemm_f16x3p_hyper_planes(int32_t N, int32_t with_row_ln) {
 
 // segments (of 32 gated columns) per row of the stats buffer of a SwiGLU GEMM with N packed weight rows
 PSAM_API int32_t psam_gemm_f16x3p_stat_segs(int32_t N) { return (N / 2 + 31) / 32; }
-
-static void f16x3p_cfg_tile(int cfg, int& bm, int& bn, int& per_cu) {
-    switch (cfg) {
-        case 4: bm = 256; bn = 128; per_cu = 1; break;
-        case 14: bm = 256; bn = 256; per_cu = 1; break;
-        case 12: case 23: bm = 256; bn = 192; per_cu = 1; break;
-        case 9: case 29: case 41: bm = 128; bn = 128; per_cu = 1; break;
-        case 42: bm = 128; bn = 96; per_cu = 1; break;
-        default: bm = 128; bn = 128; per_cu = 2; break;      // 0, 21, 28
-    }
-}
 
 // Arrival counters of the split-K fix-up: the first SK_MAX_TILES ints of the CALLER's counter block (psam_gemm_fuse_t.counters, PSAM_COUNTER_BYTES,
 // include/pointsam_hip.h): zero before the first launch, left zero by every launch (the last workgroup of a tile resets its word).  The library keeps no
@@ -698,35 +700,37 @@ constexpr int64_t SK_MAX_TILES = PSAM_CNT_GEMM_N;
 static int g_f16x3p_sk_fixup = -1;      // -1: PSAM_GEMM_SPLITK_FIXUP (default on); 0 / 1 forced (psam_gemm_f16x3p_force_splitk_fixup)
 static bool f16x3p_splitk_fixup_enabled() {
     if (g_f16x3p_sk_fixup >= 0) return g_f16x3p_sk_fixup != 0;
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PSAM_GEMM_SPLITK_FIXUP"); on = e ? (atoi(e) != 0) : 1; }
+    static const int on = psam_env_int("PSAM_GEMM_SPLITK_FIXUP", 1);
     return on != 0;
 }
 PSAM_API void psam_gemm_f16x3p_force_splitk_fixup(int32_t mode) { g_f16x3p_sk_fixup = mode; }
 
+// The configuration a split-K launch runs in place of cfg: cfg where it has a split-K form; for a ping-pong or an F16P_SK_PICK configuration the pick among the
+// two-tile-wide wave tiles; null (refused) for any other.
+static const F16PConfig* f16x3p_splitk_config(int cfg, int M, int N, int K, int act) {
+    const F16PConfig* c = f16x3p_config(cfg);
+    if (cfg >= 50 || (c && (c->caps & F16P_SK_PICK))) c = f16x3p_config(f16x3p_pick(M, N, K, act, true));
+    return c && c->splitk ? c : nullptr;
+}
+
 // Split-K factor for a shape (1: none).  A launch whose tiles cover less than half of the CUs (M = 512 rows of one cloud: 44 tiles of
 // 128x128 for the N = 1408 GEMMs of the giant encoder) leaves the rest of the chip idle for a K loop of up to 192 slabs; `ks` workgroups
 // per tile share the slabs (>= 8 each) and psam_gemm_f16x3p_ex adds the partial planes in a fixed order (deterministic).
-// PSAM_GEMM_SPLITK: 0 = never, n > 1 = always n (tuning).
+// PSAM_GEMM_SPLITK: 0 = never, n > 1 = always n (tuning).  The tiles counted are those of the configuration the split-K launch would run (a forced one
+// that it refuses: no split).
 PSAM_API int32_t psam_gemm_f16x3p_splitk(int32_t M, int32_t N, int32_t K, int32_t act) {
-    static int forced = -1;
-    if (forced < 0) { const char* e = getenv("PSAM_GEMM_SPLITK"); forced = e ? atoi(e) : 1; }
+    static const int forced = psam_env_int("PSAM_GEMM_SPLITK", 1);
+    static const int frac_pct = psam_env_int("PSAM_GEMM_SPLITK_MAX_FILL_PCT", 30);
     if (act == 3 || K < 1024 || (K & 31) || forced == 0) return 1;
     if (forced == 1 && M > 2048) return 1;      // a batch of clouds: its other GEMM stream fills the idle CUs, the extra reduction pass only costs (r03 profile)
     const int nslabs = K / 32;
     if (forced > 1) return forced <= nslabs / 4 ? forced : (nslabs / 4 > 1 ? nslabs / 4 : 1);
-    int cfg = g_f16x3p_cfg;
-    if (cfg < 0 || cfg >= 50) cfg = f16x3p_pick(M, N, K, act, true);
-    int bm, bn, per_cu;
-    f16x3p_cfg_tile(cfg, bm, bn, per_cu);
-    int ncu = 256, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    const int64_t tiles = psam_cdiv(M, bm) * psam_cdiv(N, bn), slots = (int64_t)(ncu - 8) * per_cu;
+    const F16PConfig* c = f16x3p_splitk_config(g_f16x3p_cfg < 0 ? f16x3p_pick(M, N, K, act, true) : g_f16x3p_cfg, M, N, K, act);
+    if (!c) return 1;
+    const int64_t tiles = psam_cdiv(M, c->bm) * psam_cdiv(N, c->bn), slots = (int64_t)(f16x3p_cu_count() - 8) * c->per_cu;
     // Measured per shape, alone on the chip (profiles/r06/r06_small_m.txt): splitting pays for 44 tiles on 248 slots (giant proj 24.7 -> 18.6 us, fc2 82.6 -> 38.7)
     // and LOSES for 132 and 192 tiles (giant qkv 27.9 -> 41.2 us with two splits, fc1 30.1 -> 44.1 with three: 8.6 - 12.6 MB of partial planes per split
     // through the fabric and a serial fix-up for a K loop that was only 44 slabs long).  Until round 5 the limit was 0.55 of the slots.
-    static int frac_pct = -1;
-    if (frac_pct < 0) { const char* e = getenv("PSAM_GEMM_SPLITK_MAX_FILL_PCT"); frac_pct = e ? atoi(e) : 30; }
     if (tiles * 100 > slots * frac_pct) return 1;
     int ks = (int)((slots + tiles / 2) / tiles);
     if (ks > 4) ks = 4;
@@ -752,34 +756,6 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     for (int e = 0; e < 4; ++e) a[e] = ep_act(a[e], act);
     if (residual) a += *reinterpret_cast<const sk_f32x4*>(residual + (int64_t)r * ldr + c);
     *reinterpret_cast<sk_f32x4*>(C + (int64_t)r * ldc + c) = a;
-}
-
-// The lock-step configurations of psam_gemm_f16x3p_ex (every index here is listed in tests/test_gpu_gemm_configs.py, which checks it on the GPU).
-static int32_t launch_f16x3p_config(int cfg, F16PArgs& p, hipStream_t stream) {
-    switch (cfg) {   // the configurations that won somewhere in the sweeps (profiles/r02/r02_gemm_p_sweep_*.log); numbering kept from the sweeps
-        case 0: return launch_f16x3p<2, 2, 2, 2, 2, 0>(p, stream);            // 128x128, 4 waves of 64x64, 2 stages (64 KiB): 2 workgroups per CU
-        case 4: return launch_f16x3p<4, 2, 2, 2, 3, 0>(p, stream);            // 256x128, 8 waves, 3 stages (144 KiB)
-        case 9: return launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream);            // 128x128, 8 waves of 32x64, 4 stages + look-ahead fragments (128 KiB)
-        case 12: return launch_f16x3p<4, 2, 2, 3, 2, 0>(p, stream);           // 256x192, 8 waves of 64x96, 2 stages (112 KiB); no SwiGLU epilogue
-        case 14: return launch_f16x3p<4, 2, 2, 4, 2, 0>(p, stream);           // 256x256, 8 waves of 64x128, 2 stages (128 KiB)
-        case 21: return f16x3p_use_register_epilogue(p) ? launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2, 1>(p, stream)
-                                                        : launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2>(p, stream);     // 128x128, 4 waves, mid-slab stage release
-        case 23: return launch_f16x3p<4, 2, 2, 3, 2, 0, 0, 2>(p, stream);     // 256x192, mid-slab stage release
-        case 28: return launch_f16x3p<4, 2, 1, 2, 2, 0, 0, 2>(p, stream);     // 128x128, 8 waves of 32x64, 2 stages, mid-slab release (70 KiB): 2 per CU
-        case 29: return f16x3p_use_register_epilogue(p) ? launch_f16x3p<4, 2, 1, 2, 4, 1, 0, 0, 1>(p, stream)      // cfg 9 with the register epilogue (round 6)
-                                                        : launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream);
-        // deeper rings for single-cloud shapes, whose K loop is bound by the LDS-DMA round trip / slabs in flight (round 6, profiles/r06/r06_small_m.txt)
-        case 41: return launch_f16x3p<4, 2, 1, 2, 5, 1>(p, stream);           // cfg 9 with FIVE stages (exactly 160 KiB): four slabs in flight instead of three
-        case 42: return launch_f16x3p<4, 1, 1, 3, 5, 1>(p, stream);           // 128x96, 4 waves of 32x96, five stages (140 KiB); no SwiGLU epilogue
-        // 30 / 31: three workgroups per CU.  Alone they win on the short launches (proj 38.4 -> 32.3 us, up.3 233 -> 205 us), in the pipelined
-        // bench (two batches' kernels co-scheduled) they lose 1.5 % (profiles/r02/r02_gemm_tri_tile.txt): reachable through force_config only
-        case 30: return launch_f16x3p<2, 2, 2, 1, 2, 0, 0, 2>(p, stream);     // 128x64, 4 waves of 64x32, 48 KiB (no SwiGLU / fused extras)
-        case 31: return launch_f16x3p<2, 2, 1, 2, 2, 0, 0, 2>(p, stream);     // 64x128, 4 waves of 32x64, 48 KiB: 3 workgroups per CU
-        case 40: return launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>(p, stream);     // 128x256, 4 waves of 32x256 (whole rows per wave: row epilogues), 133 KiB
-        default: break;
-    }
-    psam_set_error("psam_gemm_f16x3p: unknown config");
-    return PSAM_EINVAL;
 }
 
 // A [M, K] and W [N, K]: g8-packed, row-scaled (scaleA[M], scaleW[N] powers of two); K % 32 == 0 (pad with zeros), K >= 128.
@@ -820,31 +796,17 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
                      "psam_gemm_f16x3p_ex: split-K needs a workspace of splitk planes of >= M * N floats, N % 4 == 0");
         PSAM_REQUIRE((((uintptr_t)fuse->splitk_ws | (uintptr_t)C | (uintptr_t)bias | (uintptr_t)residual) & 15) == 0 && (ldc & 3) == 0 && (ldr & 3) == 0,
                      PSAM_EALIGN, "psam_gemm_f16x3p_ex: split-K needs 16-byte aligned rows");
-        if (cfg >= 50 || cfg == 30 || cfg == 31) cfg = f16x3p_pick(M, N, K, act, true);
+        const F16PConfig* c = f16x3p_splitk_config(cfg, M, N, K, act);
+        PSAM_REQUIRE(c, PSAM_EINVAL, "psam_gemm_f16x3p_ex: split-K has no such tile configuration");
+        cfg = c->cfg;
         // in-kernel fix-up (the last workgroup of a tile sums the partials and runs the epilogue) where the workspace holds the tiles' raw accumulators
         // and this stream has its arrival counters; otherwise partial planes + the reduction launch
-        int bm = 0, bn = 0, per_cu = 0;
-        f16x3p_cfg_tile(cfg, bm, bn, per_cu);
-        const int64_t sk_tiles = psam_cdiv(M, bm) * psam_cdiv(N, bn);
-        int* counters = (f16x3p_splitk_fixup_enabled() && sk_tiles <= SK_MAX_TILES && sk_tiles * bm * bn <= fuse->splitk_plane) ? (fuse->counters ? fuse->counters + PSAM_CNT_GEMM : nullptr) : nullptr;
+        const int64_t sk_tiles = psam_cdiv(M, c->bm) * psam_cdiv(N, c->bn);
+        int* counters = (f16x3p_splitk_fixup_enabled() && sk_tiles <= SK_MAX_TILES && sk_tiles * c->bm * c->bn <= fuse->splitk_plane) ? (fuse->counters ? fuse->counters + PSAM_CNT_GEMM : nullptr) : nullptr;
         p.ksplit = ks; p.plane = fuse->splitk_plane;
         if (counters) { p.sk_part = fuse->splitk_ws; p.sk_count = counters; }
         else { p.C = fuse->splitk_ws; p.ldc = N; p.bias = nullptr; p.residual = nullptr; p.act = 0; p.alpha = 1.f; }
-        int32_t rc = PSAM_EINVAL;
-        switch (cfg) {
-            case 0: rc = launch_f16x3p<2, 2, 2, 2, 2, 0>(p, stream); break;
-            case 4: rc = launch_f16x3p<4, 2, 2, 2, 3, 0>(p, stream); break;
-            case 9: rc = launch_f16x3p<4, 2, 1, 2, 4, 1>(p, stream); break;
-            case 12: rc = launch_f16x3p<4, 2, 2, 3, 2, 0>(p, stream); break;
-            case 14: rc = launch_f16x3p<4, 2, 2, 4, 2, 0>(p, stream); break;
-            case 21: rc = launch_f16x3p<2, 2, 2, 2, 2, 0, 0, 2>(p, stream); break;
-            case 23: rc = launch_f16x3p<4, 2, 2, 3, 2, 0, 0, 2>(p, stream); break;
-            case 28: rc = launch_f16x3p<4, 2, 1, 2, 2, 0, 0, 2>(p, stream); break;
-            case 29: rc = launch_f16x3p<4, 2, 1, 2, 4, 1, 0, 0, 1>(p, stream); break;
-            case 41: rc = launch_f16x3p<4, 2, 1, 2, 5, 1>(p, stream); break;
-            case 42: rc = launch_f16x3p<4, 1, 1, 3, 5, 1>(p, stream); break;
-            default: psam_set_error("psam_gemm_f16x3p_ex: split-K has no such tile configuration"); return PSAM_EINVAL;
-        }
+        const int32_t rc = c->splitk(p, stream);
         if (rc != PSAM_OK || counters) return f16x3p_ran(rc, cfg, ks);
         hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)psam_cdiv((int64_t)M * (N / 4), 256)), dim3(256), 0, stream, (const float*)fuse->splitk_ws,
                            fuse->splitk_plane, ks, M, N, bias, residual, ldr, alpha, act, C, ldc);
@@ -863,7 +825,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         // The register epilogue sums a row's products in another order than the LDS epilogue (same accuracy, other rounding): ONE configuration for every
         // M, so that a cloud's logits do not depend on how many clouds share the launch (tests/test_gpu_e2e.py::test_properties_full_size).
         if (g_f16x3p_cfg < 0 && f16x3p_use_register_epilogue(p)) cfg = 21;
-        else if (cfg != 4 && cfg != 9 && cfg != 41 && cfg != 21 && cfg != 28) cfg = f16x3p_pick(M, N, K, act, true);
+        else if (!f16x3p_has(cfg, F16P_TWO_WIDE)) cfg = f16x3p_pick(M, N, K, act, true);
 #ifdef PSAM_BUILD_EXPERIMENTS
     } else if (fuse && fuse->row_ln_g && N == 512) {
         // full-row tile 128x512 on the ping-pong kernel with the register epilogue: Linear (+ row bias per group) -> LayerNorm -> activation -> packed rows
@@ -895,7 +857,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         p.row_ln_g = fuse->row_ln_g; p.row_ln_b = fuse->row_ln_b; p.row_ln_eps = fuse->row_ln_eps;
         p.hyper = fuse->hyper; p.masks = fuse->masks; p.hyper_c = fuse->hyper_c; p.hyper_rows = fuse->hyper_rows;
         p.pack_out = fuse->pack_out; p.out_scale = fuse->out_scale; p.out_k1 = fuse->out_k1; p.out_k2 = fuse->out_k2; p.no_store = fuse->no_store;
-        return f16x3p_ran(launch_f16x3p<4, 1, 1, 8, 2, 0, 0, 2>(p, stream), 40, 1);      // = cfg 40
+        return f16x3p_ran(f16x3p_config(40)->lds(p, stream), 40, 1);
     }
     if (fuse && !fuse->hyper && (fuse->pack_out || fuse->stats || fuse->ln_c || fuse->gmax_out)) {
         // The fused epilogue paths exist for interior tiles of the two-tile-wide wave tiles only: whole 256-row / 128-column tiles.
@@ -916,17 +878,16 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
                      "psam_gemm_f16x3p_ex: group maximum needs groups of 32 or 64 rows, no SwiGLU, a 16-byte aligned [M / k, >= N] output");
         PSAM_REQUIRE(!fuse->no_store || fuse->gmax_out, PSAM_EINVAL, "psam_gemm_f16x3p_ex: no_store only together with the group maximum");
         p.gmax_out = fuse->gmax_out; p.gmax_ld = fuse->gmax_ld; p.gmax_k = fuse->gmax_k; p.no_store = fuse->no_store;
-        // group maximum: wave tiles of 64 rows (two stripes): 256x128 (cfg 4), 256x256 (cfg 14, N % 256 == 0), 128x128 of four waves (cfg 21);
-        // row statistics / everything else: wave tiles two 32-column tiles wide (cfg 4, 9, 21, 28)
-        // (a forced lock-step configuration without the wave tiles for the requested extras is refused, not replaced)
+        // group maximum: wave tiles of 64 rows (F16P_GMAX; in place of another configuration 256x256 where N % 256 == 0, else 256x128); row statistics /
+        // everything else: wave tiles two 32-column tiles wide (F16P_TWO_WIDE).  A forced lock-step configuration without them is refused, not replaced.
         const bool forced_ls = g_f16x3p_cfg >= 0 && g_f16x3p_cfg < 50;
         if (fuse->gmax_out) {
-            if (cfg != 4 && cfg != 14 && cfg != 21) {
-                PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the group maximum (cfg 4, 14, 21)");
+            if (!f16x3p_has(cfg, F16P_GMAX)) {
+                PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the group maximum");
                 cfg = (N % 256 == 0 && !fuse->stats) ? 14 : 4;
             }
-        } else if (cfg != 4 && cfg != 9 && cfg != 41 && cfg != 21 && cfg != 28) {
-            PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the fused extras (cfg 4, 9, 21, 28, 41)");
+        } else if (!f16x3p_has(cfg, F16P_TWO_WIDE)) {
+            PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the fused extras");
             cfg = f16x3p_pick(M, N, K, act, true);
         }
     }
@@ -950,8 +911,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
     {   // unit-ring kernel (gemm_f16x3q.hip): a forced configuration 80 .., or the environment's choice for the large encoder GEMMs
         int q = (g_f16x3p_cfg >= 80 && g_f16x3p_cfg < 90) ? g_f16x3p_cfg : 0;
         if (!q && g_f16x3p_cfg < 0) {
-            static int envq = -1;
-            if (envq < 0) { const char* e = getenv("PSAM_GEMM_Q"); envq = e ? atoi(e) : 0; }
+            static const int envq = psam_env_int("PSAM_GEMM_Q", 0);
             if (envq >= 80 && M >= 2048 && N >= 1024 && K >= 512) q = (envq == 84 && (act == 3 || N % 192 != 0)) ? 80 : envq;
         }
         if (q && f16x3q_supports(q, p)) return f16x3p_ran(launch_f16x3q(q, p, stream), q, 1);
@@ -1002,7 +962,9 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
 #undef ABL_CASE
     }
 #endif
-    return f16x3p_ran(launch_f16x3p_config(cfg, p, stream), cfg, 1);
+    const F16PConfig* c = f16x3p_config(cfg);
+    PSAM_REQUIRE(c, PSAM_EINVAL, "psam_gemm_f16x3p: unknown config");
+    return f16x3p_ran(f16p_launch(*c, p, stream), cfg, 1);
 }
 
 PSAM_API int32_t psam_gemm_f16x3p(const void* A, int64_t lda, const float* scaleA, const void* W, int64_t ldw, const float* scaleW, float* C,

@@ -53,8 +53,7 @@ __device__ __forceinline__ unsigned long long gemm_now() {
 // is fetched once.  The P with the least modelled traffic wins (ties: the widest).  PSAM_GEMM_PANEL overrides (0: plain row-major).
 // Measured (profiles/r02/r02_gemm_panel_sweep.log): qkv 81.7 -> 79.6 us, fc1 143.4 -> 138.2 us, two-stream layer 303.9 -> 292 us.
 static inline int f16x3p_panel(int tiles_m, int tiles_n, int BM, int BN, int K) {
-    static int forced = -2;
-    if (forced == -2) { const char* e = getenv("PSAM_GEMM_PANEL"); forced = e ? atoi(e) : -1; }
+    static const int forced = psam_env_int("PSAM_GEMM_PANEL", -1);
     if (forced == 0) return tiles_n;
     if (forced > 0) return forced < tiles_n ? forced : tiles_n;
     const double l2 = 2.5 * 1048576.0, a_band = (double)BM * K * 4, w_col = (double)BN * K * 4;
@@ -72,6 +71,12 @@ static inline int f16x3p_panel(int tiles_m, int tiles_n, int BM, int BN, int K) 
     return best;
 }
 
+// CUs of the current device; 256 (MI355X) where there is none to ask (host-side planning without a GPU)
+static inline int f16x3p_cu_count() {
+    int ncu = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+    return ncu;
+}
 
 // > 64 KiB of dynamic LDS must be opted into per kernel AND per device (the attribute lives with the device's code object)
 template <typename K>
@@ -90,6 +95,31 @@ int32_t launch_f16x3pp(int cfg, F16PArgs& p, hipStream_t stream);
 bool f16x3pp_supports(int cfg, int act, bool stats, bool gmax, bool hyper);
 int f16x3pp_pick(int M, int N, int K, int act);      // -1: keep the lock-step kernel
 bool f16x3p_use_register_epilogue(const F16PArgs& p);      // gemm_f16x3p.hip: whether this launch may run the register-only epilogue (gemm_epilogue_t.h)
+
+// One tile configuration of either kernel, as its file's configuration table lists it.  bm x bn: workgroup tile; per_cu: workgroups a CU holds; tn: 32-column
+// accumulator tiles per wave (the SwiGLU gate pairs tiles 2q, 2q + 1).  caps: what the wave tiles can do.  lds: the instance with the LDS-transposition epilogue;
+// reg: the one with the register epilogue where it exists, chosen per launch (f16x3p_use_register_epilogue); splitk: the instance a split-K launch runs.
+typedef int32_t (*F16PLaunch)(F16PArgs& p, hipStream_t stream);
+enum : unsigned {
+    F16P_SWIGLU = 1,          // the SwiGLU epilogue (act == 3)
+    F16P_TWO_WIDE = 2,        // row statistics and hyper products (and, on the lock-step kernel, packed output and the folded LayerNorm): two-tile-wide wave tiles
+    F16P_GMAX = 4,            // group maximum: 64-row wave tiles
+    F16P_SK_PICK = 8,         // a split-K launch replaces this configuration by the pick (f16x3p_splitk_config)
+};
+struct F16PConfig {
+    int cfg, bm, bn, per_cu, tn;
+    unsigned caps;
+    F16PLaunch lds, reg, splitk;
+};
+template <int N>
+static inline const F16PConfig* f16p_find(const F16PConfig (&table)[N], int cfg) {
+    for (const F16PConfig& c : table)
+        if (c.cfg == cfg && c.lds) return &c;
+    return nullptr;
+}
+static inline int32_t f16p_launch(const F16PConfig& c, F16PArgs& p, hipStream_t stream) {
+    return (c.reg && f16x3p_use_register_epilogue(p) ? c.reg : c.lds)(p, stream);
+}
 // gemm_f16x3c.hip: persistent form of the 128x128 register-epilogue configuration -- whole tiles from a queue, one continuous stream of K slabs per
 // workgroup; true = it took the launch (rc = status)
 bool launch_f16x3c(F16PArgs& p, hipStream_t stream, int32_t& rc, int wgs_per_cu = 2);

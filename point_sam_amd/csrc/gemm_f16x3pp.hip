@@ -287,22 +287,54 @@ static int32_t launch_pp(F16PArgs& p, hipStream_t stream) {
     return psam_launch_status("psam_gemm_f16x3p: launch failed");
 }
 
-// Which fused extras a ping-pong configuration's wave tile supports (same rules as the lock-step kernel: SwiGLU pairs accumulator tiles
-// (even TN); row statistics and hyper products are written for two-tile-wide wave tiles; the group maximum needs 64-row wave tiles).
+// The ping-pong configurations (psam_gemm_f16x3p_force_config 50 ..; every one is checked on the GPU by tests/test_gpu_gemm_configs.py).  Fused extras follow the
+// lock-step kernel's rules: row statistics and hyper products need an epilogue chunk two tiles wide (the wide wave tiles of 62 - 64 run the two-tile epilogue
+// chunk by chunk; 53's is four wide), the group maximum 64-row wave tiles; packed output and the folded LayerNorm take any.  A probe build
+// (scripts/kernel_resources.py -DPSAM_PP_ONLY=65) instantiates only the entry it names.
+#ifndef PSAM_PP_ONLY
+#define PSAM_PP_ONLY 0
+#endif
+template <int CFG, int GWM, int WN, int TM, int TN, int S, int P, int PRIO, int ABL = 0, int TR = 0, int OCC = 2>
+constexpr F16PLaunch pp_instance() {
+    if constexpr (PSAM_PP_ONLY == 0 || PSAM_PP_ONLY == CFG) return &launch_pp<GWM, WN, TM, TN, S, P, PRIO, ABL, TR, OCC>;
+    else return nullptr;
+}
+constexpr unsigned PP_ALL = F16P_SWIGLU | F16P_TWO_WIDE | F16P_GMAX, PP_TWO_WIDE = F16P_SWIGLU | F16P_TWO_WIDE;
+static const F16PConfig k_pp_configs[] = {
+    // 256x256, waves of 128x64, 5 units (160 KiB), priority around the MFMAs; 51: no priority changes; 52: static priority for group 1; 59: 4 units (128 KiB);
+    // 60 / 61: two-step phases (48 MFMAs between barriers), 5 / 4 units
+    {50, 256, 256, 1, 2, PP_ALL, pp_instance<50, 1, 4, 4, 2, 5, 1, 1>(), nullptr, nullptr},
+    {51, 256, 256, 1, 2, PP_ALL, pp_instance<51, 1, 4, 4, 2, 5, 1, 0>(), pp_instance<51, 1, 4, 4, 2, 5, 1, 0, 0, 1>(), nullptr},
+    {52, 256, 256, 1, 2, PP_ALL, pp_instance<52, 1, 4, 4, 2, 5, 1, 2>(), nullptr, nullptr},
+    {59, 256, 256, 1, 2, PP_ALL, pp_instance<59, 1, 4, 4, 2, 4, 1, 1>(), nullptr, nullptr},
+    {60, 256, 256, 1, 2, PP_ALL, pp_instance<60, 1, 4, 4, 2, 5, 2, 0>(), nullptr, nullptr},
+    {61, 256, 256, 1, 2, PP_ALL, pp_instance<61, 1, 4, 4, 2, 4, 2, 0>(), nullptr, nullptr},
+    {53, 256, 256, 1, 4, F16P_SWIGLU | F16P_GMAX, pp_instance<53, 2, 2, 2, 4, 5, 1, 1>(), nullptr, nullptr},      // waves of 64x128
+    // 256x128, waves of 64x64, 6 units (144 KiB), two-step phases (24 MFMAs); 56: one-step phases (12 MFMAs)
+    {55, 256, 128, 1, 2, PP_ALL, pp_instance<55, 2, 2, 2, 2, 6, 2, 1>(), pp_instance<55, 2, 2, 2, 2, 6, 2, 1, 0, 1>(), nullptr},
+    {56, 256, 128, 1, 2, PP_ALL, pp_instance<56, 2, 2, 2, 2, 6, 1, 1>(), nullptr, nullptr},
+    // 128x128, waves of 32x64, 8 units (128 KiB), two-step phases (12 MFMAs); 58: 4 units (64 KiB): two workgroups per CU
+    {57, 128, 128, 1, 2, PP_TWO_WIDE, pp_instance<57, 2, 2, 1, 2, 8, 2, 1>(), pp_instance<57, 2, 2, 1, 2, 8, 2, 1, 0, 1>(), nullptr},
+    {58, 128, 128, 2, 2, PP_TWO_WIDE, pp_instance<58, 2, 2, 1, 2, 4, 2, 1>(), nullptr, nullptr},
+    // round 5: TWO ping-pong workgroups per CU (72 KiB, 128 registers): four waves per SIMD, two of them in a compute interval at any time.  256x128, waves of
+    // 64x64, 3 units, one-step phases (12 MFMAs); 66: priority around the MFMAs; 67: 128x256
+    {65, 256, 128, 2, 2, PP_ALL, pp_instance<65, 2, 2, 2, 2, 3, 1, 0, 0, 0, 4>(), nullptr, nullptr},
+    {66, 256, 128, 2, 2, PP_ALL, pp_instance<66, 2, 2, 2, 2, 3, 1, 1, 0, 0, 4>(), nullptr, nullptr},
+    {67, 128, 256, 2, 2, PP_ALL, pp_instance<67, 1, 4, 2, 2, 3, 1, 0, 0, 0, 4>(), nullptr, nullptr},
+    // right-sized tiles (round 4): eight waves of 32 rows x the whole tile width, so that a launch's tiles fill #CU - 8 workgroup slots in whole rounds.
+    // 256x224 (150 KiB): qkv 4096x3072 = 224 tiles, one round (seven tiles wide: no SwiGLU); 256x192 (140 KiB): fc1 4096x5504 = 464 tiles, two rounds;
+    // 256x256 with the same wave layout (160 KiB)
+    {62, 256, 224, 1, 7, F16P_TWO_WIDE, pp_instance<62, 4, 1, 1, 7, 5, 1, 1>(), nullptr, nullptr},
+    {63, 256, 192, 1, 6, PP_TWO_WIDE, pp_instance<63, 4, 1, 1, 6, 5, 1, 1>(), nullptr, nullptr},
+    {64, 256, 256, 1, 8, PP_TWO_WIDE, pp_instance<64, 4, 1, 1, 8, 5, 1, 1>(), nullptr, nullptr},
+};
+
 bool f16x3pp_supports(int cfg, int act, bool stats, bool gmax, bool hyper) {
-    int tm, tn;
-    switch (cfg) {
-        case 50: case 51: case 52: case 59: case 60: case 61: tm = 4; tn = 2; break;
-        case 53: tm = 2; tn = 4; break;
-        case 55: case 56: case 65: case 66: case 67: tm = 2; tn = 2; break;
-        case 57: case 58: tm = 1; tn = 2; break;
-        case 62: case 63: case 64: tm = 1; tn = 2; break;      // wide wave tiles run the two-tile epilogue chunk by chunk (odd widths: no SwiGLU, checked at launch)
-        default: return false;
-    }
-    if (act == 3 && ((tn & 1) || cfg == 62)) return false;      // SwiGLU pairs column tiles (2q, 2q+1): even widths only (cfg 62 is seven tiles wide)
-    if ((stats || hyper) && tn != 2) return false;
-    if (gmax && tm < 2) return false;
-    return true;
+    const F16PConfig* c = f16p_find(k_pp_configs, cfg);
+    if (!c) return false;
+    if (act == 3 && !(c->caps & F16P_SWIGLU)) return false;
+    if ((stats || hyper) && !(c->caps & F16P_TWO_WIDE)) return false;
+    return !gmax || (c->caps & F16P_GMAX);
 }
 
 // Where the ping-pong kernel replaces the lock-step one.  Measured (profiles/r03/r03_gemm_pp_bench.log, r03_bench_ab.log): alone it wins on fc1
@@ -313,8 +345,7 @@ bool f16x3pp_supports(int cfg, int act, bool stats, bool gmax, bool hyper) {
 // more than the kernel's own gain.  So the default is OFF.  PSAM_GEMM_PP (read once): 0 (default) = never; 1 = fc1 and conv2.3; 2 = every
 // encoder-sized GEMM on the 256x128 tile as well; 3 = on the 256x256 tile where N allows.
 int f16x3pp_pick(int M, int N, int K, int act) {
-    static int mode = -1;
-    if (mode < 0) { const char* e = getenv("PSAM_GEMM_PP"); mode = e ? atoi(e) : 0; }
+    static const int mode = psam_env_int("PSAM_GEMM_PP", 0);
     if (mode == 0 || K < 128 || (K & 31)) return -1;
     if (M >= 32768) return (N >= 256 && (N & 127) == 0 && K >= 512) ? 51 : -1;      // mini-PointNet conv2.3: 256x256 tiles, many rounds
     if (mode == 4) {
@@ -322,17 +353,16 @@ int f16x3pp_pick(int M, int N, int K, int act) {
         // the width whose tile count fills whole rounds of #CU - 8 workgroup slots best -- wide GEMMs only (N >= 1536: with 128-column tiles
         // and one workgroup per CU the narrow ones leave half of the chip idle, the lock-step kernel keeps them)
         if (M < 2048 || (M & 255) || (N & 127) || N < 1536) return -1;
-        static int ncu = 0;
-        if (!ncu) { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256; }
+        static const int ncu = f16x3p_cu_count();
         const int slots = ncu > 16 ? ncu - 8 : ncu;
         int best = -1; double best_cost = 1e300;
-        const int cfgs[3] = {51, 62, 63}, widths[3] = {256, 224, 192};
-        for (int i = 0; i < 3; ++i) {
-            if (act == 3 && (widths[i] / 32) % 2) continue;
-            const int64_t tiles = (int64_t)(M / 256) * ((N + widths[i] - 1) / widths[i]);
+        for (const int cfg : {51, 62, 63}) {
+            const F16PConfig* c = f16p_find(k_pp_configs, cfg);
+            if (!c || (act == 3 && !(c->caps & F16P_SWIGLU))) continue;
+            const int64_t tiles = (int64_t)(M / 256) * ((N + c->bn - 1) / c->bn);
             const double rounds = (double)((tiles + slots - 1) / slots);
-            const double cost = rounds * widths[i] * (1.0 + 24.0 / widths[i]);      // per-round time ~ tile width + a fixed part (prologue, epilogue ramp)
-            if (cost < best_cost) { best_cost = cost; best = cfgs[i]; }
+            const double cost = rounds * c->bn * (1.0 + 24.0 / c->bn);      // per-round time ~ tile width + a fixed part (prologue, epilogue ramp)
+            if (cost < best_cost) { best_cost = cost; best = cfg; }
         }
         return best;
     }
@@ -369,44 +399,10 @@ int32_t launch_f16x3pp(int cfg, F16PArgs& p, hipStream_t stream) {
 #undef PP_ABL
     }
 #endif
-#ifdef PSAM_PP_ONLY      // probe builds (scripts/kernel_resources.py -DPSAM_PP_ONLY=65 -save-temps): one configuration, seconds to compile
-    if (cfg == PSAM_PP_ONLY) {
-        switch (PSAM_PP_ONLY) {
-            case 65: return launch_pp<2, 2, 2, 2, 3, 1, 0, 0, 0, 4>(p, stream);
-            case 58: return launch_pp<2, 2, 1, 2, 4, 2, 1>(p, stream);
-            default: break;
-        }
-    }
-    return PSAM_EINVAL;
-#else
-    switch (cfg) {
-        case 50: return launch_pp<1, 4, 4, 2, 5, 1, 1>(p, stream);      // 256x256, waves of 128x64, 5 units (160 KiB), priority around the MFMAs
-        case 51: return f16x3p_use_register_epilogue(p) ? launch_pp<1, 4, 4, 2, 5, 1, 0, 0, 1>(p, stream) : launch_pp<1, 4, 4, 2, 5, 1, 0>(p, stream);      //   no priority changes
-        case 52: return launch_pp<1, 4, 4, 2, 5, 1, 2>(p, stream);      //   static priority for group 1
-        case 59: return launch_pp<1, 4, 4, 2, 4, 1, 1>(p, stream);      //   4 units (128 KiB)
-        case 60: return launch_pp<1, 4, 4, 2, 5, 2, 0>(p, stream);      //   two-step phases (48 MFMAs between barriers), 5 units
-        case 61: return launch_pp<1, 4, 4, 2, 4, 2, 0>(p, stream);      //   two-step phases, 4 units
-        case 53: return launch_pp<2, 2, 2, 4, 5, 1, 1>(p, stream);      // 256x256, waves of 64x128
-        case 55: return f16x3p_use_register_epilogue(p) ? launch_pp<2, 2, 2, 2, 6, 2, 1, 0, 1>(p, stream)
-                                                        : launch_pp<2, 2, 2, 2, 6, 2, 1>(p, stream);      // 256x128, waves of 64x64, 6 units (144 KiB), two-step phases (24 MFMAs)
-        case 56: return launch_pp<2, 2, 2, 2, 6, 1, 1>(p, stream);      //   one-step phases (12 MFMAs)
-        case 57: return f16x3p_use_register_epilogue(p) ? launch_pp<2, 2, 1, 2, 8, 2, 1, 0, 1>(p, stream)
-                                                        : launch_pp<2, 2, 1, 2, 8, 2, 1>(p, stream);      // 128x128, waves of 32x64, 8 units (128 KiB), two-step phases (12 MFMAs)
-        case 58: return launch_pp<2, 2, 1, 2, 4, 2, 1>(p, stream);      //   4 units (64 KiB): two workgroups per CU
-        // round 5: TWO ping-pong workgroups per CU (72 KiB, 128 registers): four waves per SIMD, two of them in a compute interval at any time
-        case 65: return launch_pp<2, 2, 2, 2, 3, 1, 0, 0, 0, 4>(p, stream);      // 256x128, waves of 64x64, 3 units, one-step phases (12 MFMAs)
-        case 66: return launch_pp<2, 2, 2, 2, 3, 1, 1, 0, 0, 4>(p, stream);      //   priority around the MFMAs
-        case 67: return launch_pp<1, 4, 2, 2, 3, 1, 0, 0, 0, 4>(p, stream);      // 128x256, waves of 64x64
-        // right-sized tiles (round 4): eight waves of 32 rows x the whole tile width, so that a launch's tiles fill #CU - 8 workgroup slots in whole rounds
-        case 62: return launch_pp<4, 1, 1, 7, 5, 1, 1>(p, stream);      // 256x224 (150 KiB): qkv 4096x3072 = 224 tiles, one round
-        case 63: return launch_pp<4, 1, 1, 6, 5, 1, 1>(p, stream);      // 256x192 (140 KiB): fc1 4096x5504 = 464 tiles, two rounds
-        case 64: return launch_pp<4, 1, 1, 8, 5, 1, 1>(p, stream);      // 256x256 with the same wave layout (160 KiB)
 #ifdef PSAM_BUILD_EXPERIMENTS
-        case 70: return launch_pp<1, 4, 2, 4, 3, 1, 1, 0, 2>(p, stream);      // 128x512 full-row tile, waves of 64x128, 3 units (120 KiB): row LayerNorm epilogue (N == 512)
+    if (cfg == 70) return launch_pp<1, 4, 2, 4, 3, 1, 1, 0, 2>(p, stream);      // 128x512 full-row tile, waves of 64x128, 3 units (120 KiB): row LayerNorm epilogue (N == 512)
 #endif
-        default: break;
-    }
+    if (const F16PConfig* c = f16p_find(k_pp_configs, cfg)) return f16p_launch(*c, p, stream);
     psam_set_error("psam_gemm_f16x3p: unknown ping-pong config");
     return PSAM_EINVAL;
-#endif
 }

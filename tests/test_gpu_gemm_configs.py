@@ -2,8 +2,8 @@
 
 The packed-operand f16x3 GEMM (csrc/gemm_f16x3p.hip: lock-step ring kernel, csrc/gemm_f16x3pp.hip: ping-pong kernel) ships about thirty
 configurations that force_config hooks and documented environment switches reach; the f32 and bf16x6 GEMMs two or three each.  CONFIGS lists
-them all with what each can do; a CPU test keeps it equal to the `case` labels of the production dispatch switches, so a configuration
-added later without coverage here fails without a GPU.  On the GPU every entry runs (and `psam_gemm_f16x3p_last_config` confirms it ran, not
+them all with what each can do; a CPU test keeps it equal to the configuration tables the f16x3 dispatch is driven by (and to the `case` labels of
+the f32 / bf16x6 switches), so a configuration added or changed later without coverage here fails without a GPU.  On the GPU every entry runs (and `psam_gemm_f16x3p_last_config` confirms it ran, not
 a replacement) against an fp64 reference, bit for bit against cfg 21, on selection matrices that must reproduce the packed operands
 exactly, with the fused extras and split-K where it takes them, and through the environment switches in fresh child processes."""
 import ctypes
@@ -118,32 +118,107 @@ def _switch_cases(body, after=None):
     return {int(c) for c in re.findall(r"\bcase\s+(\d+)\s*:", _body(body[start:], "switch (cfg)"))}
 
 
+def _split_top(text):
+    """text split at the commas outside <> and ()."""
+    parts, depth, cur = [], 0, ""
+    for ch in text:
+        depth += {"<": 1, "(": 1, ">": -1, ")": -1}.get(ch, 0)
+        if ch == "," and depth == 0:
+            parts.append(cur.strip())
+            cur = ""
+        else:
+            cur += ch
+    return parts + [cur.strip()]
+
+
+def config_table(src, name, caps_names):
+    """{cfg: dict(bm, bn, per_cu, tn, caps, lds, reg, splitk)} of the F16PConfig table `name` (launchers as source text, None for nullptr)."""
+    body = src[src.index(f"static const F16PConfig {name}[] = {{"):]
+    body = body[body.index("\n"):body.index("\n};")]
+    rows = {}
+    for line in body.splitlines():
+        line = line.split("//")[0].strip()
+        if not line:
+            continue
+        assert line.startswith("{") and line.endswith("},"), line
+        f = _split_top(line[1:-2])
+        assert len(f) == 9, line
+        cfg, bm, bn, per_cu, tn = map(int, f[:5])
+        caps = 0
+        for t in f[5].split("|"):
+            caps |= int(t) if t.strip().isdigit() else caps_names[t.strip()]
+        launch = [None if x == "nullptr" else x for x in f[6:]]
+        assert cfg not in rows, cfg
+        rows[cfg] = dict(bm=bm, bn=bn, per_cu=per_cu, tn=tn, caps=caps, lds=launch[0], reg=launch[1], splitk=launch[2])
+    return rows
+
+
+def _caps_names(args_h, *srcs):
+    """The capability bits of gemm_f16x3p_args.h and the constexpr unions of them the tables use."""
+    names = {m.group(1): int(m.group(2)) for m in re.finditer(r"\b(F16P_\w+) = (\d+),", args_h)}
+    for src in srcs:
+        for m in re.finditer(r"constexpr unsigned ([^;]+);", src):
+            for part in m.group(1).split(","):
+                k, v = part.split("=")
+                names[k.strip()] = 0
+                for t in v.split("|"):
+                    names[k.strip()] |= names[t.strip()]
+    return names
+
+
 def dispatched_configs():
     rd = lambda f: _default_build(open(os.path.join(CSRC, f)).read())
-    p, pp, g32, gsp = rd("gemm_f16x3p.hip"), rd("gemm_f16x3pp.hip"), rd("gemm.hip"), rd("gemm_split.hip")
-    ex = _body(p, "PSAM_API int32_t psam_gemm_f16x3p_ex(")
+    p, pp, g32, gsp, args = rd("gemm_f16x3p.hip"), rd("gemm_f16x3pp.hip"), rd("gemm.hip"), rd("gemm_split.hip"), rd("gemm_f16x3p_args.h")
+    caps = _caps_names(args, p, pp)
     return {
-        "lockstep": _switch_cases(_body(p, "static int32_t launch_f16x3p_config(")),
-        "pingpong": _switch_cases(_body(pp, "int32_t launch_f16x3pp(")),
-        "pingpong_supports": {int(c) for c in re.findall(r"\bcase\s+(\d+)\s*:", _body(pp, "bool f16x3pp_supports("))},
-        "splitk": _switch_cases(ex, after="fuse->splitk > 1"),
+        "lockstep": config_table(p, "k_f16x3p_configs", caps),
+        "pingpong": config_table(pp, "k_pp_configs", caps),
+        "caps": caps,
         "f32": _switch_cases(_body(g32, "PSAM_API int32_t psam_gemm_f32(")),
         "bf16x6": _switch_cases(_body(gsp, "PSAM_API int32_t psam_gemm_bf16x6(")),
     }
 
 
-def test_registry_matches_the_dispatch_switches():
-    """CPU guard: the registry above is exactly the set of configurations the default build can launch (a `case` added to or removed from a
-    dispatch switch -- or from CONFIGS -- fails here until the GPU tests below cover it)."""
+def test_registry_matches_the_configuration_tables():
+    """CPU guard: the registry above is exactly what the default build can launch -- the configuration tables of the f16x3 kernels, entry by entry (tile,
+    workgroups per CU, accumulator tiles per wave, SwiGLU, fused extras, split-K form), and the `case` labels of the f32 / bf16x6 switches.  An entry
+    added to, removed from or changed in a table -- or in CONFIGS -- fails here until the GPU tests below cover it."""
     d = dispatched_configs()
+    bit = d["caps"]
     kind = lambda k: {c for (g, c), v in CONFIGS.items() if v.kernel == k}
-    assert kind("lockstep") == d["lockstep"], kind("lockstep") ^ d["lockstep"]
-    assert kind("pingpong") == d["pingpong"] == d["pingpong_supports"], (kind("pingpong") ^ d["pingpong"], d["pingpong"] ^ d["pingpong_supports"])
-    assert set(SPLITK) == d["splitk"], set(SPLITK) ^ d["splitk"]
+    for k in ("lockstep", "pingpong"):
+        assert kind(k) == set(d[k]), (k, kind(k) ^ set(d[k]))
+        for c, e in d[k].items():
+            v = CONFIGS["f16x3p", c]
+            swiglu = bool(e["caps"] & bit["F16P_SWIGLU"])
+            # fused extras: row statistics and hyper products need the two-tile-wide wave tiles (on the lock-step kernel so do packed output and the folded
+            # LayerNorm), the group maximum 64-row wave tiles; row statistics come with the SwiGLU epilogue only
+            extras = set(_TWO_WIDE if e["caps"] & bit["F16P_TWO_WIDE"] else ()) | ({"pack", "ln_fold"} if k == "pingpong" else set())
+            extras |= {"gmax"} if e["caps"] & bit["F16P_GMAX"] else set()
+            if not swiglu:
+                extras.discard("stats")
+            got = Cfg(k, e["bm"], e["bn"], e["per_cu"], e["tn"], swiglu, frozenset(extras), e["splitk"] is not None)
+            assert got == v, (c, got, v)
+            assert e["lds"] is not None and not (e["caps"] & bit["F16P_SK_PICK"] and e["splitk"]), c
     assert kind("f32") == d["f32"] and kind("bf16x6") == d["bf16x6"], (d["f32"], d["bf16x6"])
     for (g, c), v in CONFIGS.items():
         assert v.swiglu == (v.tn % 2 == 0), (g, c)      # the SwiGLU gate pairs accumulator tiles (2q, 2q + 1)
         assert v.splitk <= (v.kernel == "lockstep") and not (v.extras and v.kernel in ("f32", "bf16x6")), (g, c)
+
+
+def test_splitk_suggestion_resolves_the_forced_configuration_like_the_launch():
+    """psam_gemm_f16x3p_splitk counts the tiles of the configuration a split-K launch would run: with a forced configuration that has no split-K form the
+    launch runs the pick (30, 31: the same factor as unforced) or refuses to split (40: no split suggested).  Host logic: no GPU needed."""
+    L = _lib()
+    shapes = [(512, 1408, 6144, 0), (512, 1408, 1408, 1), (300, 260, 1024, 2), (1024, 1024, 2784, 0), (256, 4096, 4096, 0)]
+    unforced = [L.psam_gemm_f16x3p_splitk(*s) for s in shapes]
+    assert unforced[0] > 1
+    try:
+        for cfg, want in ((30, unforced), (31, unforced), (40, [1] * len(shapes))):
+            L.psam_gemm_f16x3p_force_config(cfg)
+            assert [L.psam_gemm_f16x3p_splitk(*s) for s in shapes] == want, cfg
+    finally:
+        L.psam_gemm_f16x3p_force_config(-1)
 
 
 def test_default_build_filter():
@@ -216,6 +291,7 @@ def ops():
 
 
 def _lib():
+    import torch as _torch  # noqa: F401  (first: the library must bind to the HIP runtime torch uses, see _lib.load)
     from point_sam_amd import _lib as L
     return L.load()
 
@@ -783,6 +859,163 @@ def test_environment_switches_in_child_processes(ops, tmp_path):
                 bad.append((k, v, name, "ran cfg", r["cfg"], "expected", sorted(ENV_EXPECT[k, v][name])))
             elif r["sha"] != base[name]["sha"]:
                 bad.append((k, v, name, "bits differ from the default process", r["cfg"], base[name]["cfg"]))
+    assert not bad, bad
+
+
+# ------------------------------------------------------------------------------------------------ 7. dispatch pins
+# What the default process runs, unforced: (psam_gemm_f16x3p_last_config, psam_gemm_f16x3p_last_splitk) of one launch and psam_gemm_f16x3p_splitk
+# of its shape, over the bench model's GEMM shapes (ViT-L qkv / proj / SwiGLU fc1 / fc2 with its padded K, the patch encoder's narrow ones, a ragged N)
+# from one row to 64 clouds, each fused extra and split-K requested.  PINS holds the values the library gave before its dispatch became table-driven.
+PIN_M = (1, 100, 512, 1000, 2047, 2048, 4096, 32768, 65536)
+PIN_NK = ((3072, 1024), (1024, 1024), (5504, 1024), (1024, 2752), (2730, 1024), (256, 128), (512, 256))
+PIN_EXTRAS = ("pack", "stats_pack", "ln_fold", "gmax", "hyper", "row_ln", "splitk")
+
+
+def pin_cases():
+    """(M, N, K, act, extra) of every pinned launch; extra None = plain."""
+    cases = []
+    for M in PIN_M:
+        for N, K in PIN_NK:
+            cases += [(M, N, K, act, None) for act in ((0, 3) if N % 64 == 0 else (0,))]
+            if M % 256 == 0 and N % 128 == 0 and M * N <= 4096 * 5504:
+                cases += [(M, N, K, 3 if x == "stats_pack" else 0, x) for x in PIN_EXTRAS if x not in ("row_ln", "splitk")]
+            if N == 256 and M % 128 == 0:
+                cases.append((M, N, K, 1, "row_ln"))
+            if M <= 4096 and N % 4 == 0 and K >= 256:
+                cases.append((M, N, K, 0, "splitk"))
+    return cases
+
+
+def _pin_launch(M, N, K, act, extra):
+    """One unforced launch on zero operands; returns (config, split factor) the library reports."""
+    from point_sam_amd import _lib as Lm
+    import torch as T
+    dev = "cuda"
+    A, W = (T.zeros(M, K, device=dev), T.ones(M, device=dev)), (T.zeros(N, K, device=dev), T.ones(N, device=dev))
+    ncol = N // 2 if act == 3 else N
+    C = T.empty(M, ncol, device=dev)
+    fuse, keep = None, []
+    if extra:
+        fuse = Lm.GemmFuse()
+        new = lambda *shape: keep.append(T.zeros(*shape, device=dev)) or keep[-1].data_ptr()
+        if extra in ("pack", "stats_pack"):
+            fuse.out_scale, fuse.out_k1, fuse.out_k2, fuse.pack_out = new(M), 1.0, 1.0, 1
+        if extra == "stats_pack":
+            fuse.stats, fuse.stat_cols = new(M, (N // 2 + 31) // 32, 2), N // 2
+        elif extra == "ln_fold":
+            fuse.ln_mean, fuse.ln_rstd, fuse.ln_c = new(M), new(M), new(N)
+        elif extra == "gmax":
+            fuse.gmax_out, fuse.gmax_ld, fuse.gmax_k = new(M // 64, N), N, 64
+        elif extra == "hyper":
+            Z, c, rows = M // 256, 4, 256
+            fuse.hyper, fuse.hyper_c, fuse.hyper_rows = new(Z, c, N), c, rows
+            fuse.masks, fuse.hyper_pstride = new(N // 64, Z * c * rows), Z * c * rows
+        elif extra == "row_ln":
+            fuse.row_ln_g, fuse.row_ln_b, fuse.row_ln_eps = new(N), new(N), 1e-6
+        elif extra == "splitk":
+            fuse.splitk_ws, fuse.splitk_plane, fuse.splitk = new(2, M * N), M * N, 2
+            from point_sam_amd import ops as o
+            keep.append(o.new_counters(dev))
+            fuse.counters = keep[-1].data_ptr()
+    _, cfg, ks = f16x3p(None, A, W, M, N, K, C, act=act, fuse=fuse)
+    T.cuda.synchronize()
+    return cfg, ks
+
+
+def dispatch_pins():
+    """{"M,N,K,act,extra": (config, split factor, psam_gemm_f16x3p_splitk(M, N, K, act))} over pin_cases()."""
+    L = _lib()
+    return {",".join(map(str, c)): _pin_launch(*c) + (L.psam_gemm_f16x3p_splitk(*c[:4]),) for c in pin_cases()}
+
+
+PINS = {      # "M,N,K,act,extra": (config, split factor, psam_gemm_f16x3p_splitk)
+    "1,3072,1024,0,None": (9, 1, 4), "1,3072,1024,3,None": (9, 1, 1), "1,3072,1024,0,splitk": (9, 2, 4), "1,1024,1024,0,None": (9, 1, 4),
+    "1,1024,1024,3,None": (9, 1, 1), "1,1024,1024,0,splitk": (9, 2, 4), "1,5504,1024,0,None": (9, 1, 4), "1,5504,1024,3,None": (9, 1, 1),
+    "1,5504,1024,0,splitk": (9, 2, 4), "1,1024,2752,0,None": (9, 1, 4), "1,1024,2752,3,None": (9, 1, 1), "1,1024,2752,0,splitk": (9, 2, 4),
+    "1,2730,1024,0,None": (9, 1, 4), "1,256,128,0,None": (9, 1, 1), "1,256,128,3,None": (9, 1, 1), "1,512,256,0,None": (9, 1, 1),
+    "1,512,256,3,None": (9, 1, 1), "1,512,256,0,splitk": (9, 2, 1), "100,3072,1024,0,None": (9, 1, 4), "100,3072,1024,3,None": (9, 1, 1),
+    "100,3072,1024,0,splitk": (9, 2, 4), "100,1024,1024,0,None": (9, 1, 4), "100,1024,1024,3,None": (9, 1, 1), "100,1024,1024,0,splitk": (9, 2, 4),
+    "100,5504,1024,0,None": (9, 1, 4), "100,5504,1024,3,None": (9, 1, 1), "100,5504,1024,0,splitk": (9, 2, 4), "100,1024,2752,0,None": (9, 1, 4),
+    "100,1024,2752,3,None": (9, 1, 1), "100,1024,2752,0,splitk": (9, 2, 4), "100,2730,1024,0,None": (9, 1, 4), "100,256,128,0,None": (9, 1, 1),
+    "100,256,128,3,None": (9, 1, 1), "100,512,256,0,None": (9, 1, 1), "100,512,256,3,None": (9, 1, 1), "100,512,256,0,splitk": (9, 2, 1),
+    "512,3072,1024,0,None": (9, 1, 1), "512,3072,1024,3,None": (9, 1, 1), "512,3072,1024,0,pack": (9, 1, 1), "512,3072,1024,3,stats_pack": (9, 1, 1),
+    "512,3072,1024,0,ln_fold": (9, 1, 1), "512,3072,1024,0,gmax": (14, 1, 1), "512,3072,1024,0,hyper": (21, 1, 1),
+    "512,3072,1024,0,splitk": (9, 2, 1), "512,1024,1024,0,None": (9, 1, 4), "512,1024,1024,3,None": (9, 1, 1), "512,1024,1024,0,pack": (9, 1, 4),
+    "512,1024,1024,3,stats_pack": (9, 1, 1), "512,1024,1024,0,ln_fold": (9, 1, 4), "512,1024,1024,0,gmax": (14, 1, 4),
+    "512,1024,1024,0,hyper": (21, 1, 4), "512,1024,1024,0,splitk": (9, 2, 4), "512,5504,1024,0,None": (9, 1, 1), "512,5504,1024,3,None": (9, 1, 1),
+    "512,5504,1024,0,pack": (9, 1, 1), "512,5504,1024,3,stats_pack": (9, 1, 1), "512,5504,1024,0,ln_fold": (9, 1, 1),
+    "512,5504,1024,0,gmax": (4, 1, 1), "512,5504,1024,0,hyper": (21, 1, 1), "512,5504,1024,0,splitk": (9, 2, 1), "512,1024,2752,0,None": (9, 1, 4),
+    "512,1024,2752,3,None": (9, 1, 1), "512,1024,2752,0,pack": (9, 1, 4), "512,1024,2752,3,stats_pack": (9, 1, 1),
+    "512,1024,2752,0,ln_fold": (9, 1, 4), "512,1024,2752,0,gmax": (14, 1, 4), "512,1024,2752,0,hyper": (21, 1, 4),
+    "512,1024,2752,0,splitk": (9, 2, 4), "512,2730,1024,0,None": (9, 1, 1), "512,256,128,0,None": (9, 1, 1), "512,256,128,3,None": (9, 1, 1),
+    "512,256,128,0,pack": (9, 1, 1), "512,256,128,3,stats_pack": (9, 1, 1), "512,256,128,0,ln_fold": (9, 1, 1), "512,256,128,0,gmax": (14, 1, 1),
+    "512,256,128,0,hyper": (21, 1, 1), "512,256,128,1,row_ln": (40, 1, 1), "512,512,256,0,None": (9, 1, 1), "512,512,256,3,None": (9, 1, 1),
+    "512,512,256,0,pack": (9, 1, 1), "512,512,256,3,stats_pack": (9, 1, 1), "512,512,256,0,ln_fold": (9, 1, 1), "512,512,256,0,gmax": (14, 1, 1),
+    "512,512,256,0,hyper": (21, 1, 1), "512,512,256,0,splitk": (9, 2, 1), "1000,3072,1024,0,None": (9, 1, 1), "1000,3072,1024,3,None": (9, 1, 1),
+    "1000,3072,1024,0,splitk": (9, 2, 1), "1000,1024,1024,0,None": (9, 1, 4), "1000,1024,1024,3,None": (9, 1, 1),
+    "1000,1024,1024,0,splitk": (9, 2, 4), "1000,5504,1024,0,None": (21, 1, 1), "1000,5504,1024,3,None": (21, 1, 1),
+    "1000,5504,1024,0,splitk": (21, 2, 1), "1000,1024,2752,0,None": (9, 1, 4), "1000,1024,2752,3,None": (9, 1, 1),
+    "1000,1024,2752,0,splitk": (9, 2, 4), "1000,2730,1024,0,None": (9, 1, 1), "1000,256,128,0,None": (9, 1, 1), "1000,256,128,3,None": (9, 1, 1),
+    "1000,512,256,0,None": (9, 1, 1), "1000,512,256,3,None": (9, 1, 1), "1000,512,256,0,splitk": (9, 2, 1), "2047,3072,1024,0,None": (21, 1, 1),
+    "2047,3072,1024,3,None": (21, 1, 1), "2047,3072,1024,0,splitk": (21, 2, 1), "2047,1024,1024,0,None": (9, 1, 1),
+    "2047,1024,1024,3,None": (9, 1, 1), "2047,1024,1024,0,splitk": (9, 2, 1), "2047,5504,1024,0,None": (23, 1, 1),
+    "2047,5504,1024,3,None": (9, 1, 1), "2047,5504,1024,0,splitk": (23, 2, 1), "2047,1024,2752,0,None": (9, 1, 1),
+    "2047,1024,2752,3,None": (9, 1, 1), "2047,1024,2752,0,splitk": (9, 2, 1), "2047,2730,1024,0,None": (21, 1, 1), "2047,256,128,0,None": (9, 1, 1),
+    "2047,256,128,3,None": (9, 1, 1), "2047,512,256,0,None": (9, 1, 1), "2047,512,256,3,None": (9, 1, 1), "2047,512,256,0,splitk": (9, 2, 1),
+    "2048,3072,1024,0,None": (21, 1, 1), "2048,3072,1024,3,None": (21, 1, 1), "2048,3072,1024,0,pack": (21, 1, 1),
+    "2048,3072,1024,3,stats_pack": (21, 1, 1), "2048,3072,1024,0,ln_fold": (21, 1, 1), "2048,3072,1024,0,gmax": (21, 1, 1),
+    "2048,3072,1024,0,hyper": (21, 1, 1), "2048,3072,1024,0,splitk": (21, 2, 1), "2048,1024,1024,0,None": (28, 1, 4),
+    "2048,1024,1024,3,None": (28, 1, 1), "2048,1024,1024,0,pack": (28, 1, 4), "2048,1024,1024,3,stats_pack": (28, 1, 1),
+    "2048,1024,1024,0,ln_fold": (28, 1, 4), "2048,1024,1024,0,gmax": (14, 1, 4), "2048,1024,1024,0,hyper": (21, 1, 4),
+    "2048,1024,1024,0,splitk": (28, 2, 4), "2048,5504,1024,0,None": (23, 1, 1), "2048,5504,1024,3,None": (28, 1, 1),
+    "2048,5504,1024,0,pack": (28, 1, 1), "2048,5504,1024,3,stats_pack": (28, 1, 1), "2048,5504,1024,0,ln_fold": (28, 1, 1),
+    "2048,5504,1024,0,gmax": (4, 1, 1), "2048,5504,1024,0,hyper": (21, 1, 1), "2048,5504,1024,0,splitk": (23, 2, 1),
+    "2048,1024,2752,0,None": (28, 1, 4), "2048,1024,2752,3,None": (28, 1, 1), "2048,1024,2752,0,pack": (28, 1, 4),
+    "2048,1024,2752,3,stats_pack": (28, 1, 1), "2048,1024,2752,0,ln_fold": (28, 1, 4), "2048,1024,2752,0,gmax": (14, 1, 4),
+    "2048,1024,2752,0,hyper": (21, 1, 4), "2048,1024,2752,0,splitk": (28, 2, 4), "2048,2730,1024,0,None": (21, 1, 1),
+    "2048,256,128,0,None": (28, 1, 1), "2048,256,128,3,None": (28, 1, 1), "2048,256,128,0,pack": (28, 1, 1), "2048,256,128,3,stats_pack": (28, 1, 1),
+    "2048,256,128,0,ln_fold": (28, 1, 1), "2048,256,128,0,gmax": (14, 1, 1), "2048,256,128,0,hyper": (21, 1, 1), "2048,256,128,1,row_ln": (40, 1, 1),
+    "2048,512,256,0,None": (28, 1, 1), "2048,512,256,3,None": (28, 1, 1), "2048,512,256,0,pack": (28, 1, 1), "2048,512,256,3,stats_pack": (28, 1, 1),
+    "2048,512,256,0,ln_fold": (28, 1, 1), "2048,512,256,0,gmax": (14, 1, 1), "2048,512,256,0,hyper": (21, 1, 1), "2048,512,256,0,splitk": (28, 2, 1),
+    "4096,3072,1024,0,None": (21, 1, 1), "4096,3072,1024,3,None": (21, 1, 1), "4096,3072,1024,0,pack": (21, 1, 1),
+    "4096,3072,1024,3,stats_pack": (21, 1, 1), "4096,3072,1024,0,ln_fold": (21, 1, 1), "4096,3072,1024,0,gmax": (21, 1, 1),
+    "4096,3072,1024,0,hyper": (21, 1, 1), "4096,3072,1024,0,splitk": (21, 2, 1), "4096,1024,1024,0,None": (21, 1, 1),
+    "4096,1024,1024,3,None": (21, 1, 1), "4096,1024,1024,0,pack": (21, 1, 1), "4096,1024,1024,3,stats_pack": (21, 1, 1),
+    "4096,1024,1024,0,ln_fold": (21, 1, 1), "4096,1024,1024,0,gmax": (21, 1, 1), "4096,1024,1024,0,hyper": (21, 1, 1),
+    "4096,1024,1024,0,splitk": (21, 2, 1), "4096,5504,1024,0,None": (21, 1, 1), "4096,5504,1024,3,None": (21, 1, 1),
+    "4096,5504,1024,0,pack": (21, 1, 1), "4096,5504,1024,3,stats_pack": (21, 1, 1), "4096,5504,1024,0,ln_fold": (21, 1, 1),
+    "4096,5504,1024,0,gmax": (21, 1, 1), "4096,5504,1024,0,hyper": (21, 1, 1), "4096,5504,1024,0,splitk": (21, 2, 1),
+    "4096,1024,2752,0,None": (21, 1, 1), "4096,1024,2752,3,None": (21, 1, 1), "4096,1024,2752,0,pack": (21, 1, 1),
+    "4096,1024,2752,3,stats_pack": (21, 1, 1), "4096,1024,2752,0,ln_fold": (21, 1, 1), "4096,1024,2752,0,gmax": (21, 1, 1),
+    "4096,1024,2752,0,hyper": (21, 1, 1), "4096,1024,2752,0,splitk": (21, 2, 1), "4096,2730,1024,0,None": (23, 1, 1),
+    "4096,256,128,0,None": (28, 1, 1), "4096,256,128,3,None": (28, 1, 1), "4096,256,128,0,pack": (28, 1, 1), "4096,256,128,3,stats_pack": (28, 1, 1),
+    "4096,256,128,0,ln_fold": (28, 1, 1), "4096,256,128,0,gmax": (14, 1, 1), "4096,256,128,0,hyper": (21, 1, 1), "4096,256,128,1,row_ln": (40, 1, 1),
+    "4096,512,256,0,None": (28, 1, 1), "4096,512,256,3,None": (28, 1, 1), "4096,512,256,0,pack": (28, 1, 1), "4096,512,256,3,stats_pack": (28, 1, 1),
+    "4096,512,256,0,ln_fold": (28, 1, 1), "4096,512,256,0,gmax": (14, 1, 1), "4096,512,256,0,hyper": (21, 1, 1), "4096,512,256,0,splitk": (28, 2, 1),
+    "32768,3072,1024,0,None": (21, 1, 1), "32768,3072,1024,3,None": (21, 1, 1), "32768,1024,1024,0,None": (21, 1, 1),
+    "32768,1024,1024,3,None": (21, 1, 1), "32768,5504,1024,0,None": (21, 1, 1), "32768,5504,1024,3,None": (21, 1, 1),
+    "32768,1024,2752,0,None": (21, 1, 1), "32768,1024,2752,3,None": (21, 1, 1), "32768,2730,1024,0,None": (21, 1, 1),
+    "32768,256,128,0,None": (28, 1, 1), "32768,256,128,3,None": (28, 1, 1), "32768,256,128,0,pack": (28, 1, 1),
+    "32768,256,128,3,stats_pack": (28, 1, 1), "32768,256,128,0,ln_fold": (28, 1, 1), "32768,256,128,0,gmax": (14, 1, 1),
+    "32768,256,128,0,hyper": (21, 1, 1), "32768,256,128,1,row_ln": (40, 1, 1), "32768,512,256,0,None": (21, 1, 1),
+    "32768,512,256,3,None": (21, 1, 1), "32768,512,256,0,pack": (21, 1, 1), "32768,512,256,3,stats_pack": (21, 1, 1),
+    "32768,512,256,0,ln_fold": (21, 1, 1), "32768,512,256,0,gmax": (21, 1, 1), "32768,512,256,0,hyper": (21, 1, 1),
+    "65536,3072,1024,0,None": (21, 1, 1), "65536,3072,1024,3,None": (21, 1, 1), "65536,1024,1024,0,None": (21, 1, 1),
+    "65536,1024,1024,3,None": (21, 1, 1), "65536,5504,1024,0,None": (21, 1, 1), "65536,5504,1024,3,None": (21, 1, 1),
+    "65536,1024,2752,0,None": (21, 1, 1), "65536,1024,2752,3,None": (21, 1, 1), "65536,2730,1024,0,None": (21, 1, 1),
+    "65536,256,128,0,None": (21, 1, 1), "65536,256,128,3,None": (21, 1, 1), "65536,256,128,0,pack": (21, 1, 1),
+    "65536,256,128,3,stats_pack": (21, 1, 1), "65536,256,128,0,ln_fold": (21, 1, 1), "65536,256,128,0,gmax": (21, 1, 1),
+    "65536,256,128,0,hyper": (21, 1, 1), "65536,256,128,1,row_ln": (40, 1, 1), "65536,512,256,0,None": (21, 1, 1),
+    "65536,512,256,3,None": (21, 1, 1),
+}
+
+
+@pytest.mark.gpu
+def test_dispatch_pins(ops):
+    """Every pinned launch runs the configuration and split factor it ran before, and the split-K suggestion for its shape is unchanged."""
+    got = dispatch_pins()
+    assert set(got) == set(PINS), set(got) ^ set(PINS)
+    bad = {k: (v, PINS[k]) for k, v in got.items() if v != PINS[k]}
     assert not bad, bad
 
 

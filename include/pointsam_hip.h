@@ -554,6 +554,33 @@ int32_t psam_interp3(const float* src, const int64_t* idx3, const float* w3, flo
 int32_t psam_interp3_ex(const float* src, const int64_t* idx3, const float* w3, float* out, int32_t rep, int64_t Z, int32_t N, int32_t G, int32_t C,
                         float* scale_out, const float* ln_gamma, const float* ln_beta, float ln_eps, int32_t act, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- mask proposals */
+
+/* Automatic mask proposals (point_sam_amd/proposals.py): the post-processing of K candidate masks of one cloud.  A mask is a row of
+ * W = ceil(N / 64) 64-bit words: bit (n % 64) of word (n / 64) is point n, bits past N are zero.  All counts are exact integers.
+ *
+ * psam_mask_pack: rows [K, N] of logits (row stride ld floats) -> rows dst_row .. dst_row + K - 1 of bits [*, W] and of the three areas:
+ *   bit = logit > thr (fp32 compare, NaN is false); area_hi / area_lo count logit > fl32(thr + off) / logit > fl32(thr - off). */
+int32_t psam_mask_pack(const float* logits, int64_t ld, int32_t K, int32_t N, float thr, float off, int32_t dst_row, uint64_t* bits,
+                       int32_t* area, int32_t* area_hi, int32_t* area_lo, psam_stream_t stream);
+/* valid[k] = area >= min_points && (double)area < (double)max_area_frac * N && score >= pred_iou_thr (NaN false) && area_lo > 0 &&
+ *   (double)area_hi >= (double)stab_thr * (double)area_lo. */
+int32_t psam_mask_valid(const int32_t* area, const int32_t* area_hi, const int32_t* area_lo, const float* score, int32_t K, int32_t N,
+                        int32_t min_points, float max_area_frac, float pred_iou_thr, float stab_thr, uint8_t* valid, psam_stream_t stream);
+/* inter [Ka, Kb] int32 = popcount(a_i & b_j); a [Ka, W], b [Kb, W].  a == b (same pointer, Ka == Kb): the upper triangle is computed and mirrored. */
+int32_t psam_mask_intersections(const uint64_t* a, const uint64_t* b, int32_t Ka, int32_t Kb, int32_t W, int32_t* inter, psam_stream_t stream);
+/* Greedy non-maximum suppression on the device.  order [K] = a permutation of the candidates, best first; candidate i (taken in order) is kept
+ * iff valid[i] and no already kept j has (double)inter[i,j] > (double)iou_thr * (double)(area[i] + area[j] - inter[i,j]).  keep [K] uint8.
+ * K <= 16384; ws: psam_mask_nms_workspace_bytes(K) bytes, 8-byte aligned. */
+size_t psam_mask_nms_workspace_bytes(int32_t K);
+int32_t psam_mask_nms(const int32_t* order, const uint8_t* valid, const int32_t* area, const int32_t* inter, int32_t K, float iou_thr,
+                      uint8_t* keep, void* ws, size_t ws_bytes, psam_stream_t stream);
+/* labels [N] int32 = the rank (0, 1, ... among the kept masks in `order`) of the best kept mask that contains the point, -1 if none.
+ * ws: psam_mask_paint_workspace_bytes(K) bytes, 4-byte aligned. */
+size_t psam_mask_paint_workspace_bytes(int32_t K);
+int32_t psam_mask_paint(const uint64_t* bits, const int32_t* order, const uint8_t* keep, int32_t K, int32_t N, int32_t* labels, void* ws,
+                        size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

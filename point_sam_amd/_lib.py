@@ -114,6 +114,13 @@ SIGNATURES = {
     "psam_add_bcast": (i32, [ptr, i64, i32, ptr, i64, i64, ptr, i64, i64, i64, i32, ptr]),
     "psam_interp3": (i32, [ptr, ptr, ptr, ptr, i32, i64, i32, i32, i32, ptr]),
     "psam_interp3_ex": (i32, [ptr, ptr, ptr, ptr, i32, i64, i32, i32, i32, ptr, ptr, ptr, f32, i32, ptr]),
+    "psam_mask_pack": (i32, [ptr, i64, i32, i32, f32, f32, i32, ptr, ptr, ptr, ptr, ptr]),
+    "psam_mask_valid": (i32, [ptr, ptr, ptr, ptr, i32, i32, i32, f32, f32, f32, ptr, ptr]),
+    "psam_mask_intersections": (i32, [ptr, ptr, i32, i32, i32, ptr, ptr]),
+    "psam_mask_nms_workspace_bytes": (size_t, [i32]),
+    "psam_mask_nms": (i32, [ptr, ptr, ptr, ptr, i32, f32, ptr, ptr, size_t, ptr]),
+    "psam_mask_paint_workspace_bytes": (size_t, [i32]),
+    "psam_mask_paint": (i32, [ptr, ptr, ptr, i32, i32, ptr, ptr, size_t, ptr]),
 }
 
 

@@ -29,6 +29,7 @@ SOURCES = [
     ("attention.hip", []),
     ("rowops.hip", []),
     ("blocks.hip", []),
+    ("masks.hip", []),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

@@ -10,6 +10,7 @@ so the reference's front end talks to this server unchanged with no second file 
 Routes (reference line):  GET / (app.py:71-73: index.html) . GET /static/<path> (:76-78) . GET /mesh/<path> (:81-89: models/<path>)
 POST /sampled_pointcloud (app.py:92-108) . GET /pointcloud/<name> (:111-141) . POST /clear (:144-150)
 POST /next (:153-159) . POST /save (:162-175) . POST /segment (:177-206).
+POST /segment_all (not in the reference): automatic mask proposals for the whole cloud, a first pass before the per-object clicks.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -44,7 +45,8 @@ def safe_join(root: str, rel: str) -> str:
 
 class DemoSession:
     """The demo's state machine.  ``predictor`` needs ``set_pointcloud(xyz, rgb)`` and
-    ``predict_masks(points, labels, prompt_mask, multimask_output) -> (mask, scores, logits)``."""
+    ``predict_masks(points, labels, prompt_mask, multimask_output) -> (mask, scores, logits)``; ``/segment_all`` also needs
+    ``generate_masks(cfg) -> [Proposals]``."""
 
     def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None):
         self.predictor = predictor
@@ -145,6 +147,22 @@ class DemoSession:
             self.segment_mask = mask[0][best] > 0
             return {"seg": self.segment_mask.cpu().numpy().tolist()}
 
+    def segment_all(self, data: dict) -> dict:
+        """"Segment everything": automatic mask proposals on the current cloud.  Optional body keys override `ProposalConfig` fields (an unknown key
+        or a bad value is a ValueError -> 400).  {"labels": [N ints, -1 = none], "num_masks": k, "scores": [k floats]}, masks best first.  The
+        click state of /segment is not touched."""
+        from .proposals import ProposalConfig
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/segment_all before a point cloud was set")
+            if not isinstance(data, dict):
+                raise ValueError("/segment_all takes a JSON object of ProposalConfig overrides (or nothing)")
+            cfg = ProposalConfig.from_overrides(data)
+            with torch.no_grad():
+                self.predictor.set_pointcloud(self.pc_xyz, self.pc_rgb)
+                prop = self.predictor.generate_masks(cfg)[0]
+            return {"labels": prop.labels.cpu().numpy().astype(int).tolist(), "num_masks": int(len(prop)), "scores": prop.score.cpu().numpy().astype(float).tolist()}
+
 
 MAX_BODY_BYTES = 64 << 20      # a sampled 10^5-point cloud as JSON is a few MB
 
@@ -209,6 +227,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
             except json.JSONDecodeError as e:
                 return self._send(400, {"error": f"bad JSON: {e}"})
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
+                      "/segment_all": lambda: session.segment_all(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}
             fn = routes.get(self.path)
             if fn is None:

@@ -224,3 +224,24 @@ def evaluate_crop_files(model, paths: Iterable[str], rotate: bool = True) -> Dic
     paths = list(paths)
     samples = (crop_to_sample(load_labelled_crop(p, rotate)) for p in paths)
     return evaluate_clouds(model, samples, adapt_grouper=True, names=[os.path.basename(p).split("_")[0] for p in paths])
+
+
+def proposal_recall(proposals, gt_masks: torch.Tensor, iou_thresholds=(0.25, 0.5, 0.75)) -> Dict[str, np.ndarray]:
+    """How well automatic proposals (point_sam_amd/proposals.py) cover ground-truth instances: for each ground-truth mask the best IoU over the
+    kept proposals, and the share of ground-truth masks reached at each threshold.  proposals: a `Proposals` (its `bits` [k, W] and `area` [k]);
+    gt_masks [M, N] bool.  The ground truth is bit-packed like the proposals and the IoUs come from the integer intersection counts (exact)."""
+    from . import ops
+    gt = gt_masks.to(proposals.bits.device)
+    M, N = gt.shape
+    if N != proposals.n_points:
+        raise ValueError(f"ground truth has {N} points, the proposals {proposals.n_points}")
+    thr = np.asarray(list(iou_thresholds), dtype=np.float64)
+    if M == 0 or len(proposals) == 0:
+        best = np.zeros(M, dtype=np.float64)
+    else:
+        logits = torch.where(gt.bool(), 1.0, -1.0).to(torch.float32).contiguous()
+        gt_bits, gt_area, _, _ = ops.mask_pack(logits, 0.0, 0.5)
+        inter = ops.mask_intersections(gt_bits, proposals.bits.contiguous()).cpu().numpy().astype(np.int64)
+        union = gt_area.cpu().numpy().astype(np.int64)[:, None] + proposals.area.cpu().numpy().astype(np.int64)[None, :] - inter
+        best = (inter / np.maximum(union, 1)).max(axis=1)
+    return {"best_iou": best, "iou_thresholds": thr, "recall": np.array([(best >= t).mean() if M else 0.0 for t in thr], dtype=np.float64)}

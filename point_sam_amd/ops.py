@@ -1106,3 +1106,99 @@ def border_farthest(xyz: torch.Tensor, region: torch.Tensor):
     check(L.psam_border_farthest(xyz.data_ptr(), region.data_ptr(), B, Z // B, N, idx.data_ptr(), dist.data_ptr(), ws.data_ptr(), nbytes, _stream()),
           "psam_border_farthest")
     return idx, dist
+
+
+# ------------------------------------------------------------------------------------------ mask proposals (csrc/masks.hip)
+# A mask is a row of W = ceil(N / 64) 64-bit words (bit n % 64 of word n / 64 is point n, bits past N are zero).  The words travel as torch.int64:
+# same bits as the library's uint64_t, and indexing / comparison / shifts exist for that dtype on every torch build.
+def mask_words(N: int) -> int:
+    return (N + 63) // 64
+
+
+def mask_pack(logits: torch.Tensor, thr: float = 0.0, off: float = 1.0, out=None, row: int = 0):
+    """logits [K, N] f32 (or [Z, C, N], rows K = Z * C) -> (bits [K, W] int64, area, area_hi, area_lo [K] int32): bit = logit > thr (NaN false);
+    area_hi / area_lo count logit > fl32(thr + off) / logit > fl32(thr - off).  out = (bits, area, area_hi, area_lo) of a larger buffer and
+    `row`: the K rows land at rows row .. row + K - 1 of it (chunks of one cloud's candidates)."""
+    _chk(logits, name="logits")
+    N = logits.shape[-1]
+    K = logits.numel() // max(N, 1)
+    W = mask_words(N)
+    if out is None:
+        if row != 0:
+            raise ValueError("mask_pack: a destination row needs the destination buffers (out=)")
+        out = (torch.empty(K, W, dtype=torch.int64, device=logits.device),) + tuple(torch.empty(K, dtype=torch.int32, device=logits.device) for _ in range(3))
+    bits, area, area_hi, area_lo = out
+    _chk(bits, torch.int64, "bits")
+    for t in (area, area_hi, area_lo):
+        _chk(t, torch.int32, "area")
+    if bits.dim() != 2 or bits.shape[1] != W or row < 0 or row + K > bits.shape[0] or min(area.numel(), area_hi.numel(), area_lo.numel()) < bits.shape[0]:
+        raise ValueError(f"mask_pack: rows {row} .. {row + K - 1} of width {W} do not fit bits {tuple(bits.shape)} / areas [{area.numel()}]")
+    check(_lib.load().psam_mask_pack(logits.data_ptr(), N, K, N, float(thr), float(off), row, bits.data_ptr(), area.data_ptr(), area_hi.data_ptr(),
+                                     area_lo.data_ptr(), _stream()), "psam_mask_pack")
+    return bits, area, area_hi, area_lo
+
+
+def mask_valid(area, area_hi, area_lo, score, N: int, min_points: int, max_area_frac: float, pred_iou_thr: float, stab_thr: float) -> torch.Tensor:
+    """-> valid [K] uint8: area >= min_points, area < max_area_frac * N, score >= pred_iou_thr (NaN false), area_lo > 0 and
+    area_hi >= stab_thr * area_lo (products in fp64: exact)."""
+    for t in (area, area_hi, area_lo):
+        _chk(t, torch.int32, "area")
+    _chk(score, name="score")
+    K = area.numel()
+    if not (area_hi.numel() == area_lo.numel() == score.numel() == K):
+        raise ValueError("mask_valid: the areas and the scores must have one entry per candidate")
+    valid = torch.empty(K, dtype=torch.uint8, device=area.device)
+    check(_lib.load().psam_mask_valid(area.data_ptr(), area_hi.data_ptr(), area_lo.data_ptr(), score.data_ptr(), K, N, int(min_points),
+                                      float(max_area_frac), float(pred_iou_thr), float(stab_thr), valid.data_ptr(), _stream()), "psam_mask_valid")
+    return valid
+
+
+def mask_intersections(a: torch.Tensor, b: torch.Tensor = None) -> torch.Tensor:
+    """a [Ka, W], b [Kb, W] int64 words -> inter [Ka, Kb] int32 = popcount(a_i & b_j).  b None (or the same tensor): a against itself, the upper
+    triangle computed and mirrored."""
+    _chk(a, torch.int64, "a")
+    b = a if b is None else _chk(b, torch.int64, "b")
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError(f"mask_intersections: {tuple(a.shape)} against {tuple(b.shape)}")
+    inter = torch.empty(a.shape[0], b.shape[0], dtype=torch.int32, device=a.device)
+    check(_lib.load().psam_mask_intersections(a.data_ptr(), b.data_ptr(), a.shape[0], b.shape[0], a.shape[1], inter.data_ptr(), _stream()),
+          "psam_mask_intersections")
+    return inter
+
+
+def mask_nms(order, valid, area, inter, iou_thr: float) -> torch.Tensor:
+    """Greedy suppression on the device: order [K] int32 (a permutation, best first), valid [K] uint8, area [K] int32, inter [K, K] int32 ->
+    keep [K] uint8.  Candidate i is kept iff valid[i] and no already kept j has inter_ij > iou_thr * (area_i + area_j - inter_ij) (fp64)."""
+    _chk(order, torch.int32, "order"); _chk(valid, torch.uint8, "valid"); _chk(area, torch.int32, "area"); _chk(inter, torch.int32, "inter")
+    K = order.numel()
+    if valid.numel() != K or area.numel() != K or tuple(inter.shape) != (K, K):
+        raise ValueError(f"mask_nms: K = {K}, valid [{valid.numel()}], area [{area.numel()}], inter {tuple(inter.shape)}")
+    L = _lib.load()
+    nbytes = L.psam_mask_nms_workspace_bytes(K)
+    ws = torch.empty(max(nbytes, 16) // 8 + 1, dtype=torch.int64, device=order.device)
+    keep = torch.empty(K, dtype=torch.uint8, device=order.device)
+    check(L.psam_mask_nms(order.data_ptr(), valid.data_ptr(), area.data_ptr(), inter.data_ptr(), K, float(iou_thr), keep.data_ptr(), ws.data_ptr(),
+                          ws.numel() * 8, _stream()), "psam_mask_nms")
+    return keep
+
+
+def mask_paint(bits, order, keep, N: int) -> torch.Tensor:
+    """bits [K, W], order [K] int32, keep [K] uint8 -> labels [N] int32: the rank (0 = best, among the kept masks in `order`) of the best kept mask
+    that contains the point, -1 where none does."""
+    _chk(bits, torch.int64, "bits"); _chk(order, torch.int32, "order"); _chk(keep, torch.uint8, "keep")
+    K = order.numel()
+    if bits.dim() != 2 or bits.shape[0] != K or bits.shape[1] != mask_words(N) or keep.numel() != K:
+        raise ValueError(f"mask_paint: K = {K}, N = {N}, bits {tuple(bits.shape)}, keep [{keep.numel()}]")
+    L = _lib.load()
+    nbytes = L.psam_mask_paint_workspace_bytes(K)
+    ws = torch.empty(max(nbytes, 16) // 4 + 1, dtype=torch.int32, device=bits.device)
+    labels = torch.empty(N, dtype=torch.int32, device=bits.device)
+    check(L.psam_mask_paint(bits.data_ptr(), order.data_ptr(), keep.data_ptr(), K, N, labels.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream()),
+          "psam_mask_paint")
+    return labels
+
+
+def mask_unpack(bits: torch.Tensor, N: int) -> torch.Tensor:
+    """bits [k, W] int64 words -> [k, N] bool (plain torch; for inspection and tests, not on a hot path)."""
+    sh = torch.arange(64, device=bits.device, dtype=torch.int64)
+    return ((bits.unsqueeze(-1) >> sh) & 1).to(torch.bool).reshape(bits.shape[0], -1)[:, :N]

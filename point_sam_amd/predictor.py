@@ -66,3 +66,13 @@ class PointSAMPredictor:
         logits, scores = self.model.decode(self._state, prompt_points, prompt_labels, prompt_mask, multimask_output)
         self.model.check_coordinate_range()
         return logits, scores, logits
+
+    @torch.no_grad()
+    def generate_masks(self, cfg=None):
+        """Automatic mask proposals for the cached cloud(s), no prompts needed (point_sam_amd/proposals.py): a list with one `Proposals` per
+        cloud -- kept masks best first, bit-packed, and one instance label per point.  cfg: a `ProposalConfig` (None = its defaults).
+        Works for every model variant (voronoi, hierarchical): only the public `decode` is called, with single-point prompts and no mask prompt."""
+        if self._state is None:
+            raise RuntimeError("call set_pointcloud() first")
+        from .proposals import generate_proposals
+        return generate_proposals(self.model, self._state, cfg)

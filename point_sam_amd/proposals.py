@@ -1,0 +1,164 @@
+"""Automatic mask proposals: segment a whole cloud with no prompts from a person.
+
+The SAM recipe on the cached encoder state: a grid of prompt points (farthest point sampling, as Point-SAM's zero-shot object proposals),
+three candidate masks per prompt from the existing ``decode``, a filter on predicted IoU and on stability, greedy non-maximum suppression
+on mask IoU, one instance label per point.  Everything after the logits runs on bit-packed masks (``csrc/masks.hip``: 64 points per
+64-bit word, and + popcount), so every count is an exact integer, and on the device: the host synchronises once per cloud, after the last
+kernel, to compact the kept rows.
+
+    state = model.encode(xyz, rgb)
+    for p in generate_proposals(model, state, ProposalConfig(num_prompts=1024)):
+        p.labels            # [N] int32: rank of the best kept mask containing the point, -1 = unlabelled
+        p.masks()           # [k, N] bool, best first
+"""
+import dataclasses
+import math
+from dataclasses import dataclass
+from typing import List
+
+import torch
+
+from . import ops
+
+MAX_CANDIDATES = 16384      # psam_mask_nms (the walk keeps the removed set in one wave's registers)
+
+
+@dataclass
+class ProposalConfig:
+    """Defaults: ``pred_iou_thresh`` 0.88, ``stability_thresh`` 0.95, ``stability_offset`` 1.0 and ``nms_thresh`` 0.7 are the published defaults of
+    SAM's automatic mask generator, whose IoU head and stability score Point-SAM's decoder mirrors; they have NOT been tuned on a trained Point-SAM
+    checkpoint.  ``min_points`` / ``max_area_frac`` are the reference's own instance filter (at least 25 points, under 90 % of the cloud).  With random
+    weights nearly every candidate fails the two score cuts: set them to 0 to see the machinery work."""
+    num_prompts: int = 1024        # FPS-sampled prompt points per cloud
+    prompt_chunk: int = 64         # prompts per decode() call and cloud
+    mask_threshold: float = 0.0
+    pred_iou_thresh: float = 0.88
+    stability_thresh: float = 0.95
+    stability_offset: float = 1.0
+    nms_thresh: float = 0.7
+    min_points: int = 25
+    max_area_frac: float = 0.9
+
+    def validate(self) -> "ProposalConfig":
+        for name in ("num_prompts", "prompt_chunk", "min_points"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise ValueError(f"ProposalConfig.{name} must be an integer, got {v!r}")
+        for name in ("mask_threshold", "pred_iou_thresh", "stability_thresh", "stability_offset", "nms_thresh", "max_area_frac"):
+            v = getattr(self, name)
+            # the three cuts may be infinite (-inf = no cut); everything else is finite
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or (
+                    math.isinf(v) and name not in ("mask_threshold", "pred_iou_thresh", "stability_thresh")):
+                raise ValueError(f"ProposalConfig.{name} must be a number (finite, except the three thresholds), got {v!r}")
+        if self.num_prompts < 1 or self.prompt_chunk < 1:
+            raise ValueError("ProposalConfig: num_prompts and prompt_chunk must be at least 1")
+        if self.min_points < 0 or self.stability_offset < 0 or self.max_area_frac <= 0:
+            raise ValueError("ProposalConfig: min_points and stability_offset must not be negative, max_area_frac must be positive")
+        if not 0.0 <= self.nms_thresh <= 1.0:
+            raise ValueError(f"ProposalConfig.nms_thresh is an IoU: it must lie in [0, 1], got {self.nms_thresh}")
+        return self
+
+    @classmethod
+    def from_overrides(cls, overrides: dict) -> "ProposalConfig":
+        """The defaults with the given fields replaced; an unknown field is a ValueError (the demo's 400)."""
+        names = {f.name for f in dataclasses.fields(cls)}
+        unknown = sorted(set(overrides) - names)
+        if unknown:
+            raise ValueError(f"unknown ProposalConfig field(s) {unknown}; known: {sorted(names)}")
+        return cls(**overrides).validate()
+
+
+@dataclass
+class DeviceProposals:
+    """One cloud's candidates and decisions, all on the device and not yet compacted (nothing here has synchronised with the host)."""
+    n_points: int
+    masks_per_prompt: int
+    bits: torch.Tensor          # [K, W] int64 words
+    score: torch.Tensor         # [K] f32: the decoder's IoU prediction
+    area: torch.Tensor          # [K] int32 at mask_threshold
+    area_hi: torch.Tensor       # [K] int32 at mask_threshold + stability_offset
+    area_lo: torch.Tensor       # [K] int32 at mask_threshold - stability_offset
+    order: torch.Tensor         # [K] int32: candidates by descending score, ties by index
+    valid: torch.Tensor         # [K] uint8
+    keep: torch.Tensor          # [K] uint8
+    labels: torch.Tensor        # [N] int32
+
+
+@dataclass
+class Proposals:
+    """The kept masks of one cloud, best first.  All tensors live on the device."""
+    n_points: int
+    bits: torch.Tensor          # [k, W] int64: 64 points per word (the library's uint64_t words, carried as torch.int64)
+    candidate: torch.Tensor     # [k] int64: masks_per_prompt * prompt + mask
+    prompt_index: torch.Tensor  # [k] int64
+    score: torch.Tensor         # [k] f32
+    area: torch.Tensor          # [k] int32
+    stability: torch.Tensor     # [k] f32: area_hi / area_lo
+    labels: torch.Tensor        # [N] int32: row of the best kept mask that contains the point, -1 if none
+
+    def __len__(self) -> int:
+        return self.bits.shape[0]
+
+    def masks(self) -> torch.Tensor:
+        """[k, N] bool, unpacked on demand."""
+        return ops.mask_unpack(self.bits, self.n_points)
+
+
+@torch.no_grad()
+def propose_on_device(model, state, cfg: ProposalConfig) -> List[DeviceProposals]:
+    """Every kernel of generate_proposals, no host synchronisation: capturable in a HIP graph."""
+    cfg.validate()
+    coords = state.coords
+    B, N, _ = coords.shape
+    P, chunk = cfg.num_prompts, cfg.prompt_chunk
+    if P > N:
+        raise ValueError(f"num_prompts {P} exceeds the cloud's {N} points")
+    dev = coords.device
+    _, prompts = ops.fps(coords, P)                       # [B, P, 3]; FPS from index 0, the tokenizer's own sampler
+    bufs, scores, C = None, None, None
+    for m0 in range(0, P, chunk):
+        c = min(chunk, P - m0)
+        pts = prompts[:, m0:m0 + c].reshape(B * c, 1, 3)  # cloud-major: row = b * c + m
+        logits, iou = model.decode(state, pts, torch.ones(B * c, 1, dtype=torch.int64, device=dev), None, True)
+        if bufs is None:
+            C = logits.shape[1]
+            K = C * P
+            if K > MAX_CANDIDATES:
+                raise ValueError(f"{K} candidates per cloud ({P} prompts x {C} masks) exceed {MAX_CANDIDATES}")
+            W = ops.mask_words(N)
+            bufs = [(torch.empty(K, W, dtype=torch.int64, device=dev),) + tuple(torch.empty(K, dtype=torch.int32, device=dev) for _ in range(3))
+                    for _ in range(B)]
+            scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        for b in range(B):      # cloud b's [c, C, N] slice of the chunk -> rows C * m0 .. of its bit buffer; the logits are dropped after this
+            ops.mask_pack(logits[b * c:(b + 1) * c], cfg.mask_threshold, cfg.stability_offset, out=bufs[b], row=C * m0)
+        scores[:, C * m0:C * (m0 + c)] = iou.reshape(B, c * C)
+        del logits, iou
+    out = []
+    for b in range(B):
+        bits, area, area_hi, area_lo = bufs[b]
+        score = scores[b]
+        order = torch.sort(score, descending=True, stable=True).indices.to(torch.int32)
+        valid = ops.mask_valid(area, area_hi, area_lo, score, N, cfg.min_points, cfg.max_area_frac, cfg.pred_iou_thresh, cfg.stability_thresh)
+        inter = ops.mask_intersections(bits)
+        keep = ops.mask_nms(order, valid, area, inter, cfg.nms_thresh)
+        labels = ops.mask_paint(bits, order, keep, N)
+        out.append(DeviceProposals(N, C, bits, score, area, area_hi, area_lo, order, valid, keep, labels))
+    return out
+
+
+def compact(d: DeviceProposals) -> Proposals:
+    """The kept rows, best first.  The boolean index is the one host synchronisation of a cloud."""
+    order = d.order.long()
+    cand = order[d.keep[order].bool()]
+    return Proposals(d.n_points, d.bits[cand], cand, cand // d.masks_per_prompt, d.score[cand], d.area[cand],
+                     d.area_hi[cand].float() / d.area_lo[cand].float(), d.labels)
+
+
+@torch.no_grad()
+def generate_proposals(model, state, cfg: ProposalConfig = None) -> List[Proposals]:
+    """One `Proposals` per cloud of the encoder state.  Peak memory: one chunk of logits ([B * prompt_chunk, 3, N] f32), K * N / 8 bytes of
+    bits and the K x K int32 intersection matrix per cloud (K = 3 * num_prompts) -- never K * N floats."""
+    dev = propose_on_device(model, state, cfg or ProposalConfig())
+    out = [compact(d) for d in dev]
+    model.check_coordinate_range()
+    return out

@@ -173,6 +173,12 @@ void psam_gemm_f16x3p_force_continuous(int32_t mode);
 /* psam_attention_f16x3(_ex) with few workgroups (one cloud, head dim in (64, 128]): up to four workgroups per (query block, head) share the key tiles and
  * the last arrival combines their partial softmax states in split order.  0 = never split, 1 / -1 = the default (environment PSAM_ATTN_KEYSPLIT=0: off). */
 void psam_attention_f16x3_force_keysplit(int32_t mode);
+/* What the calling thread's last psam_attention_f16x3(_ex, _ex2) launched: the channel-layout instance (64: head dim 64; 96: head dims in (64, 96] on the
+ * 128-wide layout with 96 active channels; 128: the full 128-channel instance), -1 after a refused call; and the key-split factor actually used
+ * (1 = unsplit), 0 after a refused call.  psam_attention_f32_last_instance: the head dim whose instance the last psam_attention_f32 launched, or -1. */
+int32_t psam_attention_f16x3_last_instance(void);
+int32_t psam_attention_f16x3_last_keysplit(void);
+int32_t psam_attention_f32_last_instance(void);
 /* psam_twoway_decoder: 1 = the patch-side projections of a layer run on a side stream forked from (and joined back into) the caller's stream -- also
  * inside a graph capture --, 0 / -1 = everything in sequence on the caller's stream (the default: the fork measured slower, csrc/blocks.hip TwSide;
  * environment PSAM_TWOWAY_FORK=1 switches it on).  Same kernels, same bits. */
@@ -292,7 +298,18 @@ int32_t psam_attention_f16x3_ex2(const float* q, int64_t ldq, int64_t sq, const 
  * o [B*L, ldo]: g8-packed output for the projection GEMM, o_scale [B*L] = f16_row_scale(v_bound) for every row (v_bound >= max |v|). */
 int32_t psam_attention_packed(const void* qkv, int64_t ld, const float* sc, float* o, int64_t ldo, float* o_scale, int32_t B, int32_t H, int32_t L,
                               int32_t hd, float scale, float v_bound, psam_stream_t stream);
-void psam_attention_packed_force_variant(int32_t v); /* tuning hook: -1 default, 0 = 256-row workgroups / 3-tile ring, 1 = two 128-row workgroups per CU / 2-tile ring */
+/* Tuning hook: -1 default (environment PSAM_ATTN_VARIANT, else 1), 0 = 256-row workgroups of eight waves on a three-tile ring -- 128-row workgroups of four
+ * waves where the 256-row grid would leave CUs idle --, 1 = two 128-row workgroups per CU on a two-tile ring where that grid is at most four per CU (else
+ * as 0), 2 = four waves with two query blocks each (experiments builds only).  A variant the build cannot run -- 2 in a default build, anything above 2,
+ * by this hook or by the environment -- is REFUSED by psam_attention_packed (PSAM_EINVAL): a forced variant runs as forced or not at all.  The variant
+ * does not decide everything: L <= 128 always runs the eight-wave kernel, and a forced workgroup shape (below) wins over it. */
+void psam_attention_packed_force_variant(int32_t v);
+/* Test / tuning hook, the process-level twin of the environment's PSAM_ATTN_PACKED_NW: -1 default (the environment, else 0), 0 = by shape and CU count,
+ * 4 / 8 = the four- / eight-wave kernel on the three-tile ring whatever the shape and variant; any other value makes psam_attention_packed refuse. */
+void psam_attention_packed_force_nw(int32_t nw);
+/* The kernel instance the calling thread's last psam_attention_packed launched, as waves * 100 + ring tiles * 10 + query blocks per wave
+ * (831, 431, 421; 432 in experiments builds); -1 after a refused call. */
+int32_t psam_attention_packed_last_instance(void);
 
 /* y [M, N] = act(x [M, K] W [N, K]^T + bias) + residual for M <= 64 rows (K % 16 == 0, rows 16-byte aligned; act: none / GELU / ReLU),
  * exact fp32 products.  The decoder's token-side nn.Linear calls (7 output tokens per prompt): transformer.py:109-236. */
@@ -526,6 +543,9 @@ int32_t psam_attention_small(const float* q, int64_t ldq, int64_t sq, const floa
 /* Test / A-B hook: 0 = psam_attention_small always runs one wave per query; 1 (default) = few queries against >= 128 keys run one workgroup per query,
  * the keys split over its four waves. */
 void psam_attention_small_force_split(int32_t on);
+/* The kernel the calling thread's last psam_attention_small launched: 0 = one wave per query, 1 = one workgroup per query (keys split over its waves),
+ * 4 / 8 = the few-keys kernel (Lk <= 16, Lq >= 64) at head dim 16 / 32; -1 after a refused call. */
+int32_t psam_attention_small_last_instance(void);
 
 /* ---------------------------------------------------------------- encodings, token assembly, upsampling */
 

@@ -51,8 +51,13 @@ SIGNATURES = {
     "psam_gemm_f16x3p_force_splitk_fixup": (None, [i32]),
     "psam_gemm_f16x3p_force_continuous": (None, [i32]),
     "psam_attention_f16x3_force_keysplit": (None, [i32]),
+    "psam_attention_f16x3_last_instance": (i32, []),
+    "psam_attention_f16x3_last_keysplit": (i32, []),
+    "psam_attention_f32_last_instance": (i32, []),
     "psam_twoway_decoder_force_fork": (None, [i32]),
     "psam_attention_packed_force_variant": (None, [i32]),
+    "psam_attention_packed_force_nw": (None, [i32]),
+    "psam_attention_packed_last_instance": (i32, []),
     "psam_gemm_f16x3p_fused_row_ln": (i32, [i32]),
     "psam_gemm_f16x3p_stat_segs": (i32, [i32]),
     "psam_gemm_f16x3p_splitk": (i32, [i32, i32, i32, i32]),
@@ -70,6 +75,7 @@ SIGNATURES = {
     "psam_scale_pack_rows_g8_add_dual": (i32, [ptr, i64, ptr, i64, i32, i32, i32, i32, ptr, ptr, ptr, ptr, i64, ptr]),
     "psam_mlp3_pair": (i32, [ptr, ptr, i32, ptr]),
     "psam_attention_small_force_split": (None, [i32]),
+    "psam_attention_small_last_instance": (i32, []),
     "psam_linear_skinny_ln_tmp_floats": (ctypes.c_size_t, [i32, i32]),
     "psam_scale_pack_rows_g8_add": (i32, [ptr, i64, ptr, i64, i32, i32, i32, i32, ptr, i64, ptr, ptr]),
     "psam_eva_gelu_block_prepared_bytes": (size_t, [i32, i32]),

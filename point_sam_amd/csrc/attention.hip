@@ -198,11 +198,16 @@ __global__ __launch_bounds__(256) void flash_attn_f32_kernel(const FlashArgs p) 
     }
 }
 
+// the head dim whose instance the calling thread's last psam_attention_f32 launched (one instance per admitted head dim); -1 after a refused call
+static thread_local int32_t t_fa32_last = -1;
+PSAM_API int32_t psam_attention_f32_last_instance(void) { return t_fa32_last; }
+
 // q/k/v/o: [B, L, H*hd] views with row strides ld* and batch strides s* (elements); head h lives at columns
 // [h*hd, (h+1)*hd).  Works on the fused qkv buffer of a ViT block (ldq = ldk = ldv = 3*D).
 PSAM_API int32_t psam_attention_f32(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v, int64_t ldv,
                                     int64_t sv, float* o, int64_t ldo, int64_t so, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
                                     float scale, hipStream_t stream) {
+    t_fa32_last = -1;
     PSAM_REQUIRE(q && k && v && o, PSAM_EINVAL, "psam_attention_f32: null pointer");
     PSAM_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, PSAM_EINVAL, "psam_attention_f32: bad shape");
     PSAM_REQUIRE(B <= 65535 && H <= 65535, PSAM_EINVAL, "psam_attention_f32: B/H too large");
@@ -232,7 +237,9 @@ PSAM_API int32_t psam_attention_f32(const float* q, int64_t ldq, int64_t sq, con
             return PSAM_EINVAL;
     }
 #undef FA_LAUNCH
-    return psam_launch_status("psam_attention_f32: launch failed");
+    const int32_t rc = psam_launch_status("psam_attention_f32: launch failed");
+    if (rc == PSAM_OK) t_fa32_last = hd;
+    return rc;
 }
 
 // ================================================================================================================
@@ -637,6 +644,11 @@ static bool fa_keysplit_enabled() {
     return on != 0;
 }
 PSAM_API void psam_attention_f16x3_force_keysplit(int32_t mode) { g_fa_keysplit = mode; }
+// what the calling thread's last psam_attention_f16x3(_ex, _ex2) launched: the channel-layout instance (64 = <64>, 96 = <128, 96>, 128 = <128>; -1 after a
+// refused call) and the key-split factor actually used (1 = unsplit; 0 after a refused call)
+static thread_local int32_t t_fa_last_inst = -1, t_fa_last_ks = 0;
+PSAM_API int32_t psam_attention_f16x3_last_instance(void) { return t_fa_last_inst; }
+PSAM_API int32_t psam_attention_f16x3_last_keysplit(void) { return t_fa_last_ks; }
 // A/B hook: PSAM_ATTN_FULL_WIDTH=1 runs head dims in (64, 96] on the full 128-channel instance (the round-5 kernel; same bits)
 static bool fa_full_width() {
     static int on = -1;
@@ -668,6 +680,7 @@ PSAM_API int32_t psam_attention_f16x3_ex2(const float* q, int64_t ldq, int64_t s
                                           int64_t sv, float* o, int64_t ldo, int64_t so, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
                                           float scale, const float* a_scale, float k1, float k2, float* o_scale, int32_t max_keysplit, void* ks_ws,
                                           size_t ks_ws_bytes, int32_t* counters, hipStream_t stream) {
+    t_fa_last_inst = -1; t_fa_last_ks = 0;
     PSAM_REQUIRE(q && k && v && o, PSAM_EINVAL, "psam_attention_f16x3: null pointer");
     PSAM_REQUIRE((a_scale == nullptr) == (o_scale == nullptr), PSAM_EINVAL, "psam_attention_f16x3: packed output needs both a_scale and o_scale");
     PSAM_REQUIRE(!o_scale || ((ldo & 7) == 0 && ((uintptr_t)o & 31) == 0 && (so & 7) == 0 && Lq == Lk), PSAM_EINVAL,
@@ -700,14 +713,17 @@ PSAM_API int32_t psam_attention_f16x3_ex2(const float* q, int64_t ldq, int64_t s
         }
     }
     const dim3 grid((unsigned)(units * p.ksplit)), block(256);      // 1-D over (key split, query block, head, batch), see the kernel
-    if (hd == 64) hipLaunchKernelGGL((flash_attn_f16x3_kernel<64>), grid, block, 0, stream, p);
-    else if (hd > 64 && hd <= 96 && (hd & 7) == 0 && !fa_full_width()) hipLaunchKernelGGL((flash_attn_f16x3_kernel<128, 96>), grid, block, 0, stream, p);   // 128-wide layout, 96 active channels (the giant encoder's 88)
-    else if (hd > 64 && hd <= 128 && (hd & 7) == 0) hipLaunchKernelGGL((flash_attn_f16x3_kernel<128>), grid, block, 0, stream, p);   // zero-padded to 128
+    int32_t inst;
+    if (hd == 64) { inst = 64; hipLaunchKernelGGL((flash_attn_f16x3_kernel<64>), grid, block, 0, stream, p); }
+    else if (hd > 64 && hd <= 96 && (hd & 7) == 0 && !fa_full_width()) { inst = 96; hipLaunchKernelGGL((flash_attn_f16x3_kernel<128, 96>), grid, block, 0, stream, p); }   // 128-wide layout, 96 active channels (the giant encoder's 88)
+    else if (hd > 64 && hd <= 128 && (hd & 7) == 0) { inst = 128; hipLaunchKernelGGL((flash_attn_f16x3_kernel<128>), grid, block, 0, stream, p); }   // zero-padded to 128
     else {
         psam_set_error("psam_attention_f16x3: head_dim must be 64 or a multiple of 8 in (64, 128]");
         return PSAM_EINVAL;
     }
-    return psam_launch_status("psam_attention_f16x3: launch failed");
+    const int32_t rc = psam_launch_status("psam_attention_f16x3: launch failed");
+    if (rc == PSAM_OK) { t_fa_last_inst = inst; t_fa_last_ks = p.ksplit; }
+    return rc;
 }
 
 PSAM_API int32_t psam_attention_f16x3_ex(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v, int64_t ldv,
@@ -1020,13 +1036,30 @@ static int attn_variant_env() {
 }
 // tuning hook: -1 = default (environment PSAM_ATTN_VARIANT, else 1), 0 = one 256-row workgroup per CU on a three-tile ring, 1 = two 128-row
 // workgroups per CU on a two-tile ring, 2 = 256-row workgroups of four waves with two query blocks per wave
+// A variant the build cannot run (anything but 0 and 1; 2 in an experiments build) is REFUSED by psam_attention_packed -- forced by the hook or named by
+// the environment --, like a forced GEMM configuration: it runs as forced or not at all.  What a variant does NOT decide: L <= 128 (one query block) always
+// runs the eight-wave kernel, and a forced workgroup shape (below) names the kernel and wins over the variant.
 PSAM_API void psam_attention_packed_force_variant(int32_t v) { g_attn_variant = v; }
+// test / tuning hook, the process-level twin of the environment's PSAM_ATTN_PACKED_NW (read once): -1 = default (the environment, else 0), 0 = by shape and
+// CU count, 4 / 8 = the four- / eight-wave kernel on the three-tile ring whatever the shape; any other value is refused by psam_attention_packed
+static int g_attn_force_nw = -1;
+PSAM_API void psam_attention_packed_force_nw(int32_t nw) { g_attn_force_nw = nw; }
+// the kernel instance the calling thread's last psam_attention_packed launched, as NW * 100 + RING * 10 + QB (831 = <8>, 431 = <4>, 421 = <4, 2>,
+// 432 = <4, 3, 2>); -1 after a refused call
+static thread_local int32_t t_pa_last = -1;
+PSAM_API int32_t psam_attention_packed_last_instance(void) { return t_pa_last; }
+static int32_t pa_launched(int32_t inst) {
+    const int32_t rc = psam_launch_status("psam_attention_packed: launch failed");
+    if (rc == PSAM_OK) t_pa_last = inst;
+    return rc;
+}
 
 // qkv: g8-packed rows [B * L, ld] (containers of 4 bytes: q | k | v column blocks of D = H * 64 each, one scale for all rows in
 // sc[...]); o [B * L, ldo]: g8-packed attention output for the projection GEMM, o_scale [B * L] its (constant) row scales
 // f16_row_scale(v_bound), v_bound >= max |v| (an a-priori bound; attention outputs are convex combinations of V rows).
 PSAM_API int32_t psam_attention_packed(const void* qkv, int64_t ld, const float* sc, float* o, int64_t ldo, float* o_scale, int32_t B, int32_t H,
                                        int32_t L, int32_t hd, float scale, float v_bound, hipStream_t stream) {
+    t_pa_last = -1;
     PSAM_REQUIRE(qkv && sc && o && o_scale, PSAM_EINVAL, "psam_attention_packed: null pointer");
     PSAM_REQUIRE(B > 0 && H > 0 && L > 0 && hd == 64, PSAM_EINVAL, "psam_attention_packed: bad shape (head_dim 64)");
     PSAM_REQUIRE(ld >= 3 * (int64_t)H * hd && (ld & 7) == 0 && (ldo & 7) == 0 && ldo >= (int64_t)H * hd && (((uintptr_t)qkv | (uintptr_t)o) & 31) == 0, PSAM_EALIGN,
@@ -1057,8 +1090,10 @@ PSAM_API int32_t psam_attention_packed(const void* qkv, int64_t ld, const float*
             __atomic_fetch_or(&attr_done, bit, __ATOMIC_RELEASE);
         }
     }
-    static int force_nw = -1;      // tuning hook (environment, read once): PSAM_ATTN_PACKED_NW = 4 | 8
-    if (force_nw < 0) { const char* e = getenv("PSAM_ATTN_PACKED_NW"); force_nw = e ? atoi(e) : 0; }
+    static int env_nw = -1;      // tuning hook (environment, read once): PSAM_ATTN_PACKED_NW = 4 | 8
+    if (env_nw < 0) { const char* e = getenv("PSAM_ATTN_PACKED_NW"); env_nw = e ? atoi(e) : 0; }
+    const int force_nw = g_attn_force_nw >= 0 ? g_attn_force_nw : env_nw;
+    PSAM_REQUIRE(force_nw == 0 || force_nw == 4 || force_nw == 8, PSAM_EINVAL, "psam_attention_packed: forced workgroup shape must be 4 or 8 waves");
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
     // 256-row workgroups (two waves per SIMD cover each other's softmax gaps) unless they would leave CUs without work: one cloud of 2048 tokens
     // and 16 heads is 128 of them on 256 CUs (99 us); 128-row workgroups fill the chip
@@ -1066,6 +1101,11 @@ PSAM_API int32_t psam_attention_packed(const void* qkv, int64_t ld, const float*
     const bool small = force_nw ? force_nw == 4 : (wg8 < ncu && L > PA_BQ / 2);
     // two 128-row workgroups per CU on a two-tile ring where the 256-row grid is about one workgroup per CU (B = 8 clouds x 16 heads x 512 tokens: 256)
     const int variant = g_attn_variant >= 0 ? g_attn_variant : attn_variant_env();
+#ifdef PSAM_BUILD_EXPERIMENTS
+    PSAM_REQUIRE(variant >= 0 && variant <= 2, PSAM_EINVAL, "psam_attention_packed: unknown variant (0, 1 or 2)");
+#else
+    PSAM_REQUIRE(variant == 0 || variant == 1, PSAM_EINVAL, "psam_attention_packed: this build has variants 0 and 1 only (2 needs PSAM_BUILD_EXPERIMENTS)");
+#endif
     const int64_t wg4 = (int64_t)psam_cdiv(L, PA_BQ / 2) * H * B;
 #ifdef PSAM_BUILD_EXPERIMENTS
     // two query blocks per wave (QB = 2): 256-row workgroups of four waves, one per CU.  Bitwise equal to the other variants and SLOWER (44.3 vs 35.8 us at
@@ -1073,15 +1113,15 @@ PSAM_API int32_t psam_attention_packed(const void* qkv, int64_t ld, const float*
     // v_accvgpr moves per tile) and the rescale branches split the two blocks' instruction streams instead of interleaving them.  Experiments builds only.
     if (variant == 2 && !force_nw && L > PA_BQ / 2) {
         hipLaunchKernelGGL((flash_attn_packed_kernel<4, 3, 2>), dim3((unsigned)wg8), dim3(256), lds, stream, p);
-        return psam_launch_status("psam_attention_packed: launch failed");
+        return pa_launched(432);
     }
 #endif
     if (variant == 1 && !force_nw && L > PA_BQ / 2 && wg4 <= (int64_t)4 * ncu) {      // (a forced workgroup shape -- PSAM_ATTN_PACKED_NW -- names the kernel: it wins)
         hipLaunchKernelGGL((flash_attn_packed_kernel<4, 2>), dim3((unsigned)wg4), dim3(256), 2 * 2 * PA_TILE, stream, p);
         if (psam_ablate_repeat() & 1) hipLaunchKernelGGL((flash_attn_packed_kernel<4, 2>), dim3((unsigned)wg4), dim3(256), 2 * 2 * PA_TILE, stream, p);
-        return psam_launch_status("psam_attention_packed: launch failed");
+        return pa_launched(421);
     }
     if (small) hipLaunchKernelGGL(flash_attn_packed_kernel<4>, dim3((unsigned)(psam_cdiv(L, PA_BQ / 2) * H * B)), dim3(256), lds, stream, p);
     else hipLaunchKernelGGL(flash_attn_packed_kernel<8>, dim3((unsigned)wg8), dim3(512), lds, stream, p);
-    return psam_launch_status("psam_attention_packed: launch failed");
+    return pa_launched(small ? 431 : 831);
 }

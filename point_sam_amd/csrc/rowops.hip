@@ -879,9 +879,19 @@ __global__ __launch_bounds__(256) void attention_fewkeys_kernel(const float* __r
 
 static int g_attn_small_split = 1;      // test / A-B hook: 0 = always one wave per query
 PSAM_API void psam_attention_small_force_split(int32_t on) { g_attn_small_split = on; }
+// the kernel the calling thread's last psam_attention_small launched: 0 = attention_small_kernel (one wave per query), 1 = attention_small_split_kernel,
+// 4 / 8 = attention_fewkeys_kernel<4> / <8>; -1 after a refused call
+static thread_local int32_t t_attn_small_last = -1;
+PSAM_API int32_t psam_attention_small_last_instance(void) { return t_attn_small_last; }
+static int32_t attn_small_launched(int32_t inst) {
+    const int32_t rc = psam_launch_status("psam_attention_small: launch failed");
+    if (rc == PSAM_OK) t_attn_small_last = inst;
+    return rc;
+}
 PSAM_API int32_t psam_attention_small(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v,
                                       int64_t ldv, int64_t sv, float* out, int64_t ldo, int64_t so, int64_t Z, int32_t H, int32_t Lq, int32_t Lk,
                                       int32_t hd, float scale, hipStream_t stream) {
+    t_attn_small_last = -1;
     PSAM_REQUIRE(q && k && v && out && Z > 0 && H > 0 && Lq > 0 && Lk > 0 && hd > 0, PSAM_EINVAL, "psam_attention_small: bad argument");
     PSAM_REQUIRE((size_t)Lk * 16 <= 128 * 1024, PSAM_EINVAL, "psam_attention_small: Lk too large");
     const bool aligned = ((ldq | ldk | ldv | ldo | sq | sk | sv | so) & 3) == 0 && ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0);
@@ -889,17 +899,17 @@ PSAM_API int32_t psam_attention_small(const float* q, int64_t ldq, int64_t sq, c
         const dim3 grid((unsigned)psam_cdiv(Lq, 256), H, (unsigned)Z);
         if (hd == 16) hipLaunchKernelGGL(attention_fewkeys_kernel<4>, grid, dim3(256), 0, stream, q, ldq, sq, k, ldk, sk, v, ldv, sv, out, ldo, so, H, Lq, Lk, scale);
         else hipLaunchKernelGGL(attention_fewkeys_kernel<8>, grid, dim3(256), 0, stream, q, ldq, sq, k, ldk, sk, v, ldv, sv, out, ldo, so, H, Lq, Lk, scale);
-        return psam_launch_status("psam_attention_small: launch failed");
+        return attn_small_launched(hd == 16 ? 4 : 8);
     }
     const int64_t waves = Z * H * Lq;
     if (g_attn_small_split && Lk >= 128 && waves <= 2048 && aligned && (hd & 3) == 0 && hd <= 64 && (64 % (hd >> 2)) == 0) {      // few queries, many keys: a workgroup per query
         hipLaunchKernelGGL(attention_small_split_kernel, dim3((unsigned)waves), dim3(256), (size_t)(((Lk + 3) & ~3) + 4 * 68) * 4, stream, q, ldq, sq, k, ldk, sk, v, ldv,
                            sv, out, ldo, so, H, Lq, Lk, hd, scale);
-        return psam_launch_status("psam_attention_small: launch failed");
+        return attn_small_launched(1);
     }
     hipLaunchKernelGGL(attention_small_kernel, dim3((unsigned)psam_cdiv(waves, 4)), dim3(256), (size_t)Lk * 16, stream, q, ldq, sq, k, ldk, sk, v,
                        ldv, sv, out, ldo, so, Z, H, Lq, Lk, hd, scale);
-    return psam_launch_status("psam_attention_small: launch failed");
+    return attn_small_launched(0);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -97,6 +97,9 @@ int32_t psam_patch_l1_r(const float* xyz, const float* feats, const float* cente
 int32_t psam_patch_l1_ex(const float* xyz, const float* feats, const float* centers, const int64_t* knn_idx, const int64_t* center_idx,
                          const float* W, const float* bias, const float* lnw, const float* lnb, float eps, int32_t B, int32_t rep, int32_t N,
                          int32_t G, int32_t K, int32_t C, float radius, float* out, float* scale_out, psam_stream_t stream);
+/* The kernel instance the calling thread's last psam_patch_l1* launched: 10 x its input width (4 / 6: C = 1 / 3; 5 / 9: the same centralised) + 1 when it
+ * wrote the packed form; -1 after a refused call. */
+int32_t psam_patch_l1_last_instance(void);
 
 /* Click simulation of the evaluation protocol.  psam_error_regions: fn = gt & !(logit > 0), fp = !gt & (logit > 0)
  * (logits == NULL: fn = gt, fp = 0) -- sample_fixed_points, pc_sam/model/common.py:388-405.  psam_border_farthest: per
@@ -255,11 +258,18 @@ int32_t psam_layernorm_ex2(const float* x, int64_t ldx, const float* res, int64_
                            float c1, float c0, psam_stream_t stream);
 int32_t psam_layernorm_rs(const float* x, int64_t ldx, const float* res, int64_t ldr, const float* w, const float* b, float* y, int64_t ldy,
                           int64_t rows, int32_t cols, float eps, int32_t act, float* row_scale, psam_stream_t stream);
+/* The kernel instance the calling thread's last psam_layernorm* launched: NREG of the scalar kernel (2, 4, 8, 16, 44 registers per lane; 0 = the
+ * streaming kernel for more than 2816 columns), 1000 + NV4 of the float4 kernel (1, 2, 4, 8, 16), + 100 when it wrote the packed form; -1 after a
+ * refused call. */
+int32_t psam_layernorm_last_instance(void);
 
 /* out = LayerNorm_H(SiLU(gx[:,0:H]) * gx[:,xoff:xoff+H]), zero-padded to ldo columns.
  * Replaces timm SwiGLU (act, mul, norm) inside eva02 blocks (called through pc_encoder.py:138-139). */
 int32_t psam_swiglu_ln(const float* gx, int64_t ldg, int32_t xoff, const float* w, const float* b, float* out, int64_t ldo, int64_t rows,
                        int32_t H, float eps, psam_stream_t stream);
+/* The kernel instance the calling thread's last psam_swiglu_ln launched: 8, 32 or 44 registers per lane, 0 = streaming (H > 2816); -1 after a
+ * refused call. */
+int32_t psam_swiglu_ln_last_instance(void);
 
 /* softmax(q k^T * scale) v per (batch, head), flash-style on the matrix cores; q/k/v/o are [B,L,H*hd] views.
  * Replaces F.scaled_dot_product_attention inside timm EvaAttention (pc_encoder.py:138-139).
@@ -573,6 +583,9 @@ int32_t psam_interp3(const float* src, const int64_t* idx3, const float* w3, flo
  * + GELU`: the interpolation is an affine combination (weights sum to 1), so it commutes with the Linear layer. */
 int32_t psam_interp3_ex(const float* src, const int64_t* idx3, const float* w3, float* out, int32_t rep, int64_t Z, int32_t N, int32_t G, int32_t C,
                         float* scale_out, const float* ln_gamma, const float* ln_beta, float ln_eps, int32_t act, psam_stream_t stream);
+/* The kernel the calling thread's last psam_interp3* launched: 256 = the C == 256 kernel (four rows per wave), 0 = the generic one; -1 after a
+ * refused call. */
+int32_t psam_interp3_last_instance(void);
 
 /* ---------------------------------------------------------------- mask proposals */
 

@@ -76,6 +76,10 @@ SIGNATURES = {
     "psam_mlp3_pair": (i32, [ptr, ptr, i32, ptr]),
     "psam_attention_small_force_split": (None, [i32]),
     "psam_attention_small_last_instance": (i32, []),
+    "psam_layernorm_last_instance": (i32, []),
+    "psam_swiglu_ln_last_instance": (i32, []),
+    "psam_patch_l1_last_instance": (i32, []),
+    "psam_interp3_last_instance": (i32, []),
     "psam_linear_skinny_ln_tmp_floats": (ctypes.c_size_t, [i32, i32]),
     "psam_scale_pack_rows_g8_add": (i32, [ptr, i64, ptr, i64, i32, i32, i32, i32, ptr, i64, ptr, ptr]),
     "psam_eva_gelu_block_prepared_bytes": (size_t, [i32, i32]),

@@ -211,9 +211,19 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
 // float4 path: 256 <= cols <= 4096, 32-byte aligned output rows) -- the A operand of psam_gemm_f16x3p.
 // row_bound (optional, packed output only, [rows]): c2 t^2 + c1 t + c0 with t = the L2 norm of the output row (times 1.0001) -- the a-priori
 // bound of the rows of a GEMM that consumes this output, e.g. |W_n . h + b_n| <= ||W_n|| t + |b_n| (psam_gemm_fuse_t.out_bound).
+// the instance the calling thread's last psam_layernorm* launched: NREG of layernorm_kernel (0 = streaming), 1000 + NV4 of layernorm_v4_kernel, + 100 when it
+// wrote the packed form; -1 after a refused call
+static thread_local int32_t t_layernorm_last = -1;
+PSAM_API int32_t psam_layernorm_last_instance(void) { return t_layernorm_last; }
+static int32_t layernorm_launched(int32_t inst) {
+    const int32_t rc = psam_launch_status("psam_layernorm: launch failed");
+    if (rc == PSAM_OK) t_layernorm_last = inst;
+    return rc;
+}
 PSAM_API int32_t psam_layernorm_ex2(const float* x, int64_t ldx, const float* res, int64_t ldr, const float* w, const float* b, float* y,
                                     int64_t ldy, int64_t rows, int32_t cols, float eps, int32_t act, float* row_scale, int32_t pack,
                                     float* row_bound, float c2, float c1, float c0, hipStream_t stream) {
+    t_layernorm_last = -1;
     PSAM_REQUIRE(x && w && b && y, PSAM_EINVAL, "psam_layernorm: null pointer");
     PSAM_REQUIRE(!row_bound || pack, PSAM_EINVAL, "psam_layernorm: row_bound comes with the packed output");
     PSAM_REQUIRE(rows > 0 && cols > 0, PSAM_EINVAL, "psam_layernorm: bad shape");
@@ -240,7 +250,7 @@ PSAM_API int32_t psam_layernorm_ex2(const float* x, int64_t ldx, const float* re
             else LNV_LAUNCH(16);
         }
 #undef LNV_LAUNCH
-        return psam_launch_status("psam_layernorm: launch failed");
+        return layernorm_launched(1000 + (span <= 256 ? 1 : span <= 512 ? 2 : span <= 1024 ? 4 : span <= 2048 ? 8 : 16) + (pack ? 100 : 0));
     }
 #define LN_LAUNCH(R) hipLaunchKernelGGL(layernorm_kernel<R>, grid, block, 0, stream, x, ldx, res, ldr, w, b, y, ldy, rows, cols, eps, act, row_scale)
     if (cols <= 128) LN_LAUNCH(2);
@@ -250,7 +260,7 @@ PSAM_API int32_t psam_layernorm_ex2(const float* x, int64_t ldx, const float* re
     else if (cols <= 2816) LN_LAUNCH(44);
     else LN_LAUNCH(0);
 #undef LN_LAUNCH
-    return psam_launch_status("psam_layernorm: launch failed");
+    return layernorm_launched(cols <= 128 ? 2 : cols <= 256 ? 4 : cols <= 512 ? 8 : cols <= 1024 ? 16 : cols <= 2816 ? 44 : 0);
 }
 
 PSAM_API int32_t psam_layernorm_ex(const float* x, int64_t ldx, const float* res, int64_t ldr, const float* w, const float* b, float* y,
@@ -326,8 +336,12 @@ __global__ __launch_bounds__(256) void swiglu_ln_kernel(const float* __restrict_
     }
 }
 
+// NREG of the swiglu_ln_kernel instance the calling thread's last psam_swiglu_ln launched (0 = streaming); -1 after a refused call
+static thread_local int32_t t_swiglu_ln_last = -1;
+PSAM_API int32_t psam_swiglu_ln_last_instance(void) { return t_swiglu_ln_last; }
 PSAM_API int32_t psam_swiglu_ln(const float* gx, int64_t ldg, int32_t xoff, const float* w, const float* b, float* out, int64_t ldo,
                                 int64_t rows, int32_t H, float eps, hipStream_t stream) {
+    t_swiglu_ln_last = -1;
     PSAM_REQUIRE(gx && w && b && out, PSAM_EINVAL, "psam_swiglu_ln: null pointer");
     PSAM_REQUIRE(rows > 0 && H > 0 && xoff >= H && ldo >= H && ldg >= xoff + H, PSAM_EINVAL, "psam_swiglu_ln: bad shape");
     const dim3 grid((unsigned)psam_cdiv(rows, 4)), block(256);
@@ -337,7 +351,9 @@ PSAM_API int32_t psam_swiglu_ln(const float* gx, int64_t ldg, int32_t xoff, cons
     else if (H <= 44 * 64) SG_LAUNCH(44);
     else SG_LAUNCH(0);
 #undef SG_LAUNCH
-    return psam_launch_status("psam_swiglu_ln: launch failed");
+    const int32_t rc = psam_launch_status("psam_swiglu_ln: launch failed");
+    if (rc == PSAM_OK) t_swiglu_ln_last = H <= 8 * 64 ? 8 : H <= 32 * 64 ? 32 : H <= 44 * 64 ? 44 : 0;
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -664,9 +680,18 @@ __global__ __launch_bounds__(256) void interp3_c256_kernel(const float* __restri
 
 // scale_out [Z*N] != NULL (C == 256 only): out receives the g8-packed rows (A operand of psam_gemm_f16x3p) and scale_out their scales.
 // ln_gamma / ln_beta != NULL (C == 256 only): LayerNorm(ln_eps) + activation `act` (PSAM_ACT_NONE / GELU / RELU) of every interpolated row.
+// the kernel the calling thread's last psam_interp3* launched: 256 = interp3_c256_kernel, 0 = interp3_kernel (any other C); -1 after a refused call
+static thread_local int32_t t_interp3_last = -1;
+PSAM_API int32_t psam_interp3_last_instance(void) { return t_interp3_last; }
+static int32_t interp3_launched(int32_t inst) {
+    const int32_t rc = psam_launch_status("psam_interp3: launch failed");
+    if (rc == PSAM_OK) t_interp3_last = inst;
+    return rc;
+}
 PSAM_API int32_t psam_interp3_ex(const float* src, const int64_t* idx3, const float* w3, float* out, int32_t rep, int64_t Z, int32_t N, int32_t G,
                                  int32_t C, float* scale_out, const float* ln_gamma, const float* ln_beta, float ln_eps, int32_t act,
                                  hipStream_t stream) {
+    t_interp3_last = -1;
     PSAM_REQUIRE(src && idx3 && w3 && out && rep > 0 && Z > 0 && N > 0 && G > 0 && C > 0, PSAM_EINVAL, "psam_interp3: bad argument");
     PSAM_REQUIRE((C & 3) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)out & 15) == 0, PSAM_EALIGN, "psam_interp3: C % 4 and 16B alignment");
     PSAM_REQUIRE(!scale_out || (C == 256 && ((uintptr_t)out & 31) == 0), PSAM_EINVAL, "psam_interp3: packed output needs C == 256 and 32-byte aligned rows");
@@ -676,11 +701,11 @@ PSAM_API int32_t psam_interp3_ex(const float* src, const int64_t* idx3, const fl
         constexpr int R = 4;
         hipLaunchKernelGGL(interp3_c256_kernel<R>, dim3((unsigned)psam_cdiv(Z * N, 4 * R)), dim3(256), 0, stream, src, idx3, w3, out, rep, Z, N, G, scale_out,
                            ln_gamma, ln_beta, ln_eps, act);
-        return psam_launch_status("psam_interp3: launch failed");
+        return interp3_launched(256);
     }
     hipLaunchKernelGGL(interp3_kernel, dim3((unsigned)psam_cdiv(Z * N, 4)), dim3(256), 0, stream, src, idx3, w3, out, rep, Z, N, G, C, scale_out, ln_gamma,
                        ln_beta, ln_eps, act);
-    return psam_launch_status("psam_interp3: launch failed");
+    return interp3_launched(0);
 }
 
 PSAM_API int32_t psam_interp3(const float* src, const int64_t* idx3, const float* w3, float* out, int32_t rep, int64_t Z, int32_t N, int32_t G,

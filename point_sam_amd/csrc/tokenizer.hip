@@ -1247,9 +1247,13 @@ __global__ __launch_bounds__(256) void patch_l1_kernel(const float* __restrict__
 
 // W [128, Cin] (nn.Linear layout), Cin = 3 + C or 3 + 2C (centralize: center_idx [B, G] = the groups' FPS indices), bias/lnw/lnb [128];
 // out [B*rep*G*K, 128] fp32, or (scale_out != null) the g8-packed rows + their scales.  C in {1, 3}.
+// the patch_l1_kernel instance the calling thread's last psam_patch_l1* launched: CIN * 10 + PACK (CIN 4 / 6 plain, 5 / 9 centralised); -1 after a refused call
+static thread_local int32_t t_patch_l1_last = -1;
+PSAM_API int32_t psam_patch_l1_last_instance(void) { return t_patch_l1_last; }
 PSAM_API int32_t psam_patch_l1_ex(const float* xyz, const float* feats, const float* centers, const int64_t* knn_idx, const int64_t* center_idx,
                                   const float* W, const float* bias, const float* lnw, const float* lnb, float eps, int32_t B, int32_t rep,
                                   int32_t N, int32_t G, int32_t K, int32_t C, float radius, float* out, float* scale_out, hipStream_t stream) {
+    t_patch_l1_last = -1;
     PSAM_REQUIRE(xyz && feats && centers && knn_idx && W && bias && lnw && lnb && out, PSAM_EINVAL, "psam_patch_l1: null pointer");
     PSAM_REQUIRE(B > 0 && rep > 0 && N > 0 && G > 0 && K > 0, PSAM_EINVAL, "psam_patch_l1: bad shape");
     PSAM_REQUIRE(C == 1 || C == 3, PSAM_EINVAL, "psam_patch_l1: C must be 1 (mask logit) or 3 (rgb)");
@@ -1268,7 +1272,9 @@ PSAM_API int32_t psam_patch_l1_ex(const float* xyz, const float* feats, const fl
     if (scale_out) L1_PICK(true); else L1_PICK(false);
 #undef L1_PICK
 #undef L1_LAUNCH
-    return psam_launch_status("psam_patch_l1: launch failed");
+    const int32_t rc = psam_launch_status("psam_patch_l1: launch failed");
+    if (rc == PSAM_OK) t_patch_l1_last = (center_idx ? 3 + 2 * C : 3 + C) * 10 + (scale_out ? 1 : 0);
+    return rc;
 }
 
 PSAM_API int32_t psam_patch_l1_r(const float* xyz, const float* feats, const float* centers, const int64_t* knn_idx, const float* W,

@@ -642,30 +642,64 @@ def attention_packed(qkv_packed, scale_rows, out, out_scale, B, H, L, hd, scale,
     return out
 
 
-class EvaBlock:
-    """One EVA02 (SwiGLU) transformer block prepared for psam_eva_block (csrc/blocks.hip): packed weights + bounds, built once at load by the
-    library itself (psam_eva_block_prepare) from the state-dict tensors.  w: name -> fp32 device tensor; prefix 'pc_encoder.transformer.blocks.i'."""
+class _Stage:
+    """What the stages prepared for a coarse entry of csrc/blocks.hip share.  ENTRY names the entry (psam_x); psam_x_prepared_bytes, psam_x_prepare and
+    psam_x_ws_bytes go with it.  A stage binds its weights (state-dict tensors, w: name -> contiguous fp32 device tensor) and keeps them alive, has the
+    library pack them ONCE into `blob` and fill `plan`, and sizes the workspace of a call."""
+    ENTRY = None
+
+    def __init__(self):
+        self.keep = []
+
+    def _bind(self, w, name) -> int:
+        t = w[name]
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"{name}: contiguous fp32 expected")
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def _prepare(self, wt, plan, *dims):
+        L = _lib.load()
+        self.plan = plan
+        self.blob = torch.empty(int(getattr(L, self.ENTRY + "_prepared_bytes")(*dims)), dtype=torch.uint8, device=self.keep[0].device)
+        check(getattr(L, self.ENTRY + "_prepare")(ctypes.byref(wt), ctypes.byref(plan), self.blob.data_ptr(), self.blob.numel(), _stream()), self.ENTRY + "_prepare")
+
+    def _ws(self, ws, device, *shape):
+        """ws if it is large enough for a call of this shape, a new workspace otherwise."""
+        need = int(getattr(_lib.load(), self.ENTRY + "_ws_bytes")(*shape))
+        return ws if ws is not None and ws.numel() >= need else torch.empty(need, dtype=torch.uint8, device=device)
+
+
+class _EvaStage(_Stage):
+    """One transformer block of the patch encoder; prefix 'pc_encoder.transformer.blocks.i'.  NAMES: field of the weight struct -> tensor; EXTRA: further
+    fields -> value."""
+    EXTRA = {}
 
     def __init__(self, w, prefix: str, dim: int, heads: int, hidden: int, eps: float):
-        import ctypes
-        L = _lib.load()
-        wt = _lib.EvaBlockWeights()
-        self.keep = []
-        names = dict(norm1_w="norm1.weight", norm1_b="norm1.bias", q_w="attn.q_proj.weight", q_b="attn.q_proj.bias", k_w="attn.k_proj.weight",
-                     v_w="attn.v_proj.weight", v_b="attn.v_proj.bias", proj_w="attn.proj.weight", proj_b="attn.proj.bias", norm2_w="norm2.weight",
-                     norm2_b="norm2.bias", fc1_g_w="mlp.fc1_g.weight", fc1_g_b="mlp.fc1_g.bias", fc1_x_w="mlp.fc1_x.weight", fc1_x_b="mlp.fc1_x.bias",
-                     mlp_norm_w="mlp.norm.weight", mlp_norm_b="mlp.norm.bias", fc2_w="mlp.fc2.weight", fc2_b="mlp.fc2.bias")
-        for slot, n in names.items():
-            t = w[f"{prefix}.{n}"]
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{prefix}.{n}: contiguous fp32 expected")
-            self.keep.append(t)
-            setattr(wt, slot, t.data_ptr())
-        wt.dim, wt.heads, wt.hidden, wt.eps = int(dim), int(heads), int(hidden), float(eps)
-        self.plan = _lib.EvaBlockPlan()
-        self.blob = torch.empty(int(L.psam_eva_block_prepared_bytes(dim, hidden)), dtype=torch.uint8, device=self.keep[0].device)
-        check(L.psam_eva_block_prepare(ctypes.byref(wt), ctypes.byref(self.plan), self.blob.data_ptr(), self.blob.numel(), _stream()), "psam_eva_block_prepare")
+        super().__init__()
+        wt = self.WEIGHTS()
+        for slot, n in self.NAMES.items():
+            setattr(wt, slot, self._bind(w, f"{prefix}.{n}"))
+        for slot, v in dict(self.EXTRA, dim=int(dim), heads=int(heads), hidden=int(hidden), eps=float(eps)).items():
+            setattr(wt, slot, v)
         self.dim, self.hidden = int(dim), int(hidden)
+        self._prepare(wt, self.PLAN(), dim, hidden)
+
+    def _rows(self, x, B: int, L: int, ws):
+        _chk(x, name="x")
+        if x.shape != (B * L, self.dim) or not x.is_contiguous():
+            raise ValueError("x must be a contiguous [B*L, dim] tensor")
+        return self._ws(ws, x.device, B * L, self.dim, self.hidden)
+
+
+class EvaBlock(_EvaStage):
+    """One EVA02 (SwiGLU) transformer block prepared for psam_eva_block (csrc/blocks.hip): packed weights + bounds, built once at load by the
+    library itself (psam_eva_block_prepare) from the state-dict tensors.  w: name -> fp32 device tensor; prefix 'pc_encoder.transformer.blocks.i'."""
+    ENTRY, WEIGHTS, PLAN = "psam_eva_block", _lib.EvaBlockWeights, _lib.EvaBlockPlan
+    NAMES = dict(norm1_w="norm1.weight", norm1_b="norm1.bias", q_w="attn.q_proj.weight", q_b="attn.q_proj.bias", k_w="attn.k_proj.weight",
+                 v_w="attn.v_proj.weight", v_b="attn.v_proj.bias", proj_w="attn.proj.weight", proj_b="attn.proj.bias", norm2_w="norm2.weight",
+                 norm2_b="norm2.bias", fc1_g_w="mlp.fc1_g.weight", fc1_g_b="mlp.fc1_g.bias", fc1_x_w="mlp.fc1_x.weight", fc1_x_b="mlp.fc1_x.bias",
+                 mlp_norm_w="mlp.norm.weight", mlp_norm_b="mlp.norm.bias", fc2_w="mlp.fc2.weight", fc2_b="mlp.fc2.bias")
 
     @staticmethod
     def supported(dim: int, heads: int, hidden: int) -> bool:
@@ -673,43 +707,20 @@ class EvaBlock:
 
     def run(self, x, B: int, L: int, ws=None):
         """x [B*L, dim] fp32, updated in place."""
-        import ctypes
-        lib = _lib.load()
-        _chk(x, name="x")
-        M = B * L
-        if x.shape != (M, self.dim) or not x.is_contiguous():
-            raise ValueError("x must be a contiguous [B*L, dim] tensor")
-        need = int(lib.psam_eva_block_ws_bytes(M, self.dim, self.hidden))
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        check(lib.psam_eva_block(ctypes.byref(self.plan), self.blob.data_ptr(), x.data_ptr(), B, L, ws.data_ptr(), ws.numel(), _stream()), "psam_eva_block")
+        ws = self._rows(x, B, L, ws)
+        check(_lib.load().psam_eva_block(ctypes.byref(self.plan), self.blob.data_ptr(), x.data_ptr(), B, L, ws.data_ptr(), ws.numel(), _stream()), "psam_eva_block")
         return x
 
 
-class EvaGeluBlock:
+class EvaGeluBlock(_EvaStage):
     """One block of the giant encoder (fused qkv with q / v bias, GELU MLP; timm eva_giant_patch14_560) prepared for psam_eva_gelu_block
     (csrc/blocks.hip).  w: name -> fp32 device tensor; prefix 'pc_encoder.transformer.blocks.i'."""
     PRECISION_F16X3 = 2
-
-    def __init__(self, w, prefix: str, dim: int, heads: int, hidden: int, eps: float):
-        import ctypes
-        L = _lib.load()
-        wt = _lib.EvaGeluBlockWeights()
-        self.keep = []
-        names = dict(norm1_w="norm1.weight", norm1_b="norm1.bias", qkv_w="attn.qkv.weight", q_bias="attn.q_bias", v_bias="attn.v_bias", proj_w="attn.proj.weight",
-                     proj_b="attn.proj.bias", norm2_w="norm2.weight", norm2_b="norm2.bias", fc1_w="mlp.fc1.weight", fc1_b="mlp.fc1.bias", fc2_w="mlp.fc2.weight",
-                     fc2_b="mlp.fc2.bias")
-        for slot, n in names.items():
-            t = w[f"{prefix}.{n}"]
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{prefix}.{n}: contiguous fp32 expected")
-            self.keep.append(t)
-            setattr(wt, slot, t.data_ptr())
-        wt.dim, wt.heads, wt.hidden, wt.precision, wt.eps = int(dim), int(heads), int(hidden), self.PRECISION_F16X3, float(eps)
-        self.plan = _lib.EvaGeluBlockPlan()
-        self.blob = torch.empty(int(L.psam_eva_gelu_block_prepared_bytes(dim, hidden)), dtype=torch.uint8, device=self.keep[0].device)
-        check(L.psam_eva_gelu_block_prepare(ctypes.byref(wt), ctypes.byref(self.plan), self.blob.data_ptr(), self.blob.numel(), _stream()), "psam_eva_gelu_block_prepare")
-        self.dim, self.hidden = int(dim), int(hidden)
+    ENTRY, WEIGHTS, PLAN = "psam_eva_gelu_block", _lib.EvaGeluBlockWeights, _lib.EvaGeluBlockPlan
+    NAMES = dict(norm1_w="norm1.weight", norm1_b="norm1.bias", qkv_w="attn.qkv.weight", q_bias="attn.q_bias", v_bias="attn.v_bias", proj_w="attn.proj.weight",
+                 proj_b="attn.proj.bias", norm2_w="norm2.weight", norm2_b="norm2.bias", fc1_w="mlp.fc1.weight", fc1_b="mlp.fc1.bias", fc2_w="mlp.fc2.weight",
+                 fc2_b="mlp.fc2.bias")
+    EXTRA = dict(precision=PRECISION_F16X3)
 
     @staticmethod
     def supported(dim: int, heads: int, hidden: int) -> bool:
@@ -718,143 +729,106 @@ class EvaGeluBlock:
 
     def run(self, x, B: int, L: int, ws=None):
         """x [B*L, dim] fp32, updated in place."""
-        import ctypes
-        lib = _lib.load()
-        _chk(x, name="x")
-        M = B * L
-        if x.shape != (M, self.dim) or not x.is_contiguous():
-            raise ValueError("x must be a contiguous [B*L, dim] tensor")
-        need = int(lib.psam_eva_gelu_block_ws_bytes(M, self.dim, self.hidden))
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = self._rows(x, B, L, ws)
         # the key-split cap is per CONTEXT (a latency caller next to a multi-stream pipeline on the same model): a private copy of the plan (a small
         # POD the library reads during the call only) carries it; the shared plan is never written after _prepare
         plan = _lib.EvaGeluBlockPlan.from_buffer_copy(self.plan)
         plan.attn_keysplit = current_attention_keysplit()
-        check(lib.psam_eva_gelu_block(ctypes.byref(plan), self.blob.data_ptr(), x.data_ptr(), B, L, ws.data_ptr(), ws.numel(), arrival_counters(x.device).data_ptr(), _stream()),
-              "psam_eva_gelu_block")
+        check(_lib.load().psam_eva_gelu_block(ctypes.byref(plan), self.blob.data_ptr(), x.data_ptr(), B, L, ws.data_ptr(), ws.numel(), arrival_counters(x.device).data_ptr(),
+                                              _stream()), "psam_eva_gelu_block")
         return x
 
 
-class CPatchEncoder:
+class CPatchEncoder(_Stage):
     """A PatchEncoder (common.py:477-506) prepared for psam_patch_encoder (csrc/blocks.hip).  prefix: 'pc_encoder.patch_embed.patch_encoder' |
     'mask_encoder.patch_encoder'."""
+    ENTRY = "psam_patch_encoder"
 
     def __init__(self, w, prefix: str, eps: float):
-        import ctypes
-        L = _lib.load()
+        super().__init__()
         wt = _lib.PatchEncoderWeights()
-        self.keep = []
         for slot, n in (("c10", "conv1.0"), ("c11", "conv1.1"), ("c13", "conv1.3"), ("c20", "conv2.0"), ("c21", "conv2.1"), ("c23", "conv2.3")):
-            for suf, part in (("_w", ".weight"), ("_b", ".bias")):
-                t = w[f"{prefix}.{n}{part}"]
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    raise ValueError(f"{prefix}.{n}{part}: contiguous fp32 expected")
-                self.keep.append(t)
-                setattr(wt, slot + suf, t.data_ptr())
+            setattr(wt, slot + "_w", self._bind(w, f"{prefix}.{n}.weight")); setattr(wt, slot + "_b", self._bind(w, f"{prefix}.{n}.bias"))
         c10, c20, c23 = w[prefix + ".conv1.0.weight"], w[prefix + ".conv2.0.weight"], w[prefix + ".conv2.3.weight"]
         wt.cin, wt.h0, wt.h1, wt.cout, wt.eps = int(c10.shape[1]), int(c10.shape[0]), int(c20.shape[0]), int(c23.shape[0]), float(eps)
         self.h0, self.h1, self.cout = wt.h0, wt.h1, wt.cout
-        self.plan = _lib.PatchEncoderPlan()
-        self.blob = torch.empty(int(L.psam_patch_encoder_prepared_bytes(wt.h0, wt.h1, wt.cout)), dtype=torch.uint8, device=c10.device)
-        check(L.psam_patch_encoder_prepare(ctypes.byref(wt), ctypes.byref(self.plan), self.blob.data_ptr(), self.blob.numel(), _stream()), "psam_patch_encoder_prepare")
+        self._prepare(wt, _lib.PatchEncoderPlan(), wt.h0, wt.h1, wt.cout)
 
     @staticmethod
     def supported(h0: int, h1: int, cout: int) -> bool:
         return h0 == 128 and 256 <= h1 <= 4096 and h1 % 128 == 0 and cout >= 128 and cout % 128 == 0
 
-    def run(self, xyz, feats, centers, knn_idx, radius=None, center_idx=None):
-        import ctypes
-        lib = _lib.load()
+    def run(self, xyz, feats, centers, knn_idx, radius=None, center_idx=None, ws=None):
         _chk(xyz); _chk(feats); _chk(centers); _chk(knn_idx, torch.int64)
         B, N, _ = xyz.shape
         rep = feats.shape[0] // B
         G, K = knn_idx.shape[1:]
         groups = B * rep * G
         out = torch.empty(groups, self.cout, dtype=torch.float32, device=xyz.device)
-        ws = torch.empty(int(lib.psam_patch_encoder_ws_bytes(groups * K, groups, self.h0, self.h1)), dtype=torch.uint8, device=xyz.device)
-        check(lib.psam_patch_encoder(ctypes.byref(self.plan), self.blob.data_ptr(), xyz.data_ptr(), feats.data_ptr(), centers.data_ptr(), knn_idx.data_ptr(),
-                                     _p(center_idx), B, rep, N, G, K, feats.shape[-1], float(radius or 0.0), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+        ws = self._ws(ws, xyz.device, groups * K, groups, self.h0, self.h1)
+        check(_lib.load().psam_patch_encoder(ctypes.byref(self.plan), self.blob.data_ptr(), xyz.data_ptr(), feats.data_ptr(), centers.data_ptr(), knn_idx.data_ptr(),
+                                             _p(center_idx), B, rep, N, G, K, feats.shape[-1], float(radius or 0.0), out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
               "psam_patch_encoder")
         return out
 
 
-class CUpscale:
+class CUpscale(_Stage):
     """The mask decoder's upscaling + hyper-network products prepared for psam_upscale_masks (csrc/blocks.hip; mask_decoder.py:146-176)."""
+    ENTRY = "psam_upscale_masks"
 
     def __init__(self, w, eps: float):
-        import ctypes
-        L = _lib.load()
+        super().__init__()
         wt = _lib.UpscaleWeights()
-        self.keep = []
         for slot, n in (("u0", "0"), ("u1", "1"), ("u3", "3")):
-            for suf, part in (("_w", ".weight"), ("_b", ".bias")):
-                t = w[f"mask_decoder.output_upscaling.{n}{part}"]
-                self.keep.append(t)
-                setattr(wt, slot + suf, t.data_ptr())
+            setattr(wt, slot + "_w", self._bind(w, f"mask_decoder.output_upscaling.{n}.weight")); setattr(wt, slot + "_b", self._bind(w, f"mask_decoder.output_upscaling.{n}.bias"))
         wt.dim, wt.eps = int(w["mask_decoder.output_upscaling.0.weight"].shape[0]), float(eps)
         self.dim = wt.dim
-        self.plan = _lib.UpscalePlan()
-        self.blob = torch.empty(int(L.psam_upscale_masks_prepared_bytes(wt.dim)), dtype=torch.uint8, device=self.keep[0].device)
-        check(L.psam_upscale_masks_prepare(ctypes.byref(wt), ctypes.byref(self.plan), self.blob.data_ptr(), self.blob.numel(), _stream()), "psam_upscale_masks_prepare")
+        self._prepare(wt, _lib.UpscalePlan(), wt.dim)
 
-    def run(self, keys, idx3, w3, hyper, masks, rep, Z, N, G, C):
-        import ctypes
-        lib = _lib.load()
+    def run(self, keys, idx3, w3, hyper, masks, rep, Z, N, G, C, ws=None):
         _chk(keys); _chk(idx3, torch.int64); _chk(w3); _chk(hyper); _chk(masks)
-        ws = torch.empty(int(lib.psam_upscale_masks_ws_bytes(Z, N, G, C, self.dim)), dtype=torch.uint8, device=keys.device)
-        check(lib.psam_upscale_masks(ctypes.byref(self.plan), self.blob.data_ptr(), keys.data_ptr(), idx3.data_ptr(), w3.data_ptr(), hyper.data_ptr(), rep, Z, N, G, C,
-                                     masks.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "psam_upscale_masks")
+        ws = self._ws(ws, keys.device, Z, N, G, C, self.dim)
+        check(_lib.load().psam_upscale_masks(ctypes.byref(self.plan), self.blob.data_ptr(), keys.data_ptr(), idx3.data_ptr(), w3.data_ptr(), hyper.data_ptr(), rep, Z, N, G, C,
+                                             masks.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "psam_upscale_masks")
         return masks
 
 
-class CTwoWay:
+class CTwoWay(_Stage):
     """The decoder's TwoWayTransformer prepared for psam_twoway_decoder (csrc/blocks.hip; transformer.py:61-100).  w: name -> fp32 tensor."""
+    ENTRY = "psam_twoway_decoder"
 
     def __init__(self, w, prefix: str, depth: int, dim: int, heads: int, mlp: int, downsample: int, eps: float):
-        import ctypes
-        L = _lib.load()
+        super().__init__()
         if depth > _lib.TWOWAY_MAX_DEPTH:
             raise ValueError("psam_twoway_decoder: depth > PSAM_TWOWAY_MAX_DEPTH")
-        self.keep = []
-
-        def P(name):
-            t = w[name]
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise ValueError(f"{name}: contiguous fp32 expected")
-            self.keep.append(t)
-            return t.data_ptr()
 
         def attn(dst, p):
             for slot, n in (("q", "q_proj"), ("k", "k_proj"), ("v", "v_proj"), ("o", "out_proj")):
-                setattr(dst, slot + "_w", P(f"{p}.{n}.weight")); setattr(dst, slot + "_b", P(f"{p}.{n}.bias"))
+                setattr(dst, slot + "_w", self._bind(w, f"{p}.{n}.weight")); setattr(dst, slot + "_b", self._bind(w, f"{p}.{n}.bias"))
 
         self.layers = (_lib.TwoWayLayerW * depth)()
         for i in range(depth):
             lp, lw = f"{prefix}.layers.{i}", self.layers[i]
             attn(lw.self_attn, lp + ".self_attn"); attn(lw.t2i, lp + ".cross_attn_token_to_image"); attn(lw.i2t, lp + ".cross_attn_image_to_token")
             for j in (1, 2, 3, 4):
-                setattr(lw, f"n{j}_w", P(f"{lp}.norm{j}.weight")); setattr(lw, f"n{j}_b", P(f"{lp}.norm{j}.bias"))
-            lw.m1_w, lw.m1_b, lw.m2_w, lw.m2_b = P(lp + ".mlp.lin1.weight"), P(lp + ".mlp.lin1.bias"), P(lp + ".mlp.lin2.weight"), P(lp + ".mlp.lin2.bias")
+                setattr(lw, f"n{j}_w", self._bind(w, f"{lp}.norm{j}.weight")); setattr(lw, f"n{j}_b", self._bind(w, f"{lp}.norm{j}.bias"))
+            for j in (1, 2):
+                setattr(lw, f"m{j}_w", self._bind(w, f"{lp}.mlp.lin{j}.weight")); setattr(lw, f"m{j}_b", self._bind(w, f"{lp}.mlp.lin{j}.bias"))
         wt = _lib.TwoWayWeights()
         wt.depth, wt.dim, wt.heads, wt.mlp, wt.downsample, wt.eps = depth, dim, heads, mlp, downsample, float(eps)
         wt.layers = ctypes.cast(self.layers, ctypes.POINTER(_lib.TwoWayLayerW))
         attn(wt.final_attn, prefix + ".final_attn_token_to_image")
-        wt.nf_w, wt.nf_b = P(prefix + ".norm_final_attn.weight"), P(prefix + ".norm_final_attn.bias")
+        wt.nf_w, wt.nf_b = self._bind(w, prefix + ".norm_final_attn.weight"), self._bind(w, prefix + ".norm_final_attn.bias")
         self.dim, self.mlp = dim, mlp
-        self.plan = _lib.TwoWayPlan()
-        self.blob = torch.empty(int(L.psam_twoway_decoder_prepared_bytes(depth, dim, mlp, downsample)), dtype=torch.uint8, device=self.keep[0].device)
-        check(L.psam_twoway_decoder_prepare(ctypes.byref(wt), ctypes.byref(self.plan), self.blob.data_ptr(), self.blob.numel(), _stream()), "psam_twoway_decoder_prepare")
+        self._prepare(wt, _lib.TwoWayPlan(), depth, dim, mlp, downsample)
 
-    def run(self, tokens, keys, pos, rep, Z, T, G):
+    def run(self, tokens, keys, pos, rep, Z, T, G, ws=None):
         """tokens [Z*T, E], keys [Z*G, E] (updated in place), pos [Z/rep, G, E] -> queries [Z*T, E]."""
-        import ctypes
-        lib = _lib.load()
         _chk(tokens); _chk(keys); _chk(pos)
         queries = torch.empty(Z * T, self.dim, dtype=torch.float32, device=tokens.device)
-        ws = torch.empty(int(lib.psam_twoway_decoder_ws_bytes(Z, T, G, self.dim, self.mlp)), dtype=torch.uint8, device=tokens.device)
-        check(lib.psam_twoway_decoder(ctypes.byref(self.plan), self.blob.data_ptr(), tokens.data_ptr(), keys.data_ptr(), pos.data_ptr(), rep, Z, T, G, queries.data_ptr(),
-                                      ws.data_ptr(), ws.numel(), arrival_counters(tokens.device).data_ptr(), _stream()), "psam_twoway_decoder")
+        ws = self._ws(ws, tokens.device, Z, T, G, self.dim, self.mlp)
+        check(_lib.load().psam_twoway_decoder(ctypes.byref(self.plan), self.blob.data_ptr(), tokens.data_ptr(), keys.data_ptr(), pos.data_ptr(), rep, Z, T, G, queries.data_ptr(),
+                                              ws.data_ptr(), ws.numel(), arrival_counters(tokens.device).data_ptr(), _stream()), "psam_twoway_decoder")
         return queries, keys
 
 

@@ -322,6 +322,140 @@ def test_c_eva_gelu_block_matches_python_sequence(gpu):
     assert lib.psam_eva_gelu_block(ctypes.byref(blk.plan), blk.blob.data_ptr(), x.data_ptr(), 2, 256, small.data_ptr(), small.numel(), None, None) == -3      # PSAM_EWORKSPACE
 
 
+GUARD = 4096
+
+
+def _check_exact_workspace(need, call, reset, outputs, want):
+    """A coarse entry of csrc/blocks.hip on a workspace of exactly its *_ws_bytes.  call(ws, ws_bytes) -> status runs the entry through the C ABI;
+    reset() puts back what it updates in place or writes; outputs() are those tensors, want what the Python wrapper computed with a workspace of its
+    own.  The workspace sits between two guards inside a buffer filled with 0xA5: the call leaves both guards alone and gives the wrapper's bits;
+    with one byte less it answers PSAM_EWORKSPACE and touches nothing."""
+    assert need > 0 and need % 256 == 0
+    buf = torch.full((GUARD + need + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    reset()
+    assert call(buf.data_ptr() + GUARD, need) == 0
+    torch.cuda.synchronize()
+    assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[GUARD + need:] == 0xA5).all()), "the call wrote outside its workspace"
+    assert len(outputs()) == len(want) and all(torch.equal(a, b) for a, b in zip(outputs(), want))
+    reset()
+    before = [t.clone() for t in outputs()]
+    assert call(buf.data_ptr() + GUARD, need - 1) == -3      # PSAM_EWORKSPACE
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(outputs(), before))
+
+
+def _record_runs(stage):
+    """Every later stage.run(...) also leaves (args, kwargs) in the returned list, tensors cloned before the call."""
+    calls, run = [], stage.run
+    keep = lambda v: v.clone() if torch.is_tensor(v) else v
+
+    def recording(*args, **kwargs):
+        calls.append((tuple(keep(v) for v in args), {k: keep(v) for k, v in kwargs.items()}))
+        return run(*args, **kwargs)
+    stage.run = recording
+    return calls
+
+
+@pytest.mark.parametrize("kind,B,L", [("swiglu", 2, 128), ("gelu", 2, 256), ("gelu", 9, 256)])
+def test_exact_workspace_of_the_encoder_blocks(gpu, kind, B, L):
+    """psam_eva_block (block 0 of ViT-B) and psam_eva_gelu_block (the mini giant block: one cloud, M = 512, split-K planes and counters in use; a batch,
+    M = 2304, the fused GELU hand-over) on a workspace of exactly *_ws_bytes (_check_exact_workspace)."""
+    import ctypes
+    from point_sam_amd import ops
+    from point_sam_amd.config import ViTConfig
+    lib = ops._lib.load()
+    cfg = get_config("base", 128, 32) if kind == "swiglu" else replace(get_config("giant", 256, 16), vit=ViTConfig("mini_eva_giant", 352, 3, 4, 1024, False))
+    blk = gpu(cfg, random_state_dict(cfg, seed=8), precision="f16x3").blocks[0].c_block
+    assert isinstance(blk, ops.EvaBlock if kind == "swiglu" else ops.EvaGeluBlock)
+    x0 = torch.randn(B * L, cfg.vit.dim, device="cuda")
+    x, want = x0.clone(), blk.run(x0.clone(), B, L)
+    assert torch.isfinite(want).all() and not torch.equal(want, x0)
+    if kind == "swiglu":
+        need = lib.psam_eva_block_ws_bytes(B * L, blk.dim, blk.hidden)
+        call = lambda ws, n: lib.psam_eva_block(ctypes.byref(blk.plan), blk.blob.data_ptr(), x.data_ptr(), B, L, ws, n, ops._stream())
+    else:
+        need = lib.psam_eva_gelu_block_ws_bytes(B * L, blk.dim, blk.hidden)
+        counters = ops.arrival_counters(x.device)
+        call = lambda ws, n: lib.psam_eva_gelu_block(ctypes.byref(blk.plan), blk.blob.data_ptr(), x.data_ptr(), B, L, ws, n, counters.data_ptr(), ops._stream())
+    _check_exact_workspace(need, call, lambda: x.copy_(x0), lambda: [x], [want])
+
+
+@pytest.mark.parametrize("G,K", [(128, 64), (32, 256)])
+def test_exact_workspace_of_the_patch_encoder(gpu, G, K):
+    """psam_patch_encoder as the patch embedding calls it, groups of 64 and of 256 (pooled in 64-row parts: the partial maxima reuse two buffers of the
+    workspace), on a workspace of exactly psam_patch_encoder_ws_bytes (_check_exact_workspace)."""
+    import ctypes
+    from point_sam_amd import ops
+    lib = ops._lib.load()
+    cfg = get_config("tiny", G, K)
+    model = gpu(cfg, random_state_dict(cfg, seed=3), precision="f16x3")
+    enc = model.c_patch["pc_encoder.patch_embed.patch_encoder"]
+    calls = _record_runs(enc)
+    xyz, rgb, _, _ = O.synthetic_batch(2, 9000, seed=4)
+    model.encode(xyz.cuda(), rgb.cuda())
+    (pts, feats, centers, knn_idx), kw = calls[0]
+    want = enc.run(pts, feats, centers, knn_idx, **kw)
+    B, N, rep = pts.shape[0], pts.shape[1], feats.shape[0] // pts.shape[0]
+    groups = B * rep * G
+    assert tuple(knn_idx.shape[1:]) == (G, K) and want.shape == (groups, enc.cout) and torch.isfinite(want).all()
+    out = torch.empty_like(want)
+    call = lambda ws, n: lib.psam_patch_encoder(ctypes.byref(enc.plan), enc.blob.data_ptr(), pts.data_ptr(), feats.data_ptr(), centers.data_ptr(), knn_idx.data_ptr(),
+                                                ops._p(kw.get("center_idx")), B, rep, N, G, K, feats.shape[-1], float(kw.get("radius") or 0.0), out.data_ptr(), ws, n,
+                                                ops._stream())
+    _check_exact_workspace(lib.psam_patch_encoder_ws_bytes(groups * K, groups, enc.h0, enc.h1), call, lambda: out.fill_(-7.0), lambda: [out], [want])
+
+
+def test_exact_workspace_of_the_upscaling(gpu):
+    """psam_upscale_masks as the decoder calls it on a workspace of exactly psam_upscale_masks_ws_bytes (_check_exact_workspace)."""
+    import ctypes
+    from point_sam_amd import ops
+    lib = ops._lib.load()
+    cfg = get_config("tiny", 64, 16)
+    model = gpu(cfg, random_state_dict(cfg, seed=8), precision="f16x3")
+    up = model.c_upscale
+    calls = _record_runs(up)
+    xyz, rgb, prompt, labels = O.synthetic_batch(2, 4096, seed=5)
+    model.predict_masks(xyz.cuda(), rgb.cuda(), prompt.cuda(), labels.cuda())
+    (keys, idx3, w3, hyper, masks, rep, Z, N, G, C), _ = calls[0]
+    want = up.run(keys, idx3, w3, hyper, torch.empty_like(masks), rep, Z, N, G, C)
+    assert (N, G) == (4096, 64) and torch.isfinite(want).all()
+    call = lambda ws, n: lib.psam_upscale_masks(ctypes.byref(up.plan), up.blob.data_ptr(), keys.data_ptr(), idx3.data_ptr(), w3.data_ptr(), hyper.data_ptr(), rep, Z, N, G, C,
+                                                masks.data_ptr(), ws, n, ops._stream())
+    _check_exact_workspace(lib.psam_upscale_masks_ws_bytes(Z, N, G, C, up.dim), call, lambda: masks.fill_(-7.0), lambda: [masks], [want])
+
+
+def test_exact_workspace_of_the_twoway_decoder(gpu):
+    """psam_twoway_decoder as the decoder calls it (two clouds, three prompt points each) on a workspace of exactly psam_twoway_decoder_ws_bytes
+    (_check_exact_workspace), in each of its three launch sequences: they use different buffers of the workspace."""
+    import ctypes
+    from point_sam_amd import ops
+    lib = ops._lib.load()
+    cfg = get_config("base", 256, 32)
+    model = gpu(cfg, random_state_dict(cfg, seed=18), precision="f16x3")
+    tw = model.c_twoway
+    calls = _record_runs(tw)
+    xyz, rgb, prompt, labels = O.synthetic_batch(2, 8192, seed=19, num_prompts=3)
+    model.predict_masks(xyz.cuda(), rgb.cuda(), prompt.cuda(), labels.cuda())
+    (tokens, keys0, pos, rep, Z, T, G), _ = calls[0]
+    assert (Z, G) == (2, 256) and T > 3
+    keys, queries = keys0.clone(), torch.empty(Z * T, tw.dim, device="cuda")
+    counters = ops.arrival_counters(tokens.device)
+    call = lambda ws, n: lib.psam_twoway_decoder(ctypes.byref(tw.plan), tw.blob.data_ptr(), tokens.data_ptr(), keys.data_ptr(), pos.data_ptr(), rep, Z, T, G, queries.data_ptr(),
+                                                 ws, n, counters.data_ptr(), ops._stream())
+
+    def reset():
+        keys.copy_(keys0)
+        queries.fill_(-7.0)
+    try:
+        for mode in (0, 1, 2):
+            lib.psam_twoway_decoder_force_fast(mode)
+            want = tw.run(tokens, keys0.clone(), pos, rep, Z, T, G)
+            assert all(torch.isfinite(t).all() for t in want) and not torch.equal(want[1], keys0)
+            _check_exact_workspace(lib.psam_twoway_decoder_ws_bytes(Z, T, G, tw.dim, tw.mlp), call, reset, lambda: [queries, keys], list(want))
+    finally:
+        lib.psam_twoway_decoder_force_fast(-1)
+
+
 def test_attention_packed_output_is_transparent(gpu):
     """Attention writing its output packed for the projection (bound-derived per-cloud scale) vs fp32 output + separate pack pass: a
     power-of-two scale does not change the decoded hi + lo except where lo goes subnormal (elements ~2^-10 below the row maximum, since

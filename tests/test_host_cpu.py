@@ -202,6 +202,72 @@ def test_host_side_planning_functions_without_a_gpu():
         assert lib.psam_twoway_tokens_ws_floats(2048) == 64 * (5 * 256 + 2048) + 64
 
 
+# What the ten size functions of the coarse entries (csrc/blocks.hip) returned before each became "walk the layout on a null base": argument tuple -> bytes
+COARSE_ENTRY_SIZES = {
+    "psam_eva_block_prepared_bytes": {
+        (1024, 2730): 50678784,
+        (768, 2048): 28375040,
+        (256, 176): 1651712,
+    },
+    "psam_eva_block_ws_bytes": {
+        (256, 1024, 2730): 8244224,
+        (4096, 1024, 2730): 131907584,
+        (256, 768, 2048): 6167552,
+        (4096, 768, 2048): 98680832,
+        (256, 256, 176): 1526784,
+        (4096, 256, 176): 24428544,
+    },
+    "psam_eva_gelu_block_prepared_bytes": {
+        (1408, 6144): 100995072,
+        (352, 1024): 4881920,
+    },
+    "psam_eva_gelu_block_ws_bytes": {
+        (512, 1408, 6144): 123478016,
+        (4608, 1408, 6144): 842866688,
+        (512, 352, 1024): 50012160,
+        (4608, 352, 1024): 181673984,
+    },
+    "psam_patch_encoder_prepared_bytes": {
+        (128, 512, 256): 1119744,
+        (128, 256, 128): 461824,
+    },
+    "psam_patch_encoder_ws_bytes": {
+        (262144, 4096, 128, 512): 821051392,
+        (16384, 64, 128, 256): 33882368,
+    },
+    "psam_upscale_masks_prepared_bytes": {
+        (256,): 526336,
+    },
+    "psam_upscale_masks_ws_bytes": {
+        (8, 32768, 512, 3, 256): 290471936,
+        (2, 4096, 64, 1, 256): 8815104,
+    },
+    "psam_twoway_decoder_prepared_bytes": {
+        (2, 256, 2048, 2): 13675008,
+        (4, 256, 512, 1): 20004864,
+    },
+    "psam_twoway_decoder_ws_bytes": {
+        (8, 6, 512, 256, 2048): 68386816,
+        (1, 7, 64, 256, 2048): 1228544,
+        (6, 14, 256, 256, 2048): 27334656,
+    },
+}
+
+
+def test_coarse_entry_sizes_are_pinned():
+    """The workspace and prepared-blob sizes of the five coarse entries, to the byte: a buffer that enters, leaves or changes size in a layout
+    shows here.  A non-positive argument, whichever, gives 0."""
+    lib = _lib.load()
+    for name, cases in COARSE_ENTRY_SIZES.items():
+        fn = getattr(lib, name)
+        for args, nbytes in cases.items():
+            assert fn(*args) == nbytes, (name, args, fn(*args), nbytes)
+        args = next(iter(cases))
+        for i in range(len(args)):
+            for bad in (0, -1):
+                assert fn(*args[:i], bad, *args[i + 1:]) == 0, (name, i, bad)
+
+
 def test_gemm_mode_is_per_context():
     """The GEMM arithmetic mode is a context variable: a model (or server thread) entering its own precision does not change what another
     thread sees (two models of different precision, the threaded demo server)."""

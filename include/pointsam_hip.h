@@ -614,6 +614,31 @@ size_t psam_mask_paint_workspace_bytes(int32_t K);
 int32_t psam_mask_paint(const uint64_t* bits, const int32_t* order, const uint8_t* keep, int32_t K, int32_t N, int32_t* labels, void* ws,
                         size_t ws_bytes, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- full-resolution scenes */
+
+/* A scan of M points is reduced to a working cloud (one real point per occupied voxel), the model runs on the working cloud, and every point of
+ * the scan receives the result of its voxel's representative (point_sam_amd/scene.py).  Integer work and bit-for-bit copies only: every output is
+ * exact and does not depend on the order in which the waves run.
+ *
+ * psam_voxel_downsample: xyz [M, 3] on the device, 0 < M <= 2^28; origin: three floats in HOST memory.  Cell of a point, per axis, in fp32 with every operation rounded on its own:
+ *   c = floorf((x - origin) * inv_h), inv_h = fl32(1) / fl32(voxel size), computed by the caller.  Voxel key = cx | cy << 21 | cz << 42; the
+ *   representative of a voxel is its point with the lowest index.  keep_idx[0 .. *count) = the representatives in increasing order (room for M
+ *   entries), inv[i] = the position in keep_idx of point i's representative; keep_idx == inv == NULL: only *count is written.
+ *   *flag = 1 if a coordinate is not finite or a cell falls outside [0, 2^21) on any axis, else 0 (the call clears it); with the flag raised the
+ *   other outputs are in range but meaningless.  ws: psam_voxel_downsample_workspace_bytes(M) bytes, 16-byte aligned (an open-addressing table
+ *   at load factor <= 0.5 and the scan's counters).  A null pointer, a bad M, an inv_h that is not finite and positive, or a short workspace: -1. */
+size_t psam_voxel_downsample_workspace_bytes(int32_t M);
+int32_t psam_voxel_downsample(const float* xyz, int32_t M, const float* origin, float inv_h, int64_t* keep_idx, int64_t* inv, int32_t* count,
+                              int32_t* flag, void* ws, size_t ws_bytes, psam_stream_t stream);
+/* dst[r, i] = src[r, inv[i]], i < M, for R rows of Nw 32-bit words copied bit for bit (fp32 logits, int32 labels); src_ld / dst_ld = row strides
+ * in words.  inv is read once per point for all rows; an index outside [0, Nw) stores a zero word. */
+int32_t psam_scene_expand_rows(const void* src, int64_t src_ld, const int64_t* inv, int32_t R, int32_t Nw, int32_t M, void* dst, int64_t dst_ld,
+                               psam_stream_t stream);
+/* Packed masks (the layout of psam_mask_pack): bit i of row k of bits_f [K, ceil(M / 64)] = bit inv[i] of row k of bits_w [K, ceil(Nw / 64)];
+ * bits past M are zero.  area_f [K] (may be NULL) = the popcount of each full row, an integer sum. */
+int32_t psam_scene_expand_bits(const uint64_t* bits_w, const int64_t* inv, int32_t K, int32_t Nw, int32_t M, uint64_t* bits_f, int32_t* area_f,
+                               psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

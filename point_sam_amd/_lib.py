@@ -131,6 +131,10 @@ SIGNATURES = {
     "psam_mask_nms": (i32, [ptr, ptr, ptr, ptr, i32, f32, ptr, ptr, size_t, ptr]),
     "psam_mask_paint_workspace_bytes": (size_t, [i32]),
     "psam_mask_paint": (i32, [ptr, ptr, ptr, i32, i32, ptr, ptr, size_t, ptr]),
+    "psam_voxel_downsample_workspace_bytes": (size_t, [i32]),
+    "psam_voxel_downsample": (i32, [ptr, i32, ptr, f32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_scene_expand_rows": (i32, [ptr, i64, ptr, i32, i32, i32, ptr, i64, ptr]),
+    "psam_scene_expand_bits": (i32, [ptr, ptr, i32, i32, i32, ptr, ptr, ptr]),
 }
 
 

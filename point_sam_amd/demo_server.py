@@ -48,8 +48,10 @@ class DemoSession:
     ``predict_masks(points, labels, prompt_mask, multimask_output) -> (mask, scores, logits)``; ``/segment_all`` also needs
     ``generate_masks(cfg) -> [Proposals]``."""
 
-    def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None):
+    def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None,
+                 working_points: int = None):
         self.predictor = predictor
+        self.working_points = working_points   # None: the model runs on every loaded point; N: on a voxel working cloud of at most N (predictor.set_scene)
         self.models_dir, self.pointcloud, self.output_dir = models_dir, pointcloud, output_dir
         self.static_dir = static_dir           # the front end's files (reference: demo/static); None = not served
         self.device = torch.device(device)
@@ -59,6 +61,12 @@ class DemoSession:
         self.masks = []
         self._reset_prompts()
         self.segment_mask = None
+
+    def _set_cloud(self):
+        if self.working_points is None:
+            self.predictor.set_pointcloud(self.pc_xyz, self.pc_rgb)
+        else:
+            self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points)
 
     def _reset_prompts(self):
         self.prompts, self.labels, self.prompt_mask = [], [], None
@@ -139,7 +147,7 @@ class DemoSession:
             pts = torch.from_numpy(np.array(prompts, dtype=np.float32)).to(self.device).float()[None]
             lab = torch.from_numpy(np.array(labels)).to(self.device)[None]
             with torch.no_grad():
-                self.predictor.set_pointcloud(self.pc_xyz, self.pc_rgb)
+                self._set_cloud()
                 mask, scores, logits = self.predictor.predict_masks(pts, lab, self.prompt_mask, self.prompt_mask is None)
             self.prompts, self.labels = prompts, labels
             best = torch.argmax(scores[0])
@@ -159,7 +167,7 @@ class DemoSession:
                 raise ValueError("/segment_all takes a JSON object of ProposalConfig overrides (or nothing)")
             cfg = ProposalConfig.from_overrides(data)
             with torch.no_grad():
-                self.predictor.set_pointcloud(self.pc_xyz, self.pc_rgb)
+                self._set_cloud()
                 prop = self.predictor.generate_masks(cfg)[0]
             return {"labels": prop.labels.cpu().numpy().astype(int).tolist(), "num_masks": int(len(prop)), "scores": prop.score.cpu().numpy().astype(float).tolist()}
 
@@ -254,10 +262,12 @@ def main():
     ap.add_argument("--models-dir", default="demo/static/models")
     ap.add_argument("--static-dir", default="demo/static", help="the reference front end's files (index.html, *.js, models/)")
     ap.add_argument("--precision", default="f16x3")
+    ap.add_argument("--working-points", type=int, default=None,
+                    help="run the model on a voxel working cloud of at most this many points and answer per loaded point (large scans); default: every point")
     args = ap.parse_args()
     from .predictor import PointSAMPredictor
     pred = PointSAMPredictor.from_config(args.config, args.ckpt, precision=args.precision)
-    srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir), args.host, args.port)
+    srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points), args.host, args.port)
     print(f"Point-SAM demo back end on http://{args.host}:{args.port}")
     srv.serve_forever()
 

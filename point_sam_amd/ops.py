@@ -1176,3 +1176,94 @@ def mask_unpack(bits: torch.Tensor, N: int) -> torch.Tensor:
     """bits [k, W] int64 words -> [k, N] bool (plain torch; for inspection and tests, not on a hot path)."""
     sh = torch.arange(64, device=bits.device, dtype=torch.int64)
     return ((bits.unsqueeze(-1) >> sh) & 1).to(torch.bool).reshape(bits.shape[0], -1)[:, :N]
+
+
+# ------------------------------------------------------------------------------------------ full-resolution scenes (csrc/scene.hip)
+def _voxel_call(xyz, voxel_size, origin, full: bool):
+    import numpy as np
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    _chk(xyz, name="xyz")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f"voxel_downsample: xyz must be [M, 3] with M >= 1 (one scene), got {tuple(xyz.shape)}")
+    h = np.float32(voxel_size)
+    if not (np.isfinite(h) and h > 0):
+        raise ValueError(f"voxel_downsample: voxel_size must be finite and positive, got {voxel_size!r}")
+    inv_h = np.float32(1) / h                              # fp32, as the header defines it
+    if not (np.isfinite(inv_h) and inv_h > 0):
+        raise ValueError(f"voxel_downsample: 1 / voxel_size is not a positive fp32 number for voxel_size {voxel_size!r}")
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    M, dev = xyz.shape[0], xyz.device
+    L = _lib.load()
+    nbytes = L.psam_voxel_downsample_workspace_bytes(M)
+    if nbytes == 0:
+        raise ValueError(f"voxel_downsample: {M} points exceed the 2^28 the table is built for")
+    ws = torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    keep_idx = torch.empty(M, dtype=torch.int64, device=dev) if full else None
+    inv = torch.empty(M, dtype=torch.int64, device=dev) if full else None
+    cf = torch.empty(2, dtype=torch.int32, device=dev)    # count, flag: read together, the call's one host synchronisation
+    check(L.psam_voxel_downsample(xyz.data_ptr(), M, ctypes.addressof(org), float(inv_h), _p(keep_idx), _p(inv), cf.data_ptr(), cf.data_ptr() + 4,
+                                  ws.data_ptr(), ws.numel() * 8, _stream()), "psam_voxel_downsample")
+    count, flag = cf.tolist()
+    if flag != 0:
+        raise ValueError(f"voxel_downsample: a coordinate is not finite, or its cell at voxel size {float(h)} from origin {tuple(float(v) for v in origin)} "
+                         "falls outside [0, 2^21)")
+    return count, keep_idx, inv
+
+
+def voxel_downsample(xyz: torch.Tensor, voxel_size: float, origin=(-1.0, -1.0, -1.0)):
+    """xyz [M, 3] f32 -> (keep_idx [count] int64, inv [M] int64).  Cell = floor((x - origin) * fl32(1 / voxel_size)) per axis in fp32; keep_idx = the
+    lowest point index of every occupied voxel, increasing; inv[i] = the position in keep_idx of point i's representative (inv[keep_idx[j]] == j).
+    ValueError for a non-finite coordinate or a cell outside [0, 2^21).  One host synchronisation: the read of the count."""
+    count, keep_idx, inv = _voxel_call(xyz, voxel_size, origin, True)
+    return keep_idx[:count], inv
+
+
+def voxel_count(xyz: torch.Tensor, voxel_size: float, origin=(-1.0, -1.0, -1.0)) -> int:
+    """The number of occupied voxels (the length of voxel_downsample's keep_idx) without writing the index arrays."""
+    return _voxel_call(xyz, voxel_size, origin, False)[0]
+
+
+def scene_expand_rows(src: torch.Tensor, inv: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """src [..., Nw] f32 or int32 (the leading dimensions are R rows with one stride; last stride 1), inv [M] int64 -> [..., M] of the same dtype:
+    out[r, i] = src[r, inv[i]] bit for bit.  out: a [R, M] destination with its own row stride."""
+    if not src.is_cuda:
+        raise _lib.PointSamHipError("src must live on the GPU: the HIP path has no CPU fallback")
+    if src.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"scene_expand_rows: rows of 32-bit words (float32 / int32), got {src.dtype}")
+    _chk(inv, torch.int64, "inv")
+    Nw, M = src.shape[-1], inv.numel()
+    lead = tuple(src.shape[:-1])
+    rows = src.reshape(-1, Nw) if src.dim() != 2 else src
+    if rows.stride(1) != 1 and Nw > 1:
+        rows = rows.contiguous()
+    R = rows.shape[0]
+    if R < 1 or Nw < 1 or M < 1:
+        raise ValueError(f"scene_expand_rows: empty input: src {tuple(src.shape)}, inv [{M}]")
+    src_ld = rows.stride(0) if R > 1 else Nw
+    if src_ld < Nw:
+        rows, src_ld = rows.contiguous(), Nw
+    if out is None:
+        dst = torch.empty(R, M, dtype=src.dtype, device=src.device)
+    else:
+        dst = out
+        if dst.dtype != src.dtype or dst.dim() != 2 or tuple(dst.shape) != (R, M) or (M > 1 and dst.stride(1) != 1) or (R > 1 and dst.stride(0) < M):
+            raise ValueError(f"scene_expand_rows: out must be [{R}, {M}] {src.dtype} with unit column stride, got {tuple(dst.shape)} {dst.dtype}")
+    dst_ld = dst.stride(0) if R > 1 else M
+    check(_lib.load().psam_scene_expand_rows(rows.data_ptr(), src_ld, inv.data_ptr(), R, Nw, M, dst.data_ptr(), dst_ld, _stream()), "psam_scene_expand_rows")
+    return dst if out is not None else dst.reshape(lead + (M,))
+
+
+def scene_expand_bits(bits_w: torch.Tensor, inv: torch.Tensor, Nw: int, area: bool = True):
+    """bits_w [K, ceil(Nw / 64)] int64 words (mask_pack's layout), inv [M] int64 -> (bits_f [K, ceil(M / 64)] int64, area_f [K] int32 or None):
+    bit i of a full row = bit inv[i] of the working row; bits past M are zero; area_f = the full rows' popcounts."""
+    _chk(bits_w, torch.int64, "bits_w"); _chk(inv, torch.int64, "inv")
+    M = inv.numel()
+    if bits_w.dim() != 2 or Nw < 1 or bits_w.shape[1] != mask_words(Nw) or M < 1:
+        raise ValueError(f"scene_expand_bits: bits_w {tuple(bits_w.shape)} for Nw = {Nw}, inv [{M}]")
+    K = bits_w.shape[0]
+    bits_f = torch.empty(K, mask_words(M), dtype=torch.int64, device=bits_w.device)
+    area_f = torch.empty(K, dtype=torch.int32, device=bits_w.device) if area else None
+    if K > 0:
+        check(_lib.load().psam_scene_expand_bits(bits_w.data_ptr(), inv.data_ptr(), K, Nw, M, bits_f.data_ptr(), _p(area_f), _stream()), "psam_scene_expand_bits")
+    return bits_f, area_f

@@ -13,6 +13,7 @@ from typing import Optional
 
 import torch
 
+from . import ops
 from .config import ModelConfig, get_config
 from .model import EncoderState, PointCloudSAM
 from .weights import load_safetensors, random_state_dict
@@ -24,6 +25,7 @@ class PointSAMPredictor:
         self._state: Optional[EncoderState] = None
         self._key = None
         self._prompts = None
+        self.scene = None               # set_scene(): the scan <-> working-cloud mapping (point_sam_amd/scene.py); None after set_pointcloud()
 
     @classmethod
     def from_config(cls, name: str, ckpt_path: str = None, num_groups: int = None, group_size: int = None, seed: int = 42,
@@ -49,6 +51,25 @@ class PointSAMPredictor:
             self._state = self.model.encode(xyz, rgb)
             self._key = key
             self._keepalive = (xyz, rgb)  # the cache key uses data_ptr: keep the tensors alive
+            self.scene = None
+
+    @torch.no_grad()
+    def set_scene(self, xyz: torch.Tensor, rgb: torch.Tensor, voxel_size: float = None, max_points: int = None) -> None:
+        """A full-resolution scan, xyz / rgb [M, 3] normalised as for set_pointcloud, served through a voxel-grid working cloud: one real point per
+        occupied voxel of size `voxel_size`, or of the smallest ladder size that leaves at most `max_points` (scene.choose_voxel_size); a scan of at
+        most `max_points` points is its own working cloud.  predict_masks / generate_masks then answer per point of the scan.  Cached like
+        set_pointcloud; `self.scene` holds keep_idx, inv and num_working."""
+        from . import scene as S
+        xyz, rgb = S.check_scene_arguments(xyz, rgb, voxel_size, max_points)
+        g = self.model.pc_encoder.patch_embed.grouper
+        key = self._cloud_key(xyz, rgb) + (g.num_groups, g.group_size, "scene", voxel_size, max_points)
+        if key != self._key:
+            sc = S.build_scene(xyz, voxel_size, max_points)
+            wx, wr = (xyz, rgb) if sc.identity else (xyz.index_select(0, sc.keep_idx), rgb.index_select(0, sc.keep_idx))
+            self._state = self.model.encode(wx[None], wr[None])
+            self._key = key
+            self._keepalive = (xyz, rgb)
+            self.scene = sc
 
     def set_prompts(self, prompt_points, prompt_labels, prompt_mask=None) -> None:
         self._prompts = (prompt_points, prompt_labels, prompt_mask)
@@ -56,15 +77,22 @@ class PointSAMPredictor:
     @torch.no_grad()
     def predict_masks(self, prompt_points=None, prompt_labels=None, prompt_mask=None, multimask_output: bool = True):
         """-> (masks [BM,C,N] logits, scores [BM,C], logits [BM,C,N]); masks and logits are the same tensor, the
-        caller thresholds at 0 (demo/app.py:203-205)."""
+        caller thresholds at 0 (demo/app.py:203-205).  After set_scene: N = the scan's points; a prompt_mask may have the scan's or the working
+        cloud's width."""
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
         if prompt_points is None:
             if self._prompts is None:
                 raise RuntimeError("no prompts: pass them or call set_prompts() first")
             prompt_points, prompt_labels, prompt_mask = self._prompts
+        sc = self.scene
+        if sc is not None:
+            from .scene import reduce_prompt_mask
+            prompt_mask = reduce_prompt_mask(sc, prompt_mask)
         logits, scores = self.model.decode(self._state, prompt_points, prompt_labels, prompt_mask, multimask_output)
         self.model.check_coordinate_range()
+        if sc is not None and not sc.identity:
+            logits = ops.scene_expand_rows(logits, sc.inv)       # [M', C, num_working] -> [M', C, M]: each point takes its representative's logit
         return logits, scores, logits
 
     @torch.no_grad()
@@ -75,4 +103,8 @@ class PointSAMPredictor:
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
         from .proposals import generate_proposals
-        return generate_proposals(self.model, self._state, cfg)
+        out = generate_proposals(self.model, self._state, cfg)
+        if self.scene is not None:
+            from .scene import expand_proposals
+            out = [expand_proposals(self.scene, p) for p in out]
+        return out

@@ -1,0 +1,111 @@
+"""Full-resolution scenes: a scan of M points (one to several million) served by the model through a voxel-grid working cloud.
+
+One real point per occupied voxel is kept (the one with the lowest index), the model runs on those, and every point of the scan receives the result of
+its voxel's representative.  The reduction and the transfer are ``csrc/scene.hip``: a device hash of the scan and gathers of 32-bit words or of single
+bits, all integer work or bit-for-bit copies, so a result at full resolution is exactly the working cloud's result indexed by ``inv``.
+
+    pred.set_scene(xyz, rgb, max_points=131072)          # xyz [M, 3] in [-1, 1], rgb as for set_pointcloud
+    logits, scores, _ = pred.predict_masks(points, labels)   # logits [M', C, M]
+    pred.scene.keep_idx, pred.scene.inv, pred.scene.num_working
+"""
+from dataclasses import dataclass
+from typing import Callable, Optional
+
+import torch
+
+from . import ops
+
+LADDER_STEPS = 80                                         # voxel sizes 2 ** (1 - k / 4), k = 0 .. 80: from the whole cube down to 2^-19
+
+
+def ladder(k: int) -> float:
+    return 2.0 ** (1.0 - k / 4.0)
+
+
+def choose_voxel_size(xyz: torch.Tensor, max_points: int, count: Optional[Callable[[int], int]] = None) -> float:
+    """The smallest voxel size of the ladder ``h_k = 2 ** (1 - k / 4)``, k = 0 .. 80, found by bisection, that leaves at most `max_points` occupied
+    voxels (origin (-1, -1, -1)).  The procedure is the definition: ``lo, hi = 0, 80``; while ``hi - lo > 1``: ``mid = (lo + hi) // 2``, ``lo = mid`` if
+    ``count(mid) <= max_points`` else ``hi = mid``; the result is ``h_lo``.  ValueError if even h_0 leaves more than `max_points`.  About seven
+    count-only passes over the scan.  count: k -> occupied voxels at h_k (default: ops.voxel_count on `xyz`)."""
+    if isinstance(max_points, bool) or not isinstance(max_points, int) or max_points < 1:
+        raise ValueError(f"max_points must be a positive integer, got {max_points!r}")
+    if count is None:
+        count = lambda k: ops.voxel_count(xyz, ladder(k))
+    n0 = count(0)
+    if n0 > max_points:
+        raise ValueError(f"the coarsest voxel size {ladder(0)} still leaves {n0} points, more than max_points = {max_points}")
+    lo, hi = 0, LADDER_STEPS
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if count(mid) <= max_points:
+            lo = mid
+        else:
+            hi = mid
+    return ladder(lo)
+
+
+@dataclass
+class Scene:
+    """The mapping between a scan and its working cloud.  ``inv[keep_idx[j]] == j``; ``keep_idx`` is strictly increasing."""
+    num_points: int                 # M
+    num_working: int
+    keep_idx: torch.Tensor          # [num_working] int64: the scan indices of the working cloud's points
+    inv: torch.Tensor               # [M] int64: the working-cloud row of each scan point's representative
+    voxel_size: Optional[float]     # None: the scene is its own working cloud
+    identity: bool                  # keep_idx == inv == arange(M): nothing is gathered or expanded
+
+
+def check_scene_arguments(xyz, rgb, voxel_size, max_points):
+    """-> (xyz [M, 3], rgb [M, 3]).  One cloud; exactly one of voxel_size / max_points."""
+    if (voxel_size is None) == (max_points is None):
+        raise ValueError("set_scene: give exactly one of voxel_size and max_points")
+    if voxel_size is not None and (isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float)) or not 0 < voxel_size < float("inf")):
+        raise ValueError(f"set_scene: voxel_size must be a finite positive number, got {voxel_size!r}")
+    if max_points is not None and (isinstance(max_points, bool) or not isinstance(max_points, int) or max_points < 1):
+        raise ValueError(f"set_scene: max_points must be a positive integer, got {max_points!r}")
+    if xyz.dim() == 3:
+        if xyz.shape[0] != 1:
+            raise ValueError(f"set_scene: a scene is one cloud (B = 1), got a batch of {xyz.shape[0]}")
+        xyz = xyz[0]
+    if rgb.dim() == 3:
+        if rgb.shape[0] != 1:
+            raise ValueError(f"set_scene: a scene is one cloud (B = 1), got a batch of {rgb.shape[0]}")
+        rgb = rgb[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1 or tuple(rgb.shape) != tuple(xyz.shape):
+        raise ValueError(f"set_scene: xyz and rgb must both be [M, 3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+    return xyz, rgb
+
+
+def build_scene(xyz: torch.Tensor, voxel_size: Optional[float], max_points: Optional[int]) -> Scene:
+    """xyz [M, 3] on the device.  With max_points and M <= max_points the scene is its own working cloud and no kernel runs."""
+    M = xyz.shape[0]
+    if max_points is not None:
+        if M <= max_points:
+            ar = torch.arange(M, dtype=torch.int64, device=xyz.device)
+            return Scene(M, M, ar, ar, None, True)
+        voxel_size = choose_voxel_size(xyz, max_points)
+    keep_idx, inv = ops.voxel_downsample(xyz, voxel_size)
+    return Scene(M, keep_idx.numel(), keep_idx, inv, float(voxel_size), False)
+
+
+def reduce_prompt_mask(scene: Scene, prompt_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A mask prompt of the scan's width -> the working cloud's width: the representatives' own values (exact: inv[keep_idx[j]] == j).  A mask of
+    the working cloud's width passes unchanged."""
+    if prompt_mask is None or scene.identity or prompt_mask.shape[-1] == scene.num_working:
+        return prompt_mask
+    if prompt_mask.shape[-1] != scene.num_points:
+        raise ValueError(f"prompt_mask has width {prompt_mask.shape[-1]}: neither the scene's {scene.num_points} points nor its {scene.num_working} working points")
+    return prompt_mask.to(scene.keep_idx.device).index_select(-1, scene.keep_idx)
+
+
+def expand_proposals(scene: Scene, p):
+    """A working-cloud `Proposals` -> the same proposals at full resolution: bits, area and labels per scan point; scores, candidates, stability and the
+    order are the working cloud's (filtering and suppression were decided there)."""
+    import dataclasses
+    if scene.identity:
+        return p
+    if len(p) > 0:
+        bits, area = ops.scene_expand_bits(p.bits.contiguous(), scene.inv, scene.num_working)
+    else:
+        bits, area = p.bits.new_zeros(0, ops.mask_words(scene.num_points)), p.area
+    return dataclasses.replace(p, n_points=scene.num_points, bits=bits, area=area, labels=ops.scene_expand_rows(p.labels, scene.inv))

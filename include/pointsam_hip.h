@@ -639,6 +639,36 @@ int32_t psam_scene_expand_rows(const void* src, int64_t src_ld, const int64_t* i
 int32_t psam_scene_expand_bits(const uint64_t* bits_w, const int64_t* inv, int32_t K, int32_t Nw, int32_t M, uint64_t* bits_f, int32_t* area_f,
                                psam_stream_t stream);
 
+/* ---------------------------------------------------------------- connected components of masks */
+
+/* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel
+ * downsample above (same origin and inv_h); keep_idx [V] and inv [N] are its outputs for the cloud at that voxel size.  Points i and j are
+ * adjacent iff their cells differ by at most 1 on every axis; the components of a point set are those of the subgraph it induces.  A
+ * component's id is the lowest inv[] among its points, its size its number of points.  Integers and bits only: every output is exact and does
+ * not depend on the order in which the waves run.  No call allocates or synchronises with the host; a null pointer or a bad shape returns -1, a
+ * short workspace -3, a workspace that is not 16-byte aligned -2.  K <= 65535 rows per call; N, V <= 2^28.
+ *
+ * Neighbours: nbr [V, 26] int32, entry o of voxel v = the rank (position in keep_idx) of the occupied voxel at v's cell + offset o, or -1; the
+ *   offsets run over (dz, dy, dx) in {-1, 0, 1}^3 with dz slowest and (0, 0, 0) skipped, so offset 25 - o is the opposite of o.  A cell outside
+ *   [0, 2^21) on an axis is -1.  origin: three floats in HOST memory. */
+size_t psam_region_neighbors_workspace_bytes(int32_t V);
+int32_t psam_region_neighbors(const float* xyz, const int64_t* keep_idx, int32_t V, const float* origin, float inv_h, int32_t* nbr, void* ws,
+                              size_t ws_bytes, psam_stream_t stream);
+/* labels [K, N] int32: per point the id of its component within row k of bits [K, ceil(N / 64)] (the layout of the mask proposals), -1 outside
+ *   the set; complement != 0: the set is the points below N that are NOT in the row. */
+size_t psam_region_labels_workspace_bytes(int32_t K, int32_t N, int32_t V);
+int32_t psam_region_labels(const uint64_t* bits, const int64_t* inv, const int32_t* nbr, int32_t K, int32_t N, int32_t V, int32_t complement,
+                           int32_t* labels, void* ws, size_t ws_bytes, psam_stream_t stream);
+/* Clean-up of every row with select[k] != 0 (select NULL: every row), in this order: (1) min_hole > 0: every component of the complement with
+ *   fewer than min_hole points joins the mask; (2) min_island > 0: every component of the result with fewer than min_island points is removed,
+ *   except the largest (size ties: the lowest id); (3) S > 0, seeds [K, S] int32 point indices, -1 = unused: if a seed of the row is a member
+ *   after (2), only the components that hold such a seed stay.  An empty row stays empty; an unselected row is copied bit for bit.  bits_out
+ *   [K, W] (must not alias bits; bits past N are zero), area_out [K] = the popcounts, changed [K] uint8 = the row differs from its input. */
+size_t psam_region_clean_workspace_bytes(int32_t K, int32_t N, int32_t V, int32_t S);
+int32_t psam_region_clean(const uint64_t* bits, const uint8_t* select, const int64_t* inv, const int32_t* nbr, const int32_t* seeds, int32_t K,
+                          int32_t N, int32_t V, int32_t S, int32_t min_island, int32_t min_hole, uint64_t* bits_out, int32_t* area_out,
+                          uint8_t* changed, void* ws, size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

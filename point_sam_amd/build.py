@@ -31,6 +31,7 @@ SOURCES = [
     ("blocks.hip", []),
     ("masks.hip", []),
     ("scene.hip", ["-ffp-contract=off"]),      # voxel cells: floorf((x - origin) * inv_h) with every operation rounded on its own
+    ("regions.hip", ["-ffp-contract=off"]),    # the same cells as scene.hip (csrc/voxel_cell.h)
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

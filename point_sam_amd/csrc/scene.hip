@@ -19,25 +19,15 @@
 // Which slot a key lands in depends on the arrival order of the waves; slot numbers never leave the workspace, and the lowest index of a slot,
 // the flags and the ranks do not depend on them.
 #include "common.h"
+#include "voxel_cell.h"      // cells, keys, the hash, the table's capacity: shared with regions.hip
 
 #include <cmath>
 
-typedef unsigned long long u64;
-
-constexpr int VOXEL_AXIS_BITS = 21;
-constexpr int VOXEL_MAX_POINTS = 1 << 28;        // the table then has 2^29 slots: slot numbers and ranks stay in int32
-constexpr u64 VOXEL_EMPTY = ~0ull;                // also the key of a point that has no cell (non-finite / out of range)
 constexpr int SCAN_THREADS = 1024;                // points per block of the look-up and rank kernels
 constexpr int SCAN_WAVES = SCAN_THREADS / WAVE;
 constexpr int VOXEL_THREADS = 256;
 
-static inline int64_t voxel_capacity(int64_t M) {
-    int64_t c = 64;
-    while (c < 2 * M) c <<= 1;
-    return c;
-}
 static inline int64_t scan_blocks(int64_t M) { return psam_cdiv(M, SCAN_THREADS); }
-static inline size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 struct VoxelWs {
     u64* keys;            // [C]
@@ -69,22 +59,6 @@ __global__ __launch_bounds__(VOXEL_THREADS) void voxel_clear_kernel(uint4* __res
 }
 
 // ------------------------------------------------------------------------------------------------ insert
-__device__ __forceinline__ bool voxel_axis(float x, float origin, float inv_h, u64& cell) {
-#pragma clang fp contract(off)
-    const float d = x - origin;
-    const float s = d * inv_h;
-    const float c = floorf(s);
-    if (!(c >= 0.0f && c < (float)(1 << VOXEL_AXIS_BITS))) return false;      // NaN compares false: never an out-of-range cast
-    cell = (u64)(unsigned)(int)c;
-    return true;
-}
-
-__device__ __forceinline__ u64 voxel_hash(u64 k) {      // the 64-bit finaliser of MurmurHash3
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull;
-    k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull;
-    return k ^ (k >> 33);
-}
-
 __global__ __launch_bounds__(VOXEL_THREADS) void voxel_insert_kernel(const float* __restrict__ xyz, int M, float ox, float oy, float oz, float inv_h,
                                                                     u64* __restrict__ keys, unsigned* __restrict__ low, int capacity,
                                                                     int* __restrict__ slot_of, int* __restrict__ flag) {
@@ -95,7 +69,7 @@ __global__ __launch_bounds__(VOXEL_THREADS) void voxel_insert_kernel(const float
         u64 cx, cy, cz;
         const bool ok = voxel_axis(xyz[(int64_t)i * 3 + 0], ox, inv_h, cx) & voxel_axis(xyz[(int64_t)i * 3 + 1], oy, inv_h, cy) &
                         voxel_axis(xyz[(int64_t)i * 3 + 2], oz, inv_h, cz);
-        if (ok) key = cx | (cy << VOXEL_AXIS_BITS) | (cz << (2 * VOXEL_AXIS_BITS));
+        if (ok) key = voxel_key(cx, cy, cz);
         else *flag = 1;                                            // every writer stores the same value
     }
     // a run of equal keys on consecutive lanes: its first lane probes and takes the minimum for all of them

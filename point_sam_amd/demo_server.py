@@ -46,11 +46,17 @@ def safe_join(root: str, rel: str) -> str:
 class DemoSession:
     """The demo's state machine.  ``predictor`` needs ``set_pointcloud(xyz, rgb)`` and
     ``predict_masks(points, labels, prompt_mask, multimask_output) -> (mask, scores, logits)``; ``/segment_all`` also needs
-    ``generate_masks(cfg) -> [Proposals]``."""
+    ``generate_masks(cfg) -> [Proposals]``; with ``clean_min_points`` ``/segment`` also needs
+    ``clean_masks(logits, cfg, points, labels) -> (bits, area, changed)``."""
 
     def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None,
-                 working_points: int = None):
+                 working_points: int = None, clean_min_points: int = None):
         self.predictor = predictor
+        if clean_min_points is not None and (isinstance(clean_min_points, bool) or not isinstance(clean_min_points, int) or clean_min_points < 1):
+            raise ValueError(f"clean_min_points must be a positive integer or None, got {clean_min_points!r}")
+        # None: /segment answers with the thresholded mask; N: with the part of it that hangs together with the positive clicks, holes and islands
+        # below N points filled / removed (predictor.clean_masks)
+        self.clean_min_points = clean_min_points
         self.working_points = working_points   # None: the model runs on every loaded point; N: on a voxel working cloud of at most N (predictor.set_scene)
         self.models_dir, self.pointcloud, self.output_dir = models_dir, pointcloud, output_dir
         self.static_dir = static_dir           # the front end's files (reference: demo/static); None = not served
@@ -152,7 +158,15 @@ class DemoSession:
             self.prompts, self.labels = prompts, labels
             best = torch.argmax(scores[0])
             self.prompt_mask = logits[0][best][None]
-            self.segment_mask = mask[0][best] > 0
+            if self.clean_min_points is None:
+                self.segment_mask = mask[0][best] > 0
+            else:
+                from . import ops
+                from .regions import RegionConfig
+                cfg = RegionConfig(min_island=self.clean_min_points, min_hole=self.clean_min_points, keep_clicked=True)
+                with torch.no_grad():
+                    bits, _, _ = self.predictor.clean_masks(logits[:1, best:best + 1], cfg, pts, lab)
+                self.segment_mask = ops.mask_unpack(bits, mask.shape[-1])[0]
             return {"seg": self.segment_mask.cpu().numpy().tolist()}
 
     def segment_all(self, data: dict) -> dict:
@@ -264,10 +278,13 @@ def main():
     ap.add_argument("--precision", default="f16x3")
     ap.add_argument("--working-points", type=int, default=None,
                     help="run the model on a voxel working cloud of at most this many points and answer per loaded point (large scans); default: every point")
+    ap.add_argument("--clean-min-points", type=int, default=None,
+                    help="answer /segment with the cleaned mask: holes and islands below this many points filled / removed, only the clicked part kept")
     args = ap.parse_args()
     from .predictor import PointSAMPredictor
     pred = PointSAMPredictor.from_config(args.config, args.ckpt, precision=args.precision)
-    srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points), args.host, args.port)
+    srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points,
+                            clean_min_points=args.clean_min_points), args.host, args.port)
     print(f"Point-SAM demo back end on http://{args.host}:{args.port}")
     srv.serve_forever()
 

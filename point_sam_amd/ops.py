@@ -1267,3 +1267,97 @@ def scene_expand_bits(bits_w: torch.Tensor, inv: torch.Tensor, Nw: int, area: bo
     if K > 0:
         check(_lib.load().psam_scene_expand_bits(bits_w.data_ptr(), inv.data_ptr(), K, Nw, M, bits_f.data_ptr(), _p(area_f), _stream()), "psam_scene_expand_bits")
     return bits_f, area_f
+
+
+# ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)
+def _region_ws(nbytes: int, dev, what: str):
+    if nbytes == 0:
+        raise ValueError(f"{what}: the shape is outside what the kernels are built for (K <= 65535 rows per call, N, V <= 2^28)")
+    return torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+
+
+def _region_graph_chk(inv, nbr, what: str):
+    _chk(inv, torch.int64, "inv"); _chk(nbr, torch.int32, "nbr")
+    if inv.dim() != 1 or nbr.dim() != 2 or nbr.shape[1] != 26 or nbr.shape[0] < 1 or inv.numel() < 1:
+        raise ValueError(f"{what}: inv must be [N] and nbr [V, 26], got {tuple(inv.shape)} and {tuple(nbr.shape)}")
+    return inv.numel(), nbr.shape[0]
+
+
+def region_neighbors(xyz: torch.Tensor, keep_idx: torch.Tensor, voxel_size: float, origin=(-1.0, -1.0, -1.0)) -> torch.Tensor:
+    """xyz [N, 3] f32, keep_idx [V] int64 (voxel_downsample's, at the same voxel_size and origin) -> nbr [V, 26] int32: the rank of the occupied voxel
+    at voxel v's cell + offset o, or -1; offsets over (dz, dy, dx) in {-1, 0, 1}^3, dz slowest, the centre skipped (offset 25 - o is the opposite of
+    o).  No host synchronisation."""
+    import numpy as np
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    _chk(xyz, name="xyz"); _chk(keep_idx, torch.int64, "keep_idx")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or keep_idx.dim() != 1 or not 1 <= keep_idx.numel() <= xyz.shape[0]:
+        raise ValueError(f"region_neighbors: xyz must be [N, 3] and keep_idx [V] with 1 <= V <= N, got {tuple(xyz.shape)} and {tuple(keep_idx.shape)}")
+    h = np.float32(voxel_size)
+    inv_h = np.float32(1) / h if np.isfinite(h) and h > 0 else np.float32("nan")      # fp32, as the header defines it
+    if not (np.isfinite(inv_h) and inv_h > 0):
+        raise ValueError(f"region_neighbors: voxel_size must be finite and positive with a positive fp32 inverse, got {voxel_size!r}")
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    V = keep_idx.numel()
+    L = _lib.load()
+    nbytes = L.psam_region_neighbors_workspace_bytes(V)
+    ws = _region_ws(nbytes, xyz.device, "region_neighbors")
+    nbr = torch.empty(V, 26, dtype=torch.int32, device=xyz.device)
+    check(L.psam_region_neighbors(xyz.data_ptr(), keep_idx.data_ptr(), V, ctypes.addressof(org), float(inv_h), nbr.data_ptr(), ws.data_ptr(),
+                                  ws.numel() * 8, _stream()), "psam_region_neighbors")
+    return nbr
+
+
+def region_labels(bits: torch.Tensor, inv: torch.Tensor, nbr: torch.Tensor, complement: bool = False) -> torch.Tensor:
+    """bits [K, W] int64 words (mask_pack's layout), inv [N] int64, nbr [V, 26] int32 -> labels [K, N] int32: per point the id of its component
+    within the row's mask (the lowest voxel rank in the component), -1 outside the set; complement: the set is the points not in the row."""
+    _chk(bits, torch.int64, "bits")
+    N, V = _region_graph_chk(inv, nbr, "region_labels")
+    if bits.dim() != 2 or bits.shape[0] < 1 or bits.shape[1] != mask_words(N):
+        raise ValueError(f"region_labels: bits {tuple(bits.shape)} for N = {N}")
+    K = bits.shape[0]
+    L = _lib.load()
+    nbytes = L.psam_region_labels_workspace_bytes(K, N, V)
+    ws = _region_ws(nbytes, bits.device, "region_labels")
+    labels = torch.empty(K, N, dtype=torch.int32, device=bits.device)
+    check(L.psam_region_labels(bits.data_ptr(), inv.data_ptr(), nbr.data_ptr(), K, N, V, 1 if complement else 0, labels.data_ptr(), ws.data_ptr(),
+                               ws.numel() * 8, _stream()), "psam_region_labels")
+    return labels
+
+
+def region_clean_workspace_bytes(K: int, N: int, V: int, S: int) -> int:
+    return _lib.load().psam_region_clean_workspace_bytes(K, N, V, S)
+
+
+def region_clean(bits: torch.Tensor, inv: torch.Tensor, nbr: torch.Tensor, min_island: int = 0, min_hole: int = 0, select: torch.Tensor = None,
+                 seeds: torch.Tensor = None):
+    """bits [K, W] int64, inv [N] int64, nbr [V, 26] int32, select [K] uint8 or None (every row), seeds [K, S] int32 point indices (-1 = unused) or
+    None -> (bits_out [K, W] int64, area [K] int32, changed [K] uint8).  Per selected row, in order: complement components below min_hole points join
+    the mask; components below min_island points leave it, except the largest (ties: lowest id); if a seed is a member then, only the components
+    holding one stay.  An empty row stays empty; an unselected row is copied."""
+    _chk(bits, torch.int64, "bits")
+    N, V = _region_graph_chk(inv, nbr, "region_clean")
+    if bits.dim() != 2 or bits.shape[0] < 1 or bits.shape[1] != mask_words(N):
+        raise ValueError(f"region_clean: bits {tuple(bits.shape)} for N = {N}")
+    K, S = bits.shape[0], 0
+    if select is not None:
+        _chk(select, torch.uint8, "select")
+        if select.numel() != K:
+            raise ValueError(f"region_clean: select [{select.numel()}] for K = {K}")
+    if seeds is not None:
+        _chk(seeds, torch.int32, "seeds")
+        if seeds.dim() != 2 or seeds.shape[0] != K:
+            raise ValueError(f"region_clean: seeds {tuple(seeds.shape)} for K = {K}")
+        S = seeds.shape[1]
+    if min(int(min_island), int(min_hole)) < 0:
+        raise ValueError("region_clean: min_island and min_hole must not be negative")
+    L = _lib.load()
+    nbytes = L.psam_region_clean_workspace_bytes(K, N, V, S)
+    ws = _region_ws(nbytes, bits.device, "region_clean")
+    out = torch.empty_like(bits)
+    area = torch.empty(K, dtype=torch.int32, device=bits.device)
+    changed = torch.empty(K, dtype=torch.uint8, device=bits.device)
+    check(L.psam_region_clean(bits.data_ptr(), _p(select), inv.data_ptr(), nbr.data_ptr(), _p(seeds) if S > 0 else 0, K, N, V, S, int(min_island),
+                              int(min_hole), out.data_ptr(), area.data_ptr(), changed.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()),
+          "psam_region_clean")
+    return out, area, changed

@@ -26,6 +26,7 @@ class PointSAMPredictor:
         self._key = None
         self._prompts = None
         self.scene = None               # set_scene(): the scan <-> working-cloud mapping (point_sam_amd/scene.py); None after set_pointcloud()
+        self._graphs = None             # clean_masks(): (key, [regions.PointGraph per cloud]) of the cached cloud and voxel settings
 
     @classmethod
     def from_config(cls, name: str, ckpt_path: str = None, num_groups: int = None, group_size: int = None, seed: int = 42,
@@ -108,3 +109,63 @@ class PointSAMPredictor:
             from .scene import expand_proposals
             out = [expand_proposals(self.scene, p) for p in out]
         return out
+
+    # -- connected-component clean-up ------------------------------------------------------------------------
+    def _region_graphs(self, cfg):
+        """One neighbourhood graph per cached cloud, rebuilt when the cloud or the voxel settings change."""
+        from .regions import build_graph
+        key = (self._key, cfg.voxel_size, cfg.points_per_voxel)
+        if self._graphs is None or self._graphs[0] != key:
+            coords = self._state.coords
+            self._graphs = (key, [build_graph(coords[b], cfg.voxel_size, cfg.points_per_voxel) for b in range(coords.shape[0])])
+        return self._graphs[1]
+
+    @torch.no_grad()
+    def clean_masks(self, logits: torch.Tensor, cfg, prompt_points=None, prompt_labels=None, threshold: float = 0.0):
+        """Masks ``logits > threshold`` of the cached cloud with small holes filled, small islands removed and, with ``cfg.keep_clicked``, only the
+        parts that hang together with a positive click kept (point_sam_amd/regions.py; cfg: a `RegionConfig`).
+
+        logits [BM, C, N] as predict_masks returns them -> (bits [K, W] int64 words, area [K] int32, changed [K] uint8), K = BM * C rows in the
+        logits' order; ``ops.mask_unpack(bits, N)`` gives booleans.  keep_clicked: the seeds of a row are the cloud points nearest to the positive
+        prompts (label 1) of its prompt set, prompt_points [BM, P, 3] / prompt_labels [BM, P] (default: those of set_prompts); the C masks of a
+        prompt set share them.  After set_scene, logits of the scan's width are reduced to the working cloud (the representatives' values), cleaned
+        there and expanded, so every scan point has its representative's bit; logits of the working cloud's width are returned at that width."""
+        if self._state is None:
+            raise RuntimeError("call set_pointcloud() first")
+        from .regions import RegionConfig, clean_bits
+        if not isinstance(cfg, RegionConfig):
+            raise TypeError(f"clean_masks: cfg must be a RegionConfig, got {type(cfg).__name__}")
+        cfg.validate()
+        coords = self._state.coords
+        B, Nw, _ = coords.shape
+        if logits.dim() != 3 or logits.shape[0] % B != 0:
+            raise ValueError(f"clean_masks: logits must be [BM, C, N] with BM a multiple of the {B} cached cloud(s), got {tuple(logits.shape)}")
+        sc = self.scene if self.scene is not None and not self.scene.identity else None
+        expand = sc is not None and logits.shape[-1] == sc.num_points and sc.num_points != Nw
+        if expand:
+            logits = logits.index_select(-1, sc.keep_idx)
+        if logits.shape[-1] != Nw:
+            raise ValueError(f"clean_masks: logits of width {logits.shape[-1]} do not fit the cached cloud's {Nw} points")
+        BM, C, _ = logits.shape
+        Mp = BM // B
+        seeds = None
+        if cfg.keep_clicked:
+            if prompt_points is None:
+                if self._prompts is None:
+                    raise RuntimeError("keep_clicked needs the prompts: pass them or call set_prompts() first")
+                prompt_points, prompt_labels = self._prompts[0], self._prompts[1]
+            P = prompt_points.shape[-2]
+            pts = prompt_points.to(coords.device, torch.float32).reshape(B, Mp * P, 3).contiguous()
+            near = ops.knn(pts, coords.contiguous(), 1).reshape(BM, P)                      # the nearest cloud point of every prompt
+            positive = prompt_labels.to(coords.device).reshape(BM, P) == 1
+            seeds = torch.where(positive, near, torch.full_like(near, -1)).to(torch.int32)
+            seeds = seeds.repeat_interleave(C, dim=0).contiguous()                          # every mask of a prompt set shares its seeds
+        bits, _, _, _ = ops.mask_pack(logits.float().contiguous(), threshold, 0.0)
+        graphs = self._region_graphs(cfg)
+        rows = Mp * C
+        out = [clean_bits(graphs[b], bits[b * rows:(b + 1) * rows], seeds=None if seeds is None else seeds[b * rows:(b + 1) * rows], cfg=cfg)
+               for b in range(B)]
+        bits, area, changed = (torch.cat([o[i] for o in out]) if B > 1 else out[0][i] for i in range(3))
+        if expand:
+            bits, area = ops.scene_expand_bits(bits.contiguous(), sc.inv, Nw)
+        return bits, area, changed

@@ -14,7 +14,7 @@ kernel, to compact the kept rows.
 import dataclasses
 import math
 from dataclasses import dataclass
-from typing import List
+from typing import List, Optional
 
 import torch
 
@@ -28,7 +28,12 @@ class ProposalConfig:
     """Defaults: ``pred_iou_thresh`` 0.88, ``stability_thresh`` 0.95, ``stability_offset`` 1.0 and ``nms_thresh`` 0.7 are the published defaults of
     SAM's automatic mask generator, whose IoU head and stability score Point-SAM's decoder mirrors; they have NOT been tuned on a trained Point-SAM
     checkpoint.  ``min_points`` / ``max_area_frac`` are the reference's own instance filter (at least 25 points, under 90 % of the cloud).  With random
-    weights nearly every candidate fails the two score cuts: set them to 0 to see the machinery work."""
+    weights nearly every candidate fails the two score cuts: set them to 0 to see the machinery work.
+
+    ``min_region_points`` > 0 (SAM's ``min_mask_region_area``): every candidate that passes the score and stability cuts is cleaned before the area
+    filter and the suppression -- complement components (holes) with fewer points are filled, then mask components (islands) with fewer points are
+    removed, the largest always kept (point_sam_amd/regions.py).  ``region_voxel_size`` is the cell size of the neighbourhood graph, 0 = chosen so that
+    a voxel holds ``region_points_per_voxel`` points on average: a geometric rule that has NOT been tuned on real data either."""
     num_prompts: int = 1024        # FPS-sampled prompt points per cloud
     prompt_chunk: int = 64         # prompts per decode() call and cloud
     mask_threshold: float = 0.0
@@ -38,13 +43,16 @@ class ProposalConfig:
     nms_thresh: float = 0.7
     min_points: int = 25
     max_area_frac: float = 0.9
+    min_region_points: int = 0     # 0 = no clean-up, no graph is built
+    region_voxel_size: float = 0.0  # 0 = automatic
+    region_points_per_voxel: int = 4
 
     def validate(self) -> "ProposalConfig":
-        for name in ("num_prompts", "prompt_chunk", "min_points"):
+        for name in ("num_prompts", "prompt_chunk", "min_points", "min_region_points", "region_points_per_voxel"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, int):
                 raise ValueError(f"ProposalConfig.{name} must be an integer, got {v!r}")
-        for name in ("mask_threshold", "pred_iou_thresh", "stability_thresh", "stability_offset", "nms_thresh", "max_area_frac"):
+        for name in ("mask_threshold", "pred_iou_thresh", "stability_thresh", "stability_offset", "nms_thresh", "max_area_frac", "region_voxel_size"):
             v = getattr(self, name)
             # the three cuts may be infinite (-inf = no cut); everything else is finite
             if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or (
@@ -54,6 +62,8 @@ class ProposalConfig:
             raise ValueError("ProposalConfig: num_prompts and prompt_chunk must be at least 1")
         if self.min_points < 0 or self.stability_offset < 0 or self.max_area_frac <= 0:
             raise ValueError("ProposalConfig: min_points and stability_offset must not be negative, max_area_frac must be positive")
+        if self.min_region_points < 0 or self.region_voxel_size < 0 or self.region_points_per_voxel < 1:
+            raise ValueError("ProposalConfig: min_region_points and region_voxel_size must not be negative, region_points_per_voxel must be at least 1")
         if not 0.0 <= self.nms_thresh <= 1.0:
             raise ValueError(f"ProposalConfig.nms_thresh is an IoU: it must lie in [0, 1], got {self.nms_thresh}")
         return self
@@ -82,6 +92,7 @@ class DeviceProposals:
     valid: torch.Tensor         # [K] uint8
     keep: torch.Tensor          # [K] uint8
     labels: torch.Tensor        # [N] int32
+    changed: Optional[torch.Tensor] = None      # [K] uint8: the clean-up altered the row; None with min_region_points == 0 (bits / area are then raw)
 
 
 @dataclass
@@ -95,6 +106,7 @@ class Proposals:
     area: torch.Tensor          # [k] int32
     stability: torch.Tensor     # [k] f32: area_hi / area_lo
     labels: torch.Tensor        # [N] int32: row of the best kept mask that contains the point, -1 if none
+    changed: Optional[torch.Tensor] = None      # [k] uint8: the clean-up altered the mask; None with min_region_points == 0
 
     def __len__(self) -> int:
         return self.bits.shape[0]
@@ -105,11 +117,24 @@ class Proposals:
 
 
 @torch.no_grad()
-def propose_on_device(model, state, cfg: ProposalConfig) -> List[DeviceProposals]:
-    """Every kernel of generate_proposals, no host synchronisation: capturable in a HIP graph."""
+def build_region_graphs(state, cfg: ProposalConfig):
+    """One `regions.PointGraph` per cloud of the state (None with min_region_points == 0).  Synchronises with the host: the voxel counts."""
+    if cfg.min_region_points == 0:
+        return None
+    from .regions import build_graph
+    return [build_graph(state.coords[b], cfg.region_voxel_size or None, cfg.region_points_per_voxel) for b in range(state.coords.shape[0])]
+
+
+@torch.no_grad()
+def propose_on_device(model, state, cfg: ProposalConfig, graphs=None) -> List[DeviceProposals]:
+    """Every kernel of generate_proposals, no host synchronisation: capturable in a HIP graph.  graphs: build_region_graphs(state, cfg), needed
+    (ValueError without) when cfg.min_region_points > 0 -- building them reads voxel counts on the host, so it is not done here."""
     cfg.validate()
     coords = state.coords
     B, N, _ = coords.shape
+    if cfg.min_region_points > 0 and (graphs is None or len(graphs) != B):
+        raise ValueError(f"min_region_points = {cfg.min_region_points} needs one region graph per cloud (build_region_graphs): got "
+                         f"{'none' if graphs is None else len(graphs)} for {B} cloud(s)")
     P, chunk = cfg.num_prompts, cfg.prompt_chunk
     if P > N:
         raise ValueError(f"num_prompts {P} exceeds the cloud's {N} points")
@@ -138,11 +163,17 @@ def propose_on_device(model, state, cfg: ProposalConfig) -> List[DeviceProposals
         bits, area, area_hi, area_lo = bufs[b]
         score = scores[b]
         order = torch.sort(score, descending=True, stable=True).indices.to(torch.int32)
+        changed = None
+        if cfg.min_region_points > 0:      # only rows that pass the score and stability cuts are worth cleaning; the others are copied
+            from .regions import RegionConfig, clean_bits
+            select = ops.mask_valid(area, area_hi, area_lo, score, N, 0, 2.0, cfg.pred_iou_thresh, cfg.stability_thresh)
+            bits, area, changed = clean_bits(graphs[b], bits, select=select,
+                                             cfg=RegionConfig(min_island=cfg.min_region_points, min_hole=cfg.min_region_points))
         valid = ops.mask_valid(area, area_hi, area_lo, score, N, cfg.min_points, cfg.max_area_frac, cfg.pred_iou_thresh, cfg.stability_thresh)
         inter = ops.mask_intersections(bits)
         keep = ops.mask_nms(order, valid, area, inter, cfg.nms_thresh)
         labels = ops.mask_paint(bits, order, keep, N)
-        out.append(DeviceProposals(N, C, bits, score, area, area_hi, area_lo, order, valid, keep, labels))
+        out.append(DeviceProposals(N, C, bits, score, area, area_hi, area_lo, order, valid, keep, labels, changed))
     return out
 
 
@@ -151,14 +182,15 @@ def compact(d: DeviceProposals) -> Proposals:
     order = d.order.long()
     cand = order[d.keep[order].bool()]
     return Proposals(d.n_points, d.bits[cand], cand, cand // d.masks_per_prompt, d.score[cand], d.area[cand],
-                     d.area_hi[cand].float() / d.area_lo[cand].float(), d.labels)
+                     d.area_hi[cand].float() / d.area_lo[cand].float(), d.labels, None if d.changed is None else d.changed[cand])
 
 
 @torch.no_grad()
 def generate_proposals(model, state, cfg: ProposalConfig = None) -> List[Proposals]:
     """One `Proposals` per cloud of the encoder state.  Peak memory: one chunk of logits ([B * prompt_chunk, 3, N] f32), K * N / 8 bytes of
     bits and the K x K int32 intersection matrix per cloud (K = 3 * num_prompts) -- never K * N floats."""
-    dev = propose_on_device(model, state, cfg or ProposalConfig())
+    cfg = (cfg or ProposalConfig()).validate()
+    dev = propose_on_device(model, state, cfg, build_region_graphs(state, cfg))
     out = [compact(d) for d in dev]
     model.check_coordinate_range()
     return out

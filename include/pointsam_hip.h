@@ -639,6 +639,41 @@ int32_t psam_scene_expand_rows(const void* src, int64_t src_ld, const int64_t* i
 int32_t psam_scene_expand_bits(const uint64_t* bits_w, const int64_t* inv, int32_t K, int32_t Nw, int32_t M, uint64_t* bits_f, int32_t* area_f,
                                psam_stream_t stream);
 
+/* ---------------------------------------------------------------- scene crops */
+
+/* A ball of a scan -- centre c, radius r -- as a cloud of its own: its points normalised to (x - c) / r, reduced to one real point per occupied
+ * voxel of the normalised ball, and the crop cloud's result pasted back into the scan (point_sam_amd/scene.py: build_crop).  One call selects,
+ * normalises, voxel-reduces, compacts and gathers; every output is exact and does not depend on the order in which the waves run.
+ *
+ * psam_crop_downsample: xyz, rgb [M, 3] on the device, 0 < M <= 2^28; center: three floats in HOST memory; r2 = fl32(r) * fl32(r),
+ *   inv_r = fl32(1) / fl32(r), inv_h = fl32(1) / fl32(voxel size in crop units) or 0 for no voxel reduction, all computed by the caller.  In fp32
+ *   with every operation rounded on its own:
+ *     member      d = x - c per axis, q = (dx dx + dy dy) + dz dz; a point is a member iff q <= r2 (NaN compares false: a non-finite point is
+ *                 not a member, and not an error)
+ *     coordinate  u = fminf(fmaxf(d * inv_r, -1), 1) per axis
+ *     cell        floorf((u - (-1)) * inv_h) per axis, the cell of psam_voxel_downsample at origin (-1, -1, -1); key = cx | cy << 21 | cz << 42.
+ *                 The representative of a voxel is its MEMBER with the lowest scan index (points off the ball never enter the table); with
+ *                 inv_h == 0 every member is its own representative.
+ *   keep_idx[0 .. count) = the representatives' scan indices, increasing; inv[i] = the position in keep_idx of member i's representative, -1 for
+ *   a non-member; wxyz[j] = u of point keep_idx[j]; wrgb[j] = rgb[keep_idx[j]] copied bit for bit.  keep_idx, wxyz and wrgb need room for M
+ *   entries.  keep_idx == inv == wxyz == wrgb == NULL (rgb may then be NULL): counts only.
+ *   result: three adjacent int32 on the device, cleared by the call: result[0] = count, result[1] = the number of members, result[2] = 1 if a
+ *   member's cell falls outside [0, 2^21) on any axis (the other outputs are then in range but meaningless), else 0.
+ *   ws: psam_crop_downsample_workspace_bytes(M) bytes, 16-byte aligned.  A null pointer, a bad M, a centre that is not finite, r2 / inv_r not
+ *   finite and positive, inv_h negative or not finite, or a short workspace: -1. */
+size_t psam_crop_downsample_workspace_bytes(int32_t M);
+int32_t psam_crop_downsample(const float* xyz, const float* rgb, int32_t M, const float* center, float r2, float inv_r, float inv_h,
+                             int64_t* keep_idx, int64_t* inv, float* wxyz, float* wrgb, int32_t* result, void* ws, size_t ws_bytes,
+                             psam_stream_t stream);
+/* dst[r, i] = inv[i] in [0, Nw) ? src[r, inv[i]] : fill, i < M, for R rows of 32-bit words copied bit for bit; fill is a 32-bit pattern
+ * (0xFF800000 = -inf for fp32 logits, 0xFFFFFFFF = -1 for int32 labels); src_ld / dst_ld = row strides in words. */
+int32_t psam_crop_expand_rows(const void* src, int64_t src_ld, const int64_t* inv, int32_t R, int32_t Nw, int32_t M, uint32_t fill, void* dst,
+                              int64_t dst_ld, psam_stream_t stream);
+/* Packed masks: bit i of row k of bits_f [K, ceil(M / 64)] = inv[i] in [0, Nw) ? bit inv[i] of row k of bits_w [K, ceil(Nw / 64)] : 0; bits
+ * past M are zero.  area_f [K] (may be NULL) = the popcount of each full row. */
+int32_t psam_crop_expand_bits(const uint64_t* bits_w, const int64_t* inv, int32_t K, int32_t Nw, int32_t M, uint64_t* bits_f, int32_t* area_f,
+                              psam_stream_t stream);
+
 /* ---------------------------------------------------------------- connected components of masks */
 
 /* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel

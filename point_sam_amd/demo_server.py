@@ -11,6 +11,8 @@ Routes (reference line):  GET / (app.py:71-73: index.html) . GET /static/<path> 
 POST /sampled_pointcloud (app.py:92-108) . GET /pointcloud/<name> (:111-141) . POST /clear (:144-150)
 POST /next (:153-159) . POST /save (:162-175) . POST /segment (:177-206).
 POST /segment_all (not in the reference): automatic mask proposals for the whole cloud, a first pass before the per-object clicks.
+POST /crop {center, radius} . POST /crop/clear (not in the reference): zoom into a ball of the loaded cloud -- /segment and /segment_all then answer
+from the ball's own working cloud (predictor.set_crop), still per loaded point, until the crop is cleared or another cloud is loaded.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -50,8 +52,12 @@ class DemoSession:
     ``clean_masks(logits, cfg, points, labels) -> (bits, area, changed)``."""
 
     def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None,
-                 working_points: int = None, clean_min_points: int = None):
+                 working_points: int = None, clean_min_points: int = None, crop_points: int = None):
         self.predictor = predictor
+        if crop_points is not None and (isinstance(crop_points, bool) or not isinstance(crop_points, int) or crop_points < 1):
+            raise ValueError(f"crop_points must be a positive integer or None, got {crop_points!r}")
+        self.crop_points = crop_points         # /crop: the crop cloud's max_points; None: every point of the ball
+        self.crop = None                       # (center, radius) of the active /crop
         if clean_min_points is not None and (isinstance(clean_min_points, bool) or not isinstance(clean_min_points, int) or clean_min_points < 1):
             raise ValueError(f"clean_min_points must be a positive integer or None, got {clean_min_points!r}")
         # None: /segment answers with the thresholded mask; N: with the part of it that hangs together with the positive clicks, holes and islands
@@ -69,7 +75,10 @@ class DemoSession:
         self.segment_mask = None
 
     def _set_cloud(self):
-        if self.working_points is None:
+        if self.crop is not None:              # a crop zooms into a scene; without --working-points the scene is the loaded cloud itself
+            self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points or self.pc_xyz.shape[1])
+            self.predictor.set_crop(self.crop[0], self.crop[1], max_points=self.crop_points)      # cached: built and encoded once per crop
+        elif self.working_points is None:
             self.predictor.set_pointcloud(self.pc_xyz, self.pc_rgb)
         else:
             self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points)
@@ -85,6 +94,7 @@ class DemoSession:
         with self.lock:
             self.pc_xyz = torch.from_numpy(pts).to(self.device).float()[None]
             self.pc_rgb = torch.from_numpy(col).to(self.device).float()[None]
+            self.crop = None
         return {"response": "success"}
 
     def load_pointcloud(self, path: str) -> dict:
@@ -100,6 +110,7 @@ class DemoSession:
             self.obj_path = name
             self.pc_xyz = torch.from_numpy(xyz).to(self.device).float()[None]
             self.pc_rgb = torch.from_numpy(rgb).to(self.device).float()[None]
+            self.crop = None
         return {"xyz": xyz.flatten().tolist(), "rgb": rgb.flatten().tolist()}
 
     def static_file(self, rel: str):
@@ -168,6 +179,42 @@ class DemoSession:
                     bits, _, _ = self.predictor.clean_masks(logits[:1, best:best + 1], cfg, pts, lab)
                 self.segment_mask = ops.mask_unpack(bits, mask.shape[-1])[0]
             return {"seg": self.segment_mask.cpu().numpy().tolist()}
+
+    def set_crop(self, data: dict) -> dict:
+        """Zoom: {"center": [x, y, z], "radius": r} in the loaded cloud's coordinates.  The crop is built (and its cloud encoded) now, so an empty
+        ball or a bad value is this request's 400 and leaves the previous state; the clicks so far are dropped (they belong to another cloud)."""
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/crop before a point cloud was set")
+            if not isinstance(data, dict) or set(data) != {"center", "radius"}:
+                raise ValueError('/crop takes {"center": [x, y, z], "radius": r}')
+            center = np.asarray(data["center"], dtype=np.float64)
+            radius = data["radius"]
+            if center.shape != (3,) or not np.isfinite(center).all():
+                raise ValueError("center must be three finite numbers")
+            if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not 0 < radius < float("inf"):
+                raise ValueError("radius must be a finite positive number")
+            previous = self.crop
+            self.crop = (tuple(center.tolist()), float(radius))
+            try:
+                with torch.no_grad():
+                    self._set_cloud()
+            except Exception:
+                self.crop = previous
+                raise
+            self._reset_prompts()
+            self.segment_mask = None
+            crop = getattr(self.predictor, "crop", None)
+            return {"status": "cropped", "members": int(getattr(crop, "num_members", 0)), "working_points": int(getattr(crop, "num_working", 0))}
+
+    def clear_crop(self) -> dict:
+        with self.lock:
+            self.crop = None
+            if hasattr(self.predictor, "clear_crop"):
+                self.predictor.clear_crop()
+            self._reset_prompts()
+            self.segment_mask = None
+        return {"status": "cleared"}
 
     def segment_all(self, data: dict) -> dict:
         """"Segment everything": automatic mask proposals on the current cloud.  Optional body keys override `ProposalConfig` fields (an unknown key
@@ -250,6 +297,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
                 return self._send(400, {"error": f"bad JSON: {e}"})
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
                       "/segment_all": lambda: session.segment_all(data),
+                      "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/clear": session.clear, "/next": session.next, "/save": session.save}
             fn = routes.get(self.path)
             if fn is None:
@@ -280,11 +328,13 @@ def main():
                     help="run the model on a voxel working cloud of at most this many points and answer per loaded point (large scans); default: every point")
     ap.add_argument("--clean-min-points", type=int, default=None,
                     help="answer /segment with the cleaned mask: holes and islands below this many points filled / removed, only the clicked part kept")
+    ap.add_argument("--crop-points", type=int, default=None,
+                    help="POST /crop: the zoomed ball gets a working cloud of at most this many points; default: every point of the ball")
     args = ap.parse_args()
     from .predictor import PointSAMPredictor
     pred = PointSAMPredictor.from_config(args.config, args.ckpt, precision=args.precision)
     srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points,
-                            clean_min_points=args.clean_min_points), args.host, args.port)
+                            clean_min_points=args.clean_min_points, crop_points=args.crop_points), args.host, args.port)
     print(f"Point-SAM demo back end on http://{args.host}:{args.port}")
     srv.serve_forever()
 

@@ -1269,6 +1269,131 @@ def scene_expand_bits(bits_w: torch.Tensor, inv: torch.Tensor, Nw: int, area: bo
     return bits_f, area_f
 
 
+# ------------------------------------------------------------------------------------------ scene crops (csrc/crops.hip)
+def _crop_call(xyz, rgb, center, radius, voxel_size, full: bool):
+    import numpy as np
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    _chk(xyz, name="xyz")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f"crop_downsample: xyz must be [M, 3] with M >= 1 (one scene), got {tuple(xyz.shape)}")
+    if full:
+        if rgb.dim() == 3 and rgb.shape[0] == 1:
+            rgb = rgb[0]
+        _chk(rgb, name="rgb")
+        if tuple(rgb.shape) != tuple(xyz.shape):
+            raise ValueError(f"crop_downsample: rgb must be {tuple(xyz.shape)} like xyz, got {tuple(rgb.shape)}")
+    c = np.asarray([float(v) for v in center], dtype=np.float32) if len(center) == 3 else None
+    if c is None or not np.isfinite(c).all():
+        raise ValueError(f"crop_downsample: center must be three finite fp32 numbers, got {center!r}")
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.floating)):
+        raise ValueError(f"crop_downsample: radius must be a number, got {radius!r}")
+    r = np.float32(radius)
+    with np.errstate(over="ignore", divide="ignore"):
+        r2, inv_r = r * r, np.float32(1) / r               # fp32, as the header defines them
+    if not (np.isfinite(r) and r > 0 and np.isfinite(r2) and r2 > 0 and np.isfinite(inv_r)):
+        raise ValueError(f"crop_downsample: radius must be positive with fp32 r * r and 1 / r finite and positive, got {radius!r}")
+    inv_h = np.float32(0)
+    if voxel_size is not None:
+        h = np.float32(voxel_size)
+        if not (np.isfinite(h) and h > 0):
+            raise ValueError(f"crop_downsample: voxel_size must be finite and positive (None: no reduction), got {voxel_size!r}")
+        inv_h = np.float32(1) / h
+        if not (np.isfinite(inv_h) and inv_h > 0):
+            raise ValueError(f"crop_downsample: 1 / voxel_size is not a positive fp32 number for voxel_size {voxel_size!r}")
+    org = (ctypes.c_float * 3)(*[float(v) for v in c])
+    M, dev = xyz.shape[0], xyz.device
+    L = _lib.load()
+    nbytes = L.psam_crop_downsample_workspace_bytes(M)
+    if nbytes == 0:
+        raise ValueError(f"crop_downsample: {M} points exceed the 2^28 the table is built for")
+    ws = torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    keep_idx = torch.empty(M, dtype=torch.int64, device=dev) if full else None
+    inv = torch.empty(M, dtype=torch.int64, device=dev) if full else None
+    wxyz = torch.empty(M, 3, dtype=torch.float32, device=dev) if full else None
+    wrgb = torch.empty(M, 3, dtype=torch.float32, device=dev) if full else None
+    res = torch.empty(3, dtype=torch.int32, device=dev)   # count, members, flag: read together, the call's one host synchronisation
+    check(L.psam_crop_downsample(xyz.data_ptr(), _p(rgb if full else None), M, ctypes.addressof(org), float(r2), float(inv_r), float(inv_h), _p(keep_idx),
+                                 _p(inv), _p(wxyz), _p(wrgb), res.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_crop_downsample")
+    count, members, flag = res.tolist()
+    if flag != 0:
+        raise ValueError(f"crop_downsample: a cell of the ball at voxel size {voxel_size!r} (crop units) falls outside [0, 2^21)")
+    return count, members, keep_idx, inv, wxyz, wrgb
+
+
+def crop_downsample(xyz: torch.Tensor, rgb: torch.Tensor, center, radius: float, voxel_size: float = None):
+    """The ball |x - center| <= radius of a scan as a cloud of its own.  xyz, rgb [M, 3] f32 -> (keep_idx [count] int64, inv [M] int64,
+    wxyz [count, 3], wrgb [count, 3], members).  In fp32, every operation rounded on its own: d = x - c, q = (dx dx + dy dy) + dz dz, a point is a
+    member iff q <= r * r (a non-finite point is none); u = clamp(d * (1 / r), -1, 1); cell = floor((u + 1) * fl32(1 / voxel_size)), voxel_size in
+    crop units.  keep_idx = the lowest MEMBER index of every occupied voxel, increasing (voxel_size None: every member); inv[i] = the position in
+    keep_idx of member i's representative, -1 off the ball; wxyz = u of the representatives, wrgb = rgb[keep_idx].  count may be 0 (an empty ball).
+    ValueError for a non-finite centre, radius <= 0, or a cell outside [0, 2^21).  One host synchronisation: the read of the counts.  The four
+    outputs are sized for M points while the kernels run; the returned tensors are copies of the count rows actually written."""
+    count, members, keep_idx, inv, wxyz, wrgb = _crop_call(xyz, rgb, center, radius, voxel_size, True)
+    return keep_idx[:count].clone(), inv, wxyz[:count].clone(), wrgb[:count].clone(), members
+
+
+def crop_count(xyz: torch.Tensor, center, radius: float, voxel_size: float = None):
+    """-> (count, members): the lengths crop_downsample would return, without writing the index arrays or the gathered cloud."""
+    return _crop_call(xyz, None, center, radius, voxel_size, False)[:2]
+
+
+def _fill_pattern(fill, dtype) -> int:
+    import struct
+    if dtype == torch.float32:
+        return struct.unpack("<I", struct.pack("<f", float(fill)))[0]
+    if isinstance(fill, bool) or not isinstance(fill, int) or not -2 ** 31 <= fill < 2 ** 31:
+        raise ValueError(f"crop_expand_rows: the fill of int32 rows must be an int32 value, got {fill!r}")
+    return fill & 0xFFFFFFFF
+
+
+def crop_expand_rows(src: torch.Tensor, inv: torch.Tensor, fill, out: torch.Tensor = None) -> torch.Tensor:
+    """scene_expand_rows for a crop: out[r, i] = src[r, inv[i]] bit for bit where inv[i] >= 0, `fill` (a value of src's dtype: -inf for logits, -1 for
+    labels) elsewhere.  src [..., Nw] f32 or int32, inv [M] int64 -> [..., M]."""
+    if not src.is_cuda:
+        raise _lib.PointSamHipError("src must live on the GPU: the HIP path has no CPU fallback")
+    if src.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"crop_expand_rows: rows of 32-bit words (float32 / int32), got {src.dtype}")
+    _chk(inv, torch.int64, "inv")
+    pattern = _fill_pattern(fill, src.dtype)
+    Nw, M = src.shape[-1], inv.numel()
+    lead = tuple(src.shape[:-1])
+    rows = src.reshape(-1, Nw) if src.dim() != 2 else src
+    if rows.stride(1) != 1 and Nw > 1:
+        rows = rows.contiguous()
+    R = rows.shape[0]
+    if R < 1 or Nw < 1 or M < 1:
+        raise ValueError(f"crop_expand_rows: empty input: src {tuple(src.shape)}, inv [{M}]")
+    src_ld = rows.stride(0) if R > 1 else Nw
+    if src_ld < Nw:
+        rows, src_ld = rows.contiguous(), Nw
+    if out is None:
+        dst = torch.empty(R, M, dtype=src.dtype, device=src.device)
+    else:
+        dst = out
+        if dst.dtype != src.dtype or dst.dim() != 2 or tuple(dst.shape) != (R, M) or (M > 1 and dst.stride(1) != 1) or (R > 1 and dst.stride(0) < M):
+            raise ValueError(f"crop_expand_rows: out must be [{R}, {M}] {src.dtype} with unit column stride, got {tuple(dst.shape)} {dst.dtype}")
+    dst_ld = dst.stride(0) if R > 1 else M
+    check(_lib.load().psam_crop_expand_rows(rows.data_ptr(), src_ld, inv.data_ptr(), R, Nw, M, pattern, dst.data_ptr(), dst_ld, _stream()),
+          "psam_crop_expand_rows")
+    return dst if out is not None else dst.reshape(lead + (M,))
+
+
+def crop_expand_bits(bits: torch.Tensor, inv: torch.Tensor, Nw: int, area: bool = True):
+    """scene_expand_bits for a crop: bits [K, ceil(Nw / 64)] int64 words, inv [M] int64 -> (bits_f [K, ceil(M / 64)] int64, area_f [K] int32 or None):
+    bit i of a full row = bit inv[i] of the crop's row where inv[i] >= 0, zero elsewhere and past M; area_f = the full rows' popcounts."""
+    _chk(bits, torch.int64, "bits"); _chk(inv, torch.int64, "inv")
+    M = inv.numel()
+    if bits.dim() != 2 or Nw < 1 or bits.shape[1] != mask_words(Nw) or M < 1:
+        raise ValueError(f"crop_expand_bits: bits {tuple(bits.shape)} for Nw = {Nw}, inv [{M}]")
+    K = bits.shape[0]
+    bits_f = torch.empty(K, mask_words(M), dtype=torch.int64, device=bits.device)
+    area_f = torch.empty(K, dtype=torch.int32, device=bits.device) if area else None
+    if K > 0:
+        check(_lib.load().psam_crop_expand_bits(bits.data_ptr(), inv.data_ptr(), K, Nw, M, bits_f.data_ptr(), _p(area_f), _stream()), "psam_crop_expand_bits")
+    return bits_f, area_f
+
+
 # ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)
 def _region_ws(nbytes: int, dev, what: str):
     if nbytes == 0:

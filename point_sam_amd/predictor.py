@@ -26,6 +26,10 @@ class PointSAMPredictor:
         self._key = None
         self._prompts = None
         self.scene = None               # set_scene(): the scan <-> working-cloud mapping (point_sam_amd/scene.py); None after set_pointcloud()
+        self.crop = None                # set_crop(): the scan <-> crop-cloud mapping of the active ball (scene.Crop); None = the whole scene answers
+        self._crop_state: Optional[EncoderState] = None      # the crop cloud's encoder state; self._state stays the scene's, so clear_crop() re-encodes nothing
+        self._crop_key = None
+        self._crop_cache = None         # (key, Crop, state) of the last crop built: survives clear_crop() and a set_scene() of the same scene
         self._graphs = None             # clean_masks(): (key, [regions.PointGraph per cloud]) of the cached cloud and voxel settings
 
     @classmethod
@@ -53,6 +57,8 @@ class PointSAMPredictor:
             self._key = key
             self._keepalive = (xyz, rgb)  # the cache key uses data_ptr: keep the tensors alive
             self.scene = None
+            self._crop_cache = None
+        self._deactivate_crop()
 
     @torch.no_grad()
     def set_scene(self, xyz: torch.Tensor, rgb: torch.Tensor, voxel_size: float = None, max_points: int = None) -> None:
@@ -71,6 +77,40 @@ class PointSAMPredictor:
             self._key = key
             self._keepalive = (xyz, rgb)
             self.scene = sc
+            self._crop_cache = None
+        self._deactivate_crop()
+
+    def _deactivate_crop(self) -> None:
+        self.crop, self._crop_state, self._crop_key = None, None, None
+
+    @torch.no_grad()
+    def set_crop(self, center, radius: float, voxel_size: float = None, max_points: int = None) -> None:
+        """Zoom into the ball (center, radius) of the scan given to set_scene (scan coordinates): its points, normalised to (x - center) / radius, get
+        a working cloud of their own -- one real point per voxel of size `voxel_size` (crop units), or of the smallest ladder size that leaves at most
+        `max_points`; neither: every point of the ball -- and their own encoder pass (scene.build_crop).  Until clear_crop(), predict_masks /
+        generate_masks / clean_masks answer from the crop cloud, still per point of the scan and with prompts in scan coordinates: -inf logits, zero
+        bits and label -1 outside the ball.  The scene's encoder state is kept.  set_scene and set_pointcloud drop the crop.  The last crop built is
+        cached on (scene, center, radius, voxel_size, max_points): setting it again, also after clear_crop() or a set_scene() of the same scene,
+        builds and encodes nothing.  `self.crop` holds keep_idx, inv, num_members and num_working."""
+        if self.scene is None or self._state is None:
+            raise RuntimeError("set_crop() zooms into a scene: call set_scene() first")
+        from . import scene as S
+        key = (self._key, tuple(float(v) for v in center), float(radius), voxel_size, max_points)
+        if self._crop_cache is None or self._crop_cache[0] != key:
+            xyz, rgb = self._keepalive
+            crop, wxyz, wrgb = S.build_crop(xyz, rgb, center, radius, voxel_size, max_points)
+            self._crop_cache = (key, crop, self.model.encode(wxyz[None], wrgb[None]))
+        self._crop_key, self.crop, self._crop_state = self._crop_cache
+
+    def clear_crop(self) -> None:
+        """Back to the whole scene: its encoder state was kept, nothing is encoded again."""
+        self._deactivate_crop()
+
+    def _active(self):
+        """(encoder state, mapping, cache key) that answer now: the crop's while one is set, else the scene's (mapping None after set_pointcloud)."""
+        if self.crop is not None:
+            return self._crop_state, self.crop, self._crop_key
+        return self._state, self.scene, self._key
 
     def set_prompts(self, prompt_points, prompt_labels, prompt_mask=None) -> None:
         self._prompts = (prompt_points, prompt_labels, prompt_mask)
@@ -79,44 +119,92 @@ class PointSAMPredictor:
     def predict_masks(self, prompt_points=None, prompt_labels=None, prompt_mask=None, multimask_output: bool = True):
         """-> (masks [BM,C,N] logits, scores [BM,C], logits [BM,C,N]); masks and logits are the same tensor, the
         caller thresholds at 0 (demo/app.py:203-205).  After set_scene: N = the scan's points; a prompt_mask may have the scan's or the working
-        cloud's width."""
+        cloud's width.  Under set_crop: the prompts are still scan coordinates (one outside the ball is a ValueError), the logits are the crop
+        cloud's indexed by crop.inv, -inf outside the ball; a prompt_mask may have the scan's or the crop cloud's width."""
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
         if prompt_points is None:
             if self._prompts is None:
                 raise RuntimeError("no prompts: pass them or call set_prompts() first")
             prompt_points, prompt_labels, prompt_mask = self._prompts
-        sc = self.scene
+        state, sc, _ = self._active()
+        crop = self.crop is not None
         if sc is not None:
-            from .scene import reduce_prompt_mask
+            from .scene import crop_prompts, reduce_prompt_mask
             prompt_mask = reduce_prompt_mask(sc, prompt_mask)
-        logits, scores = self.model.decode(self._state, prompt_points, prompt_labels, prompt_mask, multimask_output)
+            if crop:
+                prompt_points = crop_prompts(sc, prompt_points)     # scan coordinates -> the crop's unit ball; a prompt off the ball is a ValueError
+        logits, scores = self.model.decode(state, prompt_points, prompt_labels, prompt_mask, multimask_output)
         self.model.check_coordinate_range()
-        if sc is not None and not sc.identity:
+        if crop:
+            logits = ops.crop_expand_rows(logits, sc.inv, float("-inf"))      # [M', C, num_working] -> [M', C, M]; -inf off the ball
+        elif sc is not None and not sc.identity:
             logits = ops.scene_expand_rows(logits, sc.inv)       # [M', C, num_working] -> [M', C, M]: each point takes its representative's logit
         return logits, scores, logits
 
     @torch.no_grad()
-    def generate_masks(self, cfg=None):
+    def generate_masks(self, cfg=None, crops=None):
         """Automatic mask proposals for the cached cloud(s), no prompts needed (point_sam_amd/proposals.py): a list with one `Proposals` per
         cloud -- kept masks best first, bit-packed, and one instance label per point.  cfg: a `ProposalConfig` (None = its defaults).
-        Works for every model variant (voronoi, hierarchical): only the public `decode` is called, with single-point prompts and no mask prompt."""
+        Works for every model variant (voronoi, hierarchical): only the public `decode` is called, with single-point prompts and no mask prompt.
+        Under set_crop: the crop cloud's proposals at the scan's width, zero bits and label -1 off the ball.
+
+        crops: a `CropLayerConfig` -- multi-crop proposals of a scene (set_scene, no active crop).  The scene's own proposals first; then, for each
+        of the first `num_crops` FPS samples of the scene's working cloud (index 0 first: every centre is a real point), the crop cloud of the ball
+        of `crops.radius` around it (at most `crops.max_points` points), its encoder pass and its proposals under the same `cfg`; a crop's mask
+        with a point in the ball's outer shell (scene.crop_shell_bits) is dropped -- a truncated object is the scene's or another crop's to find
+        -- and the others are expanded to the scan; proposals.merge_proposals then orders all rows by score, suppresses at `crops.nms_thresh` and
+        paints.  The result's `crop_index` names each mask's origin (-1 = the scene).  The merge holds K * M / 8 bytes of bits and a K x K int32
+        matrix for the K rows of all layers together (at most proposals.MAX_CANDIDATES, else ValueError); the crops' encoder states are not kept."""
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
         from .proposals import generate_proposals
-        out = generate_proposals(self.model, self._state, cfg)
-        if self.scene is not None:
-            from .scene import expand_proposals
-            out = [expand_proposals(self.scene, p) for p in out]
+        from .scene import expand_proposals
+        if crops is not None:
+            return [self._generate_masks_multicrop(cfg, crops)]
+        state, sc, _ = self._active()
+        out = generate_proposals(self.model, state, cfg)
+        if sc is not None:
+            out = [expand_proposals(sc, p) for p in out]
         return out
+
+    def _generate_masks_multicrop(self, cfg, crops):
+        import dataclasses
+        from . import scene as S
+        from .proposals import CropLayerConfig, generate_proposals, merge_proposals
+        if not isinstance(crops, CropLayerConfig):
+            raise TypeError(f"generate_masks: crops must be a CropLayerConfig, got {type(crops).__name__}")
+        crops.validate()
+        if self.scene is None:
+            raise RuntimeError("multi-crop proposals need a scene: call set_scene() first")
+        if self.crop is not None:
+            raise RuntimeError("multi-crop proposals run on the whole scene: call clear_crop() first")
+        sc = self.scene
+        if crops.num_crops > sc.num_working:
+            raise ValueError(f"num_crops {crops.num_crops} exceeds the scene's {sc.num_working} working points")
+        xyz, rgb = self._keepalive
+        layers = [(-1, S.expand_proposals(sc, generate_proposals(self.model, self._state, cfg)[0]))]
+        _, centers = ops.fps(self._state.coords.contiguous(), crops.num_crops)             # [1, num_crops, 3]: points of the working cloud, hence of the scan
+        for ci, center in enumerate(centers[0].cpu().tolist()):
+            crop, wxyz, wrgb = S.build_crop(xyz, rgb, center, crops.radius, max_points=crops.max_points)
+            p = generate_proposals(self.model, self.model.encode(wxyz[None], wrgb[None]), cfg)[0]
+            if len(p) > 0:
+                touches = ops.mask_intersections(p.bits.contiguous(), S.crop_shell_bits(crop, xyz, crops.edge_frac))[:, 0] > 0
+                inside = torch.nonzero(~touches)[:, 0]
+                p = dataclasses.replace(p, **{name: getattr(p, name).index_select(0, inside)
+                                              for name in ("bits", "candidate", "prompt_index", "score", "area", "stability", "changed")
+                                              if getattr(p, name) is not None})
+            layers.append((ci, S.expand_proposals(crop, p)))
+        return merge_proposals(layers, sc.num_points, crops.nms_thresh)
 
     # -- connected-component clean-up ------------------------------------------------------------------------
     def _region_graphs(self, cfg):
         """One neighbourhood graph per cached cloud, rebuilt when the cloud or the voxel settings change."""
         from .regions import build_graph
-        key = (self._key, cfg.voxel_size, cfg.points_per_voxel)
+        state, _, cloud_key = self._active()                         # under set_crop the graph is the crop cloud's: its key names the crop
+        key = (cloud_key, cfg.voxel_size, cfg.points_per_voxel)
         if self._graphs is None or self._graphs[0] != key:
-            coords = self._state.coords
+            coords = state.coords
             self._graphs = (key, [build_graph(coords[b], cfg.voxel_size, cfg.points_per_voxel) for b in range(coords.shape[0])])
         return self._graphs[1]
 
@@ -128,7 +216,8 @@ class PointSAMPredictor:
         logits [BM, C, N] as predict_masks returns them -> (bits [K, W] int64 words, area [K] int32, changed [K] uint8), K = BM * C rows in the
         logits' order; ``ops.mask_unpack(bits, N)`` gives booleans.  keep_clicked: the seeds of a row are the cloud points nearest to the positive
         prompts (label 1) of its prompt set, prompt_points [BM, P, 3] / prompt_labels [BM, P] (default: those of set_prompts); the C masks of a
-        prompt set share them.  After set_scene, logits of the scan's width are reduced to the working cloud (the representatives' values), cleaned
+        prompt set share them.  After set_scene (and under set_crop, where the working cloud is the crop's and the points off the ball come back as zero
+        bits), logits of the scan's width are reduced to the working cloud (the representatives' values), cleaned
         there and expanded, so every scan point has its representative's bit; logits of the working cloud's width are returned at that width."""
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
@@ -136,11 +225,13 @@ class PointSAMPredictor:
         if not isinstance(cfg, RegionConfig):
             raise TypeError(f"clean_masks: cfg must be a RegionConfig, got {type(cfg).__name__}")
         cfg.validate()
-        coords = self._state.coords
+        state, mapping, _ = self._active()
+        crop = self.crop is not None
+        coords = state.coords
         B, Nw, _ = coords.shape
         if logits.dim() != 3 or logits.shape[0] % B != 0:
             raise ValueError(f"clean_masks: logits must be [BM, C, N] with BM a multiple of the {B} cached cloud(s), got {tuple(logits.shape)}")
-        sc = self.scene if self.scene is not None and not self.scene.identity else None
+        sc = mapping if mapping is not None and not mapping.identity else None
         expand = sc is not None and logits.shape[-1] == sc.num_points and sc.num_points != Nw
         if expand:
             logits = logits.index_select(-1, sc.keep_idx)
@@ -155,6 +246,9 @@ class PointSAMPredictor:
                     raise RuntimeError("keep_clicked needs the prompts: pass them or call set_prompts() first")
                 prompt_points, prompt_labels = self._prompts[0], self._prompts[1]
             P = prompt_points.shape[-2]
+            if crop:
+                from .scene import crop_prompts
+                prompt_points = crop_prompts(sc, prompt_points.to(coords.device))       # the clicks are scan coordinates, the crop cloud's are the unit ball's
             pts = prompt_points.to(coords.device, torch.float32).reshape(B, Mp * P, 3).contiguous()
             near = ops.knn(pts, coords.contiguous(), 1).reshape(BM, P)                      # the nearest cloud point of every prompt
             positive = prompt_labels.to(coords.device).reshape(BM, P) == 1
@@ -167,5 +261,5 @@ class PointSAMPredictor:
                for b in range(B)]
         bits, area, changed = (torch.cat([o[i] for o in out]) if B > 1 else out[0][i] for i in range(3))
         if expand:
-            bits, area = ops.scene_expand_bits(bits.contiguous(), sc.inv, Nw)
+            bits, area = (ops.crop_expand_bits if crop else ops.scene_expand_bits)(bits.contiguous(), sc.inv, Nw)
         return bits, area, changed

@@ -106,6 +106,9 @@ class Proposals:
     area: torch.Tensor          # [k] int32
     stability: torch.Tensor     # [k] f32: area_hi / area_lo
     labels: torch.Tensor        # [N] int32: row of the best kept mask that contains the point, -1 if none
+    # [k] int64, multi-crop proposals only: the crop a mask came from, -1 = the whole scene (merge_proposals).  Keyword-only, so the positional
+    # constructor still ends with `changed`
+    crop_index: Optional[torch.Tensor] = dataclasses.field(default=None, kw_only=True)
     changed: Optional[torch.Tensor] = None      # [k] uint8: the clean-up altered the mask; None with min_region_points == 0
 
     def __len__(self) -> int:
@@ -114,6 +117,85 @@ class Proposals:
     def masks(self) -> torch.Tensor:
         """[k, N] bool, unpacked on demand."""
         return ops.mask_unpack(self.bits, self.n_points)
+
+
+@dataclass
+class CropLayerConfig:
+    """Multi-crop proposals (``predictor.generate_masks(cfg, crops=...)``, SAM's ``crop_n_layers`` for a scan): after the proposals of the whole
+    scene, ``num_crops`` balls of radius ``radius`` (scan units) around the first FPS samples of the scene's working cloud each get a crop cloud of at
+    most ``max_points`` points, their own encoder pass and their own proposals; a crop's mask that touches the ball's outer shell (a point farther
+    than ``(1 - edge_frac) * radius`` from the centre) is dropped as probably truncated, and the rest is merged with the scene's by one more
+    suppression at ``nms_thresh``."""
+    num_crops: int
+    radius: float
+    max_points: int = 32768
+    edge_frac: float = 0.05
+    nms_thresh: float = 0.7
+
+    def validate(self) -> "CropLayerConfig":
+        for name in ("num_crops", "max_points"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"CropLayerConfig.{name} must be a positive integer, got {v!r}")
+        for name in ("radius", "edge_frac", "nms_thresh"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v) or math.isinf(v):
+                raise ValueError(f"CropLayerConfig.{name} must be a finite number, got {v!r}")
+        if self.radius <= 0:
+            raise ValueError(f"CropLayerConfig.radius must be positive, got {self.radius}")
+        if not 0.0 <= self.edge_frac < 1.0:
+            raise ValueError(f"CropLayerConfig.edge_frac is a fraction of the radius: it must lie in [0, 1), got {self.edge_frac}")
+        if not 0.0 <= self.nms_thresh <= 1.0:
+            raise ValueError(f"CropLayerConfig.nms_thresh is an IoU: it must lie in [0, 1], got {self.nms_thresh}")
+        return self
+
+    @classmethod
+    def from_overrides(cls, overrides: dict) -> "CropLayerConfig":
+        """The defaults with the given fields replaced (num_crops and radius have none); an unknown or missing field is a ValueError."""
+        names = {f.name for f in dataclasses.fields(cls)}
+        unknown = sorted(set(overrides) - names)
+        if unknown:
+            raise ValueError(f"unknown CropLayerConfig field(s) {unknown}; known: {sorted(names)}")
+        missing = sorted({"num_crops", "radius"} - set(overrides))
+        if missing:
+            raise ValueError(f"CropLayerConfig needs {missing}")
+        return cls(**overrides).validate()
+
+
+@torch.no_grad()
+def merge_proposals(layers, n_points: int, nms_thresh: float) -> Proposals:
+    """Proposals of the whole scene and of crops, all already at the scan's width, -> one `Proposals`.  layers: [(crop index, Proposals)] in the order
+    base (-1), crop 0, crop 1, ...; the rows are concatenated in that order, ordered by score (descending, stable: on a tie the earlier layer wins),
+    all taken as valid (every layer applied its own filters), suppressed greedily on mask IoU at `nms_thresh` and painted.  ``crop_index`` names each
+    kept mask's layer; ``candidate`` / ``prompt_index`` stay those of its own layer.  Holds K * n_points / 8 bytes of bits and a K x K int32
+    intersection matrix for the K concatenated rows; ValueError when K exceeds MAX_CANDIDATES."""
+    if not layers:
+        raise ValueError("merge_proposals: no layer")
+    K = sum(len(p) for _, p in layers)
+    if K > MAX_CANDIDATES:
+        raise ValueError(f"{K} masks over {len(layers)} layers exceed the {MAX_CANDIDATES} one suppression handles")
+    W = ops.mask_words(n_points)
+    for _, p in layers:
+        if p.n_points != n_points or p.bits.shape[1] != W:
+            raise ValueError(f"merge_proposals: a layer of {p.n_points} points among layers of {n_points}")
+    first = layers[0][1]
+    dev = first.bits.device
+    cat = lambda name: torch.cat([getattr(p, name) for _, p in layers])
+    bits, score, area = cat("bits").contiguous(), cat("score").contiguous(), cat("area").contiguous()
+    origin = torch.cat([torch.full((len(p),), int(ci), dtype=torch.int64, device=dev) for ci, p in layers])
+    changed = cat("changed") if all(p.changed is not None for _, p in layers) else None
+    if K == 0:
+        return Proposals(n_points, bits, cat("candidate"), cat("prompt_index"), score, area, cat("stability"),
+                         torch.full((n_points,), -1, dtype=torch.int32, device=dev), changed, crop_index=origin)
+    order = torch.sort(score, descending=True, stable=True).indices.to(torch.int32)
+    valid = torch.ones(K, dtype=torch.uint8, device=dev)
+    inter = ops.mask_intersections(bits)
+    keep = ops.mask_nms(order, valid, area, inter, nms_thresh)
+    labels = ops.mask_paint(bits, order, keep, n_points)
+    sel = order.long()
+    sel = sel[keep[sel].bool()]
+    return Proposals(n_points, bits[sel], cat("candidate")[sel], cat("prompt_index")[sel], score[sel], area[sel], cat("stability")[sel], labels,
+                     None if changed is None else changed[sel], crop_index=origin[sel])
 
 
 @torch.no_grad()

@@ -7,6 +7,13 @@ bits, all integer work or bit-for-bit copies, so a result at full resolution is 
     pred.set_scene(xyz, rgb, max_points=131072)          # xyz [M, 3] in [-1, 1], rgb as for set_pointcloud
     logits, scores, _ = pred.predict_masks(points, labels)   # logits [M', C, M]
     pred.scene.keep_idx, pred.scene.inv, pred.scene.num_working
+
+A crop zooms into a ball of the scan (``csrc/crops.hip``): its points, normalised to the unit ball, get a finer working cloud and an encoder pass of
+their own, and the results come back per scan point, with -inf logits / zero bits / label -1 off the ball.
+
+    pred.set_crop(center, radius, max_points=32768)          # scan coordinates; after set_scene
+    logits, scores, _ = pred.predict_masks(points, labels)   # points in scan coordinates, inside the ball; logits [M', C, M]
+    pred.crop.keep_idx, pred.crop.inv, pred.crop.num_members; pred.clear_crop()
 """
 from dataclasses import dataclass
 from typing import Callable, Optional
@@ -88,9 +95,83 @@ def build_scene(xyz: torch.Tensor, voxel_size: Optional[float], max_points: Opti
     return Scene(M, keep_idx.numel(), keep_idx, inv, float(voxel_size), False)
 
 
-def reduce_prompt_mask(scene: Scene, prompt_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+@dataclass
+class Crop:
+    """A ball of a scan as a cloud of its own: the members (|x - center| <= radius, in the kernel's fp32 arithmetic) normalised to (x - center) / radius
+    and reduced to one real member per occupied voxel.  ``inv[keep_idx[j]] == j``; ``keep_idx`` is strictly increasing; ``inv == -1`` exactly off the ball."""
+    center: tuple                   # three floats (fp32 values), scan coordinates
+    radius: float                   # an fp32 value, scan units
+    num_points: int                 # M, the scan's
+    num_members: int                # points of the scan inside the ball
+    num_working: int
+    keep_idx: torch.Tensor          # [num_working] int64: the scan indices of the crop cloud's points
+    inv: torch.Tensor               # [M] int64: the crop-cloud row of each member's representative, -1 off the ball
+    voxel_size: Optional[float]     # in crop units (the ball has radius 1); None: every member is a point of the crop cloud
+    identity = False                # a crop is never its scan: outputs are always expanded
+
+
+def _f32(v) -> float:
+    import numpy as np
+    return float(np.float32(v))
+
+
+def build_crop(xyz: torch.Tensor, rgb: torch.Tensor, center, radius: float, voxel_size: Optional[float] = None, max_points: Optional[int] = None):
+    """-> (Crop, wxyz [n, 3], wrgb [n, 3]): the crop cloud of the ball (center, radius) of the scan xyz / rgb [M, 3] (ops.crop_downsample).  At most one of
+    `voxel_size` (crop units) and `max_points`; neither: every member is kept.  With max_points and no more members than that there is no reduction;
+    otherwise the voxel size is choose_voxel_size's, on the ladder, counting the ball's occupied voxels (about seven count-only passes).  ValueError
+    for an empty ball."""
+    if voxel_size is not None and max_points is not None:
+        raise ValueError("build_crop: give at most one of voxel_size and max_points")
+    if voxel_size is not None and (isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float)) or not 0 < voxel_size < float("inf")):
+        raise ValueError(f"build_crop: voxel_size must be a finite positive number, got {voxel_size!r}")
+    if max_points is not None and (isinstance(max_points, bool) or not isinstance(max_points, int) or max_points < 1):
+        raise ValueError(f"build_crop: max_points must be a positive integer, got {max_points!r}")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1 or tuple(rgb.shape) != tuple(xyz.shape):
+        raise ValueError(f"build_crop: xyz and rgb must both be [M, 3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+    center = tuple(float(v) for v in center)
+    if len(center) != 3:
+        raise ValueError(f"build_crop: center must be three numbers, got {center!r}")
+    if max_points is not None:
+        _, members = ops.crop_count(xyz, center, radius, None)
+        if members > max_points:
+            voxel_size = choose_voxel_size(xyz, max_points, count=lambda k: ops.crop_count(xyz, center, radius, ladder(k))[0])
+    keep_idx, inv, wxyz, wrgb, members = ops.crop_downsample(xyz, rgb, center, radius, voxel_size)
+    if members == 0:
+        raise ValueError(f"build_crop: no point of the scan lies in the ball of radius {radius} around {center}")
+    crop = Crop(tuple(_f32(v) for v in center), _f32(radius), xyz.shape[0], members, keep_idx.numel(), keep_idx, inv,
+                None if voxel_size is None else float(voxel_size))
+    return crop, wxyz, wrgb
+
+
+def crop_prompts(crop: Crop, points: torch.Tensor) -> torch.Tensor:
+    """Prompt points [..., 3] in scan coordinates -> crop coordinates, with the kernel's arithmetic (fp32, one rounded operation at a time):
+    d = p - c, u = clamp(d * fl32(1 / r), -1, 1).  ValueError for a prompt outside the ball (q = (dx dx + dy dy) + dz dz > fl32(r) * fl32(r), or NaN)."""
+    import numpy as np
+    r = np.float32(crop.radius)
+    r2, inv_r = float(r * r), float(np.float32(1) / r)
+    p = points.to(torch.float32)
+    d = p - torch.tensor(crop.center, dtype=torch.float32, device=p.device)
+    dx, dy, dz = d[..., 0], d[..., 1], d[..., 2]
+    q = (dx * dx + dy * dy) + dz * dz
+    if not bool((q <= r2).all()):
+        raise ValueError(f"a prompt point lies outside the crop (centre {crop.center}, radius {crop.radius}): prompts are scan coordinates inside the ball")
+    return torch.clamp(d * inv_r, -1.0, 1.0)
+
+
+def crop_shell_bits(crop: Crop, xyz: torch.Tensor, edge_frac: float) -> torch.Tensor:
+    """-> [1, ceil(num_working / 64)] int64: the crop cloud's points in the ball's outer shell, q > rs * rs with rs = fl32((1 - edge_frac) * r) and q
+    as in the membership test, from the scan coordinates xyz [M, 3]."""
+    import numpy as np
+    rs = np.float32((1.0 - edge_frac) * crop.radius)
+    d = xyz.index_select(0, crop.keep_idx) - torch.tensor(crop.center, dtype=torch.float32, device=xyz.device)
+    dx, dy, dz = d[:, 0], d[:, 1], d[:, 2]
+    q = (dx * dx + dy * dy) + dz * dz
+    return ops.mask_pack(q[None].contiguous(), float(rs * rs), 0.0)[0]
+
+
+def reduce_prompt_mask(scene, prompt_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """A mask prompt of the scan's width -> the working cloud's width: the representatives' own values (exact: inv[keep_idx[j]] == j).  A mask of
-    the working cloud's width passes unchanged."""
+    the working cloud's width passes unchanged.  scene: a `Scene` or a `Crop` (whose cloud is narrower than the scan: points off the ball drop out)."""
     if prompt_mask is None or scene.identity or prompt_mask.shape[-1] == scene.num_working:
         return prompt_mask
     if prompt_mask.shape[-1] != scene.num_points:
@@ -98,14 +179,16 @@ def reduce_prompt_mask(scene: Scene, prompt_mask: Optional[torch.Tensor]) -> Opt
     return prompt_mask.to(scene.keep_idx.device).index_select(-1, scene.keep_idx)
 
 
-def expand_proposals(scene: Scene, p):
+def expand_proposals(scene, p):
     """A working-cloud `Proposals` -> the same proposals at full resolution: bits, area and labels per scan point; scores, candidates, stability and the
-    order are the working cloud's (filtering and suppression were decided there)."""
+    order are the working cloud's (filtering and suppression were decided there).  For a `Crop` the points off the ball get zero bits and label -1."""
     import dataclasses
     if scene.identity:
         return p
+    crop = isinstance(scene, Crop)
     if len(p) > 0:
-        bits, area = ops.scene_expand_bits(p.bits.contiguous(), scene.inv, scene.num_working)
+        bits, area = (ops.crop_expand_bits if crop else ops.scene_expand_bits)(p.bits.contiguous(), scene.inv, scene.num_working)
     else:
         bits, area = p.bits.new_zeros(0, ops.mask_words(scene.num_points)), p.area
-    return dataclasses.replace(p, n_points=scene.num_points, bits=bits, area=area, labels=ops.scene_expand_rows(p.labels, scene.inv))
+    labels = ops.crop_expand_rows(p.labels, scene.inv, -1) if crop else ops.scene_expand_rows(p.labels, scene.inv)
+    return dataclasses.replace(p, n_points=scene.num_points, bits=bits, area=area, labels=labels)

@@ -53,6 +53,12 @@ void psam_fps_set_cooperative(int32_t on); /* test hook: 0 = never use the multi
 void psam_fps_set_pruning(int32_t mode);   /* A/B and test hook: 0 = the multi-workgroup kernel scans every point in every iteration, 1 = it buckets the cloud by
                                             * grid cell and skips, exactly, the waves whose bounding box the new centre cannot reach; -1 = default
                                             * (environment PSAM_FPS_PRUNE, else 1) */
+/* test queries (thread-local, host-side bookkeeping).  psam_fps_last_instance: the kernel instance the calling thread's last psam_fps launched,
+ * kind * 100 + PPT4 (kind 0 = the single-workgroup kernel, PPT4 = 1 .. 8 groups of 4096 points held in registers / LDS, 0 = streamed; 1 = the
+ * multi-workgroup kernel, 2 = the pruned multi-workgroup kernel, PPT4 in {1, 2, 4}); psam_fps_last_grid_x: the width of that launch's grid
+ * (workgroups per cloud x 8 with the one-XCD placement, x 1 without; 0 for kind 0).  Both -1 before the first launch and after a refused call. */
+int32_t psam_fps_last_instance(void);
+int32_t psam_fps_last_grid_x(void);
 
 /* K nearest points of each center, ascending by (squared distance, index); the [G,N] distance matrix is never
  * materialised.  Replaces knn_points(centers, xyz, K) = torch.cdist + torch.topk: pc_sam/model/common.py:27-56,97.
@@ -60,6 +66,8 @@ void psam_fps_set_pruning(int32_t mode);   /* A/B and test hook: 0 = the multi-w
 int32_t psam_knn(const float* centers, const float* xyz, int32_t B, int32_t G, int32_t N, int32_t K, int64_t* knn_idx, psam_stream_t stream);
 /* tuning / test hook: 1 = the band kernel (one or two distance evaluations per pair; default), 0 = the four-pass kernel, -1 = default (environment PSAM_KNN_BAND) */
 void psam_knn_force_band(int32_t mode);
+/* test query (thread-local): the kernel the calling thread's last psam_knn launched, 0 = four-pass, 1 = band; -1 before the first launch and after a refused call */
+int32_t psam_knn_last_instance(void);
 
 /* 3 nearest centers of every point + normalised 1/max(d^2, eps) weights.
  * Replaces compute_interp_weights(query, key): pc_sam/model/common.py:238-255 (called from mask_decoder.py:151-156).

@@ -672,9 +672,21 @@ static bool fps_prune_enabled() {
     return on != 0;
 }
 
+// the instance the calling thread's last psam_fps launched: kind * 100 + PPT4 (kind 0 = fps_kernel, PPT4 0 .. 8; 1 = fps_coop_kernel, 2 = fps_coop_pruned_kernel)
+// and the width of its grid (W * xs for the cooperative kinds, 0 for kind 0); -1 before the first launch and after a refused call.  Host-side bookkeeping only.
+static thread_local int32_t t_fps_last = -1, t_fps_grid_x = -1;
+PSAM_API int32_t psam_fps_last_instance(void) { return t_fps_last; }
+PSAM_API int32_t psam_fps_last_grid_x(void) { return t_fps_grid_x; }
+static int32_t fps_launched(int32_t code, int32_t grid_x) {
+    const int32_t rc = psam_launch_status("psam_fps: launch failed");
+    if (rc == PSAM_OK) { t_fps_last = code; t_fps_grid_x = grid_x; }
+    return rc;
+}
+
 // xyz [B,N,3] f32 -> fps_idx [B,G] i64 (start index 0), centers [B,G,3] f32 (fused batch_index_select).
 PSAM_API int32_t psam_fps(const float* xyz, int32_t B, int32_t N, int32_t G, int64_t* fps_idx, float* centers, void* ws,
                           size_t ws_bytes, hipStream_t stream) {
+    t_fps_last = -1; t_fps_grid_x = -1;
     PSAM_REQUIRE(xyz && fps_idx && centers && ws, PSAM_EINVAL, "psam_fps: null pointer");
     PSAM_REQUIRE(B > 0 && N > 0 && G > 0 && G <= N, PSAM_EINVAL, "psam_fps: need B>0, 0<G<=N");
     PSAM_REQUIRE((int64_t)N <= (int64_t)1 << 30, PSAM_EINVAL, "psam_fps: N too large");
@@ -708,13 +720,13 @@ PSAM_API int32_t psam_fps(const float* xyz, int32_t B, int32_t N, int32_t G, int
     hipLaunchKernelGGL(fps_coop_pruned_kernel<P>, dim3(W * xs, B), dim3(FPS_THREADS), 0, stream, xyz, psoa, N, npad, G, W, xs, cand, fps_idx, centers)
             if (coop == 1) FPS_COOP_PRUNED(1); else if (coop == 2) FPS_COOP_PRUNED(2); else FPS_COOP_PRUNED(4);
 #undef FPS_COOP_PRUNED
-            return psam_launch_status("psam_fps: launch failed");
+            return fps_launched(200 + coop, W * xs);
         }
 #define FPS_COOP(P) \
     hipLaunchKernelGGL(fps_coop_kernel<P>, dim3(W * xs, B), dim3(FPS_THREADS), 0, stream, xyz, soa, N, npad, G, W, xs, cand, fps_idx, centers)
         if (coop == 1) FPS_COOP(1); else if (coop == 2) FPS_COOP(2); else FPS_COOP(4);
 #undef FPS_COOP
-        return psam_launch_status("psam_fps: launch failed");
+        return fps_launched(100 + coop, W * xs);
     }
     const int groups = (int)(npad / (4 * FPS_THREADS));
 #define FPS_LAUNCH(P) \
@@ -731,7 +743,7 @@ PSAM_API int32_t psam_fps(const float* xyz, int32_t B, int32_t N, int32_t G, int
         default: FPS_LAUNCH(0); break;
     }
 #undef FPS_LAUNCH
-    return psam_launch_status("psam_fps: launch failed");
+    return fps_launched(groups <= 8 ? groups : 0, 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1042,10 +1054,14 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
 
 static int g_knn_band = -1;      // -1: environment PSAM_KNN_BAND (default 1); 0 = always the four-pass kernel (A/B, tests)
 PSAM_API void psam_knn_force_band(int32_t mode) { g_knn_band = mode; }
+// the kernel the calling thread's last psam_knn launched: 0 = knn_kernel, 1 = knn_band_kernel; -1 before the first launch and after a refused call
+static thread_local int32_t t_knn_last = -1;
+PSAM_API int32_t psam_knn_last_instance(void) { return t_knn_last; }
 
 // centers [B,G,3], xyz [B,N,3] -> knn_idx [B,G,K] i64 ascending by (squared distance, index).
 PSAM_API int32_t psam_knn(const float* centers, const float* xyz, int32_t B, int32_t G, int32_t N, int32_t K, int64_t* knn_idx,
                           hipStream_t stream) {
+    t_knn_last = -1;
     PSAM_REQUIRE(centers && xyz && knn_idx, PSAM_EINVAL, "psam_knn: null pointer");
     PSAM_REQUIRE(B > 0 && G > 0 && N > 0 && K > 0 && K <= N, PSAM_EINVAL, "psam_knn: need 0<K<=N");
     PSAM_REQUIRE(K <= KNN_MAXK, PSAM_EINVAL, "psam_knn: K > 1024 unsupported");
@@ -1058,7 +1074,9 @@ PSAM_API int32_t psam_knn(const float* centers, const float* xyz, int32_t B, int
     }
     if (!band) hipLaunchKernelGGL(knn_kernel, dim3(G, B), dim3(KNN_THREADS), 0, stream, centers, xyz, G, N, K, knn_idx);
     else hipLaunchKernelGGL(knn_band_kernel, dim3(G, B), dim3(KNN_THREADS), 0, stream, centers, xyz, G, N, K, knn_idx);
-    return psam_launch_status("psam_knn: launch failed");
+    const int32_t rc = psam_launch_status("psam_knn: launch failed");
+    if (rc == PSAM_OK) t_knn_last = band ? 1 : 0;
+    return rc;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1106,6 +1124,17 @@ PSAM_API int32_t psam_three_nn(const float* xyz, const float* centers, int32_t B
     PSAM_REQUIRE(B > 0 && N > 0 && G >= 3, PSAM_EINVAL, "psam_three_nn: need G>=3");
     PSAM_REQUIRE((size_t)G * 12 <= 144 * 1024, PSAM_EINVAL, "psam_three_nn: G too large for LDS staging");
     PSAM_REQUIRE(B <= 65535, PSAM_EINVAL, "psam_three_nn: B > 65535 unsupported");
+    if ((size_t)G * 12 > 64 * 1024) {      // > 64 KiB of dynamic LDS: opt in once per device, up to the guard's limit
+        static unsigned long long attr_done = 0;
+        int dev = 0;
+        PSAM_REQUIRE(hipGetDevice(&dev) == hipSuccess, PSAM_EINVAL, "psam_three_nn: no device");
+        const unsigned long long bit = 1ull << (dev & 63);
+        if (!(__atomic_load_n(&attr_done, __ATOMIC_ACQUIRE) & bit)) {
+            PSAM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&three_nn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) == hipSuccess,
+                         PSAM_EINVAL, "psam_three_nn: cannot reserve LDS");
+            __atomic_fetch_or(&attr_done, bit, __ATOMIC_RELEASE);
+        }
+    }
     hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)psam_cdiv(N, 256), B), dim3(256), (size_t)G * 12, stream, xyz, centers, N, G,
                        eps, idx3, w3);
     return psam_launch_status("psam_three_nn: launch failed");

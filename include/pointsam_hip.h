@@ -682,6 +682,46 @@ int32_t psam_crop_expand_rows(const void* src, int64_t src_ld, const int64_t* in
 int32_t psam_crop_expand_bits(const uint64_t* bits_w, const int64_t* inv, int32_t K, int32_t Nw, int32_t M, uint64_t* bits_f, int32_t* area_f,
                               psam_stream_t stream);
 
+/* ---------------------------------------------------------------- interpolated scene masks */
+
+/* The last step of a scene or a crop with smooth edges (point_sam_amd/scene.py: build_interp_plan): a scan point receives the inverse-distance blend
+ * of up to three working points instead of its voxel representative's value.  The arithmetic follows the model's own feature upsampling
+ * (common.py:238-274 of the reference, psam_three_nn / psam_interp3 here); the candidates are the grid's.  All arithmetic is fp32, every operation
+ * rounded on its own, division IEEE; every output is a function of the inputs alone.  No call allocates or synchronises with the host.
+ *
+ * This is NOT a true 3-NN: a working point two cells away can be nearer than the third candidate.  The definition is the 27-cell one below.  Measured
+ * on the CPU (uniform clouds and sphere surfaces, 2 - 130 points per voxel): the 27 candidates contain the true nearest working point for 100 % of
+ * 20 000 sampled scan points per case and the true three nearest for 99.9 %; the voxel's own representative is the nearest for only 51 - 72 %.
+ *
+ * Plan (common.py:238-255).  xyz [M, 3], inv [M] (the downsample's; a value outside [0, Nw), a crop's -1 among them, makes the point OFF),
+ *   wxyz [Nw, 3] the working cloud as the encoder saw it, nbr [Nw, 26] of psam_region_neighbors on the grid the working cloud was built on
+ *   (8-byte aligned).  center == NULL: a scene, the query coordinate is p = xyz[i].  center: three floats in HOST memory, a crop: p = the crop's
+ *   normalised coordinate fminf(fmaxf((x - c) * inv_r, -1), 1) per axis, the one psam_crop_downsample writes to wxyz.
+ *     candidates  v = inv[i] and every nbr[v, o] in [0, Nw), o = 0 .. 25
+ *     distance    q_r = (dx dx + dy dy) + dz dz, d = p - wxyz[r]
+ *     selection   the three candidates lowest in (q, r), lexicographic: a tie goes to the lower rank; missing entries are idx = -1, w = 0
+ *     exact hit   q_0 == 0, or a single candidate: idx3 = (r0, -1, -1), w3 = (1, 0, 0)
+ *     otherwise   a_j = 1 / fmaxf(q_j, eps); s = a0 + a1, then s = s + a2 with a third candidate; w_j = a_j / s
+ *     off point   idx3 = (-1, -1, -1), w3 = (0, 0, 0)
+ *   idx3 [M, 3] int32, w3 [M, 3] fp32: 24 bytes per scan point.  Coordinates of points that are not off must be finite.  A null pointer, M or Nw
+ *   outside (0, 2^28], a centre or inv_r that is not finite (inv_r also not positive), eps negative or not finite: -1; a misaligned pointer: -2. */
+int32_t psam_interp_scene_plan(const float* xyz, int32_t M, const int64_t* inv, const float* wxyz, const int32_t* nbr, int32_t Nw,
+                               const float* center, float inv_r, float eps, int32_t* idx3, float* w3, psam_stream_t stream);
+/* Apply (common.py:258-274), R fp32 rows; src_ld / dst_ld = row strides in floats; idx3 and w3 are read once per point for all rows.  An entry of
+ * idx3 outside [0, Nw) is unused and never dereferenced; entries are used in order (without the first the point is off, without the second the
+ * third is ignored).  With l_j = src[r, idx_j]:
+ *     off point           dst[r, i] = fill
+ *     idx_1 unused        the 32-bit word src[r, idx_0] is COPIED: no arithmetic, NaN payloads and infinities survive
+ *     otherwise           acc = w0 l0 + w1 l1, then acc = acc + w2 l2 if idx_2 is used
+ * so dst[r, keep_idx[j]] == src[r, j] bit for bit for a plan of psam_interp_scene_plan (a representative is an exact hit). */
+int32_t psam_interp_scene_rows(const float* src, int64_t src_ld, const int32_t* idx3, const float* w3, int32_t R, int32_t Nw, int32_t M,
+                               float fill, float* dst, int64_t dst_ld, psam_stream_t stream);
+/* The packed masks of the same values without the [K, M] floats in between (the layout of psam_mask_pack): bit i of row k of
+ * bits_f [K, ceil(M / 64)] = value[k, i] > thr, fp32 compare: NaN is false; an off point is 0; bits past M are zero.  area_f [K] (may be NULL) = the
+ * popcount of each row, an integer sum. */
+int32_t psam_interp_scene_bits(const float* src, int64_t src_ld, const int32_t* idx3, const float* w3, int32_t K, int32_t Nw, int32_t M,
+                               float thr, uint64_t* bits_f, int32_t* area_f, psam_stream_t stream);
+
 /* ---------------------------------------------------------------- connected components of masks */
 
 /* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel

@@ -142,6 +142,9 @@ SIGNATURES = {
     "psam_crop_downsample": (i32, [ptr, ptr, i32, ptr, f32, f32, f32, ptr, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
     "psam_crop_expand_rows": (i32, [ptr, i64, ptr, i32, i32, i32, ctypes.c_uint32, ptr, i64, ptr]),
     "psam_crop_expand_bits": (i32, [ptr, ptr, i32, i32, i32, ptr, ptr, ptr]),
+    "psam_interp_scene_plan": (i32, [ptr, i32, ptr, ptr, ptr, i32, ptr, f32, f32, ptr, ptr, ptr]),
+    "psam_interp_scene_rows": (i32, [ptr, i64, ptr, ptr, i32, i32, i32, f32, ptr, i64, ptr]),
+    "psam_interp_scene_bits": (i32, [ptr, i64, ptr, ptr, i32, i32, i32, f32, ptr, ptr, ptr]),
     "psam_region_neighbors_workspace_bytes": (size_t, [i32]),
     "psam_region_neighbors": (i32, [ptr, ptr, i32, ptr, f32, ptr, ptr, size_t, ptr]),
     "psam_region_labels_workspace_bytes": (size_t, [i32, i32, i32]),

@@ -33,6 +33,7 @@ SOURCES = [
     ("scene.hip", ["-ffp-contract=off"]),      # voxel cells: floorf((x - origin) * inv_h) with every operation rounded on its own
     ("regions.hip", ["-ffp-contract=off"]),    # the same cells as scene.hip (csrc/voxel_cell.h)
     ("crops.hip", ["-ffp-contract=off"]),      # membership, normalised coordinates and cells of a ball of the scan: every fp32 operation rounded on its own
+    ("scene_interp.hip", ["-ffp-contract=off"]),      # 3-NN blend over the voxel neighbourhood: distances, weights and the blend rounded one operation at a time
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

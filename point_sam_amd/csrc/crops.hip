@@ -20,6 +20,7 @@
 //            state[i] = ~rank.  The gather rides on the rank pass: the representative's own thread holds i and rank, so no pass reads keep_idx back
 //   inverse  inv[i] = rank of state[i], -1 for OUTSIDE
 #include "common.h"
+#include "crop_coord.h"      // CropBall, crop_member: shared with scene_interp.hip
 #include "voxel_cell.h"
 
 #include <climits>
@@ -54,22 +55,6 @@ static inline CropWs crop_layout(void* ws, int64_t M) {
     w.block_members = (int*)(p + o);   o += align16((size_t)crop_scan_blocks(M) * sizeof(int));
     w.bytes = o;
     return w;
-}
-
-struct CropBall {
-    float cx, cy, cz, r2, inv_r;
-};
-
-// d = x - c per axis; q = (dx dx + dy dy) + dz dz; member iff q <= r2 (NaN: false).  u = clamp(d inv_r, -1, 1): one definition for the insert
-// and the gather.
-__device__ __forceinline__ bool crop_member(const float* __restrict__ p, const CropBall& b, float u[3]) {
-#pragma clang fp contract(off)
-    const float dx = p[0] - b.cx, dy = p[1] - b.cy, dz = p[2] - b.cz;
-    const float q = (dx * dx + dy * dy) + dz * dz;
-    u[0] = fminf(fmaxf(dx * b.inv_r, -1.0f), 1.0f);
-    u[1] = fminf(fmaxf(dy * b.inv_r, -1.0f), 1.0f);
-    u[2] = fminf(fmaxf(dz * b.inv_r, -1.0f), 1.0f);
-    return q <= b.r2;
 }
 
 // ------------------------------------------------------------------------------------------------ clear

@@ -52,8 +52,13 @@ class DemoSession:
     ``clean_masks(logits, cfg, points, labels) -> (bits, area, changed)``."""
 
     def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None,
-                 working_points: int = None, clean_min_points: int = None, crop_points: int = None):
+                 working_points: int = None, clean_min_points: int = None, crop_points: int = None, smooth_edges: bool = False):
         self.predictor = predictor
+        if not isinstance(smooth_edges, bool):
+            raise ValueError(f"smooth_edges must be True or False, got {smooth_edges!r}")
+        # True: the masks of a voxel working cloud or a crop reach the loaded points by a 3-NN blend, not by the voxel representative's value
+        # (predictor.set_scene / set_crop smooth=True).  The keyword is only passed when set: a predictor without it keeps working.
+        self.smooth_edges = smooth_edges
         if crop_points is not None and (isinstance(crop_points, bool) or not isinstance(crop_points, int) or crop_points < 1):
             raise ValueError(f"crop_points must be a positive integer or None, got {crop_points!r}")
         self.crop_points = crop_points         # /crop: the crop cloud's max_points; None: every point of the ball
@@ -75,13 +80,14 @@ class DemoSession:
         self.segment_mask = None
 
     def _set_cloud(self):
+        smooth = {"smooth": True} if self.smooth_edges else {}
         if self.crop is not None:              # a crop zooms into a scene; without --working-points the scene is the loaded cloud itself
-            self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points or self.pc_xyz.shape[1])
-            self.predictor.set_crop(self.crop[0], self.crop[1], max_points=self.crop_points)      # cached: built and encoded once per crop
+            self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points or self.pc_xyz.shape[1], **smooth)
+            self.predictor.set_crop(self.crop[0], self.crop[1], max_points=self.crop_points, **smooth)      # cached: built and encoded once per crop
         elif self.working_points is None:
             self.predictor.set_pointcloud(self.pc_xyz, self.pc_rgb)
         else:
-            self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points)
+            self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points, **smooth)
 
     def _reset_prompts(self):
         self.prompts, self.labels, self.prompt_mask = [], [], None
@@ -314,7 +320,7 @@ def serve(session: DemoSession, host="localhost", port=5000) -> ThreadingHTTPSer
     return ThreadingHTTPServer((host, port), make_handler(session))
 
 
-def main():
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--host", default="localhost")
     ap.add_argument("--port", type=int, default=5000)
@@ -330,11 +336,18 @@ def main():
                     help="answer /segment with the cleaned mask: holes and islands below this many points filled / removed, only the clicked part kept")
     ap.add_argument("--crop-points", type=int, default=None,
                     help="POST /crop: the zoomed ball gets a working cloud of at most this many points; default: every point of the ball")
-    args = ap.parse_args()
+    ap.add_argument("--smooth-edges", action="store_true",
+                    help="with --working-points or under /crop: blend each loaded point's mask value from the three nearest working points (smooth mask edges) "
+                         "instead of copying its voxel's")
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
     from .predictor import PointSAMPredictor
     pred = PointSAMPredictor.from_config(args.config, args.ckpt, precision=args.precision)
     srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points,
-                            clean_min_points=args.clean_min_points, crop_points=args.crop_points), args.host, args.port)
+                            clean_min_points=args.clean_min_points, crop_points=args.crop_points, smooth_edges=args.smooth_edges), args.host, args.port)
     print(f"Point-SAM demo back end on http://{args.host}:{args.port}")
     srv.serve_forever()
 

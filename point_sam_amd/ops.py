@@ -1394,6 +1394,100 @@ def crop_expand_bits(bits: torch.Tensor, inv: torch.Tensor, Nw: int, area: bool 
     return bits_f, area_f
 
 
+# ------------------------------------------------------------------------------------------ interpolated scene masks (csrc/scene_interp.hip)
+def scene_interp_plan(xyz: torch.Tensor, inv: torch.Tensor, wxyz: torch.Tensor, nbr: torch.Tensor, center=None, radius: float = None, eps: float = 1e-8):
+    """xyz [M, 3] f32 (the scan), inv [M] int64, wxyz [Nw, 3] f32 (the working cloud as encoded), nbr [Nw, 26] int32 (region_neighbors on the grid the
+    working cloud was built on) -> (idx3 [M, 3] int32, w3 [M, 3] f32): per scan point the up to three nearest, by (squared distance, rank), of the
+    representatives of its voxel and of the 26 voxels around it, and their inverse-distance weights (common.py:238-255's arithmetic on the grid's
+    candidates; include/pointsam_hip.h has the definition).  center / radius: a crop's -- the query coordinate is then the crop's normalised one and
+    points with inv == -1 get idx3 = -1, w3 = 0.  No host synchronisation."""
+    import numpy as np
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    _chk(xyz, name="xyz"); _chk(inv, torch.int64, "inv"); _chk(wxyz, name="wxyz"); _chk(nbr, torch.int32, "nbr")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1 or inv.dim() != 1 or inv.numel() != xyz.shape[0]:
+        raise ValueError(f"scene_interp_plan: xyz must be [M, 3] and inv [M], got {tuple(xyz.shape)} and {tuple(inv.shape)}")
+    if wxyz.dim() != 2 or wxyz.shape[1] != 3 or wxyz.shape[0] < 1 or tuple(nbr.shape) != (wxyz.shape[0], 26):
+        raise ValueError(f"scene_interp_plan: wxyz must be [Nw, 3] and nbr [Nw, 26], got {tuple(wxyz.shape)} and {tuple(nbr.shape)}")
+    if (center is None) != (radius is None):
+        raise ValueError("scene_interp_plan: center and radius are a crop's: give both or neither")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 <= eps < float("inf"):
+        raise ValueError(f"scene_interp_plan: eps must be finite and not negative, got {eps!r}")
+    org, inv_r = None, 0.0
+    if center is not None:
+        c = np.asarray([float(v) for v in center], dtype=np.float32) if len(center) == 3 else None
+        if c is None or not np.isfinite(c).all():
+            raise ValueError(f"scene_interp_plan: center must be three finite fp32 numbers, got {center!r}")
+        if isinstance(radius, bool) or not isinstance(radius, (int, float, np.floating)):
+            raise ValueError(f"scene_interp_plan: radius must be a number, got {radius!r}")
+        r = np.float32(radius)
+        with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+            inv_r = np.float32(1) / r                      # fp32, as crop_downsample computes it
+        if not (np.isfinite(r) and r > 0 and np.isfinite(inv_r) and inv_r > 0):
+            raise ValueError(f"scene_interp_plan: radius must be positive with a finite fp32 inverse, got {radius!r}")
+        org = (ctypes.c_float * 3)(*[float(v) for v in c])
+    M, Nw, dev = xyz.shape[0], wxyz.shape[0], xyz.device
+    idx3 = torch.empty(M, 3, dtype=torch.int32, device=dev)
+    w3 = torch.empty(M, 3, dtype=torch.float32, device=dev)
+    check(_lib.load().psam_interp_scene_plan(xyz.data_ptr(), M, inv.data_ptr(), wxyz.data_ptr(), nbr.data_ptr(), Nw,
+                                             None if org is None else ctypes.addressof(org), float(inv_r), float(eps), idx3.data_ptr(), w3.data_ptr(),
+                                             _stream()), "psam_interp_scene_plan")
+    return idx3, w3
+
+
+def _interp_chk(src, idx3, w3, what: str):
+    """-> (rows [R, Nw] with unit column stride, src_ld, lead, Nw, M)."""
+    _chk(idx3, torch.int32, "idx3"); _chk(w3, name="w3")
+    if not src.is_cuda:
+        raise _lib.PointSamHipError("src must live on the GPU: the HIP path has no CPU fallback")
+    if src.dtype != torch.float32:
+        raise TypeError(f"{what}: rows of float32, got {src.dtype}")
+    if idx3.dim() != 2 or idx3.shape[1] != 3 or tuple(w3.shape) != tuple(idx3.shape):
+        raise ValueError(f"{what}: idx3 and w3 must both be [M, 3], got {tuple(idx3.shape)} and {tuple(w3.shape)}")
+    Nw, M = src.shape[-1], idx3.shape[0]
+    lead = tuple(src.shape[:-1])
+    rows = src.reshape(-1, Nw) if src.dim() != 2 else src
+    if rows.stride(1) != 1 and Nw > 1:
+        rows = rows.contiguous()
+    R = rows.shape[0]
+    if R < 1 or Nw < 1 or M < 1:
+        raise ValueError(f"{what}: empty input: src {tuple(src.shape)}, idx3 {tuple(idx3.shape)}")
+    src_ld = rows.stride(0) if R > 1 else Nw
+    if src_ld < Nw:
+        rows, src_ld = rows.contiguous(), Nw
+    return rows, src_ld, lead, Nw, M
+
+
+def scene_interp_rows(src: torch.Tensor, idx3: torch.Tensor, w3: torch.Tensor, fill=None, out: torch.Tensor = None) -> torch.Tensor:
+    """src [..., Nw] f32 (the leading dimensions are R rows with one stride; last stride 1), a plan (idx3, w3) [M, 3] -> [..., M] f32: per scan point
+    the blend w0 l0 + w1 l1 (+ w2 l2) of its sources l_j = src[r, idx3[i, j]]; a point with a single source receives that word bit for bit, an off
+    point (a crop's) `fill` (None: 0.0).  An idx3 entry outside [0, Nw) is unused.  out: a [R, M] destination with its own row stride."""
+    rows, src_ld, lead, Nw, M = _interp_chk(src, idx3, w3, "scene_interp_rows")
+    R = rows.shape[0]
+    if out is None:
+        dst = torch.empty(R, M, dtype=torch.float32, device=src.device)
+    else:
+        dst = out
+        if dst.dtype != src.dtype or dst.dim() != 2 or tuple(dst.shape) != (R, M) or (M > 1 and dst.stride(1) != 1) or (R > 1 and dst.stride(0) < M):
+            raise ValueError(f"scene_interp_rows: out must be [{R}, {M}] {src.dtype} with unit column stride, got {tuple(dst.shape)} {dst.dtype}")
+    dst_ld = dst.stride(0) if R > 1 else M
+    check(_lib.load().psam_interp_scene_rows(rows.data_ptr(), src_ld, idx3.data_ptr(), w3.data_ptr(), R, Nw, M, 0.0 if fill is None else float(fill),
+                                             dst.data_ptr(), dst_ld, _stream()), "psam_interp_scene_rows")
+    return dst if out is not None else dst.reshape(lead + (M,))
+
+
+def scene_interp_bits(src: torch.Tensor, idx3: torch.Tensor, w3: torch.Tensor, thr: float = 0.0, area: bool = True):
+    """mask_pack of scene_interp_rows without the [K, M] floats in between: src [..., Nw] f32 (K rows), a plan [M, 3] -> (bits_f [K, ceil(M / 64)] int64,
+    area_f [K] int32 or None): bit i = blend > thr (NaN false, an off point 0); bits past M are zero; area_f = the rows' popcounts."""
+    rows, src_ld, _, Nw, M = _interp_chk(src, idx3, w3, "scene_interp_bits")
+    K = rows.shape[0]
+    bits_f = torch.empty(K, mask_words(M), dtype=torch.int64, device=src.device)
+    area_f = torch.empty(K, dtype=torch.int32, device=src.device) if area else None
+    check(_lib.load().psam_interp_scene_bits(rows.data_ptr(), src_ld, idx3.data_ptr(), w3.data_ptr(), K, Nw, M, float(thr), bits_f.data_ptr(), _p(area_f),
+                                             _stream()), "psam_interp_scene_bits")
+    return bits_f, area_f
+
+
 # ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)
 def _region_ws(nbytes: int, dev, what: str):
     if nbytes == 0:

@@ -19,6 +19,15 @@ from .model import EncoderState, PointCloudSAM
 from .weights import load_safetensors, random_state_dict
 
 
+_UNBUILT = object()      # an interpolation plan not asked for yet (None is a built answer: the mapping has nothing to blend)
+
+
+def _check_smooth(smooth, what: str, allow_none: bool = False):
+    if not (isinstance(smooth, bool) or (allow_none and smooth is None)):
+        raise ValueError(f"{what}: smooth must be True or False{' or None' if allow_none else ''}, got {smooth!r}")
+    return smooth
+
+
 class PointSAMPredictor:
     def __init__(self, model: PointCloudSAM):
         self.model = model
@@ -29,7 +38,10 @@ class PointSAMPredictor:
         self.crop = None                # set_crop(): the scan <-> crop-cloud mapping of the active ball (scene.Crop); None = the whole scene answers
         self._crop_state: Optional[EncoderState] = None      # the crop cloud's encoder state; self._state stays the scene's, so clear_crop() re-encodes nothing
         self._crop_key = None
-        self._crop_cache = None         # (key, Crop, state) of the last crop built: survives clear_crop() and a set_scene() of the same scene
+        self._crop_cache = None         # [key, Crop, state, plan] of the last crop built: survives clear_crop() and a set_scene() of the same scene
+        self._smooth = False            # set_scene(smooth=): scan points receive a 3-NN blend of working logits, not their representative's
+        self._crop_smooth = False       # the same for the active crop (set_crop(smooth=None) takes the scene's setting)
+        self._scene_plan = _UNBUILT     # scene.InterpPlan of the cached scene (None: nothing to blend), built by the first predict that needs it
         self._graphs = None             # clean_masks(): (key, [regions.PointGraph per cloud]) of the cached cloud and voxel settings
 
     @classmethod
@@ -58,15 +70,23 @@ class PointSAMPredictor:
             self._keepalive = (xyz, rgb)  # the cache key uses data_ptr: keep the tensors alive
             self.scene = None
             self._crop_cache = None
+            self._scene_plan = _UNBUILT
+        self._smooth = False
         self._deactivate_crop()
 
     @torch.no_grad()
-    def set_scene(self, xyz: torch.Tensor, rgb: torch.Tensor, voxel_size: float = None, max_points: int = None) -> None:
+    def set_scene(self, xyz: torch.Tensor, rgb: torch.Tensor, voxel_size: float = None, max_points: int = None, smooth: bool = False) -> None:
         """A full-resolution scan, xyz / rgb [M, 3] normalised as for set_pointcloud, served through a voxel-grid working cloud: one real point per
         occupied voxel of size `voxel_size`, or of the smallest ladder size that leaves at most `max_points` (scene.choose_voxel_size); a scan of at
         most `max_points` points is its own working cloud.  predict_masks / generate_masks then answer per point of the scan.  Cached like
-        set_pointcloud; `self.scene` holds keep_idx, inv and num_working."""
+        set_pointcloud; `self.scene` holds keep_idx, inv and num_working.
+
+        smooth: predict_masks / predict_mask_bits give every scan point the inverse-distance blend of the up to three nearest working points among
+        its voxel's and the 26 surrounding voxels' representatives (scene.build_interp_plan) instead of its representative's logit; the
+        representatives themselves keep their logits bit for bit.  Not part of the cache key: toggling it encodes nothing; the plan (24 bytes per
+        scan point) is built by the first prediction that needs it and kept with the scene."""
         from . import scene as S
+        _check_smooth(smooth, "set_scene")
         xyz, rgb = S.check_scene_arguments(xyz, rgb, voxel_size, max_points)
         g = self.model.pc_encoder.patch_embed.grouper
         key = self._cloud_key(xyz, rgb) + (g.num_groups, g.group_size, "scene", voxel_size, max_points)
@@ -78,20 +98,26 @@ class PointSAMPredictor:
             self._keepalive = (xyz, rgb)
             self.scene = sc
             self._crop_cache = None
+            self._scene_plan = _UNBUILT
+        self._smooth = smooth
         self._deactivate_crop()
 
     def _deactivate_crop(self) -> None:
-        self.crop, self._crop_state, self._crop_key = None, None, None
+        self.crop, self._crop_state, self._crop_key, self._crop_smooth = None, None, None, False
 
     @torch.no_grad()
-    def set_crop(self, center, radius: float, voxel_size: float = None, max_points: int = None) -> None:
+    def set_crop(self, center, radius: float, voxel_size: float = None, max_points: int = None, smooth: bool = None) -> None:
         """Zoom into the ball (center, radius) of the scan given to set_scene (scan coordinates): its points, normalised to (x - center) / radius, get
         a working cloud of their own -- one real point per voxel of size `voxel_size` (crop units), or of the smallest ladder size that leaves at most
         `max_points`; neither: every point of the ball -- and their own encoder pass (scene.build_crop).  Until clear_crop(), predict_masks /
         generate_masks / clean_masks answer from the crop cloud, still per point of the scan and with prompts in scan coordinates: -inf logits, zero
         bits and label -1 outside the ball.  The scene's encoder state is kept.  set_scene and set_pointcloud drop the crop.  The last crop built is
         cached on (scene, center, radius, voxel_size, max_points): setting it again, also after clear_crop() or a set_scene() of the same scene,
-        builds and encodes nothing.  `self.crop` holds keep_idx, inv, num_members and num_working."""
+        builds and encodes nothing.  `self.crop` holds keep_idx, inv, num_members and num_working.
+
+        smooth: as for set_scene, over the crop's own voxel grid (None: the scene's setting); not part of the crop's cache key, and the plan is
+        cached with the crop."""
+        _check_smooth(smooth, "set_crop", allow_none=True)
         if self.scene is None or self._state is None:
             raise RuntimeError("set_crop() zooms into a scene: call set_scene() first")
         from . import scene as S
@@ -99,8 +125,9 @@ class PointSAMPredictor:
         if self._crop_cache is None or self._crop_cache[0] != key:
             xyz, rgb = self._keepalive
             crop, wxyz, wrgb = S.build_crop(xyz, rgb, center, radius, voxel_size, max_points)
-            self._crop_cache = (key, crop, self.model.encode(wxyz[None], wrgb[None]))
-        self._crop_key, self.crop, self._crop_state = self._crop_cache
+            self._crop_cache = [key, crop, self.model.encode(wxyz[None], wrgb[None]), _UNBUILT]
+        self._crop_key, self.crop, self._crop_state = self._crop_cache[:3]
+        self._crop_smooth = self._smooth if smooth is None else smooth
 
     def clear_crop(self) -> None:
         """Back to the whole scene: its encoder state was kept, nothing is encoded again."""
@@ -112,15 +139,24 @@ class PointSAMPredictor:
             return self._crop_state, self.crop, self._crop_key
         return self._state, self.scene, self._key
 
-    def set_prompts(self, prompt_points, prompt_labels, prompt_mask=None) -> None:
-        self._prompts = (prompt_points, prompt_labels, prompt_mask)
+    def _interp_plan(self):
+        """The active mapping's interpolation plan if smooth edges are on and there is something to blend, else None.  Built on first use."""
+        from .scene import build_interp_plan
+        xyz = self._keepalive[0]
+        if self.crop is not None:
+            if not self._crop_smooth:
+                return None
+            if self._crop_cache[3] is _UNBUILT:
+                self._crop_cache[3] = build_interp_plan(self.crop, xyz, self._crop_state.coords[0].contiguous())
+            return self._crop_cache[3]
+        if self.scene is None or not self._smooth:
+            return None
+        if self._scene_plan is _UNBUILT:
+            self._scene_plan = build_interp_plan(self.scene, xyz, self._state.coords[0].contiguous())
+        return self._scene_plan
 
-    @torch.no_grad()
-    def predict_masks(self, prompt_points=None, prompt_labels=None, prompt_mask=None, multimask_output: bool = True):
-        """-> (masks [BM,C,N] logits, scores [BM,C], logits [BM,C,N]); masks and logits are the same tensor, the
-        caller thresholds at 0 (demo/app.py:203-205).  After set_scene: N = the scan's points; a prompt_mask may have the scan's or the working
-        cloud's width.  Under set_crop: the prompts are still scan coordinates (one outside the ball is a ValueError), the logits are the crop
-        cloud's indexed by crop.inv, -inf outside the ball; a prompt_mask may have the scan's or the crop cloud's width."""
+    def _decode(self, prompt_points, prompt_labels, prompt_mask, multimask_output):
+        """-> (working-width logits, scores, mapping or None, crop?): the part predict_masks and predict_mask_bits share."""
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
         if prompt_points is None:
@@ -136,18 +172,55 @@ class PointSAMPredictor:
                 prompt_points = crop_prompts(sc, prompt_points)     # scan coordinates -> the crop's unit ball; a prompt off the ball is a ValueError
         logits, scores = self.model.decode(state, prompt_points, prompt_labels, prompt_mask, multimask_output)
         self.model.check_coordinate_range()
-        if crop:
+        return logits, scores, sc, crop
+
+    def set_prompts(self, prompt_points, prompt_labels, prompt_mask=None) -> None:
+        self._prompts = (prompt_points, prompt_labels, prompt_mask)
+
+    @torch.no_grad()
+    def predict_masks(self, prompt_points=None, prompt_labels=None, prompt_mask=None, multimask_output: bool = True):
+        """-> (masks [BM,C,N] logits, scores [BM,C], logits [BM,C,N]); masks and logits are the same tensor, the
+        caller thresholds at 0 (demo/app.py:203-205).  After set_scene: N = the scan's points; a prompt_mask may have the scan's or the working
+        cloud's width.  Under set_crop: the prompts are still scan coordinates (one outside the ball is a ValueError), the logits are the crop
+        cloud's indexed by crop.inv, -inf outside the ball; a prompt_mask may have the scan's or the crop cloud's width.  With smooth edges
+        (set_scene / set_crop smooth=True) the logits are the 3-NN blend of the working cloud's; at the representatives they are the working
+        cloud's bit for bit, so they serve as the next click's prompt_mask exactly like the working-width logits."""
+        logits, scores, sc, crop = self._decode(prompt_points, prompt_labels, prompt_mask, multimask_output)
+        plan = self._interp_plan()
+        if plan is not None:
+            logits = ops.scene_interp_rows(logits, plan.idx3, plan.w3, float("-inf") if crop else None)      # [M', C, num_working] -> [M', C, M]
+        elif crop:
             logits = ops.crop_expand_rows(logits, sc.inv, float("-inf"))      # [M', C, num_working] -> [M', C, M]; -inf off the ball
         elif sc is not None and not sc.identity:
             logits = ops.scene_expand_rows(logits, sc.inv)       # [M', C, num_working] -> [M', C, M]: each point takes its representative's logit
         return logits, scores, logits
 
     @torch.no_grad()
+    def predict_mask_bits(self, prompt_points=None, prompt_labels=None, prompt_mask=None, multimask_output: bool = True, threshold: float = 0.0):
+        """predict_masks for a caller that wants the masks, not the logits: -> (bits [BM * C, W] int64 words of ``logit > threshold`` in mask_pack's
+        layout, W = ceil(N / 64); area [BM * C] int32; scores [BM, C]).  The same bits as mask_pack of predict_masks' logits, without the
+        [BM, C, N] floats of a scan: with smooth edges the blend is thresholded in registers (ops.scene_interp_bits), otherwise the working
+        cloud's packed rows are expanded (scene_expand_bits / crop_expand_bits); after set_pointcloud it is mask_pack alone."""
+        logits, scores, sc, crop = self._decode(prompt_points, prompt_labels, prompt_mask, multimask_output)
+        logits = logits.float().contiguous()
+        plan = self._interp_plan()
+        if plan is not None:
+            bits, area = ops.scene_interp_bits(logits, plan.idx3, plan.w3, threshold)
+            return bits, area, scores
+        bits, area, _, _ = ops.mask_pack(logits, threshold, 0.0)
+        if crop:
+            bits, area = ops.crop_expand_bits(bits, sc.inv, sc.num_working)
+        elif sc is not None and not sc.identity:
+            bits, area = ops.scene_expand_bits(bits, sc.inv, sc.num_working)
+        return bits, area, scores
+
+    @torch.no_grad()
     def generate_masks(self, cfg=None, crops=None):
         """Automatic mask proposals for the cached cloud(s), no prompts needed (point_sam_amd/proposals.py): a list with one `Proposals` per
         cloud -- kept masks best first, bit-packed, and one instance label per point.  cfg: a `ProposalConfig` (None = its defaults).
         Works for every model variant (voronoi, hierarchical): only the public `decode` is called, with single-point prompts and no mask prompt.
-        Under set_crop: the crop cloud's proposals at the scan's width, zero bits and label -1 off the ball.
+        Under set_crop: the crop cloud's proposals at the scan's width, zero bits and label -1 off the ball.  Proposals keep bits, not logits:
+        they stay at voxel granularity whatever `smooth` says.
 
         crops: a `CropLayerConfig` -- multi-crop proposals of a scene (set_scene, no active crop).  The scene's own proposals first; then, for each
         of the first `num_crops` FPS samples of the scene's working cloud (index 0 first: every centre is a real point), the crop cloud of the ball
@@ -218,7 +291,8 @@ class PointSAMPredictor:
         prompts (label 1) of its prompt set, prompt_points [BM, P, 3] / prompt_labels [BM, P] (default: those of set_prompts); the C masks of a
         prompt set share them.  After set_scene (and under set_crop, where the working cloud is the crop's and the points off the ball come back as zero
         bits), logits of the scan's width are reduced to the working cloud (the representatives' values), cleaned
-        there and expanded, so every scan point has its representative's bit; logits of the working cloud's width are returned at that width."""
+        there and expanded, so every scan point has its representative's bit; logits of the working cloud's width are returned at that width.
+        The clean-up works on the voxel graph: its result is at voxel granularity also for smooth logits (only the representatives' values count)."""
         if self._state is None:
             raise RuntimeError("call set_pointcloud() first")
         from .regions import RegionConfig, clean_bits

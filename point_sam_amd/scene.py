@@ -169,6 +169,29 @@ def crop_shell_bits(crop: Crop, xyz: torch.Tensor, edge_frac: float) -> torch.Te
     return ops.mask_pack(q[None].contiguous(), float(rs * rs), 0.0)[0]
 
 
+@dataclass
+class InterpPlan:
+    """Smooth edges: per scan point up to three working points and their weights (``csrc/scene_interp.hip``).  Geometry only: one plan serves every click."""
+    idx3: torch.Tensor              # [M, 3] int32: working-cloud rows, -1 = unused (all three off a crop's ball)
+    w3: torch.Tensor                # [M, 3] float32: the weights; (1, 0, 0) where a single source is copied
+
+
+def build_interp_plan(mapping, xyz: torch.Tensor, wxyz: torch.Tensor) -> Optional[InterpPlan]:
+    """The plan that carries a working cloud's logits to the scan by a 3-NN inverse-distance blend over each point's 27-cell voxel neighbourhood.
+    mapping: a `Scene` or a `Crop`; xyz [M, 3] the scan; wxyz [num_working, 3] the working cloud as it was encoded (the scan's points for a scene,
+    the normalised ones for a crop).  The neighbour table is the grid's the working cloud was built on: the scene's voxel size from origin -1 on the
+    scan, the crop's (crop units) from origin -1 on the crop cloud, every crop point its own voxel.  None for an identity scene and for a crop
+    without a voxel size: every point is its own representative, there is nothing to blend.  24 bytes per scan point."""
+    if mapping.identity or mapping.voxel_size is None:
+        return None
+    if isinstance(mapping, Crop):
+        ranks = torch.arange(mapping.num_working, dtype=torch.int64, device=wxyz.device)
+        nbr = ops.region_neighbors(wxyz, ranks, mapping.voxel_size)
+        return InterpPlan(*ops.scene_interp_plan(xyz, mapping.inv, wxyz, nbr, center=mapping.center, radius=mapping.radius))
+    nbr = ops.region_neighbors(xyz, mapping.keep_idx, mapping.voxel_size)
+    return InterpPlan(*ops.scene_interp_plan(xyz, mapping.inv, wxyz, nbr))
+
+
 def reduce_prompt_mask(scene, prompt_mask: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """A mask prompt of the scan's width -> the working cloud's width: the representatives' own values (exact: inv[keep_idx[j]] == j).  A mask of
     the working cloud's width passes unchanged.  scene: a `Scene` or a `Crop` (whose cloud is narrower than the scan: points off the ball drop out)."""

@@ -752,6 +752,46 @@ int32_t psam_region_clean(const uint64_t* bits, const uint8_t* select, const int
                           int32_t N, int32_t V, int32_t S, int32_t min_island, int32_t min_hole, uint64_t* bits_out, int32_t* area_out,
                           uint8_t* changed, void* ws, size_t ws_bytes, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- instance geometry */
+
+/* Where a packed mask is, how big it is and what colour it has (point_sam_amd/geometry.py), straight from the bits: the work follows the set bits,
+ * no [K, N] matrix is formed.  bits [K, W] in the layout of the mask proposals, W = ceil(N / 64); a bit at a position >= N is IGNORED whatever
+ * the caller left there, and xyz / rgb are never read at an index >= N.  S_k = the member points of row k.  0 < K <= 65535, 0 < N <= 2^28.  No call
+ * allocates, creates a stream or an event, or synchronises with the host; the workspace is the caller's.  A null pointer, a bad size or a short
+ * workspace returns -1, a misaligned pointer -2, with psam_last_error_string set.
+ *
+ * A wave owns PSAM_INSTANCE_RANGE_WORDS consecutive words of a row; a row of more words is split over ceil(W / PSAM_INSTANCE_RANGE_WORDS) waves whose
+ * partial results are combined in range order by a second kernel.
+ *
+ * psam_instance_moments: xyz [N, 3] f32, rgb [N, 3] f32 or NULL.
+ *   count [K] int32   |S_k|, an exact integer
+ *   lo, hi [K, 3] f32 the component-wise minimum / maximum of the members' coordinates in the order -inf < .. < -0 < +0 < .. < +inf: exact and
+ *                     independent of any order; an empty row gives +inf / -inf
+ *   sums [K, 12] f64  sum x, sum y, sum z, sum xx, sum xy, sum xz, sum yy, sum yz, sum zz, sum r, sum g, sum b over S_k.  Every TERM is formed in
+ *                     fp64 from the fp32 inputs and is exact (the conversion, and the product of two converted values: 48 significant bits); only
+ *                     the additions round, each an IEEE fp64 addition.  With rgb == NULL the last three are 0; an empty row gives twelve zeros.
+ *   Order of the additions, fixed: a lane of the wave adds the points of words base + lane, base + 64 + lane, base + 128 + lane, base + 192 + lane
+ *   of its range, bits ascending, into its own accumulators starting from 0; the 64 lanes are combined by the xor butterfly 32, 16, 8, 4, 2, 1; the
+ *   row's ranges are added in increasing order starting from 0 (a range without members contributes an exact 0).  The order depends on N and on
+ *   the row's own bits only: row k gives the same bits from run to run, and the same bits computed alone or among K others.  No float atomics.
+ *   Error: |sums - exact| <= (n - 1) u / (1 - (n - 1) u) * sum |term|, u = 2^-53, n = count -- the bound of ANY order of n - 1 additions.
+ *   Coordinates are assumed finite; non-finite input does not fault, its results are unspecified.
+ *   ws: psam_instance_moments_workspace_bytes(K, N) bytes (0 for a bad shape), 8-byte aligned. */
+#define PSAM_INSTANCE_RANGE_WORDS 256
+size_t psam_instance_moments_workspace_bytes(int32_t K, int32_t N);
+int32_t psam_instance_moments(const float* xyz, const float* rgb, const uint64_t* bits, int32_t K, int32_t N, int32_t* count, double* sums,
+                              float* lo, float* hi, void* ws, size_t ws_bytes, psam_stream_t stream);
+/* psam_instance_extents: the members of row k in the frame origin [K, 3], axes [K, 3, 3] (row i of axes[k] = axis i; NULL: the identity, p = d), all
+ *   on the device.  In fp32, every operation rounded on its own and in exactly this order, per member point:
+ *     d   = (x - ox, y - oy, z - oz)
+ *     p_i = (d.x a_i0 + d.y a_i1) + d.z a_i2, i = 0, 1, 2                 (the axes need not be orthonormal: nothing assumes it)
+ *     r2  = (d.x d.x + d.y d.y) + d.z d.z
+ *   lo, hi [K, 3] = the component-wise minimum / maximum of p, r2max [K] = the maximum of r2, in the order above (exact, order-independent); an
+ *   empty row gives +inf / -inf / -inf.  ws: psam_instance_extents_workspace_bytes(K, N) bytes, 4-byte aligned. */
+size_t psam_instance_extents_workspace_bytes(int32_t K, int32_t N);
+int32_t psam_instance_extents(const float* xyz, const uint64_t* bits, int32_t K, int32_t N, const float* origin, const float* axes, float* lo,
+                              float* hi, float* r2max, void* ws, size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -151,6 +151,10 @@ SIGNATURES = {
     "psam_region_labels": (i32, [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr, size_t, ptr]),
     "psam_region_clean_workspace_bytes": (size_t, [i32, i32, i32, i32]),
     "psam_region_clean": (i32, [ptr, ptr, ptr, ptr, ptr, i32, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_instance_moments_workspace_bytes": (size_t, [i32, i32]),
+    "psam_instance_moments": (i32, [ptr, ptr, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_instance_extents_workspace_bytes": (size_t, [i32, i32]),
+    "psam_instance_extents": (i32, [ptr, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
 }
 
 

@@ -13,6 +13,8 @@ POST /next (:153-159) . POST /save (:162-175) . POST /segment (:177-206).
 POST /segment_all (not in the reference): automatic mask proposals for the whole cloud, a first pass before the per-object clicks.
 POST /crop {center, radius} . POST /crop/clear (not in the reference): zoom into a ball of the loaded cloud -- /segment and /segment_all then answer
 from the ball's own working cloud (predictor.set_crop), still per loaded point, until the crop is cleared or another cloud is loaded.
+POST /instances (not in the reference): /segment_all plus one box per kept mask (predictor.mask_geometry) . POST /crop/selection {margin}: zoom
+into the ball around the current /segment mask (predictor.set_crop_to_mask).
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -226,17 +228,79 @@ class DemoSession:
         """"Segment everything": automatic mask proposals on the current cloud.  Optional body keys override `ProposalConfig` fields (an unknown key
         or a bad value is a ValueError -> 400).  {"labels": [N ints, -1 = none], "num_masks": k, "scores": [k floats]}, masks best first.  The
         click state of /segment is not touched."""
+        with self.lock:
+            return self._segment_all(data, "/segment_all")[1]
+
+    def _segment_all(self, data, route: str):
+        """-> (Proposals, the /segment_all response); the caller holds the lock."""
         from .proposals import ProposalConfig
+        if self.pc_xyz is None:
+            raise ValueError(f"{route} before a point cloud was set")
+        if not isinstance(data, dict):
+            raise ValueError(f"{route} takes a JSON object of ProposalConfig overrides (or nothing)")
+        cfg = ProposalConfig.from_overrides(data)
+        with torch.no_grad():
+            self._set_cloud()
+            prop = self.predictor.generate_masks(cfg)[0]
+        return prop, {"labels": prop.labels.cpu().numpy().astype(int).tolist(), "num_masks": int(len(prop)), "scores": prop.score.cpu().numpy().astype(float).tolist()}
+
+    def instances(self, data: dict) -> dict:
+        """/segment_all plus where every kept mask is: "boxes" = one {center, half, axes (rows), aabb_lo, aabb_hi, count, mean_rgb} per mask, in the
+        masks' order, in the loaded cloud's coordinates (predictor.mask_geometry: the oriented box along the mask's principal axes).  A number that
+        does not exist (an empty mask has no box) is null."""
+        with self.lock:
+            prop, out = self._segment_all(data, "/instances")
+            boxes = []
+            if len(prop) > 0:
+                with torch.no_grad():
+                    geo = self.predictor.mask_geometry(prop)
+
+                def num(t):
+                    a = np.asarray(t.cpu().numpy(), dtype=np.float64)
+                    return np.where(np.isfinite(a), a, None).tolist() if not np.isfinite(a).all() else a.tolist()
+                for k in range(len(prop)):
+                    boxes.append({"center": num(geo.obb_center[k]), "half": num(geo.obb_half[k]), "axes": num(geo.axes[k]), "aabb_lo": num(geo.aabb_lo[k]),
+                                  "aabb_hi": num(geo.aabb_hi[k]), "count": int(geo.count[k]), "mean_rgb": None if geo.mean_rgb is None else num(geo.mean_rgb[k])})
+            return dict(out, boxes=boxes)
+
+    def crop_selection(self, data: dict) -> dict:
+        """Zoom into the object just segmented: {"margin": m} (optional, default 0.1) -> the ball around the current /segment mask, its centre the
+        mask's centroid and its radius the distance to the farthest point of the mask times 1 + m (predictor.set_crop_to_mask); from then on as
+        after /crop with that centre and radius.  Without a cloud, without a /segment mask, with an empty mask or a bad margin: a 400 that leaves
+        the previous state."""
         with self.lock:
             if self.pc_xyz is None:
-                raise ValueError("/segment_all before a point cloud was set")
-            if not isinstance(data, dict):
-                raise ValueError("/segment_all takes a JSON object of ProposalConfig overrides (or nothing)")
-            cfg = ProposalConfig.from_overrides(data)
+                raise ValueError("/crop/selection before a point cloud was set")
+            if self.segment_mask is None:
+                raise ValueError("/crop/selection before any /segment: there is no mask to zoom into")
+            if not isinstance(data, dict) or set(data) - {"margin"}:
+                raise ValueError('/crop/selection takes {"margin": m} (or nothing)')
+            margin = data.get("margin", 0.1)
+            if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not 0 <= margin < float("inf"):
+                raise ValueError("margin must be a finite number >= 0")
+            smooth = {"smooth": True} if self.smooth_edges else {}
             with torch.no_grad():
-                self._set_cloud()
-                prop = self.predictor.generate_masks(cfg)[0]
-            return {"labels": prop.labels.cpu().numpy().astype(int).tolist(), "num_masks": int(len(prop)), "scores": prop.score.cpu().numpy().astype(float).tolist()}
+                # the mask is one of the loaded cloud: it is measured on the whole scene, whatever crop was active (self._set_cloud() brings that one
+                # back on the next request if this call fails: it is cached)
+                self.predictor.set_scene(self.pc_xyz, self.pc_rgb, max_points=self.working_points or self.pc_xyz.shape[1], **smooth)
+                center, radius = self.predictor.set_crop_to_mask(pack_mask(self.segment_mask), margin=float(margin), max_points=self.crop_points, **smooth)
+            self.crop = (tuple(float(v) for v in center), float(radius))
+            self._reset_prompts()
+            self.segment_mask = None
+            crop = getattr(self.predictor, "crop", None)
+            return {"status": "cropped", "center": list(self.crop[0]), "radius": self.crop[1], "members": int(getattr(crop, "num_members", 0)),
+                    "working_points": int(getattr(crop, "num_working", 0))}
+
+
+def pack_mask(mask: torch.Tensor) -> torch.Tensor:
+    """bool [N] -> [ceil(N / 64)] int64 words of ops.mask_pack's layout (bit n % 64 of word n / 64 is point n), on the mask's device.  Plain torch
+    on purpose: ops.mask_pack thresholds fp32 logits and runs on the GPU only, while /segment keeps a boolean mask (the cleaned one has no logits)
+    and the session also runs against a predictor on the CPU; one row per request is not a hot path."""
+    n = mask.numel()
+    w = (n + 63) // 64
+    pad = torch.zeros(w * 64, dtype=torch.int64, device=mask.device)
+    pad[:n] = mask.reshape(-1).to(torch.int64)
+    return (pad.reshape(w, 64) << torch.arange(64, dtype=torch.int64, device=mask.device)).sum(1)      # distinct bits: the sum is their OR, bit 63 wraps to the sign
 
 
 MAX_BODY_BYTES = 64 << 20      # a sampled 10^5-point cloud as JSON is a few MB
@@ -304,6 +368,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
                       "/segment_all": lambda: session.segment_all(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
+                      "/instances": lambda: session.instances(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}
             fn = routes.get(self.path)
             if fn is None:

@@ -1580,3 +1580,72 @@ def region_clean(bits: torch.Tensor, inv: torch.Tensor, nbr: torch.Tensor, min_i
                               int(min_hole), out.data_ptr(), area.data_ptr(), changed.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()),
           "psam_region_clean")
     return out, area, changed
+
+
+# ------------------------------------------------------------------------------------------ instance geometry (csrc/geometry.hip)
+INSTANCE_RANGE_WORDS = 256      # PSAM_INSTANCE_RANGE_WORDS: the words of a row one wave owns; a row of more words is split over several
+
+
+def _geometry_chk(xyz, bits, what: str):
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    _chk(xyz, name="xyz"); _chk(bits, torch.int64, "bits")
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f"{what}: xyz must be [N, 3] with N >= 1 (one cloud), got {tuple(xyz.shape)}")
+    N = xyz.shape[0]
+    if bits.dim() != 2 or bits.shape[0] < 1 or bits.shape[1] != mask_words(N):
+        raise ValueError(f"{what}: bits {tuple(bits.shape)} for N = {N}: need [K >= 1, {mask_words(N)}]")
+    if bits.device != xyz.device:
+        raise ValueError(f"{what}: xyz is on {xyz.device}, bits on {bits.device}")
+    return xyz, N, bits.shape[0]
+
+
+def _geometry_ws(nbytes: int, dev, what: str):
+    if nbytes == 0:
+        raise ValueError(f"{what}: the shape is outside what the kernels are built for (K <= 65535 rows per call, N <= 2^28)")
+    return torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+
+
+def mask_moments(xyz: torch.Tensor, bits: torch.Tensor, rgb: torch.Tensor = None):
+    """xyz [N, 3] (or [1, N, 3]) f32, bits [K, W] int64 words (mask_pack's layout; bits past N are ignored), rgb like xyz or None ->
+    (count [K] int32, sums [K, 12] f64, lo [K, 3] f32, hi [K, 3] f32) per mask: the exact member count, the sums of x, y, z, xx, xy, xz, yy, yz, zz,
+    r, g, b over the members (exact fp64 terms, fp64 additions in a fixed order: bitwise reproducible, and a row's result does not depend on the
+    other rows), and the fp32 bounding box (+inf / -inf for an empty row).  Without rgb the colour sums are 0.  No host synchronisation."""
+    xyz, N, K = _geometry_chk(xyz, bits, "mask_moments")
+    if rgb is not None:
+        if rgb.dim() == 3 and rgb.shape[0] == 1:
+            rgb = rgb[0]
+        _chk(rgb, name="rgb")
+        if tuple(rgb.shape) != tuple(xyz.shape) or rgb.device != xyz.device:
+            raise ValueError(f"mask_moments: rgb must be {tuple(xyz.shape)} on {xyz.device} like xyz, got {tuple(rgb.shape)} on {rgb.device}")
+    L = _lib.load()
+    ws = _geometry_ws(L.psam_instance_moments_workspace_bytes(K, N), xyz.device, "mask_moments")
+    count = torch.empty(K, dtype=torch.int32, device=xyz.device)
+    sums = torch.empty(K, 12, dtype=torch.float64, device=xyz.device)
+    lo = torch.empty(K, 3, dtype=torch.float32, device=xyz.device)
+    hi = torch.empty(K, 3, dtype=torch.float32, device=xyz.device)
+    check(L.psam_instance_moments(xyz.data_ptr(), _p(rgb), bits.data_ptr(), K, N, count.data_ptr(), sums.data_ptr(), lo.data_ptr(), hi.data_ptr(),
+                                  ws.data_ptr(), ws.numel() * 8, _stream()), "psam_instance_moments")
+    return count, sums, lo, hi
+
+
+def mask_extents(xyz: torch.Tensor, bits: torch.Tensor, origin: torch.Tensor, axes: torch.Tensor = None):
+    """xyz [N, 3] (or [1, N, 3]) f32, bits [K, W] int64 words, origin [K, 3] f32, axes [K, 3, 3] f32 (rows are the axes; None: the identity) ->
+    (lo [K, 3], hi [K, 3], r2max [K]) f32: the box of every mask's members in its frame, p_i = (d.x a_i0 + d.y a_i1) + d.z a_i2 with d = x - origin,
+    and the largest (d.x d.x + d.y d.y) + d.z d.z, every fp32 operation rounded on its own; +inf / -inf / -inf for an empty row."""
+    xyz, N, K = _geometry_chk(xyz, bits, "mask_extents")
+    _chk(origin, name="origin")
+    if tuple(origin.shape) != (K, 3) or origin.device != xyz.device:
+        raise ValueError(f"mask_extents: origin must be [{K}, 3] on {xyz.device}, got {tuple(origin.shape)} on {origin.device}")
+    if axes is not None:
+        _chk(axes, name="axes")
+        if tuple(axes.shape) != (K, 3, 3) or axes.device != xyz.device:
+            raise ValueError(f"mask_extents: axes must be [{K}, 3, 3] on {xyz.device}, got {tuple(axes.shape)} on {axes.device}")
+    L = _lib.load()
+    ws = _geometry_ws(L.psam_instance_extents_workspace_bytes(K, N), xyz.device, "mask_extents")
+    lo = torch.empty(K, 3, dtype=torch.float32, device=xyz.device)
+    hi = torch.empty(K, 3, dtype=torch.float32, device=xyz.device)
+    r2max = torch.empty(K, dtype=torch.float32, device=xyz.device)
+    check(L.psam_instance_extents(xyz.data_ptr(), bits.data_ptr(), K, N, origin.data_ptr(), _p(axes), lo.data_ptr(), hi.data_ptr(), r2max.data_ptr(),
+                                  ws.data_ptr(), ws.numel() * 8, _stream()), "psam_instance_extents")
+    return lo, hi, r2max

@@ -11,6 +11,7 @@ the first run the decoder only -- BASELINE config #5's "encoder cached, decoder-
 """
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -337,3 +338,65 @@ class PointSAMPredictor:
         if expand:
             bits, area = (ops.crop_expand_bits if crop else ops.scene_expand_bits)(bits.contiguous(), sc.inv, Nw)
         return bits, area, changed
+
+    # -- instance geometry -------------------------------------------------------------------------------------
+    def _geometry_cloud(self, what: str, cloud: int = 0):
+        """(xyz [N, 3], rgb [N, 3]) the user gave: the scan after set_scene (with or without a crop), cloud `cloud` of the batch after set_pointcloud."""
+        if self._state is None:
+            raise RuntimeError("call set_pointcloud() first")
+        xyz, rgb = self._keepalive
+        if self.scene is not None:
+            return xyz, rgb
+        if isinstance(cloud, bool) or not isinstance(cloud, int) or not 0 <= cloud < xyz.shape[0]:
+            raise ValueError(f"{what}: cloud must be an index into the {xyz.shape[0]} cached cloud(s), got {cloud!r}")
+        return xyz[cloud], rgb[cloud]
+
+    @staticmethod
+    def _geometry_bits(masks, n_points: int, what: str, whose: str):
+        bits = masks.bits if hasattr(masks, "bits") else masks
+        if not isinstance(bits, torch.Tensor) or bits.dim() != 2 or bits.dtype != torch.int64:
+            raise ValueError(f"{what}: masks must be a Proposals or packed bits [k, W] int64, got {type(masks).__name__}"
+                             + (f" {tuple(bits.shape)} {bits.dtype}" if isinstance(bits, torch.Tensor) else ""))
+        if bits.shape[1] != ops.mask_words(n_points):
+            raise ValueError(f"{what}: masks of {bits.shape[1]} words do not fit {whose}'s {n_points} points ({ops.mask_words(n_points)} words); "
+                             "rows of a working cloud's width are the caller's to expand (ops.scene_expand_bits / crop_expand_bits)")
+        return bits.contiguous()
+
+    @torch.no_grad()
+    def mask_geometry(self, masks, cloud: int = 0, oriented: bool = True):
+        """Where the masks are: -> geometry.InstanceGeometry (count, centroid, axis-aligned and oriented box, covariance, mean colour, radius per
+        mask) in the coordinates the user gave.  masks: a `Proposals` or packed bits [k, W].  After set_scene (with or without an active crop) W
+        must be the scan's width and the scan's xyz / rgb are used; after set_pointcloud W must be the cloud's and cloud `cloud` of the batch is
+        used.  Any other width is a ValueError."""
+        from .geometry import mask_geometry
+        xyz, rgb = self._geometry_cloud("mask_geometry", cloud)
+        bits = self._geometry_bits(masks, xyz.shape[0], "mask_geometry", "the scan" if self.scene is not None else "the cloud")
+        return mask_geometry(xyz.contiguous(), bits, rgb.contiguous(), oriented)
+
+    @torch.no_grad()
+    def set_crop_to_mask(self, bits_row, margin: float = 0.1, voxel_size: float = None, max_points: int = None, smooth: bool = None):
+        """Zoom into an object: set_crop() on the ball around one mask of the scan -- centre = the mask's centroid, radius = the distance to its
+        farthest member times (1 + margin).  bits_row: [W] or [1, W] int64 words of the scan's width.  -> (center, radius) as given to set_crop
+        (a tuple of three floats, a float).  An empty mask, or one whose members all coincide (radius 0), is a ValueError and leaves the state alone."""
+        if self.scene is None or self._state is None:
+            raise RuntimeError("set_crop_to_mask() zooms into a scene: call set_scene() first")
+        if isinstance(margin, bool) or not isinstance(margin, (int, float)) or not 0 <= margin < float("inf"):
+            raise ValueError(f"set_crop_to_mask: margin must be a finite number >= 0, got {margin!r}")
+        _check_smooth(smooth, "set_crop_to_mask", allow_none=True)
+        row = bits_row[None] if isinstance(bits_row, torch.Tensor) and bits_row.dim() == 1 else bits_row
+        if isinstance(row, torch.Tensor) and row.dim() == 2 and row.shape[0] != 1:
+            raise ValueError(f"set_crop_to_mask: one mask at a time, got {row.shape[0]} rows")
+        from .geometry import mask_geometry
+        xyz, _ = self._keepalive
+        bits = self._geometry_bits(row, xyz.shape[0], "set_crop_to_mask", "the scan")
+        geo = mask_geometry(xyz, bits, None, oriented=False)
+        if not bool(geo.valid[0]):
+            raise ValueError("set_crop_to_mask: the mask is empty")
+        # The centroid as fp32 is the origin the radius was measured from, and what the crop's membership test subtracts.  One fp32 ulp on the
+        # radius covers the rounding of the square root and of the crop's r * r, so the farthest member is inside also at margin 0.
+        if not float(geo.radius[0]) > 0:                   # a single point, or coinciding ones: set_crop has no ball of radius 0 to build
+            raise ValueError("set_crop_to_mask: the mask's members coincide (radius 0): there is no ball to zoom into")
+        center = tuple(float(v) for v in geo.centroid[0].float().tolist())
+        radius = float(np.nextafter(np.float32(float(geo.radius[0]) * (1.0 + float(margin))), np.float32(np.inf)))
+        self.set_crop(center, radius, voxel_size, max_points, smooth)
+        return center, radius

@@ -86,3 +86,66 @@ def proposals(logits, score, N, thr, off, min_points, max_area_frac, pred_iou_th
     keep = nms(order, valid, area, inter, nms_thr)
     return dict(masks=m, area=area, area_hi=hi, area_lo=lo, valid=valid, order=order, inter=inter, keep=keep, labels=paint(m, order, keep),
                 candidate=np.array([i for i in order if keep[i]], dtype=np.int64))
+
+
+# ------------------------------------------------------------------------------------------------ intervals: overlaps in closed form
+# Thousands of candidates need no [K, N] booleans and no K x K matrix on the host when every mask is an interval of a line: area = e - s and
+# inter(i, j) = max(0, min(e_i, e_j) - max(s_i, s_j)).  nms() and paint() above stay the definition; the two functions below apply the same rules to
+# the closed form (tests/test_proposals_cpu.py holds them to nms() / paint() on the explicit masks).
+def interval_family(K, seed):
+    """-> (N, s, e [K] int64, score [K] f32, valid [K] bool): candidate i is [s_i, e_i) on a line of N = 2 K + 37 points, its length uniform in
+    4 .. 96, its start uniform over the positions that fit, its score uniform in [0, 1), about one row in ten invalid."""
+    rng = np.random.default_rng(seed)
+    N = 2 * K + 37
+    length = rng.integers(4, min(96, N) + 1, K)          # 96 fits every line of K >= 30 candidates
+    s = rng.integers(0, N - length + 1)
+    score = rng.random(K, dtype=f32)
+    valid = rng.random(K) >= 0.1
+    return N, s.astype(np.int64), (s + length).astype(np.int64), score, valid
+
+
+def interval_masks(s, e, N, rows=None):
+    """The explicit [k, N] boolean masks of the intervals (of the rows `rows`, a slice: the whole family can be gigabytes)."""
+    rows = slice(None) if rows is None else rows
+    n = np.arange(N, dtype=np.int64)[None]
+    return (n >= np.asarray(s)[rows, None]) & (n < np.asarray(e)[rows, None])
+
+
+def nms_intervals(s, e, order, valid, iou_thr):
+    """Greedy NMS with the decision rule of nms(), vectorised over the kept list.  -> (keep [K] bool by candidate, suppressor [K] int64 by POSITION in
+    `order`: the position of the first kept candidate that suppresses the one at this position, -1 for a kept or an invalid one).  An entry of
+    `order` outside [0, K) is skipped: it is no candidate."""
+    s, e = np.asarray(s, dtype=np.int64), np.asarray(e, dtype=np.int64)
+    K = len(s)
+    thr = float(f32(iou_thr))
+    keep = np.zeros(K, dtype=bool)
+    suppressor = np.full(len(order), -1, dtype=np.int64)
+    ks, ke, kpos = np.empty(K, dtype=np.int64), np.empty(K, dtype=np.int64), np.empty(K, dtype=np.int64)
+    n = 0
+    for p, i in enumerate(order):
+        i = int(i)
+        if not 0 <= i < K or not valid[i]:
+            continue
+        inter = np.maximum(np.minimum(e[i], ke[:n]) - np.maximum(s[i], ks[:n]), 0)
+        union = (e[i] - s[i]) + (ke[:n] - ks[:n]) - inter
+        hit = inter.astype(np.float64) > thr * union.astype(np.float64)
+        if hit.any():
+            suppressor[p] = kpos[np.argmax(hit)]
+            continue
+        keep[i] = True
+        ks[n], ke[n], kpos[n] = s[i], e[i], p
+        n += 1
+    return keep, suppressor
+
+
+def paint_intervals(s, e, order, keep, N):
+    """paint() for intervals.  Entries of `order` outside [0, K) are skipped."""
+    labels = np.full(N, -1, dtype=np.int32)
+    rank = 0
+    for i in order:
+        i = int(i)
+        if 0 <= i < len(keep) and keep[i]:
+            part = labels[s[i]:e[i]]
+            part[part < 0] = rank
+            rank += 1
+    return labels

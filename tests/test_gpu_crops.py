@@ -456,3 +456,40 @@ def test_crop_entry_points_resolve_and_reject_bad_arguments(ops):
     assert b"null" in lib.psam_last_error_string()
     assert lib.psam_crop_expand_rows(None, 1, None, 1, 1, 1, 0, None, 1, None) == -1
     assert lib.psam_crop_expand_bits(None, None, 1, 1, 1, None, None, None) == -1
+
+
+# ------------------------------------------------------------------------------------------------ 7. second-level scan with several blocks per thread
+@pytest.mark.parametrize("h", [0.025, None])
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_crop_downsample_with_one_two_and_three_blocks_per_offsets_thread(ops, which, h):
+    """M = T^2, T^2 + 1 and 2 T^2 + T + 1 points for T = CROP_SCAN_THREADS read from crops.hip: crop_offsets_kernel gives each thread 1, 2 and 3
+    block counts (the last with a ragged final span and threads with none).  Uniform points of the cube; two stretches of 4 T consecutive points
+    (the middle and the end) are copies of point 0, a member, so whole blocks count zero representatives with a voxel size (and T members).  The
+    ball holds between a quarter and three quarters of the points (a condition on the inputs)."""
+    import kernel_sizes as KS
+    T = KS.scan_constants()["CROP_SCAN_THREADS"]
+    M = KS.scan_sizes(T)[which]
+    assert -(-(-(-M // T)) // T) == which + 1
+    rng = np.random.default_rng(30 + which)
+    xyz = rng.uniform(-1, 1, (M, 3)).astype(f32)
+    xyz[0] = (0.3, -0.2, 0.1)
+    xyz[M // 2:M // 2 + 4 * T] = xyz[0]
+    xyz[M - 4 * T:] = xyz[0]
+    rgb = rng.uniform(-1, 1, (M, 3)).astype(f32)
+    center, radius = (0.05, -0.1, 0.02), 1.0
+    want_keep, want_inv, want_xyz, want_rgb, want_members = C.crop_downsample(xyz, rgb, center, radius, h)
+    print(f"M={M} h={h}: {which + 1} blocks per thread, {want_members} members, reference keeps {len(want_keep)}")
+    assert M / 4 <= want_members <= 3 * M / 4 and want_inv[0] == 0
+    if h is not None:
+        own = np.zeros(M, dtype=bool)
+        own[want_keep] = True
+        per_block = np.add.reduceat(own, np.arange(0, M, T))
+        assert (per_block[(M // 2) // T + 1:(M // 2) // T + 4] == 0).all() and (per_block[-3:] == 0).all() and len(want_keep) < want_members
+    dx, dr = torch.from_numpy(xyz).cuda(), torch.from_numpy(rgb).cuda()
+    assert ops.crop_count(dx, center, radius, h) == (len(want_keep), want_members)
+    keep_idx, inv, wxyz, wrgb, members = ops.crop_downsample(dx, dr, center, radius, h)
+    assert members == want_members and keep_idx.numel() == len(want_keep)
+    assert np.array_equal(keep_idx.cpu().numpy(), want_keep)
+    assert np.array_equal(inv.cpu().numpy(), want_inv)
+    assert np.array_equal(_bits(wxyz.cpu().numpy()), _bits(want_xyz))
+    assert np.array_equal(_bits(wrgb.cpu().numpy()), _bits(want_rgb))

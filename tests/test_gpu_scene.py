@@ -326,3 +326,40 @@ def test_segment_route_with_working_points_answers_per_loaded_point(ops, scan):
         assert st == 200 and len(out["labels"]) == M_SCAN, out
     finally:
         srv.shutdown()
+
+
+# ------------------------------------------------------------------------------------------------ 6. second-level scan with several blocks per thread
+def _scan_cloud(M, T, seed):
+    """Uniform points of the cube; two stretches of 4 T consecutive points (the middle and the end) are copies of point 0, so whole blocks of the
+    look-up kernel count zero representatives inside a thread's span of the offsets kernel."""
+    rng = np.random.default_rng(seed)
+    xyz = rng.uniform(-1, 1, (M, 3)).astype(f32)
+    xyz[M // 2:M // 2 + 4 * T] = xyz[0]
+    xyz[M - 4 * T:] = xyz[0]
+    return xyz
+
+
+@pytest.mark.parametrize("which", [0, 1, 2])
+def test_downsample_with_one_two_and_three_blocks_per_offsets_thread(ops, which):
+    """M = T^2, T^2 + 1 and 2 T^2 + T + 1 points for T = SCAN_THREADS read from scene.hip: voxel_offsets_kernel gives each thread 1, 2 and 3 block
+    counts (the last with a ragged final span and threads with none): the serial span sum, the in-place rewrite of the span, the empty spans.
+    h = 0.025: the reference keeps between M / 8 and M / 2 points (a condition on the inputs)."""
+    import kernel_sizes as KS
+    T = KS.scan_constants()["SCAN_THREADS"]
+    M = KS.scan_sizes(T)[which]
+    blocks = -(-M // T)
+    assert -(-blocks // T) == which + 1
+    xyz = _scan_cloud(M, T, 20 + which)
+    want_keep, want_inv = R.downsample(xyz, 0.025)
+    print(f"M={M}: {blocks} blocks, {which + 1} per thread, reference keeps {len(want_keep)}")
+    assert M / 8 <= len(want_keep) <= M / 2
+    own = np.zeros(M, dtype=bool)
+    own[want_keep] = True
+    per_block = np.add.reduceat(own, np.arange(0, M, T))
+    assert (per_block[(M // 2) // T + 1:(M // 2) // T + 4] == 0).all() and (per_block[-3:] == 0).all() and per_block.max() > 0
+    dev = torch.from_numpy(xyz).cuda()
+    assert ops.voxel_count(dev, 0.025) == len(want_keep)                  # the count-only call
+    keep_idx, inv = ops.voxel_downsample(dev, 0.025)
+    assert keep_idx.numel() == len(want_keep)
+    assert np.array_equal(keep_idx.cpu().numpy(), want_keep)
+    assert np.array_equal(inv.cpu().numpy(), want_inv)

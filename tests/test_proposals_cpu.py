@@ -218,3 +218,115 @@ def test_segment_all_route(server):
     assert st == 400
     # the click route and its state are untouched by a proposal pass
     assert sess.prompts == [] and sess.prompt_mask is None and sess.segment_mask is None
+
+
+# ------------------------------------------------------------------------------------------------ the interval reference and the tested sizes
+import kernel_sizes as KS
+
+
+def _with_ties(K, seed):
+    N, s, e, score, valid = R.interval_family(K, seed)
+    if K >= 8:
+        rng = np.random.default_rng(seed + 1)
+        a, b = rng.choice(K, K // 8, replace=False), rng.choice(K, K // 8, replace=False)
+        score[a] = score[b]                               # equal scores: the lower index goes first
+        s[a[:K // 16]], e[a[:K // 16]] = s[b[:K // 16]], e[b[:K // 16]]      # and outright twins (IoU exactly 1) among them
+    return N, s, e, score, valid
+
+
+@pytest.mark.parametrize("K", [1, 65, 300])
+@pytest.mark.parametrize("thr", [0.3, 0.5, 1.0])
+def test_interval_reference_equals_the_mask_reference(K, thr):
+    """nms_intervals / paint_intervals against nms() / paint() on the explicit boolean masks and the intersections() matrix, with score ties and
+    duplicated masks; the closed-form areas and intersections against the counted ones; the reported suppressor really is the first one."""
+    N, s, e, score, valid = _with_ties(K, 7 * K)
+    assert N == 2 * K + 37 and (e - s).min() >= 4 and (e - s).max() <= 96 and s.min() >= 0 and e.max() <= N and score.dtype == np.float32
+    masks = R.interval_masks(s, e, N)
+    inter = R.intersections(masks, masks)
+    assert np.array_equal(masks.sum(1), e - s)
+    assert np.array_equal(inter, np.maximum(np.minimum(e[:, None], e[None]) - np.maximum(s[:, None], s[None]), 0))
+    assert np.array_equal(R.interval_masks(s, e, N, slice(K // 2, K)), masks[K // 2:])
+    order = R.order_of(score)
+    if K >= 8:
+        assert len(np.unique(score)) < K
+    want = R.nms(order, valid, e - s, inter, thr)
+    keep, sup = R.nms_intervals(s, e, order, valid, thr)
+    assert np.array_equal(keep, want)
+    assert np.array_equal(R.paint_intervals(s, e, order, keep, N), R.paint(masks, order, want))
+    t = float(np.float32(thr))
+    for p, i in enumerate(order):
+        if sup[p] < 0:
+            assert keep[i] or not valid[i]
+            continue
+        hits = [q for q in range(p) if keep[order[q]] and float(inter[i, order[q]]) > t * float(e[i] - s[i] + e[order[q]] - s[order[q]] - inter[i, order[q]])]
+        assert not keep[i] and valid[i] and sup[p] == hits[0]
+    if thr == 1.0:
+        assert np.array_equal(keep, valid)                # nothing overlaps more than completely
+    # out-of-range entries of `order` are no candidates: the result is that of the order without them
+    if K >= 65:
+        bad = order.copy()
+        bad[[3, K // 2, K - 1]] = (-1, K, 2 ** 31 - 1)
+        k2, s2 = R.nms_intervals(s, e, bad, valid, thr)
+        short = np.delete(order, [3, K // 2, K - 1])
+        k3, _ = R.nms_intervals(s, e, short, valid, thr)
+        assert np.array_equal(k2, k3) and (s2[[3, K // 2, K - 1]] == -1).all()
+        assert np.array_equal(R.paint_intervals(s, e, bad, k2, N), R.paint_intervals(s, e, short, k3, N))
+
+
+def test_tested_sizes_follow_from_the_kernel_sources():
+    """The size lists of tests/kernel_sizes.py (what the GPU tests run) equal what the constants and launches parsed from masks.hip, scene.hip and
+    crops.hip give.  A new nms_walk_kernel instance, another KW bound or a changed NMS_MAX_K / NMS_PF / RANK_THREADS / SCAN_THREADS fails here
+    until the lists cover it."""
+    c = KS.mask_constants()
+    assert c["walks"] == [(1, 64), (2, 128), (4, 256)] and c["NMS_MAX_K"] == 16384 and c["NMS_PF"] == 8 and c["RANK_THREADS"] == 1024
+    from point_sam_amd.proposals import MAX_CANDIDATES
+    assert MAX_CANDIDATES == c["NMS_MAX_K"]
+    assert KS.nms_sizes(c) == KS.NMS_SIZES == (4096, 4097, 4300, 8192, 8193, 8400, 12500, 16384)
+    assert KS.NMS_SEGMENT == 64 * 64
+    launched = {KS.walk_of(c, K) for K in KS.NMS_SIZES}
+    assert launched == {nw for nw, _ in c["walks"]}                                  # every instance runs
+    for nw, kw in c["walks"]:
+        mine = [K for K in KS.NMS_SIZES if KS.walk_of(c, K) == nw]
+        assert min(kw * 64, c["NMS_MAX_K"]) in mine                                  # at its last K: every word of the set full
+        if nw > 1:
+            assert any(K % 64 == 1 for K in mine)                                    # at its first: one live bit in the last word
+            assert any(K % c["NMS_PF"] for K in mine)                                # a ragged prefetch group in a later word
+    for s in range(1, max(launched)):                                                # every register s >= 1 of the set ends a walk part-way
+        assert any(s * KS.NMS_SEGMENT + 64 < K < (s + 1) * KS.NMS_SEGMENT for K in KS.NMS_SIZES)
+    assert set(KS.NMS_SEGMENT_SIZES) <= set(KS.NMS_SIZES) and {(K - 1) // KS.NMS_SEGMENT for K in KS.NMS_SEGMENT_SIZES} == set(range(1, max(launched)))
+    first_r3 = min(K for K in KS.NMS_SIZES if (K + 63) // 64 > 192)
+    assert first_r3 == 12500
+    assert KS.paint_sizes(c) == KS.PAINT_SIZES
+    assert [-(-K // c["RANK_THREADS"]) for K in KS.PAINT_SIZES] == [1, 1, 2, 3, 5]
+    assert KS.valid_sizes(c) == KS.VALID_SIZES
+    sc = KS.scan_constants()
+    assert sc["SCAN_THREADS"] == sc["CROP_SCAN_THREADS"]
+    T = sc["SCAN_THREADS"]
+    assert KS.scan_sizes(T) == KS.SCAN_SIZES
+    assert [-(-(-(-M // T)) // T) for M in KS.SCAN_SIZES] == [1, 2, 3] and (-(-KS.SCAN_SIZES[2] // T)) % 3 != 0
+
+
+@pytest.mark.parametrize("K", KS.NMS_SIZES)
+def test_interval_family_exercises_every_segment_of_the_walk(K):
+    """Conditions on the inputs of the GPU test (tests/test_gpu_mask_instances.py), asserted on the reference alone: equality on an all-kept or
+    all-dropped case, or on one whose suppressions never cross a register of the walk's `removed` set, would prove nothing.  Positions are cut
+    into segments of 4096 (64 words of the set: one register per lane)."""
+    N, s, e, score, valid = R.interval_family(K, seed=K)
+    order = R.order_of(score)
+    keep, sup = R.nms_intervals(s, e, order, valid, 0.5)
+    kept, dropped = keep[order], sup >= 0
+    seg = np.arange(K) // KS.NMS_SEGMENT
+    nseg = int(seg[-1]) + 1
+    per_kept, per_drop = np.bincount(seg[kept], minlength=nseg), np.bincount(seg[dropped], minlength=nseg)
+    print(f"K={K}: kept {int(kept.sum())} ({' / '.join(map(str, per_kept))}), suppressed {int(dropped.sum())} ({' / '.join(map(str, per_drop))}), "
+          f"invalid {int((~valid).sum())}")
+    assert kept.sum() >= K / 8 and dropped.sum() >= K / 8
+    from_seg = np.where(dropped, sup // KS.NMS_SEGMENT, -1)
+    for g in range(nseg):
+        here = seg == g
+        if K in KS.NMS_SEGMENT_SIZES:
+            assert per_kept[g] >= 16 and per_drop[g] >= 64, (g, per_kept, per_drop)
+            if g >= 1:
+                assert (from_seg[here] == 0).any(), f"segment {g}: no position whose first suppressor lies in segment 0"
+        if here.sum() >= 1024 and g >= 1:
+            assert (from_seg[here] >= 1).any(), f"segment {g}: no position whose first suppressor lies in a segment >= 1"

@@ -4,7 +4,7 @@
 // The graph.  Points are adjacent iff their voxel cells (voxel_cell.h: scene.hip's cells) differ by at most 1 on every axis.  All points of a voxel
 // are mutually adjacent, so components are found on the VOXEL graph: V occupied voxels (psam_voxel_downsample's keep_idx / inv), 26 neighbour ranks
 // each (psam_region_neighbors), and a row's point set reduced to per-voxel member counts.
-//   psam_region_neighbors   a key -> rank table of its own (open addressing, load factor <= 0.5, as scene.hip's), then one look-up per (voxel, offset)
+//   psam_region_neighbors   a key -> rank table of its own (voxel_table.h's table: claimed, then found), then one look-up per (voxel, offset)
 //   psam_region_labels      per point the id of its component (the lowest voxel rank in it), -1 outside the set
 //   psam_region_clean       holes, islands, seeds: two component runs (the complement, then the filled mask) and word-wise rewrites of the rows
 //
@@ -18,7 +18,8 @@
 // The root of a finished tree is the lowest rank of its component, whatever order the waves arrived in: it IS the component's id.  Every loop has a
 // bound derived from V (a walk descends at least one rank per step; a failed hook lowers one of its two ends): a logic error ends as a wrong answer.
 #include "common.h"
-#include "voxel_cell.h"
+#include "row_popcount.h"    // block_sum, row_popcount
+#include "voxel_table.h"
 
 #include <cmath>
 
@@ -30,35 +31,12 @@ constexpr int REGION_MAX_POINTS = 1 << 28;
 static inline unsigned region_blocks(int64_t n) { return (unsigned)psam_cdiv(n, REGION_THREADS); }
 
 // ------------------------------------------------------------------------------------------------ neighbours
-struct NbrWs {
-    u64* keys;            // [C]
-    unsigned* rank;       // [C]
-    size_t bytes;
-};
-
-static inline NbrWs nbr_layout(void* ws, int64_t V) {
-    const int64_t C = voxel_capacity(V);
-    NbrWs w;
-    char* p = (char*)ws;
-    size_t o = 0;
-    w.keys = (u64*)(p + o);        o += align16((size_t)C * sizeof(u64));
-    w.rank = (unsigned*)(p + o);   o += align16((size_t)C * sizeof(unsigned));
-    w.bytes = o;
-    return w;
-}
-
-// keys and ranks are adjacent in the workspace (16-byte granules): one fill of all-ones words
-__global__ __launch_bounds__(REGION_THREADS) void region_table_clear_kernel(uint4* __restrict__ table, int64_t granules) {
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < granules; g += stride) table[g] = make_uint4(~0u, ~0u, ~0u, ~0u);
-}
-
 __device__ __forceinline__ bool region_cell(const float* __restrict__ xyz, int64_t i, float ox, float oy, float oz, float inv_h, u64& cx, u64& cy, u64& cz) {
     return voxel_axis(xyz[i * 3 + 0], ox, inv_h, cx) & voxel_axis(xyz[i * 3 + 1], oy, inv_h, cy) & voxel_axis(xyz[i * 3 + 2], oz, inv_h, cz);
 }
 
-// One thread per voxel: its key claims a slot (compare-and-swap, linear probing), the slot's rank is an unsigned minimum (keys of distinct voxels
-// differ, so the minimum is over one value; a repeated representative would still give one answer).
+// One thread per voxel: its key claims a slot, the slot's rank is an unsigned minimum (keys of distinct voxels differ, so the minimum is over one
+// value; a repeated representative would still give one answer).
 __global__ __launch_bounds__(REGION_THREADS) void region_table_insert_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ keep_idx, int V,
                                                                            float ox, float oy, float oz, float inv_h, u64* __restrict__ keys,
                                                                            unsigned* __restrict__ rank, int capacity) {
@@ -67,15 +45,8 @@ __global__ __launch_bounds__(REGION_THREADS) void region_table_insert_kernel(con
     const int64_t i = keep_idx[v];
     u64 cx, cy, cz;
     if (i < 0 || !region_cell(xyz, i, ox, oy, oz, inv_h, cx, cy, cz)) return;      // no cell: never found, every neighbour of it is -1
-    const u64 key = voxel_key(cx, cy, cz);
-    const unsigned mask = (unsigned)capacity - 1u;
-    unsigned pos = (unsigned)voxel_hash(key) & mask;
-    for (int probe = 0; probe < capacity; ++probe) {               // at most V of the >= 2 V slots are ever taken: an empty one always ends the walk
-        u64 cur = __hip_atomic_load(&keys[pos], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == VOXEL_EMPTY) cur = atomicCAS(&keys[pos], VOXEL_EMPTY, key);
-        if (cur == VOXEL_EMPTY || cur == key) { atomicMin(&rank[pos], (unsigned)v); return; }
-        pos = (pos + 1u) & mask;
-    }
+    const int slot = voxel_claim(keys, capacity, voxel_key(cx, cy, cz));
+    if (slot >= 0) atomicMin(&rank[slot], (unsigned)v);
 }
 
 // One thread per (voxel, offset).  Offset o of 26: o' = o below 13, o + 1 from 13 on (the centre is skipped); dz = o' / 9 - 1, dy = o' / 3 % 3 - 1,
@@ -93,15 +64,8 @@ __global__ __launch_bounds__(REGION_THREADS) void region_table_lookup_kernel(con
         const int64_t nx = (int64_t)cx + (oc % 3 - 1), ny = (int64_t)cy + (oc / 3 % 3 - 1), nz = (int64_t)cz + (oc / 9 - 1);
         const int64_t lim = (int64_t)1 << VOXEL_AXIS_BITS;
         if (nx >= 0 && nx < lim && ny >= 0 && ny < lim && nz >= 0 && nz < lim) {
-            const u64 key = voxel_key((u64)nx, (u64)ny, (u64)nz);
-            const unsigned mask = (unsigned)capacity - 1u;
-            unsigned pos = (unsigned)voxel_hash(key) & mask;
-            for (int probe = 0; probe < capacity; ++probe) {       // the table is finished (kernel boundary) and at most half full
-                const u64 cur = keys[pos];
-                if (cur == VOXEL_EMPTY) break;
-                if (cur == key) { found = (int)rank[pos]; break; }
-                pos = (pos + 1u) & mask;
-            }
+            const int slot = voxel_find(keys, capacity, voxel_key((u64)nx, (u64)ny, (u64)nz));      // the table is finished: a kernel boundary
+            if (slot >= 0) found = (int)rank[slot];
         }
     }
     nbr[t] = found;
@@ -109,7 +73,7 @@ __global__ __launch_bounds__(REGION_THREADS) void region_table_lookup_kernel(con
 
 PSAM_API size_t psam_region_neighbors_workspace_bytes(int32_t V) {
     if (V <= 0 || V > REGION_MAX_POINTS) return 0;
-    return nbr_layout(nullptr, V).bytes;
+    return voxel_layout(nullptr, V, false, false).bytes;
 }
 
 PSAM_API int32_t psam_region_neighbors(const float* xyz, const int64_t* keep_idx, int32_t V, const float* origin, float inv_h, int32_t* nbr, void* ws,
@@ -121,18 +85,15 @@ PSAM_API int32_t psam_region_neighbors(const float* xyz, const int64_t* keep_idx
     PSAM_REQUIRE(ws_bytes >= psam_region_neighbors_workspace_bytes(V), PSAM_EWORKSPACE,
                  "psam_region_neighbors: workspace too small (psam_region_neighbors_workspace_bytes)");
     PSAM_REQUIRE(((uintptr_t)ws & 15) == 0, PSAM_EALIGN, "psam_region_neighbors: workspace must be 16-byte aligned");
-    const NbrWs w = nbr_layout(ws, V);
+    const VoxelWs w = voxel_layout(ws, V, false, false);
     const int capacity = (int)voxel_capacity(V);
-    const int64_t granules = (int64_t)(w.bytes / 16);
-    hipLaunchKernelGGL(region_table_clear_kernel, dim3(granules < 4096 * REGION_THREADS ? region_blocks(granules) : 4096u), dim3(REGION_THREADS), 0, stream,
-                       (uint4*)w.keys, granules);
-    int32_t st = psam_launch_status("psam_region_neighbors: clear launch failed");
+    int32_t st = voxel_clear<0>(w, nullptr, stream, "psam_region_neighbors: clear launch failed");
     if (st != PSAM_OK) return st;
     hipLaunchKernelGGL(region_table_insert_kernel, dim3(region_blocks(V)), dim3(REGION_THREADS), 0, stream, xyz, keep_idx, (int)V, origin[0], origin[1],
-                       origin[2], inv_h, w.keys, w.rank, capacity);
+                       origin[2], inv_h, w.keys, w.low, capacity);
     if ((st = psam_launch_status("psam_region_neighbors: insert launch failed")) != PSAM_OK) return st;
     hipLaunchKernelGGL(region_table_lookup_kernel, dim3(region_blocks((int64_t)V * 26)), dim3(REGION_THREADS), 0, stream, xyz, keep_idx, (int)V, origin[0],
-                       origin[1], origin[2], inv_h, (const u64*)w.keys, (const unsigned*)w.rank, capacity, nbr);
+                       origin[1], origin[2], inv_h, (const u64*)w.keys, (const unsigned*)w.low, capacity, nbr);
     return psam_launch_status("psam_region_neighbors: look-up launch failed");
 }
 
@@ -301,18 +262,8 @@ __global__ __launch_bounds__(REGION_THREADS) void region_rows_kernel(const u64* 
                                                                    int* __restrict__ active) {
     __shared__ int s_cnt[REGION_WAVES];
     const int k = blockIdx.x;
-    const u64* __restrict__ row = bits + (int64_t)k * W;
-    int c = 0;
-    for (int w = threadIdx.x; w < W; w += REGION_THREADS) c += __popcll(row[w]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < REGION_WAVES; ++w) s += s_cnt[w];
-        active[k] = (s > 0 && (!select || select[k] != 0)) ? 1 : 0;
-    }
+    const int s = row_popcount<REGION_THREADS>(bits + (int64_t)k * W, W, s_cnt);
+    if (threadIdx.x == 0) active[k] = (s > 0 && (!select || select[k] != 0)) ? 1 : 0;
 }
 
 // Step 1, one wave per word: the mask plus every complement component below min_hole points (parent / size: the complement's components; unused
@@ -413,12 +364,12 @@ __global__ __launch_bounds__(REGION_THREADS) void region_area_kernel(const u64* 
         diff |= o != bits[(int64_t)k * W + w] ? 1 : 0;
     }
 #pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { c += __shfl_xor(c, d, 64); diff |= __shfl_xor(diff, d, 64); }
-    if ((threadIdx.x & 63) == 0) { s_cnt[threadIdx.x >> 6] = c; s_diff[threadIdx.x >> 6] = diff; }
-    __syncthreads();
+    for (int d = 32; d >= 1; d >>= 1) diff |= __shfl_xor(diff, d, 64);
+    if ((threadIdx.x & 63) == 0) s_diff[threadIdx.x >> 6] = diff;
+    const int s = block_sum<REGION_THREADS>(c, s_cnt);             // its barrier is s_diff's too
     if (threadIdx.x == 0) {
-        int s = 0, f = 0;
-        for (int w = 0; w < REGION_WAVES; ++w) { s += s_cnt[w]; f |= s_diff[w]; }
+        int f = 0;
+        for (int w = 0; w < REGION_WAVES; ++w) f |= s_diff[w];
         area[k] = s;
         changed[k] = f ? 1 : 0;
     }

@@ -15,6 +15,7 @@
 // function of the inputs alone: no atomics, no hand-over between threads, no data-dependent loops.
 #include "common.h"
 #include "crop_coord.h"      // the crop's normalised coordinate: the same bits as the crop cloud's own points
+#include "row_popcount.h"    // the area pass of the packed masks
 #include "voxel_cell.h"      // VOXEL_MAX_POINTS, u64
 
 #include <climits>
@@ -183,7 +184,7 @@ PSAM_API int32_t psam_interp_scene_rows(const float* src, int64_t src_ld, const 
 }
 
 // ------------------------------------------------------------------------------------------------ bits
-// The scheme of scene.hip's expand: a wave owns INTERP_BITS_WORDS consecutive output words, every lane loads the taps of its points once, and for
+// The scheme of scene_expand.h's expand: a wave owns INTERP_BITS_WORDS consecutive output words, every lane loads the taps of its points once, and for
 // every row the ballot of `value > thr` IS the output word (NaN compares false; an off point and a point past M give a zero bit); lanes
 // 0 .. INTERP_BITS_WORDS - 1 store the wave's words of the row as one contiguous segment.  The areas are a pass of their own over the finished rows.
 constexpr int INTERP_BITS_WORDS = 4;
@@ -219,24 +220,6 @@ __global__ __launch_bounds__(INTERP_BITS_THREADS) void interp_bits_kernel(const 
     }
 }
 
-constexpr int INTERP_AREA_THREADS = 256;
-
-__global__ __launch_bounds__(INTERP_AREA_THREADS) void interp_area_kernel(const u64* __restrict__ bits_f, int64_t Wf, int* __restrict__ area) {
-    __shared__ int s_cnt[INTERP_AREA_THREADS / WAVE];
-    const u64* __restrict__ row = bits_f + (int64_t)blockIdx.x * Wf;
-    int c = 0;
-    for (int64_t w = threadIdx.x; w < Wf; w += INTERP_AREA_THREADS) c += __popcll(row[w]);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int w = 0; w < INTERP_AREA_THREADS / WAVE; ++w) s += s_cnt[w];
-        area[blockIdx.x] = s;
-    }
-}
-
 PSAM_API int32_t psam_interp_scene_bits(const float* src, int64_t src_ld, const int32_t* idx3, const float* w3, int32_t K, int32_t Nw, int32_t M,
                                         float thr, uint64_t* bits_f, int32_t* area_f, hipStream_t stream) {
     PSAM_REQUIRE(src && idx3 && w3 && bits_f, PSAM_EINVAL, "psam_interp_scene_bits: null pointer");
@@ -249,6 +232,6 @@ PSAM_API int32_t psam_interp_scene_bits(const float* src, int64_t src_ld, const 
                        src_ld, (const int*)idx3, w3, (int)K, (int)Nw, (int)M, thr, (u64*)bits_f, Wf);
     int32_t st = psam_launch_status("psam_interp_scene_bits: launch failed");
     if (st != PSAM_OK || !area_f) return st;
-    hipLaunchKernelGGL(interp_area_kernel, dim3((unsigned)K), dim3(INTERP_AREA_THREADS), 0, stream, (const u64*)bits_f, Wf, area_f);
+    hipLaunchKernelGGL(row_popcount_kernel<INTERP_BITS_THREADS>, dim3((unsigned)K), dim3(INTERP_BITS_THREADS), 0, stream, (const u64*)bits_f, Wf, area_f);
     return psam_launch_status("psam_interp_scene_bits: area launch failed");
 }

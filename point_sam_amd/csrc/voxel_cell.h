@@ -1,5 +1,6 @@
-// Voxel cells and their hash, shared by scene.hip (the working cloud) and regions.hip (the neighbourhood graph): one definition, so both put a point
-// into the same cell bit for bit.  Translation units that include this are compiled with -ffp-contract=off (point_sam_amd/build.py).
+// Voxel cells and their hash, shared by scene.hip (the working cloud), crops.hip (a ball's working cloud) and regions.hip (the neighbourhood graph):
+// one definition, so all put a point into the same cell bit for bit.  The table keyed by these cells is voxel_table.h.  Translation units that
+// include this are compiled with -ffp-contract=off (point_sam_amd/build.py).
 #pragma once
 #include "common.h"
 

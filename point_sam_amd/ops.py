@@ -1179,6 +1179,68 @@ def mask_unpack(bits: torch.Tensor, N: int) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------ full-resolution scenes (csrc/scene.hip)
+def _voxel_setup(name: str, voxel_size, optional: bool, M: int, dev):
+    """What voxel_downsample and crop_downsample (`name`: voxel / crop) share -> (inv_h fp32, workspace).  optional: voxel_size None = no reduction,
+    inv_h 0."""
+    import numpy as np
+    inv_h = np.float32(0)
+    if not (optional and voxel_size is None):
+        h = np.float32(voxel_size)
+        if not (np.isfinite(h) and h > 0):
+            raise ValueError(f"{name}_downsample: voxel_size must be finite and positive{' (None: no reduction)' if optional else ''}, got {voxel_size!r}")
+        inv_h = np.float32(1) / h                          # fp32, as the header defines it
+        if not (np.isfinite(inv_h) and inv_h > 0):
+            raise ValueError(f"{name}_downsample: 1 / voxel_size is not a positive fp32 number for voxel_size {voxel_size!r}")
+    nbytes = getattr(_lib.load(), f"psam_{name}_downsample_workspace_bytes")(M)
+    if nbytes == 0:
+        raise ValueError(f"{name}_downsample: {M} points exceed the 2^28 the table is built for")
+    return inv_h, torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+
+
+def _expand_rows(name: str, src, inv, fill, out):
+    """scene_expand_rows (fill None: the entry point takes none) and crop_expand_rows."""
+    if not src.is_cuda:
+        raise _lib.PointSamHipError("src must live on the GPU: the HIP path has no CPU fallback")
+    if src.dtype not in (torch.float32, torch.int32):
+        raise TypeError(f"{name}: rows of 32-bit words (float32 / int32), got {src.dtype}")
+    _chk(inv, torch.int64, "inv")
+    pattern = () if fill is None else (_fill_pattern(fill, src.dtype),)
+    Nw, M = src.shape[-1], inv.numel()
+    lead = tuple(src.shape[:-1])
+    rows = src.reshape(-1, Nw) if src.dim() != 2 else src
+    if rows.stride(1) != 1 and Nw > 1:
+        rows = rows.contiguous()
+    R = rows.shape[0]
+    if R < 1 or Nw < 1 or M < 1:
+        raise ValueError(f"{name}: empty input: src {tuple(src.shape)}, inv [{M}]")
+    src_ld = rows.stride(0) if R > 1 else Nw
+    if src_ld < Nw:
+        rows, src_ld = rows.contiguous(), Nw
+    if out is None:
+        dst = torch.empty(R, M, dtype=src.dtype, device=src.device)
+    else:
+        dst = out
+        if dst.dtype != src.dtype or dst.dim() != 2 or tuple(dst.shape) != (R, M) or (M > 1 and dst.stride(1) != 1) or (R > 1 and dst.stride(0) < M):
+            raise ValueError(f"{name}: out must be [{R}, {M}] {src.dtype} with unit column stride, got {tuple(dst.shape)} {dst.dtype}")
+    dst_ld = dst.stride(0) if R > 1 else M
+    check(getattr(_lib.load(), "psam_" + name)(rows.data_ptr(), src_ld, inv.data_ptr(), R, Nw, M, *pattern, dst.data_ptr(), dst_ld, _stream()), "psam_" + name)
+    return dst if out is not None else dst.reshape(lead + (M,))
+
+
+def _expand_bits(name: str, arg: str, bits, inv, Nw: int, area: bool):
+    """scene_expand_bits and crop_expand_bits; arg: what the caller calls `bits`."""
+    _chk(bits, torch.int64, arg); _chk(inv, torch.int64, "inv")
+    M = inv.numel()
+    if bits.dim() != 2 or Nw < 1 or bits.shape[1] != mask_words(Nw) or M < 1:
+        raise ValueError(f"{name}: {arg} {tuple(bits.shape)} for Nw = {Nw}, inv [{M}]")
+    K = bits.shape[0]
+    bits_f = torch.empty(K, mask_words(M), dtype=torch.int64, device=bits.device)
+    area_f = torch.empty(K, dtype=torch.int32, device=bits.device) if area else None
+    if K > 0:
+        check(getattr(_lib.load(), "psam_" + name)(bits.data_ptr(), inv.data_ptr(), K, Nw, M, bits_f.data_ptr(), _p(area_f), _stream()), "psam_" + name)
+    return bits_f, area_f
+
+
 def _voxel_call(xyz, voxel_size, origin, full: bool):
     import numpy as np
     if xyz.dim() == 3 and xyz.shape[0] == 1:
@@ -1186,28 +1248,18 @@ def _voxel_call(xyz, voxel_size, origin, full: bool):
     _chk(xyz, name="xyz")
     if xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
         raise ValueError(f"voxel_downsample: xyz must be [M, 3] with M >= 1 (one scene), got {tuple(xyz.shape)}")
-    h = np.float32(voxel_size)
-    if not (np.isfinite(h) and h > 0):
-        raise ValueError(f"voxel_downsample: voxel_size must be finite and positive, got {voxel_size!r}")
-    inv_h = np.float32(1) / h                              # fp32, as the header defines it
-    if not (np.isfinite(inv_h) and inv_h > 0):
-        raise ValueError(f"voxel_downsample: 1 / voxel_size is not a positive fp32 number for voxel_size {voxel_size!r}")
-    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
     M, dev = xyz.shape[0], xyz.device
-    L = _lib.load()
-    nbytes = L.psam_voxel_downsample_workspace_bytes(M)
-    if nbytes == 0:
-        raise ValueError(f"voxel_downsample: {M} points exceed the 2^28 the table is built for")
-    ws = torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    inv_h, ws = _voxel_setup("voxel", voxel_size, False, M, dev)
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
     keep_idx = torch.empty(M, dtype=torch.int64, device=dev) if full else None
     inv = torch.empty(M, dtype=torch.int64, device=dev) if full else None
     cf = torch.empty(2, dtype=torch.int32, device=dev)    # count, flag: read together, the call's one host synchronisation
-    check(L.psam_voxel_downsample(xyz.data_ptr(), M, ctypes.addressof(org), float(inv_h), _p(keep_idx), _p(inv), cf.data_ptr(), cf.data_ptr() + 4,
-                                  ws.data_ptr(), ws.numel() * 8, _stream()), "psam_voxel_downsample")
+    check(_lib.load().psam_voxel_downsample(xyz.data_ptr(), M, ctypes.addressof(org), float(inv_h), _p(keep_idx), _p(inv), cf.data_ptr(),
+                                            cf.data_ptr() + 4, ws.data_ptr(), ws.numel() * 8, _stream()), "psam_voxel_downsample")
     count, flag = cf.tolist()
     if flag != 0:
-        raise ValueError(f"voxel_downsample: a coordinate is not finite, or its cell at voxel size {float(h)} from origin {tuple(float(v) for v in origin)} "
-                         "falls outside [0, 2^21)")
+        raise ValueError(f"voxel_downsample: a coordinate is not finite, or its cell at voxel size {float(np.float32(voxel_size))} from origin "
+                         f"{tuple(float(v) for v in origin)} falls outside [0, 2^21)")
     return count, keep_idx, inv
 
 
@@ -1227,46 +1279,13 @@ def voxel_count(xyz: torch.Tensor, voxel_size: float, origin=(-1.0, -1.0, -1.0))
 def scene_expand_rows(src: torch.Tensor, inv: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
     """src [..., Nw] f32 or int32 (the leading dimensions are R rows with one stride; last stride 1), inv [M] int64 -> [..., M] of the same dtype:
     out[r, i] = src[r, inv[i]] bit for bit.  out: a [R, M] destination with its own row stride."""
-    if not src.is_cuda:
-        raise _lib.PointSamHipError("src must live on the GPU: the HIP path has no CPU fallback")
-    if src.dtype not in (torch.float32, torch.int32):
-        raise TypeError(f"scene_expand_rows: rows of 32-bit words (float32 / int32), got {src.dtype}")
-    _chk(inv, torch.int64, "inv")
-    Nw, M = src.shape[-1], inv.numel()
-    lead = tuple(src.shape[:-1])
-    rows = src.reshape(-1, Nw) if src.dim() != 2 else src
-    if rows.stride(1) != 1 and Nw > 1:
-        rows = rows.contiguous()
-    R = rows.shape[0]
-    if R < 1 or Nw < 1 or M < 1:
-        raise ValueError(f"scene_expand_rows: empty input: src {tuple(src.shape)}, inv [{M}]")
-    src_ld = rows.stride(0) if R > 1 else Nw
-    if src_ld < Nw:
-        rows, src_ld = rows.contiguous(), Nw
-    if out is None:
-        dst = torch.empty(R, M, dtype=src.dtype, device=src.device)
-    else:
-        dst = out
-        if dst.dtype != src.dtype or dst.dim() != 2 or tuple(dst.shape) != (R, M) or (M > 1 and dst.stride(1) != 1) or (R > 1 and dst.stride(0) < M):
-            raise ValueError(f"scene_expand_rows: out must be [{R}, {M}] {src.dtype} with unit column stride, got {tuple(dst.shape)} {dst.dtype}")
-    dst_ld = dst.stride(0) if R > 1 else M
-    check(_lib.load().psam_scene_expand_rows(rows.data_ptr(), src_ld, inv.data_ptr(), R, Nw, M, dst.data_ptr(), dst_ld, _stream()), "psam_scene_expand_rows")
-    return dst if out is not None else dst.reshape(lead + (M,))
+    return _expand_rows("scene_expand_rows", src, inv, None, out)
 
 
 def scene_expand_bits(bits_w: torch.Tensor, inv: torch.Tensor, Nw: int, area: bool = True):
     """bits_w [K, ceil(Nw / 64)] int64 words (mask_pack's layout), inv [M] int64 -> (bits_f [K, ceil(M / 64)] int64, area_f [K] int32 or None):
     bit i of a full row = bit inv[i] of the working row; bits past M are zero; area_f = the full rows' popcounts."""
-    _chk(bits_w, torch.int64, "bits_w"); _chk(inv, torch.int64, "inv")
-    M = inv.numel()
-    if bits_w.dim() != 2 or Nw < 1 or bits_w.shape[1] != mask_words(Nw) or M < 1:
-        raise ValueError(f"scene_expand_bits: bits_w {tuple(bits_w.shape)} for Nw = {Nw}, inv [{M}]")
-    K = bits_w.shape[0]
-    bits_f = torch.empty(K, mask_words(M), dtype=torch.int64, device=bits_w.device)
-    area_f = torch.empty(K, dtype=torch.int32, device=bits_w.device) if area else None
-    if K > 0:
-        check(_lib.load().psam_scene_expand_bits(bits_w.data_ptr(), inv.data_ptr(), K, Nw, M, bits_f.data_ptr(), _p(area_f), _stream()), "psam_scene_expand_bits")
-    return bits_f, area_f
+    return _expand_bits("scene_expand_bits", "bits_w", bits_w, inv, Nw, area)
 
 
 # ------------------------------------------------------------------------------------------ scene crops (csrc/crops.hip)
@@ -1293,28 +1312,17 @@ def _crop_call(xyz, rgb, center, radius, voxel_size, full: bool):
         r2, inv_r = r * r, np.float32(1) / r               # fp32, as the header defines them
     if not (np.isfinite(r) and r > 0 and np.isfinite(r2) and r2 > 0 and np.isfinite(inv_r)):
         raise ValueError(f"crop_downsample: radius must be positive with fp32 r * r and 1 / r finite and positive, got {radius!r}")
-    inv_h = np.float32(0)
-    if voxel_size is not None:
-        h = np.float32(voxel_size)
-        if not (np.isfinite(h) and h > 0):
-            raise ValueError(f"crop_downsample: voxel_size must be finite and positive (None: no reduction), got {voxel_size!r}")
-        inv_h = np.float32(1) / h
-        if not (np.isfinite(inv_h) and inv_h > 0):
-            raise ValueError(f"crop_downsample: 1 / voxel_size is not a positive fp32 number for voxel_size {voxel_size!r}")
-    org = (ctypes.c_float * 3)(*[float(v) for v in c])
     M, dev = xyz.shape[0], xyz.device
-    L = _lib.load()
-    nbytes = L.psam_crop_downsample_workspace_bytes(M)
-    if nbytes == 0:
-        raise ValueError(f"crop_downsample: {M} points exceed the 2^28 the table is built for")
-    ws = torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    inv_h, ws = _voxel_setup("crop", voxel_size, True, M, dev)
+    org = (ctypes.c_float * 3)(*[float(v) for v in c])
     keep_idx = torch.empty(M, dtype=torch.int64, device=dev) if full else None
     inv = torch.empty(M, dtype=torch.int64, device=dev) if full else None
     wxyz = torch.empty(M, 3, dtype=torch.float32, device=dev) if full else None
     wrgb = torch.empty(M, 3, dtype=torch.float32, device=dev) if full else None
     res = torch.empty(3, dtype=torch.int32, device=dev)   # count, members, flag: read together, the call's one host synchronisation
-    check(L.psam_crop_downsample(xyz.data_ptr(), _p(rgb if full else None), M, ctypes.addressof(org), float(r2), float(inv_r), float(inv_h), _p(keep_idx),
-                                 _p(inv), _p(wxyz), _p(wrgb), res.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_crop_downsample")
+    check(_lib.load().psam_crop_downsample(xyz.data_ptr(), _p(rgb if full else None), M, ctypes.addressof(org), float(r2), float(inv_r), float(inv_h),
+                                           _p(keep_idx), _p(inv), _p(wxyz), _p(wrgb), res.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()),
+          "psam_crop_downsample")
     count, members, flag = res.tolist()
     if flag != 0:
         raise ValueError(f"crop_downsample: a cell of the ball at voxel size {voxel_size!r} (crop units) falls outside [0, 2^21)")
@@ -1350,48 +1358,13 @@ def _fill_pattern(fill, dtype) -> int:
 def crop_expand_rows(src: torch.Tensor, inv: torch.Tensor, fill, out: torch.Tensor = None) -> torch.Tensor:
     """scene_expand_rows for a crop: out[r, i] = src[r, inv[i]] bit for bit where inv[i] >= 0, `fill` (a value of src's dtype: -inf for logits, -1 for
     labels) elsewhere.  src [..., Nw] f32 or int32, inv [M] int64 -> [..., M]."""
-    if not src.is_cuda:
-        raise _lib.PointSamHipError("src must live on the GPU: the HIP path has no CPU fallback")
-    if src.dtype not in (torch.float32, torch.int32):
-        raise TypeError(f"crop_expand_rows: rows of 32-bit words (float32 / int32), got {src.dtype}")
-    _chk(inv, torch.int64, "inv")
-    pattern = _fill_pattern(fill, src.dtype)
-    Nw, M = src.shape[-1], inv.numel()
-    lead = tuple(src.shape[:-1])
-    rows = src.reshape(-1, Nw) if src.dim() != 2 else src
-    if rows.stride(1) != 1 and Nw > 1:
-        rows = rows.contiguous()
-    R = rows.shape[0]
-    if R < 1 or Nw < 1 or M < 1:
-        raise ValueError(f"crop_expand_rows: empty input: src {tuple(src.shape)}, inv [{M}]")
-    src_ld = rows.stride(0) if R > 1 else Nw
-    if src_ld < Nw:
-        rows, src_ld = rows.contiguous(), Nw
-    if out is None:
-        dst = torch.empty(R, M, dtype=src.dtype, device=src.device)
-    else:
-        dst = out
-        if dst.dtype != src.dtype or dst.dim() != 2 or tuple(dst.shape) != (R, M) or (M > 1 and dst.stride(1) != 1) or (R > 1 and dst.stride(0) < M):
-            raise ValueError(f"crop_expand_rows: out must be [{R}, {M}] {src.dtype} with unit column stride, got {tuple(dst.shape)} {dst.dtype}")
-    dst_ld = dst.stride(0) if R > 1 else M
-    check(_lib.load().psam_crop_expand_rows(rows.data_ptr(), src_ld, inv.data_ptr(), R, Nw, M, pattern, dst.data_ptr(), dst_ld, _stream()),
-          "psam_crop_expand_rows")
-    return dst if out is not None else dst.reshape(lead + (M,))
+    return _expand_rows("crop_expand_rows", src, inv, fill, out)
 
 
 def crop_expand_bits(bits: torch.Tensor, inv: torch.Tensor, Nw: int, area: bool = True):
     """scene_expand_bits for a crop: bits [K, ceil(Nw / 64)] int64 words, inv [M] int64 -> (bits_f [K, ceil(M / 64)] int64, area_f [K] int32 or None):
     bit i of a full row = bit inv[i] of the crop's row where inv[i] >= 0, zero elsewhere and past M; area_f = the full rows' popcounts."""
-    _chk(bits, torch.int64, "bits"); _chk(inv, torch.int64, "inv")
-    M = inv.numel()
-    if bits.dim() != 2 or Nw < 1 or bits.shape[1] != mask_words(Nw) or M < 1:
-        raise ValueError(f"crop_expand_bits: bits {tuple(bits.shape)} for Nw = {Nw}, inv [{M}]")
-    K = bits.shape[0]
-    bits_f = torch.empty(K, mask_words(M), dtype=torch.int64, device=bits.device)
-    area_f = torch.empty(K, dtype=torch.int32, device=bits.device) if area else None
-    if K > 0:
-        check(_lib.load().psam_crop_expand_bits(bits.data_ptr(), inv.data_ptr(), K, Nw, M, bits_f.data_ptr(), _p(area_f), _stream()), "psam_crop_expand_bits")
-    return bits_f, area_f
+    return _expand_bits("crop_expand_bits", "bits", bits, inv, Nw, area)
 
 
 # ------------------------------------------------------------------------------------------ interpolated scene masks (csrc/scene_interp.hip)

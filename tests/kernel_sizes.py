@@ -1,6 +1,7 @@
-"""The sizes at which the integer kernels of csrc/masks.hip, scene.hip and crops.hip change their code path, read from the sources: which
-nms_walk_kernel<NW> instance the host code launches for which K, how many positions a thread of paint_rank_kernel takes, how many block counts a
-thread of the two offsets kernels scans.  The literal size lists below are what the GPU tests run; tests/test_proposals_cpu.py derives the same
+"""The sizes at which the integer kernels of csrc/masks.hip and the scan of csrc/voxel_table.h (scene.hip's and crops.hip's downsample) change their
+code path, read from the sources: which nms_walk_kernel<NW> instance the host code launches for which K, how many positions a thread of
+paint_rank_kernel takes, how many block counts a thread of the two offsets kernels (both scan_block_offsets) scans.
+The literal size lists below are what the GPU tests run; tests/test_proposals_cpu.py derives the same
 lists from the parsed constants, so a new instance or a changed constant without a matching size fails without a GPU."""
 import os
 import re
@@ -47,7 +48,11 @@ def mask_constants():
 
 
 def scan_constants():
-    return {"SCAN_THREADS": _constant(_read("scene.hip"), "SCAN_THREADS"), "CROP_SCAN_THREADS": _constant(_read("crops.hip"), "CROP_SCAN_THREADS")}
+    """The one SCAN_THREADS of voxel_table.h under both names: scene.hip and crops.hip define none of their own."""
+    for f in ("scene.hip", "crops.hip"):
+        assert '#include "voxel_table.h"' in _read(f) and "SCAN_THREADS =" not in _read(f), f
+    T = _constant(_read("voxel_table.h"), "SCAN_THREADS")
+    return {"SCAN_THREADS": T, "CROP_SCAN_THREADS": T}
 
 
 def nms_sizes(c):

@@ -66,6 +66,31 @@ def test_crop_downsample_sizes_around_wave_block_and_second_level(ops, M, h):
         assert M < 1025 or keep_idx.numel() < members
 
 
+@pytest.mark.parametrize("h", [0.05, 2.0])
+@pytest.mark.parametrize("M", [65, 1025])
+def test_crop_downsample_of_the_unit_ball_equals_voxel_downsample(ops, M, h):
+    """The two downsamples share the table and the scan (csrc/voxel_table.h), so they agree where their definitions coincide: centre 0 and radius 1
+    make x - 0 and x * 1 exact, points of [-0.55, 0.55]^3 have q <= 0.9075 (all members, the clamp idle), and both grids start at -1.  Then
+    keep_idx and inv are voxel_downsample's, wxyz = xyz[keep_idx] and wrgb = rgb[keep_idx] bit for bit.  M = 65: a wave and one lane; 1025: two
+    scan blocks.  h = 2: one voxel.  Point 5 repeats point 2 and one coordinate is -0.0.  (tests/scene_reference.py and tests/crop_reference.py
+    agree bit for bit on these inputs: the statement holds for the definitions, not only for the kernels.)"""
+    rng = np.random.default_rng(700 + M)
+    xyz = rng.uniform(-0.55, 0.55, (M, 3)).astype(f32)
+    xyz[5] = xyz[2]
+    xyz[7, 1] = f32(-0.0)
+    rgb = rng.uniform(-1, 1, (M, 3)).astype(f32)
+    assert float(((xyz.astype(np.float64)) ** 2).sum(1).max()) <= 0.9075 and np.signbit(xyz[7, 1])
+    dx, dr = torch.from_numpy(xyz).cuda(), torch.from_numpy(rgb).cuda()
+    want_keep, want_inv = ops.voxel_downsample(dx, h)
+    keep_idx, inv, wxyz, wrgb, members = ops.crop_downsample(dx, dr, (0.0, 0.0, 0.0), 1.0, h)
+    assert members == M
+    assert torch.equal(keep_idx, want_keep) and torch.equal(inv, want_inv)
+    assert int(inv[5]) == int(inv[2]) and (h < 2.0 or keep_idx.tolist() == [0])
+    keep = keep_idx.cpu().numpy()
+    assert np.array_equal(_bits(wxyz.cpu().numpy()), _bits(xyz[keep]))
+    assert np.array_equal(_bits(wrgb.cpu().numpy()), _bits(rgb[keep]))
+
+
 # ------------------------------------------------------------------------------------------------ 2. boundary and ordering cases
 def test_membership_is_exact_on_the_sphere_and_non_finite_points_are_outside(ops):
     """c = 0, r = 0.5: every operation is exact, so (0.5, 0, 0) and (0, -0.5, 0) lie ON the sphere and are members (q == r2), and the next float
@@ -462,8 +487,9 @@ def test_crop_entry_points_resolve_and_reject_bad_arguments(ops):
 @pytest.mark.parametrize("h", [0.025, None])
 @pytest.mark.parametrize("which", [0, 1, 2])
 def test_crop_downsample_with_one_two_and_three_blocks_per_offsets_thread(ops, which, h):
-    """M = T^2, T^2 + 1 and 2 T^2 + T + 1 points for T = CROP_SCAN_THREADS read from crops.hip: crop_offsets_kernel gives each thread 1, 2 and 3
-    block counts (the last with a ragged final span and threads with none).  Uniform points of the cube; two stretches of 4 T consecutive points
+    """M = T^2, T^2 + 1 and 2 T^2 + T + 1 points for T = SCAN_THREADS read from voxel_table.h (the one constant behind both keys of scan_constants):
+    crop_offsets_kernel -- the shared scan_block_offsets and the members' sum over the same spans -- gives each thread 1, 2 and 3 block counts
+    (the last with a ragged final span and threads with none).  Uniform points of the cube; two stretches of 4 T consecutive points
     (the middle and the end) are copies of point 0, a member, so whole blocks count zero representatives with a voxel size (and T members).  The
     ball holds between a quarter and three quarters of the points (a condition on the inputs)."""
     import kernel_sizes as KS

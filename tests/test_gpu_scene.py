@@ -341,8 +341,9 @@ def _scan_cloud(M, T, seed):
 
 @pytest.mark.parametrize("which", [0, 1, 2])
 def test_downsample_with_one_two_and_three_blocks_per_offsets_thread(ops, which):
-    """M = T^2, T^2 + 1 and 2 T^2 + T + 1 points for T = SCAN_THREADS read from scene.hip: voxel_offsets_kernel gives each thread 1, 2 and 3 block
-    counts (the last with a ragged final span and threads with none): the serial span sum, the in-place rewrite of the span, the empty spans.
+    """M = T^2, T^2 + 1 and 2 T^2 + T + 1 points for T = SCAN_THREADS read from voxel_table.h: scan_block_offsets (voxel_offsets_kernel) gives each
+    thread 1, 2 and 3 block counts (the last with a ragged final span and threads with none): the serial span sum, the in-place rewrite of the span,
+    the empty spans.
     h = 0.025: the reference keeps between M / 8 and M / 2 points (a condition on the inputs)."""
     import kernel_sizes as KS
     T = KS.scan_constants()["SCAN_THREADS"]

@@ -274,9 +274,9 @@ def test_interval_reference_equals_the_mask_reference(K, thr):
 
 
 def test_tested_sizes_follow_from_the_kernel_sources():
-    """The size lists of tests/kernel_sizes.py (what the GPU tests run) equal what the constants and launches parsed from masks.hip, scene.hip and
-    crops.hip give.  A new nms_walk_kernel instance, another KW bound or a changed NMS_MAX_K / NMS_PF / RANK_THREADS / SCAN_THREADS fails here
-    until the lists cover it."""
+    """The size lists of tests/kernel_sizes.py (what the GPU tests run) equal what the constants and launches parsed from masks.hip and voxel_table.h
+    (the scan of scene.hip and crops.hip) give.  A new nms_walk_kernel instance, another KW bound or a changed NMS_MAX_K / NMS_PF / RANK_THREADS /
+    SCAN_THREADS fails here until the lists cover it."""
     c = KS.mask_constants()
     assert c["walks"] == [(1, 64), (2, 128), (4, 256)] and c["NMS_MAX_K"] == 16384 and c["NMS_PF"] == 8 and c["RANK_THREADS"] == 1024
     from point_sam_amd.proposals import MAX_CANDIDATES
@@ -300,7 +300,7 @@ def test_tested_sizes_follow_from_the_kernel_sources():
     assert [-(-K // c["RANK_THREADS"]) for K in KS.PAINT_SIZES] == [1, 1, 2, 3, 5]
     assert KS.valid_sizes(c) == KS.VALID_SIZES
     sc = KS.scan_constants()
-    assert sc["SCAN_THREADS"] == sc["CROP_SCAN_THREADS"]
+    assert sc["SCAN_THREADS"] == sc["CROP_SCAN_THREADS"]      # one constant in voxel_table.h: scan_constants refuses a second definition in either file
     T = sc["SCAN_THREADS"]
     assert KS.scan_sizes(T) == KS.SCAN_SIZES
     assert [-(-(-(-M // T)) // T) for M in KS.SCAN_SIZES] == [1, 2, 3] and (-(-KS.SCAN_SIZES[2] // T)) % 3 != 0

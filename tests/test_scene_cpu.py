@@ -34,6 +34,23 @@ def test_scene_entry_points_are_declared_bound_and_exported():
     assert lib.psam_version() == 100
 
 
+def test_the_voxel_table_and_the_row_popcount_live_in_one_file_each():
+    """The table's format, its probe and the scan are csrc/voxel_table.h's: scene.hip, crops.hip and regions.hip include it and keep no copy.  The
+    claiming compare-and-swap and the row popcount each occur in exactly one file of csrc/ (experiments/ aside)."""
+    csrc = os.path.join(ROOT, "point_sam_amd", "csrc")
+    table = open(os.path.join(csrc, "voxel_table.h")).read()
+    for word in ("int voxel_claim(", "int voxel_find(", "int voxel_claim_run(", "void scan_block_offsets(", "constexpr int SCAN_THREADS", "struct VoxelWs"):
+        assert table.count(word) == 1, word
+    for f in ("scene.hip", "crops.hip", "regions.hip"):
+        src = open(os.path.join(csrc, f)).read()
+        assert '#include "voxel_table.h"' in src, f
+        assert "atomicCAS(&keys" not in src and "VOXEL_EMPTY, key)" not in src and "__shfl_up" not in src and "make_uint4" not in src, f
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h", ".cpp"))}
+    assert [f for f, src in sources.items() if "atomicCAS(&keys" in src] == ["voxel_table.h"]
+    assert [f for f, src in sources.items() if "__popcll(row[w])" in src] == ["row_popcount.h"]
+    assert sources["voxel_table.h"].count("atomicCAS(&keys") == 1 and sources["row_popcount.h"].count("__popcll(row[w])") == 1
+
+
 def test_scene_entry_points_reject_bad_arguments_on_the_host():
     """Null pointers, empty shapes, a bad inv_h and a short workspace return -1 with a message before any launch."""
     lib = _lib.load()

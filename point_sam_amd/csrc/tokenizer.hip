@@ -66,6 +66,47 @@ __device__ __forceinline__ float fps_min(float a, float b) {
     return r;
 }
 
+// The steps every FPS kernel repeats, once each.  Bit-exact by contract: a change here changes all of them together.
+// Running minima of the four points at base .. base + 3: padding never wins, real min-distances are >= 0.
+__device__ __forceinline__ f32x4 fps_md_init(int base, int N) {
+    f32x4 m;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m[e] = base + e < N ? INFINITY : -1.0f;
+    return m;
+}
+
+// The scan of one group of four points against the centre (c2x, c2y, c2z: wave-uniform, SGPR pairs): 5.5 VALU instructions per point -- packed fp32
+// subtract / multiply / add, every operation individually rounded (the bits of dist2_exact), one min per point, the thread's maximum VALUE only.
+__device__ __forceinline__ void fps_visit(f32x4& m, const f32x4 x, const f32x4 y, const f32x4 z, const fps_f32x2 c2x, const fps_f32x2 c2y, const fps_f32x2 c2z,
+                                          float& best) {
+    const f32x4 dx = fps_sub_bcast(x, c2x), dy = fps_sub_bcast(y, c2y), dz = fps_sub_bcast(z, c2z);
+    const f32x4 d = (dx * dx + dy * dy) + dz * dz;      // -ffp-contract=off: no FMA, each op rounded (dist2_exact)
+    m = f32x4{fps_min(m.x, d.x), fps_min(m.y, d.y), fps_min(m.z, d.z), fps_min(m.w, d.w)};
+    best = fmaxf(fmaxf(best, m.x), m.y);
+    best = fmaxf(fmaxf(best, m.z), m.w);
+}
+
+// The lowest of a thread's 4 NG slots that holds v (0 when none does).
+template <int NG>
+__device__ __forceinline__ int fps_lowest_slot(const f32x4 (&md)[NG], float v) {
+    int bslot = 0;
+#pragma unroll
+    for (int g = NG - 1; g >= 0; --g) {      // descending: the lowest slot is assigned last
+        if (md[g].w == v) bslot = 4 * g + 3;
+        if (md[g].z == v) bslot = 4 * g + 2;
+        if (md[g].y == v) bslot = 4 * g + 1;
+        if (md[g].x == v) bslot = 4 * g;
+    }
+    return bslot;
+}
+
+// Sample j of cloud b is point `last`: its index and (fused batch_index_select) its coordinates.
+__device__ __forceinline__ void fps_publish(const float* __restrict__ P, int b, int G, int j, int last, int64_t* __restrict__ idx_out, float* __restrict__ centers_out) {
+    const int tid = threadIdx.x;
+    if (tid == 0) idx_out[(int64_t)b * G + j] = last;
+    if (tid < 3) centers_out[((int64_t)b * G + j) * 3 + tid] = P[(int64_t)last * 3 + tid];
+}
+
 template <int PPT4>
 __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restrict__ xyz, const float* __restrict__ soa,
                                                           float* __restrict__ mdg, int N, int64_t npad, int G,
@@ -98,13 +139,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restric
     f32x4 rx[RG], ry[RG], rz[RG];
     if (PPT4 > 0) {
 #pragma unroll
-        for (int g = 0; g < NREG; ++g) {
-            const int base = (g * FPS_THREADS + tid) * 4;
-            md[g].x = base + 0 < N ? INFINITY : -1.0f;  // padding never wins: real min-distances are >= 0
-            md[g].y = base + 1 < N ? INFINITY : -1.0f;
-            md[g].z = base + 2 < N ? INFINITY : -1.0f;
-            md[g].w = base + 3 < N ? INFINITY : -1.0f;
-        }
+        for (int g = 0; g < NREG; ++g) md[g] = fps_md_init((g * FPS_THREADS + tid) * 4, N);
 #pragma unroll
         for (int g = 0; g < RG; ++g) { rx[g] = gload(g, 0); ry[g] = gload(g, 1); rz[g] = gload(g, 2); }
 #pragma unroll
@@ -115,24 +150,16 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restric
         }
     } else {
         for (int g = 0; g < ngroups; ++g) {
-            const int base = (g * FPS_THREADS + tid) * 4;
-            float4 m;
-            m.x = base + 0 < N ? INFINITY : -1.0f;
-            m.y = base + 1 < N ? INFINITY : -1.0f;
-            m.z = base + 2 < N ? INFINITY : -1.0f;
-            m.w = base + 3 < N ? INFINITY : -1.0f;
-            MD4[g * FPS_THREADS + tid] = m;
+            const f32x4 m = fps_md_init((g * FPS_THREADS + tid) * 4, N);
+            MD4[g * FPS_THREADS + tid] = make_float4(m.x, m.y, m.z, m.w);
         }
     }
 
     int last = 0;
-    if (tid == 0) idx_out[(int64_t)b * G] = 0;
-    if (tid < 3) centers_out[(int64_t)b * G * 3 + tid] = P[tid];
+    fps_publish(P, b, G, 0, 0, idx_out, centers_out);
 
     if constexpr (PPT4 > 0) {
-        // On-chip cloud.  An iteration is (a) the scan: 5.5 VALU instructions per point -- packed fp32 subtract / multiply / add (v_pk_*,
-        // two points per instruction, every operation individually rounded: the same bits as dist2_exact), one min per point, one
-        // v_max3 per two points for the thread's maximum VALUE only; (b) the maximum over the workgroup (wave reduction, LDS, barrier);
+        // On-chip cloud.  An iteration is (a) the scan, fps_visit per group; (b) the maximum over the workgroup (wave reduction, LDS, barrier);
         // (c) the index: only the lanes that hold the maximum look for its lowest slot, the lowest global index among them wins (wave
         // minimum, then the minimum over the waves' records), and that lane publishes index AND coordinates from its own registers /
         // LDS slots -- the next iteration starts from LDS instead of a dependent load through L2.
@@ -144,23 +171,17 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restric
         for (int j = 1; j < G; ++j) {
             float best = -1.0f;
             const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};      // wave-uniform: SGPR pairs
-            auto visit = [&](f32x4& m, const f32x4 x, const f32x4 y, const f32x4 z) {
-                const f32x4 dx = fps_sub_bcast(x, c2x), dy = fps_sub_bcast(y, c2y), dz = fps_sub_bcast(z, c2z);
-                const f32x4 d = (dx * dx + dy * dy) + dz * dz;      // -ffp-contract=off: no FMA, each op rounded (dist2_exact)
-                m = f32x4{fps_min(m.x, d.x), fps_min(m.y, d.y), fps_min(m.z, d.z), fps_min(m.w, d.w)};
-                best = fmaxf(fmaxf(best, m.x), m.y);
-                best = fmaxf(fmaxf(best, m.z), m.w);
-            };
             f32x4 sx, sy, sz;
             if (SG > 0) { sx = gload(RG + LG, 0); sy = gload(RG + LG, 1); sz = gload(RG + LG, 2); }
 #pragma unroll
-            for (int g = 0; g < RG; ++g) visit(md[g], rx[g], ry[g], rz[g]);
+            for (int g = 0; g < RG; ++g) fps_visit(md[g], rx[g], ry[g], rz[g], c2x, c2y, c2z, best);
 #pragma unroll
             for (int g = 0; g < LG; ++g) {
                 __builtin_amdgcn_sched_barrier(0);  // one LDS group (12 VGPRs) in flight at a time: the register file is full
-                visit(md[RG + g], s_xyz[(g * 3 + 0) * FPS_THREADS + tid], s_xyz[(g * 3 + 1) * FPS_THREADS + tid], s_xyz[(g * 3 + 2) * FPS_THREADS + tid]);
+                fps_visit(md[RG + g], s_xyz[(g * 3 + 0) * FPS_THREADS + tid], s_xyz[(g * 3 + 1) * FPS_THREADS + tid], s_xyz[(g * 3 + 2) * FPS_THREADS + tid],
+                          c2x, c2y, c2z, best);
             }
-            if (SG > 0) visit(md[RG + LG], sx, sy, sz);
+            if (SG > 0) fps_visit(md[RG + LG], sx, sy, sz, c2x, c2y, c2z, best);
             // (b) maximum value over the workgroup
             const int slot = j & 1;
             const float wmax = wave_max(best);
@@ -173,13 +194,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restric
             if (__builtin_amdgcn_ballot_w64(mine) != 0) {      // wave-uniform
                 int cand = 0x7fffffff, bslot = 0;
                 if (mine) {
-#pragma unroll
-                    for (int g = NREG - 1; g >= 0; --g) {      // descending: the lowest slot is assigned last
-                        if (md[g].w == gmax) bslot = 4 * g + 3;
-                        if (md[g].z == gmax) bslot = 4 * g + 2;
-                        if (md[g].y == gmax) bslot = 4 * g + 1;
-                        if (md[g].x == gmax) bslot = 4 * g;
-                    }
+                    bslot = fps_lowest_slot(md, gmax);
                     cand = ((bslot >> 2) * FPS_THREADS + tid) * 4 + (bslot & 3);
                 }
                 const int wmin = wave_min_dpp(cand);
@@ -255,8 +270,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const float* __restric
             if (ov > v || (ov == v && oi < vi)) { v = ov; vi = oi; }
         }
         last = __builtin_amdgcn_readfirstlane(vi);
-        if (tid == 0) idx_out[(int64_t)b * G + j] = last;
-        if (tid < 3) centers_out[((int64_t)b * G + j) * 3 + tid] = P[(int64_t)last * 3 + tid];
+        fps_publish(P, b, G, j, last, idx_out, centers_out);
     }
 }
 
@@ -294,6 +308,14 @@ __device__ __forceinline__ unsigned long long fps_wave_max_u64(unsigned long lon
 // work on ONE stream, so they never do); more than two concurrent cooperative launches from different streams are not supported.
 // Same arithmetic and tie-break as fps_kernel -> bit-identical indices.
 // ------------------------------------------------------------------------------------------------
+// The centre just selected: three scalar loads (uniform address; ~0.1 us from L2, scripts/exp/fabric_probe.hip)
+__device__ __forceinline__ void fps_load_centre(const float* __restrict__ P, int last, float& cx, float& cy, float& cz) {
+    cx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 0])));
+    cy = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 1])));
+    cz = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 2])));
+    asm volatile("s_nop 4");      // SGPRs possibly written by the VALU feed packed-fp32 VALU operands (inline asm) right after
+}
+
 template <int PPT4>
 __global__ __launch_bounds__(FPS_THREADS) void fps_coop_kernel(const float* __restrict__ xyz, const float* __restrict__ soa, int N, int64_t npad,
                                                                int G, int W, int xcd_stride, unsigned long long* __restrict__ cand,
@@ -322,40 +344,23 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_kernel(const float* __re
 #pragma unroll
     for (int g = 0; g < PPT4; ++g) {
         const int gg = w * PPT4 + g;
-        const int base = (gg * FPS_THREADS + tid) * 4;
-        md[g].x = base + 0 < N ? INFINITY : -1.0f;
-        md[g].y = base + 1 < N ? INFINITY : -1.0f;
-        md[g].z = base + 2 < N ? INFINITY : -1.0f;
-        md[g].w = base + 3 < N ? INFINITY : -1.0f;
+        md[g] = fps_md_init((gg * FPS_THREADS + tid) * 4, N);
         const int off = gg * (FPS_THREADS * 16);
         rx[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, off, 0));
         ry[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, off + plane_bytes, 0));
         rz[g] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, tid * 16, off + 2 * plane_bytes, 0));
     }
     int last = 0;
-    if (w == 0) {
-        if (tid == 0) idx_out[(int64_t)b * G] = 0;
-        if (tid < 3) centers_out[(int64_t)b * G * 3 + tid] = P[tid];
-    }
+    if (w == 0) fps_publish(P, b, G, 0, 0, idx_out, centers_out);
     for (int j = 1; j < G; ++j) {
-        // the centre just selected: three scalar loads (uniform address; ~0.1 us from L2, scripts/exp/fabric_probe.hip)
-        const float cx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 0])));
-        const float cy = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 1])));
-        const float cz = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 2])));
-        asm volatile("s_nop 4");      // SGPRs possibly written by the VALU feed packed-fp32 VALU operands (inline asm) right below
-        // (a) the scan of fps_kernel: packed fp32, every operation individually rounded (the bits of dist2_exact), the thread's maximum VALUE
-        // only -- 5.5 VALU instructions per point instead of 12 with a (value, slot) pair carried along; with 16 waves sharing four SIMDs
-        // the scan of 16 points per thread was 1.4 us of a 2.5 us iteration
+        float cx, cy, cz;
+        fps_load_centre(P, last, cx, cy, cz);
+        // (a) the scan of fps_kernel: 5.5 VALU instructions per point instead of 12 with a (value, slot) pair carried along; with 16 waves sharing
+        // four SIMDs the scan of 16 points per thread was 1.4 us of a 2.5 us iteration
         float best = -1.0f;
         const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
-        for (int g = 0; g < PPT4; ++g) {
-            const f32x4 dx = fps_sub_bcast(rx[g], c2x), dy = fps_sub_bcast(ry[g], c2y), dz = fps_sub_bcast(rz[g], c2z);
-            const f32x4 d = (dx * dx + dy * dy) + dz * dz;      // -ffp-contract=off: no FMA
-            md[g] = f32x4{fps_min(md[g].x, d.x), fps_min(md[g].y, d.y), fps_min(md[g].z, d.z), fps_min(md[g].w, d.w)};
-            best = fmaxf(fmaxf(best, md[g].x), md[g].y);
-            best = fmaxf(fmaxf(best, md[g].z), md[g].w);
-        }
+        for (int g = 0; g < PPT4; ++g) fps_visit(md[g], rx[g], ry[g], rz[g], c2x, c2y, c2z, best);
         // (b) the wave's candidate: its maximum, then -- only in the lanes that hold it -- the lowest slot, the lowest global index among them.
         // key: [63:32] min-distance bits (larger wins), [31:20] iteration tag, [19:0] 0xFFFFF - index (then the LOWER index wins; all keys
         // of an iteration carry the same tag, so it never decides).  A wave of pure padding (maximum < 0) holds distance 0, index field 0.
@@ -366,14 +371,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_kernel(const float* __re
         if (wmax >= 0.f) {      // wave-uniform
             int cand = 0x7fffffff;
             if (best == wmax) {
-                int bslot = 0;
-#pragma unroll
-                for (int g = PPT4 - 1; g >= 0; --g) {      // descending: the lowest slot is assigned last
-                    if (md[g].w == wmax) bslot = 4 * g + 3;
-                    if (md[g].z == wmax) bslot = 4 * g + 2;
-                    if (md[g].y == wmax) bslot = 4 * g + 1;
-                    if (md[g].x == wmax) bslot = 4 * g;
-                }
+                const int bslot = fps_lowest_slot(md, wmax);
                 cand = ((w * PPT4 + (bslot >> 2)) * FPS_THREADS + tid) * 4 + (bslot & 3);
             }
             const unsigned wmin = (unsigned)wave_min_dpp(cand);
@@ -386,22 +384,18 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_kernel(const float* __re
             static_assert(FPS_WAVES == 16, "one 16-lane row holds the waves' keys");
             const unsigned long long wk = fps_row16_max_u64(s_key[slot][lane & 15]);
             if (lane == 0) __hip_atomic_store(cand_b + slot * 64 + w, wk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            // every lane < W polls one workgroup's slot until all of them carry this iteration's tag
             unsigned long long k;
             for (;;) {
                 k = lane < W ? __hip_atomic_load(cand_b + slot * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ((unsigned long long)tag << 20);
                 if (__all((((unsigned)k >> 20) & 0xFFFu) == tag)) break;
                 __builtin_amdgcn_s_sleep(1);
             }
-            k = W <= 16 ? fps_row16_max_u64(k) : fps_wave_max_u64(k);      // W <= 16: the keys sit in lanes 0..15, one row
+            k = W <= 16 ? fps_row16_max_u64(k) : fps_wave_max_u64(k);
             if (lane == 0) s_last[slot] = (int)(0xFFFFFu - ((unsigned)k & 0xFFFFFu));
         }
         __syncthreads();
         last = __builtin_amdgcn_readfirstlane(s_last[slot]);
-        if (w == 0) {
-            if (tid == 0) idx_out[(int64_t)b * G + j] = last;
-            if (tid < 3) centers_out[((int64_t)b * G + j) * 3 + tid] = P[(int64_t)last * 3 + tid];
-        }
+        if (w == 0) fps_publish(P, b, G, j, last, idx_out, centers_out);
     }
 }
 
@@ -422,7 +416,9 @@ __global__ void fps_coop_reset_kernel(unsigned long long* cand, int n) {
 // wave's current maximum, no running minimum of the wave can change (min(m, d) with d >= box distance >= maximum >= m): the wave re-publishes its
 // cached candidate and skips the scan.  Same distances, same minima, same tie-break (lowest original index) as fps_kernel: bit-identical indices.
 // On a surface-like cloud the number of waves that scan falls like (1 + 16 / sqrt(j))^2 of 256 at iteration j; what remains per iteration is the
-// hand-over between the workgroups.
+// hand-over between the workgroups.  Centre load (fps_load_centre), scan (fps_visit) and result write (fps_publish) are the functions fps_coop_kernel uses;
+// placement, key and hand-over are that kernel's, copied (as functions they cost 1 - 3 % of a call: profiles/tokenizer/README.md); only the index in the
+// key differs: the point's ORIGINAL one.
 // ------------------------------------------------------------------------------------------------
 constexpr int FPS_CELL_BITS = 5, FPS_NCELL = 1 << (3 * FPS_CELL_BITS);
 __device__ __forceinline__ int fps_ordered(float f) { const int i = __builtin_bit_cast(int, f); return i >= 0 ? i : i ^ 0x7fffffff; }
@@ -546,18 +542,13 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_pruned_kernel(const floa
     }
     blx = -wave_max(-blx); bly = -wave_max(-bly); blz = -wave_max(-blz);      // an empty wave keeps lo = +inf, hi = -inf: its box distance is +inf, it never scans
     bhx = wave_max(bhx); bhy = wave_max(bhy); bhz = wave_max(bhz);
-    float c_wmax = wave_max(md[0][0]) >= 0.f ? INFINITY : -1.0f;      // (position order: a wave with any valid point has a valid lane 0, slot 0)
+    float c_wmax = wave_max(md[0][0]) >= 0.f ? INFINITY : -1.0f;      // +inf, or -1 for a wave of padding (position order: a wave with any valid point has a valid lane 0, slot 0)
     unsigned c_idx = 0;
     int last = 0;
-    if (w == 0) {
-        if (tid == 0) idx_out[(int64_t)b * G] = 0;
-        if (tid < 3) centers_out[(int64_t)b * G * 3 + tid] = P[tid];
-    }
+    if (w == 0) fps_publish(P, b, G, 0, 0, idx_out, centers_out);
     for (int j = 1; j < G; ++j) {
-        const float cx = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 0])));
-        const float cy = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 1])));
-        const float cz = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, P[(int64_t)last * 3 + 2])));
-        asm volatile("s_nop 4");      // SGPRs possibly written by the VALU feed packed-fp32 VALU operands (inline asm) right below
+        float cx, cy, cz;
+        fps_load_centre(P, last, cx, cy, cz);
         // the centre's distance to the wave's box, in the scan's arithmetic (a - c and -(c - a) are the same bits; contraction is off in this file)
         const float ax = fmaxf(fmaxf(blx - cx, cx - bhx), 0.f), ay = fmaxf(fmaxf(bly - cy, cy - bhy), 0.f), az = fmaxf(fmaxf(blz - cz, cz - bhz), 0.f);
         const float dbox = (ax * ax + ay * ay) + az * az;
@@ -566,13 +557,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_pruned_kernel(const floa
             float best = -1.0f;
             const fps_f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
 #pragma unroll
-            for (int g = 0; g < PPT4; ++g) {
-                const f32x4 dx = fps_sub_bcast(rx[g], c2x), dy = fps_sub_bcast(ry[g], c2y), dz = fps_sub_bcast(rz[g], c2z);
-                const f32x4 d = (dx * dx + dy * dy) + dz * dz;      // -ffp-contract=off: no FMA
-                md[g] = f32x4{fps_min(md[g].x, d.x), fps_min(md[g].y, d.y), fps_min(md[g].z, d.z), fps_min(md[g].w, d.w)};
-                best = fmaxf(fmaxf(best, md[g].x), md[g].y);
-                best = fmaxf(fmaxf(best, md[g].z), md[g].w);
-            }
+            for (int g = 0; g < PPT4; ++g) fps_visit(md[g], rx[g], ry[g], rz[g], c2x, c2y, c2z, best);
             c_wmax = wave_max(best);
             unsigned cnd = 0x7fffffffu;      // the lowest ORIGINAL index among the points that hold the maximum
             if (best == c_wmax) {
@@ -605,10 +590,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_pruned_kernel(const floa
         }
         __syncthreads();
         last = __builtin_amdgcn_readfirstlane(s_last[slot]);
-        if (w == 0) {
-            if (tid == 0) idx_out[(int64_t)b * G + j] = last;
-            if (tid < 3) centers_out[((int64_t)b * G + j) * 3 + tid] = P[(int64_t)last * 3 + tid];
-        }
+        if (w == 0) fps_publish(P, b, G, j, last, idx_out, centers_out);
     }
 }
 
@@ -656,7 +638,8 @@ static int fps_coop_ppt4(int B, int N, int* W) {
 PSAM_API size_t psam_fps_workspace_bytes(int32_t B, int32_t N, int32_t G) {
     (void)G;
     if (B <= 0 || N <= 0) return 0;
-    // planar xyz (3) + streamed min-distance (1) + cooperative hand-over: 2 x 64 candidate slots and one barrier counter per cloud
+    // planar xyz (3) + streamed min-distance (1) + cooperative hand-over: 2 x 64 tagged key slots per cloud (and 16 bytes that once held a barrier
+    // counter: nothing reads them, the size is kept)
     // + the pruned cooperative kernel's counting sort: per cloud a bounding box (8 ints) and FPS_NCELL cell counters
     return (size_t)B * 4 * (size_t)fps_npad(N) * sizeof(float) + (size_t)B * (2 * 64 * sizeof(unsigned long long) + 16) + (size_t)B * (FPS_NCELL + 8) * sizeof(int);
 }
@@ -777,12 +760,67 @@ __device__ __forceinline__ int block_excl_scan_256(int v, int* s_wave, int& tota
     return off + inc - v;
 }
 
+// The bin of hist[2048] (eight per thread) that holds rank `remaining` (1-based): after the call sm[0] is that bin, sm[1] the count below it.
+__device__ __forceinline__ void knn_locate_bin(const unsigned* hist, int remaining, int* s_wave, int* sm) {
+    const int tid = threadIdx.x;
+    int loc[8], sum = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { loc[i] = (int)hist[tid * 8 + i]; sum += loc[i]; }
+    int total;
+    int before = block_excl_scan_256(sum, s_wave, total);
+    if (remaining > before && remaining <= before + sum) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            if (remaining > before && remaining <= before + loc[i]) { sm[0] = tid * 8 + i; sm[1] = before; }
+            before += loc[i];
+        }
+    }
+    __syncthreads();
+}
+
+// The end of a radix pass over bits shift + log2(nb) - 1 : shift: the bin of rank `remaining`, the prefix extended by it.  eq_total: how many patterns share
+// the new prefix.
+__device__ __forceinline__ void knn_pass_tail(const unsigned* hist, int shift, int nb, int* s_wave, int* sm, int& remaining, int& eq_total, unsigned& prefix_mask,
+                                              unsigned& prefix_val) {
+    knn_locate_bin(hist, remaining, s_wave, sm);
+    const int bin = sm[0];
+    remaining -= sm[1];
+    eq_total = (int)hist[bin];
+    prefix_val |= (unsigned)bin << shift;
+    prefix_mask |= (unsigned)(nb - 1) << shift;
+    __syncthreads();
+}
+
+// Bitonic sort of the K keys (d2 pattern, index) padded to a power of two, then the indices in that order.
+__device__ __forceinline__ void knn_sort_write(unsigned long long* keys, int K, int64_t* __restrict__ out) {
+    const int tid = threadIdx.x;
+    int P2 = 1;
+    while (P2 < K) P2 <<= 1;
+    __syncthreads();
+    for (int i = K + tid; i < P2; i += KNN_THREADS) keys[i] = ~0ull;
+    __syncthreads();
+    for (int k = 2; k <= P2; k <<= 1) {
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int i = tid; i < P2; i += KNN_THREADS) {
+                const int ixj = i ^ jj;
+                if (ixj > i) {
+                    const unsigned long long a = keys[i], bb = keys[ixj];
+                    const bool up = (i & k) == 0;
+                    if ((a > bb) == up) { keys[i] = bb; keys[ixj] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < K; i += KNN_THREADS) out[i] = (int64_t)(keys[i] & 0xffffffffull);
+}
+
 // The whole selection for one center with every pass over the whole cloud (four distance evaluations per point): the general path -- any band size, ties
 // at the K-th value cut by index.  LDS arrays are the caller's (hist[2048], keys[KNN_MAXK], s_wave[4], sm[4] = bin / below / count-less / count-equal).
 __device__ __forceinline__ void knn_select_full(const float* __restrict__ P, float cx, float cy, float cz, int N, int K, int64_t* __restrict__ out, unsigned* hist,
                                                 unsigned long long* keys, int* s_wave, int* sm) {
     const int tid = threadIdx.x;
-    int& s_bin = sm[0]; int& s_below = sm[1]; int& s_cnt_less = sm[2]; int& s_cnt_eq = sm[3];
+    int& s_cnt_less = sm[2]; int& s_cnt_eq = sm[3];
 
     unsigned prefix_mask = 0, prefix_val = 0;
     int remaining = K;  // rank (1-based) of the K-th smallest inside the current candidate set
@@ -798,26 +836,7 @@ __device__ __forceinline__ void knn_select_full(const float* __restrict__ P, flo
             if ((u & prefix_mask) == prefix_val) atomicAdd(&hist[(u >> shift) & (nb - 1)], 1u);
         }
         __syncthreads();
-        // locate the bin that holds rank `remaining`
-        int loc[8], sum = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { loc[i] = (int)hist[tid * 8 + i]; sum += loc[i]; }
-        int total;
-        int before = block_excl_scan_256(sum, s_wave, total);
-        if (remaining > before && remaining <= before + sum) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                if (remaining > before && remaining <= before + loc[i]) { s_bin = tid * 8 + i; s_below = before; }
-                before += loc[i];
-            }
-        }
-        __syncthreads();
-        const int bin = s_bin;
-        remaining -= s_below;
-        eq_total = (int)hist[bin];
-        prefix_val |= (unsigned)bin << shift;
-        prefix_mask |= (unsigned)(nb - 1) << shift;
-        __syncthreads();
+        knn_pass_tail(hist, shift, nb, s_wave, sm, remaining, eq_total, prefix_mask, prefix_val);
     }
     const unsigned T = prefix_val;     // bit pattern of the K-th smallest d2
     const int need_eq = remaining;     // how many of the points with d2 == T belong to the answer (lowest indices)
@@ -855,26 +874,7 @@ __device__ __forceinline__ void knn_select_full(const float* __restrict__ P, flo
             eq_taken += total;
         }
     }
-    // bitonic sort of K keys padded to a power of two
-    int P2 = 1;
-    while (P2 < K) P2 <<= 1;
-    __syncthreads();
-    for (int i = K + tid; i < P2; i += KNN_THREADS) keys[i] = ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int i = tid; i < P2; i += KNN_THREADS) {
-                const int ixj = i ^ jj;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], bb = keys[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > bb) == up) { keys[i] = bb; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < K; i += KNN_THREADS) out[i] = (int64_t)(keys[i] & 0xffffffffull);
+    knn_sort_write(keys, K, out);
 }
 
 __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(const float* __restrict__ centers, const float* __restrict__ xyz,
@@ -914,7 +914,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
     __shared__ int s_wave[4];
     __shared__ int sm[4];
     __shared__ int s_cnt_cand;
-    int& s_bin = sm[0]; int& s_below = sm[1]; int& s_cnt_less = sm[2];
+    int& s_cnt_less = sm[2];
     int64_t* const out = out_idx + ((int64_t)b * G + g) * K;
 
     // points in groups of four (48 contiguous bytes = three 16-byte loads when the cloud is 16-byte aligned); group q = i * 256 + tid
@@ -950,7 +950,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
     }
     __syncthreads();
     int remaining = K;
-    {
+    {      // knn_locate_bin, kept in place: called here it costs this kernel five VGPRs (47 -> 52; profiles/tokenizer/README.md)
         int loc[8], sum = 0;
 #pragma unroll
         for (int i = 0; i < 8; ++i) { loc[i] = (int)hist[tid * 8 + i]; sum += loc[i]; }
@@ -959,15 +959,15 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
         if (remaining > before && remaining <= before + sum) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                if (remaining > before && remaining <= before + loc[i]) { s_bin = tid * 8 + i; s_below = before; }
+                if (remaining > before && remaining <= before + loc[i]) { sm[0] = tid * 8 + i; sm[1] = before; }
                 before += loc[i];
             }
         }
         __syncthreads();
     }
-    const unsigned bin0 = (unsigned)s_bin;
+    const unsigned bin0 = (unsigned)sm[0];
     const int n_band = (int)hist[bin0];
-    remaining -= s_below;      // rank of the K-th smallest inside the band
+    remaining -= sm[1];      // rank of the K-th smallest inside the band
     if (n_band > KNN_CAND) {      // uniform: the band does not fit the list
         __syncthreads();
         knn_select_full(P, cx, cy, cz, N, K, out, hist, keys, s_wave, sm);
@@ -999,25 +999,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
             if ((u & prefix_mask) == prefix_val) atomicAdd(&hist[(u >> shift) & (nb - 1)], 1u);
         }
         __syncthreads();
-        int loc[8], sum = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { loc[i] = (int)hist[tid * 8 + i]; sum += loc[i]; }
-        int total;
-        int before = block_excl_scan_256(sum, s_wave, total);
-        if (remaining > before && remaining <= before + sum) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                if (remaining > before && remaining <= before + loc[i]) { s_bin = tid * 8 + i; s_below = before; }
-                before += loc[i];
-            }
-        }
-        __syncthreads();
-        const int bin = s_bin;
-        remaining -= s_below;
-        eq_total = (int)hist[bin];
-        prefix_val |= (unsigned)bin << shift;
-        prefix_mask |= (unsigned)(nb - 1) << shift;
-        __syncthreads();
+        knn_pass_tail(hist, shift, nb, s_wave, sm, remaining, eq_total, prefix_mask, prefix_val);
     }
     const unsigned T = prefix_val;     // bit pattern of the K-th smallest d2
     const int need_eq = remaining;     // how many of the points with d2 == T belong to the answer (lowest indices)
@@ -1030,26 +1012,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
         const unsigned u = cand_u[i];
         if (u <= T) { const int p = atomicAdd(&s_cnt_less, 1); keys[p] = ((unsigned long long)u << 32) | (unsigned)cand_n[i]; }
     }
-    // ---- bitonic sort of K keys padded to a power of two (as knn_kernel)
-    int P2 = 1;
-    while (P2 < K) P2 <<= 1;
-    __syncthreads();
-    for (int i = K + tid; i < P2; i += KNN_THREADS) keys[i] = ~0ull;
-    __syncthreads();
-    for (int k = 2; k <= P2; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int i = tid; i < P2; i += KNN_THREADS) {
-                const int ixj = i ^ jj;
-                if (ixj > i) {
-                    const unsigned long long a = keys[i], bb = keys[ixj];
-                    const bool up = (i & k) == 0;
-                    if ((a > bb) == up) { keys[i] = bb; keys[ixj] = a; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    for (int i = tid; i < K; i += KNN_THREADS) out[i] = (int64_t)(keys[i] & 0xffffffffull);
+    knn_sort_write(keys, K, out);
 }
 
 static int g_knn_band = -1;      // -1: environment PSAM_KNN_BAND (default 1); 0 = always the four-pass kernel (A/B, tests)

@@ -190,6 +190,82 @@ def test_the_model_copies_the_constants_of_the_source():
         assert pinned_constants(src.replace(old, new)) != MODEL, old
 
 
+# the steps that FPS and kNN kernels share, each by a piece of text only its one implementation contains
+SINGLE_COPY = ("fps_sub_bcast(",                        # the scan of one group of four points (a call; the definition's own name is not in a body)
+               "__hip_atomic_store(",                   # the hand-over: publishing the key ...
+               "__builtin_amdgcn_s_sleep(",             # ... and polling the slots
+               "0xFFFFFu -",                            # the key's index field, packed and unpacked
+               "(blockIdx.x & 7) != (b & 7)",           # the one-XCD placement
+               "const int ixj = i ^ jj;",               # the bitonic network
+               "remaining <= before + loc[i]",          # the bin that holds rank `remaining`
+               "? INFINITY : -1.0f")                    # the padding rule of the running minima
+# the kernels that keep a step in place, by name, and why (profiles/tokenizer/README.md)
+COOP = ("fps_coop_kernel", "fps_coop_pruned_kernel")      # placement, key and hand-over as functions: 1 - 3 % slower calls on four of six instances
+KEPT_IN_PLACE = {"__hip_atomic_store(": COOP, "__builtin_amdgcn_s_sleep(": COOP, "0xFFFFFu -": COOP, "(blockIdx.x & 7) != (b & 7)": COOP,
+                 "? INFINITY : -1.0f": ("fps_coop_pruned_kernel",),      # its initialisation also feeds the bounding box; with fps_md_init: other code, slower
+                 "remaining <= before + loc[i]": ("knn_band_kernel",)}      # its first bin search: through knn_locate_bin the kernel needs 52 VGPRs, not 47
+
+
+def function_bodies(src):
+    """[(name, body)] of every function defined at file scope, comments stripped: a body is a brace block at depth 0 whose header ends in a parameter list."""
+    text = re.sub(r"/\*.*?\*/", "", re.sub(r"//[^\n]*", "", src), flags=re.S)
+    out, depth, start, prev = [], 0, 0, 0
+    for i, ch in enumerate(text):
+        if ch == "{":
+            if depth == 0:
+                start = i
+            depth += 1
+        elif ch == "}":
+            depth -= 1
+            assert depth >= 0, text[max(0, i - 200):i]
+            if depth == 0:
+                head = re.sub(r"__launch_bounds__\(\w+\)|__attribute__\(\(.*?\)\)", "", text[prev:start])
+                head = head[head.rfind(";") + 1:]
+                m = re.search(r"(\w+)\s*\(", head)
+                if m and head.rstrip().endswith(")"):
+                    out.append((m.group(1), text[start:i + 1]))
+                prev = i + 1
+    assert depth == 0
+    return out
+
+
+def holders(src, needle, kept=False):
+    """The functions whose body contains `needle` (white space normalised): those listed in KEPT_IN_PLACE for it (kept=True), or all others."""
+    squash = lambda s: re.sub(r"\s+", " ", s)
+    return [name for name, body in function_bodies(src) if squash(needle) in squash(body) and (name in KEPT_IN_PLACE.get(needle, ())) == kept]
+
+
+def test_each_shared_step_has_one_copy():
+    """The scan of a group, the hand-over, the key layout, the one-XCD placement, the bitonic sort, the bin search and the padding rule are bit-exact by
+    contract and were once pasted into two to four kernels each: each now sits in exactly one function body, and a copy planted back is seen."""
+    src = _src()
+    names = [n for n, _ in function_bodies(src)]
+    for k in KERNELS + ("fps_coop_reset_kernel", "knn_select_full", "psam_fps", "psam_knn", "three_nn_kernel"):
+        assert names.count(k) == 1, (k, names)
+    where = {needle: holders(src, needle) for needle in SINGLE_COPY}
+    for needle, v in where.items():      # one shared function; none where every kernel that needs the step keeps it in place
+        assert len(v) == (0 if KEPT_IN_PLACE.get(needle) == COOP else 1), where
+        assert sorted(holders(src, needle, kept=True)) == sorted(KEPT_IN_PLACE.get(needle, ())), needle      # no exception outlives its copy
+    assert not set(sum(where.values(), [])) & set(KERNELS), where      # in helpers, not in a kernel
+    # a copy pasted into another function
+    anchor = "__global__ void fps_coop_reset_kernel(unsigned long long* cand, int n) {"
+    assert src.count(anchor) == 1
+    for needle in SINGLE_COPY:
+        assert sorted(holders(src.replace(anchor, anchor + "\n    " + needle + " 0);"), needle)) == sorted(where[needle] + ["fps_coop_reset_kernel"]), needle
+    # a call replaced by what it stands for, as the kernels had it
+    for call, inline, needle, kernel in (
+            ("for (int g = 0; g < PPT4; ++g) fps_visit(md[g], rx[g], ry[g], rz[g], c2x, c2y, c2z, best);",
+             "for (int g = 0; g < PPT4; ++g) { const f32x4 dx = fps_sub_bcast(rx[g], c2x), dy = fps_sub_bcast(ry[g], c2y), dz = fps_sub_bcast(rz[g], c2z); }",
+             "fps_sub_bcast(", "fps_coop_kernel"),
+            ("md[g] = fps_md_init((gg * FPS_THREADS + tid) * 4, N);", "for (int e = 0; e < 4; ++e) md[g][e] = base + e < N ? INFINITY : -1.0f;", "? INFINITY : -1.0f",
+             "fps_coop_kernel"),
+            ("knn_locate_bin(hist, remaining, s_wave, sm);", "if (remaining > before && remaining <= before + loc[i]) { sm[0] = tid * 8 + i; sm[1] = before; }",
+             "remaining <= before + loc[i]", "knn_pass_tail")):
+        assert call in src, call
+        planted = src.replace(call, inline, 1)
+        assert sorted(holders(planted, needle)) == sorted(where[needle] + [kernel]), (needle, holders(planted, needle))
+
+
 def test_queries_report_minus_one_before_a_launch_and_after_a_refusal():
     """No GPU needed: a thread that never launched reads -1 from the three queries, and so does one whose call was refused on the host (null pointers)."""
     from point_sam_amd import _lib

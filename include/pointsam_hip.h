@@ -12,7 +12,9 @@
  *   - tensors are fp32 row-major unless stated; indices are int64 (torch.long) as in the reference;
  *   - return value: 0 = ok, < 0 = invalid argument (PSAM_E*), > 0 = hipError_t of the failed launch;
  *     psam_last_error_string() describes the last failure on the calling thread;
- *   - thread-safe for distinct streams / workspaces.
+ *   - thread-safe for distinct streams / workspaces.  The psam_*_force_* / psam_*_set_* hooks are process-wide atomic switches (csrc/knob.h; the table
+ *     of all of them with their environment variables: INTEGRATION.md): any thread may set one while others run calls; a value < 0 hands the switch
+ *     back to its environment variable (read once per process) or its default.
  */
 #ifndef POINTSAM_HIP_H
 #define POINTSAM_HIP_H
@@ -182,7 +184,8 @@ void psam_gemm_f16x3p_force_continuous(int32_t mode);
  * NULL where an entry takes `counters`: the entry runs without the in-kernel fix-up (reduction pass, unsplit attention, two launches). */
 #define PSAM_COUNTER_BYTES 65536
 /* psam_attention_f16x3(_ex) with few workgroups (one cloud, head dim in (64, 128]): up to four workgroups per (query block, head) share the key tiles and
- * the last arrival combines their partial softmax states in split order.  0 = never split, 1 / -1 = the default (environment PSAM_ATTN_KEYSPLIT=0: off). */
+ * the last arrival combines their partial softmax states in split order.  0 = never split, 1 = split wherever it pays (also where the environment
+ * says PSAM_ATTN_KEYSPLIT=0), -1 = the default (environment PSAM_ATTN_KEYSPLIT, else 1). */
 void psam_attention_f16x3_force_keysplit(int32_t mode);
 /* What the calling thread's last psam_attention_f16x3(_ex, _ex2) launched: the channel-layout instance (64: head dim 64; 96: head dims in (64, 96] on the
  * 128-wide layout with 96 active channels; 128: the full 128-channel instance), -1 after a refused call; and the key-split factor actually used
@@ -191,8 +194,8 @@ int32_t psam_attention_f16x3_last_instance(void);
 int32_t psam_attention_f16x3_last_keysplit(void);
 int32_t psam_attention_f32_last_instance(void);
 /* psam_twoway_decoder: 1 = the patch-side projections of a layer run on a side stream forked from (and joined back into) the caller's stream -- also
- * inside a graph capture --, 0 / -1 = everything in sequence on the caller's stream (the default: the fork measured slower, csrc/blocks.hip TwSide;
- * environment PSAM_TWOWAY_FORK=1 switches it on).  Same kernels, same bits. */
+ * inside a graph capture --, 0 = everything in sequence on the caller's stream, -1 = the default (environment PSAM_TWOWAY_FORK, else 0: the fork measured
+ * slower, csrc/blocks.hip TwSide).  Same kernels, same bits. */
 #ifdef PSAM_BUILD_EXPERIMENTS      /* measured-and-rejected paths: built only with PSAM_BUILD_EXPERIMENTS=1 (point_sam_amd/build.py) */
 void psam_twoway_decoder_force_fork(int32_t mode);
 #endif
@@ -498,7 +501,8 @@ size_t psam_twoway_decoder_ws_bytes(int64_t Z, int32_t T, int32_t G, int32_t dim
 int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void* prepared, const float* tokens, float* keys, const float* pos, int32_t rep, int64_t Z,
                             int32_t T, int32_t G, float* queries, void* ws, size_t ws_bytes, int32_t* counters, psam_stream_t stream);
 /* A/B and test hook: 0 = the operator-by-operator launch sequence (what the Python host issues), 1 = the regrouped sequence (fused Linear + LayerNorm
- * launches of the token side, merged projections; csrc/blocks.hip), -1 = default (environment PSAM_TWOWAY_FAST, else 1). */
+ * launches of the token side, merged projections; csrc/blocks.hip) with packed-operand GEMMs on the patch side, 2 = the regrouped sequence with the
+ * exact-fp32 row kernel there, -1 = default (environment PSAM_TWOWAY_FAST, else 2). */
 void psam_twoway_decoder_force_fast(int32_t mode);
 
 /* Token side of one TwoWayAttentionBlock in ONE launch (csrc/twoway.hip): self-attention + norm1, token -> image attention + norm2, the MLP

@@ -42,8 +42,8 @@ struct FlashArgs {
 };
 #ifdef PSAM_ATTN_ABLATE
 #define FA_ABL(bit) (p.abl & (bit))
-static int g_attn_abl = 0;
-PSAM_API void psam_attention_set_ablation(int32_t a) { g_attn_abl = a; }
+static psam_knob k_attn_abl(nullptr, 0);
+PSAM_API void psam_attention_set_ablation(int32_t a) { k_attn_abl.force(a); }
 #else
 #define FA_ABL(bit) false
 #endif
@@ -199,15 +199,15 @@ __global__ __launch_bounds__(256) void flash_attn_f32_kernel(const FlashArgs p) 
 }
 
 // the head dim whose instance the calling thread's last psam_attention_f32 launched (one instance per admitted head dim); -1 after a refused call
-static thread_local int32_t t_fa32_last = -1;
-PSAM_API int32_t psam_attention_f32_last_instance(void) { return t_fa32_last; }
+static thread_local psam_launch_record<> t_fa32;
+PSAM_API int32_t psam_attention_f32_last_instance(void) { return t_fa32.a; }
 
 // q/k/v/o: [B, L, H*hd] views with row strides ld* and batch strides s* (elements); head h lives at columns
 // [h*hd, (h+1)*hd).  Works on the fused qkv buffer of a ViT block (ldq = ldk = ldv = 3*D).
 PSAM_API int32_t psam_attention_f32(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v, int64_t ldv,
                                     int64_t sv, float* o, int64_t ldo, int64_t so, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
                                     float scale, hipStream_t stream) {
-    t_fa32_last = -1;
+    t_fa32.reset();
     PSAM_REQUIRE(q && k && v && o, PSAM_EINVAL, "psam_attention_f32: null pointer");
     PSAM_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, PSAM_EINVAL, "psam_attention_f32: bad shape");
     PSAM_REQUIRE(B <= 65535 && H <= 65535, PSAM_EINVAL, "psam_attention_f32: B/H too large");
@@ -237,9 +237,7 @@ PSAM_API int32_t psam_attention_f32(const float* q, int64_t ldq, int64_t sq, con
             return PSAM_EINVAL;
     }
 #undef FA_LAUNCH
-    const int32_t rc = psam_launch_status("psam_attention_f32: launch failed");
-    if (rc == PSAM_OK) t_fa32_last = hd;
-    return rc;
+    return t_fa32.done("psam_attention_f32: launch failed", hd);
 }
 
 // ================================================================================================================
@@ -636,33 +634,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
 // (query block, head) count in through the caller's arrival-counter block (PSAM_COUNTER_BYTES, include/pointsam_hip.h: words PSAM_CNT_ATTN ..); the
 // library allocates nothing and keeps no per-stream state.  PSAM_ATTN_KEYSPLIT=0 / psam_attention_f16x3_force_keysplit(0) switch the split off.
 constexpr int64_t FA_SK_MAX_UNITS = PSAM_CNT_ATTN_N;
-static int g_fa_keysplit = -1;
-static bool fa_keysplit_enabled() {
-    if (g_fa_keysplit >= 0) return g_fa_keysplit != 0;
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PSAM_ATTN_KEYSPLIT"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0;
-}
-PSAM_API void psam_attention_f16x3_force_keysplit(int32_t mode) { g_fa_keysplit = mode; }
+static psam_knob k_fa_keysplit("PSAM_ATTN_KEYSPLIT", 1);
+PSAM_API void psam_attention_f16x3_force_keysplit(int32_t mode) { k_fa_keysplit.force(mode); }
 // what the calling thread's last psam_attention_f16x3(_ex, _ex2) launched: the channel-layout instance (64 = <64>, 96 = <128, 96>, 128 = <128>; -1 after a
 // refused call) and the key-split factor actually used (1 = unsplit; 0 after a refused call)
-static thread_local int32_t t_fa_last_inst = -1, t_fa_last_ks = 0;
-PSAM_API int32_t psam_attention_f16x3_last_instance(void) { return t_fa_last_inst; }
-PSAM_API int32_t psam_attention_f16x3_last_keysplit(void) { return t_fa_last_ks; }
+static thread_local psam_launch_record<0> t_fa;
+PSAM_API int32_t psam_attention_f16x3_last_instance(void) { return t_fa.a; }
+PSAM_API int32_t psam_attention_f16x3_last_keysplit(void) { return t_fa.b; }
 // A/B hook: PSAM_ATTN_FULL_WIDTH=1 runs head dims in (64, 96] on the full 128-channel instance (the round-5 kernel; same bits)
-static bool fa_full_width() {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PSAM_ATTN_FULL_WIDTH"); on = e ? (atoi(e) != 0) : 0; }
-    return on != 0;
-}
+static psam_knob k_fa_full_width("PSAM_ATTN_FULL_WIDTH", 0);
 // the split factor the launch would use, given unlimited scratch (0 / 1: unsplit)
 static int fa_keysplit_factor(int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd, int32_t max_keysplit) {
     if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || hd <= 64) return 1;      // (head dim 64 at this size runs on the packed-operand kernel)
     const int64_t units = (int64_t)psam_cdiv(Lq, FA_BQ) * H * B;
-    int dev = 0, ncu = 256;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
     const int ntiles = (int)psam_cdiv(Lk, FA_BKV);
-    int ks = fa_keysplit_enabled() ? (int)(ncu / units) : 1;
+    int ks = k_fa_keysplit.get() != 0 ? (int)(psam_cu_count() / units) : 1;
     if (ks > 4) ks = 4;
     if (ks > max_keysplit) ks = max_keysplit;
     if (ks > ntiles / 2) ks = ntiles / 2;
@@ -680,7 +666,7 @@ PSAM_API int32_t psam_attention_f16x3_ex2(const float* q, int64_t ldq, int64_t s
                                           int64_t sv, float* o, int64_t ldo, int64_t so, int32_t B, int32_t H, int32_t Lq, int32_t Lk, int32_t hd,
                                           float scale, const float* a_scale, float k1, float k2, float* o_scale, int32_t max_keysplit, void* ks_ws,
                                           size_t ks_ws_bytes, int32_t* counters, hipStream_t stream) {
-    t_fa_last_inst = -1; t_fa_last_ks = 0;
+    t_fa.reset();
     PSAM_REQUIRE(q && k && v && o, PSAM_EINVAL, "psam_attention_f16x3: null pointer");
     PSAM_REQUIRE((a_scale == nullptr) == (o_scale == nullptr), PSAM_EINVAL, "psam_attention_f16x3: packed output needs both a_scale and o_scale");
     PSAM_REQUIRE(!o_scale || ((ldo & 7) == 0 && ((uintptr_t)o & 31) == 0 && (so & 7) == 0 && Lq == Lk), PSAM_EINVAL,
@@ -698,7 +684,7 @@ PSAM_API int32_t psam_attention_f16x3_ex2(const float* q, int64_t ldq, int64_t s
     p.scale_log2e = scale * 1.4426950408889634f;
     p.a_scale = a_scale; p.o_scale = o_scale; p.k1 = k1; p.k2 = k2; p.hd = hd;
 #ifdef PSAM_ATTN_ABLATE
-    p.abl = g_attn_abl;
+    p.abl = k_attn_abl.get();
 #endif
     // few workgroups (one cloud: 16 heads x 4 query blocks = 64 on 256 CUs, each walking all key tiles in sequence): split the keys over up to four
     // workgroups per (query block, head); the last arrival combines the partial softmax states in the kernel (no second launch)
@@ -715,15 +701,13 @@ PSAM_API int32_t psam_attention_f16x3_ex2(const float* q, int64_t ldq, int64_t s
     const dim3 grid((unsigned)(units * p.ksplit)), block(256);      // 1-D over (key split, query block, head, batch), see the kernel
     int32_t inst;
     if (hd == 64) { inst = 64; hipLaunchKernelGGL((flash_attn_f16x3_kernel<64>), grid, block, 0, stream, p); }
-    else if (hd > 64 && hd <= 96 && (hd & 7) == 0 && !fa_full_width()) { inst = 96; hipLaunchKernelGGL((flash_attn_f16x3_kernel<128, 96>), grid, block, 0, stream, p); }   // 128-wide layout, 96 active channels (the giant encoder's 88)
+    else if (hd > 64 && hd <= 96 && (hd & 7) == 0 && k_fa_full_width.get() == 0) { inst = 96; hipLaunchKernelGGL((flash_attn_f16x3_kernel<128, 96>), grid, block, 0, stream, p); }   // 128-wide layout, 96 active channels (the giant encoder's 88)
     else if (hd > 64 && hd <= 128 && (hd & 7) == 0) { inst = 128; hipLaunchKernelGGL((flash_attn_f16x3_kernel<128>), grid, block, 0, stream, p); }   // zero-padded to 128
     else {
         psam_set_error("psam_attention_f16x3: head_dim must be 64 or a multiple of 8 in (64, 128]");
         return PSAM_EINVAL;
     }
-    const int32_t rc = psam_launch_status("psam_attention_f16x3: launch failed");
-    if (rc == PSAM_OK) { t_fa_last_inst = inst; t_fa_last_ks = p.ksplit; }
-    return rc;
+    return t_fa.done("psam_attention_f16x3: launch failed", inst, p.ksplit);
 }
 
 PSAM_API int32_t psam_attention_f16x3_ex(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v, int64_t ldv,
@@ -1028,38 +1012,29 @@ __global__ __launch_bounds__(64 * NW, RING == 2 ? 2 : 1) void flash_attn_packed_
     }
 }
 
-static int g_attn_variant = -1;
-static int attn_variant_env() {
-    static int v = -2;
-    if (v == -2) { const char* e = getenv("PSAM_ATTN_VARIANT"); v = e ? atoi(e) : 1; }
-    return v;
-}
+static psam_knob k_attn_variant("PSAM_ATTN_VARIANT", 1);
 // tuning hook: -1 = default (environment PSAM_ATTN_VARIANT, else 1), 0 = one 256-row workgroup per CU on a three-tile ring, 1 = two 128-row
 // workgroups per CU on a two-tile ring, 2 = 256-row workgroups of four waves with two query blocks per wave
 // A variant the build cannot run (anything but 0 and 1; 2 in an experiments build) is REFUSED by psam_attention_packed -- forced by the hook or named by
 // the environment --, like a forced GEMM configuration: it runs as forced or not at all.  What a variant does NOT decide: L <= 128 (one query block) always
 // runs the eight-wave kernel, and a forced workgroup shape (below) names the kernel and wins over the variant.
-PSAM_API void psam_attention_packed_force_variant(int32_t v) { g_attn_variant = v; }
+PSAM_API void psam_attention_packed_force_variant(int32_t v) { k_attn_variant.force(v); }
 // test / tuning hook, the process-level twin of the environment's PSAM_ATTN_PACKED_NW (read once): -1 = default (the environment, else 0), 0 = by shape and
 // CU count, 4 / 8 = the four- / eight-wave kernel on the three-tile ring whatever the shape; any other value is refused by psam_attention_packed
-static int g_attn_force_nw = -1;
-PSAM_API void psam_attention_packed_force_nw(int32_t nw) { g_attn_force_nw = nw; }
+static psam_knob k_attn_nw("PSAM_ATTN_PACKED_NW", 0);
+PSAM_API void psam_attention_packed_force_nw(int32_t nw) { k_attn_nw.force(nw); }
 // the kernel instance the calling thread's last psam_attention_packed launched, as NW * 100 + RING * 10 + QB (831 = <8>, 431 = <4>, 421 = <4, 2>,
 // 432 = <4, 3, 2>); -1 after a refused call
-static thread_local int32_t t_pa_last = -1;
-PSAM_API int32_t psam_attention_packed_last_instance(void) { return t_pa_last; }
-static int32_t pa_launched(int32_t inst) {
-    const int32_t rc = psam_launch_status("psam_attention_packed: launch failed");
-    if (rc == PSAM_OK) t_pa_last = inst;
-    return rc;
-}
+static thread_local psam_launch_record<> t_pa;
+PSAM_API int32_t psam_attention_packed_last_instance(void) { return t_pa.a; }
+static int32_t pa_launched(int32_t inst) { return t_pa.done("psam_attention_packed: launch failed", inst); }
 
 // qkv: g8-packed rows [B * L, ld] (containers of 4 bytes: q | k | v column blocks of D = H * 64 each, one scale for all rows in
 // sc[...]); o [B * L, ldo]: g8-packed attention output for the projection GEMM, o_scale [B * L] its (constant) row scales
 // f16_row_scale(v_bound), v_bound >= max |v| (an a-priori bound; attention outputs are convex combinations of V rows).
 PSAM_API int32_t psam_attention_packed(const void* qkv, int64_t ld, const float* sc, float* o, int64_t ldo, float* o_scale, int32_t B, int32_t H,
                                        int32_t L, int32_t hd, float scale, float v_bound, hipStream_t stream) {
-    t_pa_last = -1;
+    t_pa.reset();
     PSAM_REQUIRE(qkv && sc && o && o_scale, PSAM_EINVAL, "psam_attention_packed: null pointer");
     PSAM_REQUIRE(B > 0 && H > 0 && L > 0 && hd == 64, PSAM_EINVAL, "psam_attention_packed: bad shape (head_dim 64)");
     PSAM_REQUIRE(ld >= 3 * (int64_t)H * hd && (ld & 7) == 0 && (ldo & 7) == 0 && ldo >= (int64_t)H * hd && (((uintptr_t)qkv | (uintptr_t)o) & 31) == 0, PSAM_EALIGN,
@@ -1070,37 +1045,28 @@ PSAM_API int32_t psam_attention_packed(const void* qkv, int64_t ld, const float*
     p.qkv = (const unsigned char*)qkv; p.sc = sc; p.o = o; p.o_scale = o_scale; p.ld = ld; p.ldo = ldo; p.H = H; p.L = L; p.B = B; p.D = H * hd;
     p.scale_log2e = scale * 1.4426950408889634f; p.v_bound = v_bound;
 #ifdef PSAM_ATTN_ABLATE
-    p.abl = g_attn_abl;
+    p.abl = k_attn_abl.get();
 #endif
     constexpr int lds = 3 * 2 * PA_TILE;        // 96 KiB
-    static unsigned long long attr_done = 0;      // > 64 KiB of dynamic LDS: opt in per device (both instances at once)
-    int dev = 0, ncu = 256;
+    static unsigned long long attr_done[4] = {0, 0, 0, 0};      // > 64 KiB of dynamic LDS: opt in per device, every instance before the first launch
+    int dev = 0;
     PSAM_REQUIRE(hipGetDevice(&dev) == hipSuccess, PSAM_EINVAL, "psam_attention_packed: no device");
-    {
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(__atomic_load_n(&attr_done, __ATOMIC_ACQUIRE) & bit)) {
-            PSAM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_packed_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
-                         hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_packed_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess &&
-                         hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_packed_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * PA_TILE) == hipSuccess
+    PSAM_REQUIRE(psam_reserve_lds(&flash_attn_packed_kernel<8>, lds, attr_done[0]) && psam_reserve_lds(&flash_attn_packed_kernel<4>, lds, attr_done[1]) &&
+                 psam_reserve_lds(&flash_attn_packed_kernel<4, 2>, 2 * 2 * PA_TILE, attr_done[2])
 #ifdef PSAM_BUILD_EXPERIMENTS
-                         && hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_attn_packed_kernel<4, 3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) == hipSuccess
+                 && psam_reserve_lds(&flash_attn_packed_kernel<4, 3, 2>, lds, attr_done[3])
 #endif
-                         ,
-                         PSAM_EINVAL, "psam_attention_packed: cannot reserve LDS");
-            __atomic_fetch_or(&attr_done, bit, __ATOMIC_RELEASE);
-        }
-    }
-    static int env_nw = -1;      // tuning hook (environment, read once): PSAM_ATTN_PACKED_NW = 4 | 8
-    if (env_nw < 0) { const char* e = getenv("PSAM_ATTN_PACKED_NW"); env_nw = e ? atoi(e) : 0; }
-    const int force_nw = g_attn_force_nw >= 0 ? g_attn_force_nw : env_nw;
+                 ,
+                 PSAM_EINVAL, "psam_attention_packed: cannot reserve LDS");
+    const int force_nw = k_attn_nw.get();
     PSAM_REQUIRE(force_nw == 0 || force_nw == 4 || force_nw == 8, PSAM_EINVAL, "psam_attention_packed: forced workgroup shape must be 4 or 8 waves");
-    if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+    const int ncu = psam_cu_count();
     // 256-row workgroups (two waves per SIMD cover each other's softmax gaps) unless they would leave CUs without work: one cloud of 2048 tokens
     // and 16 heads is 128 of them on 256 CUs (99 us); 128-row workgroups fill the chip
     const int64_t wg8 = (int64_t)psam_cdiv(L, PA_BQ) * H * B;
     const bool small = force_nw ? force_nw == 4 : (wg8 < ncu && L > PA_BQ / 2);
     // two 128-row workgroups per CU on a two-tile ring where the 256-row grid is about one workgroup per CU (B = 8 clouds x 16 heads x 512 tokens: 256)
-    const int variant = g_attn_variant >= 0 ? g_attn_variant : attn_variant_env();
+    const int variant = k_attn_variant.get();
 #ifdef PSAM_BUILD_EXPERIMENTS
     PSAM_REQUIRE(variant >= 0 && variant <= 2, PSAM_EINVAL, "psam_attention_packed: unknown variant (0, 1 or 2)");
 #else

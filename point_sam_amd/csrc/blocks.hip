@@ -93,8 +93,8 @@ psam_skinny_jobs_t skinny_jobs(std::initializer_list<Job> js) {
 // The choice is made from the rows of ONE cloud (its G patch tokens), never from the batch: a cloud's results must not depend on how many clouds share
 // the launch (bit-exact batch independence, tests/test_gpu_e2e.py::test_batch_independence_across_the_row_kernel_threshold).
 bool rows_multi_fits(int64_t rows_per_cloud, int K) {
-    static const bool enabled = psam_env_int("PSAM_ROWS_MULTI", 1) != 0;
-    return enabled && rows_per_cloud <= 2048 && (K & 15) == 0;
+    static psam_knob k_rows_multi("PSAM_ROWS_MULTI", 1);
+    return k_rows_multi.get() != 0 && rows_per_cloud <= 2048 && (K & 15) == 0;
 }
 
 // The host's choice of kernel for one Linear (point_sam_amd/ops.py linear).  cloud_rows > 0: the M rows are the patch tokens of whole clouds, cloud_rows
@@ -718,23 +718,15 @@ TwWs tw_ws(Carve& cv, int64_t Z, int T, int G, int dim, int mlp) {
 // six short launches they take off the critical path -- eager two-way stage 0.43 -> 0.43 ms (no gain), and inside captured graphs every fork / join
 // splits the graph into segments: cfg #2 792 -> 704 clouds/s, cfg #5 131 -> 94 sessions/s, a replayed click 0.61 -> 1.27 ms (profiles/r04/r04_twoway_fork.txt).
 struct TwSide { hipStream_t side; hipEvent_t fork, join1, join2; };
-int g_tw_fork = -1;
-bool tw_fork_enabled() {
-#ifndef PSAM_BUILD_EXPERIMENTS
-    return false;      // the forked form lost (profiles/r04/r04_twoway_fork.txt): reachable in experiments builds only
-#endif
-    if (g_tw_fork >= 0) return g_tw_fork != 0;
-    static const bool on = psam_env_int("PSAM_TWOWAY_FORK", 0) != 0;
-    return on;
-}
+psam_knob k_tw_fork("PSAM_TWOWAY_FORK", 0);      // read by experiments builds only
 const TwSide* tw_side(hipStream_t stream) {
 #ifndef PSAM_BUILD_EXPERIMENTS
     (void)stream;
-    return nullptr;      // the default build creates no streams or events and keeps no per-stream state
+    return nullptr;      // the forked form lost (profiles/r04/r04_twoway_fork.txt): the default build creates no streams or events and keeps no per-stream state
 #else
     static std::mutex mu;
     static std::map<std::pair<int, hipStream_t>, TwSide> table;
-    if (!tw_fork_enabled()) return nullptr;
+    if (k_tw_fork.get() == 0) return nullptr;
     int dev = 0;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipGetDevice(&dev) != hipSuccess || hipStreamIsCapturing(stream, &cs) != hipSuccess) return nullptr;
@@ -752,18 +744,13 @@ const TwSide* tw_side(hipStream_t stream) {
 
 // The launch sequence of psam_twoway_decoder: 0 the operator-by-operator sequence, 1 regrouped with packed-operand GEMMs on the patch side, 2 (default)
 // regrouped with the exact-fp32 row kernel there.  psam_twoway_decoder_force_fast: -1 = environment PSAM_TWOWAY_FAST, otherwise the mode.
-int g_tw_fast = -1;
-int tw_fast_mode() {
-    if (g_tw_fast >= 0) return g_tw_fast;
-    static const int mode = psam_env_int("PSAM_TWOWAY_FAST", 2);
-    return mode;
-}
+psam_knob k_tw_fast("PSAM_TWOWAY_FAST", 2);
 }  // namespace
 
 #ifdef PSAM_BUILD_EXPERIMENTS
-PSAM_API void psam_twoway_decoder_force_fork(int32_t mode) { g_tw_fork = mode; }
+PSAM_API void psam_twoway_decoder_force_fork(int32_t mode) { k_tw_fork.force(mode); }
 #endif
-PSAM_API void psam_twoway_decoder_force_fast(int32_t mode) { g_tw_fast = mode; }
+PSAM_API void psam_twoway_decoder_force_fast(int32_t mode) { k_tw_fast.force(mode); }
 
 PSAM_API size_t psam_twoway_decoder_prepared_bytes(int32_t depth, int32_t dim, int32_t mlp, int32_t downsample) {
     if (depth <= 0 || depth > PSAM_TWOWAY_MAX_DEPTH || dim <= 0 || mlp <= 0 || downsample <= 0) return 0;
@@ -860,6 +847,7 @@ PSAM_API int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void*
 #define TWCK(call) do { rc = (call); if (rc) return rc; } while (0)
 #define TWHIP(call) do { if ((call) != hipSuccess) { psam_set_error("psam_twoway_decoder: stream fork / join failed"); return PSAM_EINVAL; } } while (0)
     const TwSide* sd = tok_fast ? tw_side(stream) : nullptr;      // patch-side projections on a forked side stream (see TwSide)
+    const int tw_fast = k_tw_fast.get();
     // ---- Round 5: the short sequence (36 launches for depth 2 against 50; profiles/r05/r05_click_kernels_*.txt).  Same operators, regrouped along their
     // data dependences:
     //  * every `queries = norm(queries + Linear(..))` of the token side is ONE launch (psam_linear_skinny_ln: the last workgroup of the Linear
@@ -869,13 +857,13 @@ PSAM_API int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void*
     //  * patch side: keys + key_pe and keys are packed in one pass (psam_scale_pack_rows_g8_add_dual), the k projection of tokens -> patches and the
     //    q projection of patches -> tokens are one GEMM on the concatenated weight (both read keys + key_pe).
     // Needs the caller's arrival-counter block (`counters`) and embedding_dim 256.
-    const bool fast = tok_fast && !sd && tw_fast_mode() != 0 && E == 256 && IX >= 128 && 2 * IX <= E && IX <= 512 && I >= 256 && (mlp & 15) == 0 && (IX & 15) == 0 &&
+    const bool fast = tok_fast && !sd && tw_fast != 0 && E == 256 && IX >= 128 && 2 * IX <= E && IX <= 512 && I >= 256 && (mlp & 15) == 0 && (IX & 15) == 0 &&
                       plan->o_cat_packed[0] != 0 && counters != nullptr;
     if (fast) {
         auto lin_ln = [&](const Lin& l, const float* x, const float* res, const float* nw, const float* nb) -> int32_t {
             return psam_linear_skinny_ln(x, l.K, l.w, l.K, l.b, res, E, nw, nb, W.eps, b.lntmp, queries, E, (int32_t)R, E, l.K, counters, stream);
         };
-        const bool small_rows = tw_fast_mode() >= 2 && rows_multi_fits(G, E);
+        const bool small_rows = tw_fast >= 2 && rows_multi_fits(G, E);
         // Linears on the I patch rows (`keys`, key_pe added on load where xadd = pos) as one launch of the exact-fp32 row kernel
         auto rows_multi = [&](std::initializer_list<Job> js) -> int32_t {
             const psam_skinny_jobs_t jobs = skinny_jobs(js);

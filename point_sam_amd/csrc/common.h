@@ -15,8 +15,8 @@
 // compile error (C linkage cannot be overloaded), and the structs that cross the ABI exist once.
 #pragma GCC visibility push(default)
 #include "../../include/pointsam_hip.h"
-#include <cstdlib>
 #pragma GCC visibility pop
+#include "knob.h"
 
 void psam_set_error(const char* msg);
 
@@ -36,6 +36,44 @@ static inline int32_t psam_launch_status(const char* what) {
         return (int32_t)e;
     }
     return PSAM_OK;
+}
+
+// What the calling thread's last call of an entry point launched, for its psam_*_last_* queries: one or two numbers (-1, or B0 for the second, before the
+// first launch and after a refused call).  One `static thread_local` record per entry point; host-side bookkeeping only.
+template <int32_t B0 = -1>
+struct psam_launch_record {
+    int32_t a = -1, b = B0;
+    void reset() { a = -1; b = B0; }
+    // rc: the status of the launch just issued; the numbers are stored only where it succeeded
+    int32_t set(int32_t rc, int32_t a_, int32_t b_ = B0) {
+        if (rc == PSAM_OK) { a = a_; b = b_; }
+        return rc;
+    }
+    int32_t done(const char* what, int32_t a_, int32_t b_ = B0) { return set(psam_launch_status(what), a_, b_); }
+};
+
+// CUs of the current device; 256 (MI355X) where there is none to ask (host-side planning without a GPU).  Asked once per process and translation unit: every
+// caller sees the cached count (the devices of one machine are of one type).
+static inline int psam_cu_count() {
+    static const int cached = [] {
+        int ncu = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+        return ncu;
+    }();
+    return cached;
+}
+
+// > 64 KiB of dynamic LDS must be opted into per kernel AND per device (the attribute lives with the device's code object).  done_mask: the caller's
+// `static unsigned long long` (zero at first), one bit per device that has the attribute.  False: no device, or the attribute was refused.
+template <typename K>
+static inline bool psam_reserve_lds(K kernel, int lds, unsigned long long& done_mask) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (__atomic_load_n(&done_mask, __ATOMIC_ACQUIRE) & bit) return true;
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
+    __atomic_fetch_or(&done_mask, bit, __ATOMIC_RELEASE);
+    return true;
 }
 
 static inline int64_t psam_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
@@ -129,25 +167,13 @@ __device__ __forceinline__ float dist2_exact(float ax, float ay, float az, float
     return s;
 }
 
-// An environment switch: its value (atoi / atof), dflt when it is unset.  Read once per process and thread-safely as the initialiser of a function-local
-// static: `static const int x = psam_env_int("NAME", dflt);`.
-static inline int psam_env_int(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-static inline double psam_env_double(const char* name, double dflt) {
-    const char* e = getenv(name);
-    return e ? atof(e) : dflt;
-}
-
-// Experiments builds only: PSAM_ABLATE_REPEAT (bit mask, environment, read once) makes an idempotent kernel launch TWICE -- the throughput lost to the second
+// Experiments builds only: PSAM_ABLATE_REPEAT (bit mask, environment) makes an idempotent kernel launch TWICE -- the throughput lost to the second
 // launch is the kernel's exposed time in the pipeline (profiles/r06/r06_refill.txt): 1 = psam_attention_packed, 2 = psam_layernorm (out of place),
 // 4 = psam_ln_stats_finalize.
 static inline int psam_ablate_repeat() {
 #ifdef PSAM_BUILD_EXPERIMENTS
-    static int m = -1;
-    if (m < 0) { const char* e = getenv("PSAM_ABLATE_REPEAT"); m = e ? atoi(e) : 0; }
-    return m;
+    static psam_knob k_ablate_repeat("PSAM_ABLATE_REPEAT", 0);
+    return k_ablate_repeat.get();
 #else
     return 0;
 #endif

@@ -273,7 +273,7 @@ static int32_t launch_c(const F16CArgs& a, int grid, hipStream_t stream) {
     if (!TIMING && a.g.dbg) return launch_c<F, true>(a, grid, stream);      // a timing buffer is set: the stamped instance
 #endif
     static unsigned long long attr_done = 0;
-    if (!f16x3p_reserve_lds(&gemm_f16x3c_kernel<F, TIMING>, CK_LDS, attr_done)) {
+    if (!psam_reserve_lds(&gemm_f16x3c_kernel<F, TIMING>, CK_LDS, attr_done)) {
         psam_set_error("psam_gemm_f16x3p: cannot reserve LDS");
         return PSAM_EINVAL;
     }
@@ -303,11 +303,7 @@ bool launch_f16x3c(F16PArgs& p, hipStream_t stream, int32_t& rc, int wgs_per_cu)
     const bool vec_ok = ((p.ldc & 3) == 0) && (((uintptr_t)p.C & 15) == 0) && (!p.residual || (((p.ldr & 3) == 0) && (((uintptr_t)p.residual & 15) == 0))) &&
                         (!p.bias || (((uintptr_t)p.bias & 15) == 0)) && ((((uintptr_t)p.scaleW | (uintptr_t)p.ln_c) & 15) == 0);
     if (!vec_ok) return false;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
+    const int ncu = psam_cu_count();
     F16CArgs a;
     p.tiles_m = p.M / CK_BM; p.tiles_n = p.N / CK_BN;
     p.panel = f16x3p_panel(p.tiles_m, p.tiles_n, CK_BM, CK_BN, p.K);
@@ -334,7 +330,7 @@ bool launch_f16x3c(F16PArgs& p, hipStream_t stream, int32_t& rc, int wgs_per_cu)
     return true;
 }
 
-// After a failed launch: re-zero the stream's queue words (psam_gemm_f16x3p_reset_splitk_state calls this too).
+// After a failed launch: re-zero the stream's queue words.
 void f16x3c_reset_state(hipStream_t stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return;

@@ -156,7 +156,7 @@ static int32_t launch_q(F16PArgs& p, hipStream_t stream) {
     p.tiles_n = (int)psam_cdiv(p.N, BN);
     p.panel = f16x3p_panel(p.tiles_m, p.tiles_n, BM, BN, p.K);
     static unsigned long long attr_done = 0;
-    if (!f16x3p_reserve_lds(&gemm_f16x3q_kernel<WM, WN, TM, TN, S>, lds, attr_done)) {
+    if (!psam_reserve_lds(&gemm_f16x3q_kernel<WM, WN, TM, TN, S>, lds, attr_done)) {
         psam_set_error("psam_gemm_f16x3p: cannot reserve LDS");
         return PSAM_EINVAL;
     }

@@ -332,7 +332,7 @@ static int32_t launch_s(const F16SArgs& a, int grid, hipStream_t stream) {
     if (!TIMING && a.g.dbg) return launch_s<F, true>(a, grid, stream);      // a timing buffer is set (psam_gemm_f16x3p_set_timing_buffer): the stamped instance
 #endif
     static unsigned long long attr_done = 0;
-    if (!f16x3p_reserve_lds(&gemm_f16x3s_kernel<F, TIMING>, SK_LDS, attr_done)) {
+    if (!psam_reserve_lds(&gemm_f16x3s_kernel<F, TIMING>, SK_LDS, attr_done)) {
         psam_set_error("psam_gemm_f16x3p: cannot reserve LDS");
         return PSAM_EINVAL;
     }
@@ -365,11 +365,7 @@ bool launch_f16x3s(F16PArgs& p, hipStream_t stream, int32_t& rc, int mode) {
     const bool vec_ok = ((p.ldc & 3) == 0) && (((uintptr_t)p.C & 15) == 0) && (!p.residual || (((p.ldr & 3) == 0) && (((uintptr_t)p.residual & 15) == 0))) &&
                         (!p.bias || (((uintptr_t)p.bias & 15) == 0)) && ((((uintptr_t)p.scaleW | (uintptr_t)p.ln_c) & 15) == 0);
     if (!vec_ok) return false;
-    static int ncu = 0;
-    if (!ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    }
+    const int ncu = psam_cu_count();
     F16SArgs a;
     p.tiles_m = p.M / SK_BM; p.tiles_n = p.N / SK_BN;
     p.panel = f16x3p_panel(p.tiles_m, p.tiles_n, SK_BM, SK_BN, p.K);
@@ -377,8 +373,8 @@ bool launch_f16x3s(F16PArgs& p, hipStream_t stream, int32_t& rc, int mode) {
     a.nslabs = p.K / 32;
     if (tiles > SK_MAX_TILES_S || tiles * a.nslabs >= ((int64_t)1 << 30)) return false;
     a.units = (int)(tiles * a.nslabs);
-    static int reserve = -1;
-    if (reserve < 0) { const char* e = getenv("PSAM_GEMM_RESERVE_CUS"); reserve = e ? atoi(e) : 8; }
+    static psam_knob k_reserve("PSAM_GEMM_RESERVE_CUS", 8);
+    const int reserve = k_reserve.get();
     const int cus = (mode == 0 && ncu > 2 * reserve) ? ncu - reserve : ncu;
     int grid = mode == 2 ? cus : 2 * cus;
     if ((int64_t)grid * 16 > a.units) grid = a.units / 16;      // at least 16 slabs per workgroup
@@ -406,10 +402,9 @@ bool launch_f16x3s(F16PArgs& p, hipStream_t stream, int32_t& rc, int mode) {
     return true;
 }
 
-// After a failed launch: re-zero the stream's arrival counters (see psam_gemm_f16x3p_reset_splitk_state, which calls this too).
+// After a failed launch: re-zero the stream's arrival counters.
 void f16x3s_reset_state(hipStream_t stream) {
-    int ncu = 256, dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int ncu = psam_cu_count();
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return;
     const SkBlock blk = sk_block(stream, 2 * ncu);

@@ -269,8 +269,8 @@ PSAM_API int32_t psam_twoway_tokens(const psam_twoway_tokens_t* args, hipStream_
     d.wq = a.ws; d.wk = d.wq + 64 * TW_E; d.wv = d.wk + 64 * TW_E; d.wa = d.wv + 64 * TW_E; d.wy = d.wa + 64 * TW_E; d.wm = d.wy + 64 * TW_E;
     d.bar = reinterpret_cast<unsigned*>(a.ws + psam_twoway_tokens_ws_floats(a.mode == 0 ? a.mlp : 0) - 64);
     if (hipMemsetAsync(d.bar, 0, 64 * sizeof(float), stream) != hipSuccess) { psam_set_error("psam_twoway_tokens: cannot reset the barrier counter"); return PSAM_EINVAL; }
-    static int nwg = 0;      // team size (tuning hook, environment, read once): 16 | 32 | 64 workgroups
-    if (!nwg) { const char* e = getenv("PSAM_TW_NWG"); nwg = e ? atoi(e) : 64; if (nwg != 16 && nwg != 32) nwg = 64; }
+    static psam_knob k_nwg("PSAM_TW_NWG", 64);      // team size (tuning hook, environment): 16 | 32 workgroups, anything else 64
+    const int nwg = k_nwg.get();
     if (nwg == 16) hipLaunchKernelGGL(twoway_tokens_kernel<16>, dim3(8 * 16), dim3(256), lds, stream, d);
     else if (nwg == 32) hipLaunchKernelGGL(twoway_tokens_kernel<32>, dim3(8 * 32), dim3(256), lds, stream, d);
     else hipLaunchKernelGGL(twoway_tokens_kernel<64>, dim3(8 * 64), dim3(256), lds, stream, d);

@@ -176,8 +176,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const GemmArgs p) {
     gemm_store_tile<TM, TN>(p, acc, smem + wave * gemm_epilogue_lds_floats_per_wave<TN>(), m0 + wm * TM * 32, n0 + wn * TN * 32, lane, C, R);
 }
 
-static int g_force_cfg = -1;  // test/bench hook: 0=128x128, 1=128x64, 2=64x64, -1=auto
-PSAM_API void psam_gemm_force_config(int32_t cfg) { g_force_cfg = cfg; }
+static psam_knob k_gemm_cfg(nullptr, -1);  // test/bench hook: 0=128x128, 1=128x64, 2=64x64, -1=auto
+PSAM_API void psam_gemm_force_config(int32_t cfg) { k_gemm_cfg.force(cfg); }
 
 // Fully general entry point (strided-batched, two-level batch index z = z1*batch2 + z2).
 PSAM_API int32_t psam_gemm_f32(const float* A, int64_t lda, int64_t sA1, int64_t sA2, const float* W, int64_t ldw, int64_t sW1,
@@ -201,7 +201,8 @@ PSAM_API int32_t psam_gemm_f32(const float* A, int64_t lda, int64_t sA1, int64_t
     p.sA1 = sA1; p.sA2 = sA2; p.sW1 = sW1; p.sW2 = sW2; p.sC1 = sC1; p.sC2 = sC2; p.sR1 = sR1; p.sR2 = sR2;
     p.M = M; p.N = N; p.K = K; p.batch2 = batch2; p.rowgroup = rowgroup > 0 ? rowgroup : 1; p.act = act; p.alpha = alpha;
     const int64_t batch = (int64_t)batch1 * batch2;
-    int cfg = g_force_cfg;
+    const int forced_cfg = k_gemm_cfg.get();
+    int cfg = forced_cfg;
     if (cfg < 0) {
         // Measured on MI355X (scripts/gemm_bench.py): with f32 MFMA the matrix pipe is slow enough that the extra
         // operand traffic of small tiles is free, while more resident waves (3 WG/CU at 128x64, 5 at 64x64) and finer
@@ -212,7 +213,7 @@ PSAM_API int32_t psam_gemm_f32(const float* A, int64_t lda, int64_t sA1, int64_t
     if (act == 3) {
         PSAM_REQUIRE((N & 63) == 0 && !residual && !rowbias, PSAM_EINVAL, "psam_gemm_f32: SwiGLU epilogue needs N % 64 == 0, no residual/rowbias");
         if (cfg == 2) {   // needs paired accumulator tiles (TN even): the automatic choice moves to 128x64, a forced 64x64 is refused
-            PSAM_REQUIRE(g_force_cfg < 0, PSAM_EINVAL, "psam_gemm_f32: the forced 64x64 configuration cannot apply the SwiGLU epilogue");
+            PSAM_REQUIRE(forced_cfg < 0, PSAM_EINVAL, "psam_gemm_f32: the forced 64x64 configuration cannot apply the SwiGLU epilogue");
             cfg = 1;
         }
     }

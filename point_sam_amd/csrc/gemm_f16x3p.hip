@@ -515,26 +515,18 @@ PSAM_API int32_t psam_scale_pack_rows_g8_add_dual(const float* X, int64_t ldx, c
 }
 
 // ---------------------------------------------------------------------------------------------- host
-static int g_f16x3p_cfg = -1;
-PSAM_API void psam_gemm_f16x3p_force_config(int32_t cfg) { g_f16x3p_cfg = cfg; }
+static psam_knob k_f16x3p_cfg(nullptr, -1);      // -1 = by shape (f16x3p_pick)
+PSAM_API void psam_gemm_f16x3p_force_config(int32_t cfg) { k_f16x3p_cfg.force(cfg); }
 // Test hook: the configuration index (ping-pong: 50 ..) and split-K factor of the calling thread's last psam_gemm_f16x3p(_ex) launch; -1 / 0 when it was refused.
-static thread_local int32_t t_f16x3p_last_cfg = -1, t_f16x3p_last_splitk = 0;
-PSAM_API int32_t psam_gemm_f16x3p_last_config(void) { return t_f16x3p_last_cfg; }
-PSAM_API int32_t psam_gemm_f16x3p_last_splitk(void) { return t_f16x3p_last_splitk; }
-static int32_t f16x3p_ran(int32_t rc, int cfg, int ksplit) {
-    if (rc == PSAM_OK) { t_f16x3p_last_cfg = cfg; t_f16x3p_last_splitk = ksplit; }
-    return rc;
-}
+static thread_local psam_launch_record<0> t_f16x3p;
+PSAM_API int32_t psam_gemm_f16x3p_last_config(void) { return t_f16x3p.a; }
+PSAM_API int32_t psam_gemm_f16x3p_last_splitk(void) { return t_f16x3p.b; }
+static int32_t f16x3p_ran(int32_t rc, int cfg, int ksplit) { return t_f16x3p.set(rc, cfg, ksplit); }
 #ifdef PSAM_BUILD_EXPERIMENTS
 // Persistent form of the 128x128 register-epilogue configuration (gemm_f16x3c.hip: whole tiles from a queue, one continuous slab stream per workgroup)
 // for batch-sized launches: -1 = default (environment PSAM_GEMM_CONTINUOUS, else OFF: measured neutral), 0 = never, 1 = wherever it applies.
-static int g_f16x3p_continuous = -1;
-PSAM_API void psam_gemm_f16x3p_force_continuous(int32_t mode) { g_f16x3p_continuous = mode; }
-static bool f16x3p_continuous_enabled() {
-    if (g_f16x3p_continuous >= 0) return g_f16x3p_continuous != 0;
-    static const int on = psam_env_int("PSAM_GEMM_CONTINUOUS", 0);
-    return on != 0;
-}
+static psam_knob k_f16x3p_continuous("PSAM_GEMM_CONTINUOUS", 0);
+PSAM_API void psam_gemm_f16x3p_force_continuous(int32_t mode) { k_f16x3p_continuous.force(mode); }
 #endif
 #ifdef PSAM_GEMM_ABLATE
 static unsigned* g_f16x3p_dbg = nullptr;      // measurement builds: 16 words per wave of the timing instances (ABL & 64)
@@ -542,12 +534,8 @@ extern "C" __attribute__((visibility("default"))) void psam_gemm_f16x3p_set_timi
 #endif
 // Epilogue of the packed-operand GEMMs: 1 = the register-only epilogue on transposed accumulator tiles (gemm_epilogue_t.h) wherever the launch's
 // options allow it, 0 = always the LDS-transposition epilogue (gemm_epilogue.h), -1 = the default (environment PSAM_GEMM_TR, else 1).
-static int g_f16x3p_tr = -1;
-PSAM_API void psam_gemm_f16x3p_force_epilogue(int32_t mode) { g_f16x3p_tr = mode; }
-static int f16x3p_epilogue_mode() {
-    static const int env = psam_env_int("PSAM_GEMM_TR", 1);
-    return g_f16x3p_tr >= 0 ? g_f16x3p_tr : env;
-}
+static psam_knob k_f16x3p_tr("PSAM_GEMM_TR", 1);
+PSAM_API void psam_gemm_f16x3p_force_epilogue(int32_t mode) { k_f16x3p_tr.force(mode); }
 // Whether psam_gemm_f16x3p_ex takes psam_gemm_fuse_t.row_ln_* (Linear -> LayerNorm -> activation in one GEMM) for N output columns: 256 always
 // (full-row wave tiles, LDS epilogue), 512 with the register epilogue (128x512 workgroup tiles).
 // N == 512 is OFF by default (environment PSAM_GEMM_ROWLN512=1 turns it on): measured SLOWER than the two launches it replaces at the benchmark's
@@ -559,16 +547,16 @@ PSAM_API int32_t psam_gemm_f16x3p_fused_row_ln(int32_t N) {
 #ifndef PSAM_BUILD_EXPERIMENTS
     return 0;      // the 128x512 full-row tile is an experiments-build configuration (measured slower, see above)
 #endif
-    static const int on = psam_env_int("PSAM_GEMM_ROWLN512", 0);
-    return N == 512 && on > 0 && f16x3p_epilogue_mode() > 0 ? 1 : 0;
+    static psam_knob k_rowln512("PSAM_GEMM_ROWLN512", 0);
+    return N == 512 && k_rowln512.get() > 0 && k_f16x3p_tr.get() > 0 ? 1 : 0;
 }
 bool f16x3p_use_register_epilogue(const F16PArgs& p) {
-    if (f16x3p_epilogue_mode() <= 0) return false;
+    if (k_f16x3p_tr.get() <= 0) return false;
     if (p.gmax_out || p.row_ln_g || (p.no_store && !p.hyper)) return false;      // options only gemm_epilogue.h implements
     // per-group row bias: implemented, bitwise equal, but only when forced -- its one user (PatchEncoder conv2.0, K = 128, 512 MB of fp32 output)
     // is bound by the stores, and one-row-per-lane 16-byte stores lose against the LDS epilogue's full rows (247 vs 235 us,
     // profiles/r04/r04_gemm_experiments.txt)
-    if (p.rowbias && (g_f16x3p_tr <= 0 || (p.ldrb & 3) != 0 || (((uintptr_t)p.rowbias) & 15) != 0 || p.act == 3)) return false;
+    if (p.rowbias && (k_f16x3p_tr.forced() <= 0 || (p.ldrb & 3) != 0 || (((uintptr_t)p.rowbias) & 15) != 0 || p.act == 3)) return false;
     if (p.hyper && (p.hyper_rows % 32 != 0 || (((uintptr_t)p.hyper) & 15) != 0 || (p.N & 3) != 0)) return false;
     if ((((uintptr_t)p.scaleW | (uintptr_t)p.bias | (uintptr_t)p.ln_c) & 15) != 0) return false;      // float4 loads of the column constants
     return true;
@@ -588,7 +576,7 @@ static int32_t launch_f16x3p(F16PArgs& p, hipStream_t stream) {
     p.tiles_n = (int)psam_cdiv(p.N, BN);
     p.panel = f16x3p_panel(p.tiles_m, p.tiles_n, BM, BN, p.K);
     static unsigned long long attr_done = 0;   // per device (bit = device id)
-    if (!f16x3p_reserve_lds(&gemm_f16x3p_kernel<WM, WN, TM, TN, S, LA, ABL, PF, TR>, lds, attr_done)) {
+    if (!psam_reserve_lds(&gemm_f16x3p_kernel<WM, WN, TM, TN, S, LA, ABL, PF, TR>, lds, attr_done)) {
         psam_set_error("psam_gemm_f16x3p: cannot reserve LDS");
         return PSAM_EINVAL;
     }
@@ -648,11 +636,10 @@ static bool f16x3p_has(int cfg, unsigned caps) {
 // (300 ~ the epilogue of a tile in k-steps; penalty: operand bytes per flop of the smaller tiles, LDS-DMA path ~32 B/clk/CU; share: two
 // resident tiles on a CU each progress at ~60 % of a lone tile's speed).
 static int f16x3p_pick(int M, int N, int K, int act, bool two_wide_only) {
-    static const int ncu = f16x3p_cu_count();
-    // tuning hooks (environment, read once): CUs assumed busy elsewhere; slowdown of two co-resident tiles; penalty of the eight-wave 128x128 tile
-    static const int reserve = psam_env_int("PSAM_GEMM_RESERVE_CUS", 8);
+    // tuning hooks (environment): CUs assumed busy elsewhere; slowdown of two co-resident tiles; penalty of the eight-wave 128x128 tile
+    static psam_knob k_reserve("PSAM_GEMM_RESERVE_CUS", 8), k_small_ring("PSAM_GEMM_SMALL_M_RING", 0), k_sub9("PSAM_GEMM_SUB9", 0);
     static const double share2 = psam_env_double("PSAM_GEMM_SHARE", 1.6), pen9 = psam_env_double("PSAM_GEMM_PEN9", 1.15);
-    static const int small_ring = psam_env_int("PSAM_GEMM_SMALL_M_RING", 0), sub9 = psam_env_int("PSAM_GEMM_SUB9", 0);
+    const int ncu = psam_cu_count(), reserve = k_reserve.get(), small_ring = k_small_ring.get(), sub9 = k_sub9.get();
     const int ncu_eff = ncu > 2 * reserve ? ncu - reserve : ncu;
     struct Cand { int cfg; double pen; };
     // 41 = the eight-wave 128x128 tile on a FIVE-stage ring (exactly 160 KiB), 42 = 128x96 on five stages (140 KiB; single-cloud launches of one round): the same
@@ -697,13 +684,8 @@ PSAM_API int32_t psam_gemm_f16x3p_stat_segs(int32_t N) { return (N / 2 + 31) / 3
 // state and allocates nothing; without a block the launch writes partial planes and a reduction pass adds them.  PSAM_GEMM_SPLITK_FIXUP=0 switches
 // the fix-up off.
 constexpr int64_t SK_MAX_TILES = PSAM_CNT_GEMM_N;
-static int g_f16x3p_sk_fixup = -1;      // -1: PSAM_GEMM_SPLITK_FIXUP (default on); 0 / 1 forced (psam_gemm_f16x3p_force_splitk_fixup)
-static bool f16x3p_splitk_fixup_enabled() {
-    if (g_f16x3p_sk_fixup >= 0) return g_f16x3p_sk_fixup != 0;
-    static const int on = psam_env_int("PSAM_GEMM_SPLITK_FIXUP", 1);
-    return on != 0;
-}
-PSAM_API void psam_gemm_f16x3p_force_splitk_fixup(int32_t mode) { g_f16x3p_sk_fixup = mode; }
+static psam_knob k_f16x3p_sk_fixup("PSAM_GEMM_SPLITK_FIXUP", 1);
+PSAM_API void psam_gemm_f16x3p_force_splitk_fixup(int32_t mode) { k_f16x3p_sk_fixup.force(mode); }
 
 // The configuration a split-K launch runs in place of cfg: cfg where it has a split-K form; for a ping-pong or an F16P_SK_PICK configuration the pick among the
 // two-tile-wide wave tiles; null (refused) for any other.
@@ -719,15 +701,15 @@ static const F16PConfig* f16x3p_splitk_config(int cfg, int M, int N, int K, int 
 // PSAM_GEMM_SPLITK: 0 = never, n > 1 = always n (tuning).  The tiles counted are those of the configuration the split-K launch would run (a forced one
 // that it refuses: no split).
 PSAM_API int32_t psam_gemm_f16x3p_splitk(int32_t M, int32_t N, int32_t K, int32_t act) {
-    static const int forced = psam_env_int("PSAM_GEMM_SPLITK", 1);
-    static const int frac_pct = psam_env_int("PSAM_GEMM_SPLITK_MAX_FILL_PCT", 30);
+    static psam_knob k_splitk("PSAM_GEMM_SPLITK", 1), k_fill_pct("PSAM_GEMM_SPLITK_MAX_FILL_PCT", 30);
+    const int forced = k_splitk.get(), frac_pct = k_fill_pct.get(), forced_cfg = k_f16x3p_cfg.get();
     if (act == 3 || K < 1024 || (K & 31) || forced == 0) return 1;
     if (forced == 1 && M > 2048) return 1;      // a batch of clouds: its other GEMM stream fills the idle CUs, the extra reduction pass only costs (r03 profile)
     const int nslabs = K / 32;
     if (forced > 1) return forced <= nslabs / 4 ? forced : (nslabs / 4 > 1 ? nslabs / 4 : 1);
-    const F16PConfig* c = f16x3p_splitk_config(g_f16x3p_cfg < 0 ? f16x3p_pick(M, N, K, act, true) : g_f16x3p_cfg, M, N, K, act);
+    const F16PConfig* c = f16x3p_splitk_config(forced_cfg < 0 ? f16x3p_pick(M, N, K, act, true) : forced_cfg, M, N, K, act);
     if (!c) return 1;
-    const int64_t tiles = psam_cdiv(M, c->bm) * psam_cdiv(N, c->bn), slots = (int64_t)(f16x3p_cu_count() - 8) * c->per_cu;
+    const int64_t tiles = psam_cdiv(M, c->bm) * psam_cdiv(N, c->bn), slots = (int64_t)(psam_cu_count() - 8) * c->per_cu;
     // Measured per shape, alone on the chip (profiles/r06/r06_small_m.txt): splitting pays for 44 tiles on 248 slots (giant proj 24.7 -> 18.6 us, fc2 82.6 -> 38.7)
     // and LOSES for 132 and 192 tiles (giant qkv 27.9 -> 41.2 us with two splits, fc1 30.1 -> 44.1 with three: 8.6 - 12.6 MB of partial planes per split
     // through the fabric and a serial fix-up for a K loop that was only 44 slabs long).  Until round 5 the limit was 0.55 of the slots.
@@ -763,7 +745,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
                                      int64_t ldc, const float* bias, const float* residual, int64_t ldr, const float* rowbias, int64_t ldrb,
                                      int32_t rowgroup, int32_t M, int32_t N, int32_t K, float alpha, int32_t act, const psam_gemm_fuse_t* fuse,
                                      hipStream_t stream) {
-    t_f16x3p_last_cfg = -1; t_f16x3p_last_splitk = 0;
+    t_f16x3p.reset();
     PSAM_REQUIRE(A && W && C && scaleA && scaleW, PSAM_EINVAL, "psam_gemm_f16x3p: null pointer");
     PSAM_REQUIRE(M > 0 && N > 0 && K >= 128 && (K & 31) == 0, PSAM_EINVAL, "psam_gemm_f16x3p: bad shape (K % 32 == 0, K >= 128)");
     PSAM_REQUIRE(act >= 0 && act <= 3, PSAM_EINVAL, "psam_gemm_f16x3p: bad activation code");
@@ -785,7 +767,8 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
 #ifdef PSAM_GEMM_ABLATE
     p.dbg = g_f16x3p_dbg;
 #endif
-    int cfg = g_f16x3p_cfg;
+    const int forced_cfg = k_f16x3p_cfg.get();      // read once: every decision of this call sees one value
+    int cfg = forced_cfg;
     if (cfg < 0) cfg = f16x3p_pick(M, N, K, act, false);
     if (fuse && fuse->splitk > 1) {
         const int ks = fuse->splitk;
@@ -802,7 +785,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         // in-kernel fix-up (the last workgroup of a tile sums the partials and runs the epilogue) where the workspace holds the tiles' raw accumulators
         // and this stream has its arrival counters; otherwise partial planes + the reduction launch
         const int64_t sk_tiles = psam_cdiv(M, c->bm) * psam_cdiv(N, c->bn);
-        int* counters = (f16x3p_splitk_fixup_enabled() && sk_tiles <= SK_MAX_TILES && sk_tiles * c->bm * c->bn <= fuse->splitk_plane) ? (fuse->counters ? fuse->counters + PSAM_CNT_GEMM : nullptr) : nullptr;
+        int* counters = (k_f16x3p_sk_fixup.get() != 0 && sk_tiles <= SK_MAX_TILES && sk_tiles * c->bm * c->bn <= fuse->splitk_plane) ? (fuse->counters ? fuse->counters + PSAM_CNT_GEMM : nullptr) : nullptr;
         p.ksplit = ks; p.plane = fuse->splitk_plane;
         if (counters) { p.sk_part = fuse->splitk_ws; p.sk_count = counters; }
         else { p.C = fuse->splitk_ws; p.ldc = N; p.bias = nullptr; p.residual = nullptr; p.act = 0; p.alpha = 1.f; }
@@ -824,12 +807,12 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         p.no_store = fuse->no_store;
         // The register epilogue sums a row's products in another order than the LDS epilogue (same accuracy, other rounding): ONE configuration for every
         // M, so that a cloud's logits do not depend on how many clouds share the launch (tests/test_gpu_e2e.py::test_properties_full_size).
-        if (g_f16x3p_cfg < 0 && f16x3p_use_register_epilogue(p)) cfg = 21;
+        if (forced_cfg < 0 && f16x3p_use_register_epilogue(p)) cfg = 21;
         else if (!f16x3p_has(cfg, F16P_TWO_WIDE)) cfg = f16x3p_pick(M, N, K, act, true);
 #ifdef PSAM_BUILD_EXPERIMENTS
     } else if (fuse && fuse->row_ln_g && N == 512) {
         // full-row tile 128x512 on the ping-pong kernel with the register epilogue: Linear (+ row bias per group) -> LayerNorm -> activation -> packed rows
-        PSAM_REQUIRE(f16x3p_epilogue_mode() > 0, PSAM_EINVAL, "psam_gemm_f16x3p_ex: row LayerNorm over N == 512 needs the register epilogue (psam_gemm_f16x3p_force_epilogue)");
+        PSAM_REQUIRE(k_f16x3p_tr.get() > 0, PSAM_EINVAL, "psam_gemm_f16x3p_ex: row LayerNorm over N == 512 needs the register epilogue (psam_gemm_f16x3p_force_epilogue)");
         PSAM_REQUIRE((M & 127) == 0 && act != 3 && fuse->row_ln_b && !fuse->hyper && !fuse->stats && !fuse->ln_c && !fuse->gmax_out && !fuse->no_store && !residual, PSAM_EINVAL,
                      "psam_gemm_f16x3p_ex: row LayerNorm over N == 512 needs M % 128 == 0 and combines only with bias / rowbias / activation / packed output");
         PSAM_REQUIRE(!rowbias || ((p.rowgroup & 31) == 0 && (ldrb & 3) == 0 && ((uintptr_t)rowbias & 15) == 0), PSAM_EINVAL,
@@ -880,7 +863,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         p.gmax_out = fuse->gmax_out; p.gmax_ld = fuse->gmax_ld; p.gmax_k = fuse->gmax_k; p.no_store = fuse->no_store;
         // group maximum: wave tiles of 64 rows (F16P_GMAX; in place of another configuration 256x256 where N % 256 == 0, else 256x128); row statistics /
         // everything else: wave tiles two 32-column tiles wide (F16P_TWO_WIDE).  A forced lock-step configuration without them is refused, not replaced.
-        const bool forced_ls = g_f16x3p_cfg >= 0 && g_f16x3p_cfg < 50;
+        const bool forced_ls = forced_cfg >= 0 && forced_cfg < 50;
         if (fuse->gmax_out) {
             if (!f16x3p_has(cfg, F16P_GMAX)) {
                 PSAM_REQUIRE(!forced_ls, PSAM_EINVAL, "psam_gemm_f16x3p_ex: the forced configuration cannot apply the group maximum");
@@ -895,23 +878,23 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
         const bool w_stats = p.stats != nullptr, w_gmax = p.gmax_out != nullptr, w_hyper = p.hyper != nullptr;
         const bool fused_any = w_stats || w_gmax || w_hyper || p.pack_out || p.ln_c;
         const bool shape_ok = !fused_any || ((M & 255) == 0 && (N & 127) == 0);
-        const int forced = g_f16x3p_cfg;
-        if (forced >= 50 && forced < 80) {      // a forced ping-pong configuration runs as forced or is refused (no silent lock-step replacement)
-            PSAM_REQUIRE(shape_ok && f16x3pp_supports(forced, act, w_stats, w_gmax, w_hyper), PSAM_EINVAL,
+        if (forced_cfg >= 50 && forced_cfg < 80) {      // a forced ping-pong configuration runs as forced or is refused (no silent lock-step replacement)
+            PSAM_REQUIRE(shape_ok && f16x3pp_supports(forced_cfg, act, w_stats, w_gmax, w_hyper), PSAM_EINVAL,
                          "psam_gemm_f16x3p_ex: the forced ping-pong configuration does not exist or cannot apply this epilogue / these extras");
-            cfg = forced;
-        } else if (forced >= 80 && forced < 100) {
-            if (shape_ok && f16x3pp_supports(forced, act, w_stats, w_gmax, w_hyper)) cfg = forced;
-        } else if (forced < 0) {
+            cfg = forced_cfg;
+        } else if (forced_cfg >= 80 && forced_cfg < 100) {
+            if (shape_ok && f16x3pp_supports(forced_cfg, act, w_stats, w_gmax, w_hyper)) cfg = forced_cfg;
+        } else if (forced_cfg < 0) {
             const int pp = f16x3pp_pick(M, N, K, act);
             if (pp >= 0 && shape_ok && f16x3pp_supports(pp, act, w_stats, w_gmax, w_hyper)) cfg = pp;
         }
     }
 #ifdef PSAM_BUILD_EXPERIMENTS
     {   // unit-ring kernel (gemm_f16x3q.hip): a forced configuration 80 .., or the environment's choice for the large encoder GEMMs
-        int q = (g_f16x3p_cfg >= 80 && g_f16x3p_cfg < 90) ? g_f16x3p_cfg : 0;
-        if (!q && g_f16x3p_cfg < 0) {
-            static const int envq = psam_env_int("PSAM_GEMM_Q", 0);
+        int q = (forced_cfg >= 80 && forced_cfg < 90) ? forced_cfg : 0;
+        if (!q && forced_cfg < 0) {
+            static psam_knob k_q("PSAM_GEMM_Q", 0);
+            const int envq = k_q.get();
             if (envq >= 80 && M >= 2048 && N >= 1024 && K >= 512) q = (envq == 84 && (act == 3 || N % 192 != 0)) ? 80 : envq;
         }
         if (q && f16x3q_supports(q, p)) return f16x3p_ran(launch_f16x3q(q, p, stream), q, 1);
@@ -922,7 +905,7 @@ PSAM_API int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* sc
     // persistent forms of cfg 21, both measured and not adopted (profiles/r05/r05_continuous_sweep.txt, r05_streamk_sweep.txt): 94 = whole tiles from per-XCD
     // queues, one continuous slab stream per workgroup (gemm_f16x3c.hip: the same bits as cfg 21, the same time; 95: one workgroup per CU; PSAM_GEMM_CONTINUOUS=1
     // switches it in for the batch-sized launches), 90 .. 93 = even shares of the K slabs (stream-K, gemm_f16x3s.hip: slower)
-    if (cfg == 94 || cfg == 95 || (cfg == 21 && g_f16x3p_cfg < 0 && M >= 2048 && f16x3p_continuous_enabled())) {
+    if (cfg == 94 || cfg == 95 || (cfg == 21 && forced_cfg < 0 && M >= 2048 && k_f16x3p_continuous.get() != 0)) {
         int32_t rc = PSAM_OK;
         if (f16x3p_use_register_epilogue(p) && launch_f16x3c(p, stream, rc, cfg == 95 ? 1 : 2)) return f16x3p_ran(rc, cfg == 95 ? 95 : 94, 1);
         if (cfg >= 90) cfg = 21;

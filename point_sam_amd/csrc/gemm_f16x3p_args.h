@@ -1,7 +1,6 @@
 // Shared by the two packed-operand GEMM translation units (gemm_f16x3p.hip: lock-step ring kernels; gemm_f16x3pp.hip: the
 // ping-pong kernel): argument block, LDS-DMA macro, tile-order panel model.
 #pragma once
-#include <cstdlib>
 #include "common.h"
 
 typedef float pf32x16 __attribute__((ext_vector_type(16)));
@@ -53,7 +52,8 @@ __device__ __forceinline__ unsigned long long gemm_now() {
 // is fetched once.  The P with the least modelled traffic wins (ties: the widest).  PSAM_GEMM_PANEL overrides (0: plain row-major).
 // Measured (profiles/r02/r02_gemm_panel_sweep.log): qkv 81.7 -> 79.6 us, fc1 143.4 -> 138.2 us, two-stream layer 303.9 -> 292 us.
 static inline int f16x3p_panel(int tiles_m, int tiles_n, int BM, int BN, int K) {
-    static const int forced = psam_env_int("PSAM_GEMM_PANEL", -1);
+    static psam_knob k_panel("PSAM_GEMM_PANEL", -1);
+    const int forced = k_panel.get();
     if (forced == 0) return tiles_n;
     if (forced > 0) return forced < tiles_n ? forced : tiles_n;
     const double l2 = 2.5 * 1048576.0, a_band = (double)BM * K * 4, w_col = (double)BN * K * 4;
@@ -69,25 +69,6 @@ static inline int f16x3p_panel(int tiles_m, int tiles_n, int BM, int BN, int K) 
         if (cost < best_cost * 0.999) { best_cost = cost; best = P; }
     }
     return best;
-}
-
-// CUs of the current device; 256 (MI355X) where there is none to ask (host-side planning without a GPU)
-static inline int f16x3p_cu_count() {
-    int ncu = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
-    return ncu;
-}
-
-// > 64 KiB of dynamic LDS must be opted into per kernel AND per device (the attribute lives with the device's code object)
-template <typename K>
-static inline bool f16x3p_reserve_lds(K kernel, int lds, unsigned long long& done_mask) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (__atomic_load_n(&done_mask, __ATOMIC_ACQUIRE) & bit) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return false;
-    __atomic_fetch_or(&done_mask, bit, __ATOMIC_RELEASE);
-    return true;
 }
 
 // gemm_f16x3pp.hip: ping-pong configurations (cfg 50 ..); returns PSAM_EINVAL for an unknown one

@@ -279,7 +279,7 @@ static int32_t launch_pp(F16PArgs& p, hipStream_t stream) {
     p.tiles_n = (int)psam_cdiv(p.N, BN);
     p.panel = f16x3p_panel(p.tiles_m, p.tiles_n, BM, BN, p.K);
     static unsigned long long attr_done = 0;
-    if (!f16x3p_reserve_lds(&gemm_f16x3pp_kernel<GWM, WN, TM, TN, S, P, PRIO, ABL, TR, OCC>, lds, attr_done)) {
+    if (!psam_reserve_lds(&gemm_f16x3pp_kernel<GWM, WN, TM, TN, S, P, PRIO, ABL, TR, OCC>, lds, attr_done)) {
         psam_set_error("psam_gemm_f16x3p: cannot reserve LDS");
         return PSAM_EINVAL;
     }
@@ -342,10 +342,11 @@ bool f16x3pp_supports(int cfg, int act, bool stats, bool gmax, bool hyper) {
 // 67.5 us); in three-stream layer loops the 256x256 tile is the fastest arrangement measured (268 vs 281 us per layer).  In the pipelined
 // benchmark (two dense streams + the tokenizer stream, HIP graphs) none of it shows: 751 clouds/s with and without it, 736 / 722 when every
 // encoder GEMM runs on it -- one 8-wave workgroup per CU cannot share a CU with the other batch's kernels, and that co-scheduling is worth
-// more than the kernel's own gain.  So the default is OFF.  PSAM_GEMM_PP (read once): 0 (default) = never; 1 = fc1 and conv2.3; 2 = every
+// more than the kernel's own gain.  So the default is OFF.  PSAM_GEMM_PP: 0 (default) = never; 1 = fc1 and conv2.3; 2 = every
 // encoder-sized GEMM on the 256x128 tile as well; 3 = on the 256x256 tile where N allows.
 int f16x3pp_pick(int M, int N, int K, int act) {
-    static const int mode = psam_env_int("PSAM_GEMM_PP", 0);
+    static psam_knob k_pp("PSAM_GEMM_PP", 0);
+    const int mode = k_pp.get();
     if (mode == 0 || K < 128 || (K & 31)) return -1;
     if (M >= 32768) return (N >= 256 && (N & 127) == 0 && K >= 512) ? 51 : -1;      // mini-PointNet conv2.3: 256x256 tiles, many rounds
     if (mode == 4) {
@@ -353,7 +354,7 @@ int f16x3pp_pick(int M, int N, int K, int act) {
         // the width whose tile count fills whole rounds of #CU - 8 workgroup slots best -- wide GEMMs only (N >= 1536: with 128-column tiles
         // and one workgroup per CU the narrow ones leave half of the chip idle, the lock-step kernel keeps them)
         if (M < 2048 || (M & 255) || (N & 127) || N < 1536) return -1;
-        static const int ncu = f16x3p_cu_count();
+        const int ncu = psam_cu_count();
         const int slots = ncu > 16 ? ncu - 8 : ncu;
         int best = -1; double best_cost = 1e300;
         for (const int cfg : {51, 62, 63}) {

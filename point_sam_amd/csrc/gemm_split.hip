@@ -218,8 +218,8 @@ __global__ __launch_bounds__(256) void gemm_bf16x6_kernel(const SplitGemmArgs p)
                             n0 + wn * TN * 32, lane, C, R);
 }
 
-static int g_split_cfg = -1;  // tuning hook: 0 = 128x128 (2x2 waves of 64x64), 1 = 128x64 (4x1 waves of 32x64), -1 = auto
-PSAM_API void psam_gemm_bf16x6_force_config(int32_t cfg) { g_split_cfg = cfg; }
+static psam_knob k_split_cfg(nullptr, -1);  // tuning hook: 0 = 128x128 (2x2 waves of 64x64), 1 = 128x64 (4x1 waves of 32x64), -1 = auto
+PSAM_API void psam_gemm_bf16x6_force_config(int32_t cfg) { k_split_cfg.force(cfg); }
 
 // Same argument list as psam_gemm_f32 (include/pointsam_hip.h).
 PSAM_API int32_t psam_gemm_bf16x6(const float* A, int64_t lda, int64_t sA1, int64_t sA2, const float* W, int64_t ldw, int64_t sW1,
@@ -243,7 +243,7 @@ PSAM_API int32_t psam_gemm_bf16x6(const float* A, int64_t lda, int64_t sA1, int6
     p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.ldr = ldr; p.ldrb = ldrb;
     p.sA1 = sA1; p.sA2 = sA2; p.sW1 = sW1; p.sW2 = sW2; p.sC1 = sC1; p.sC2 = sC2; p.sR1 = sR1; p.sR2 = sR2;
     p.M = M; p.N = N; p.K = K; p.batch2 = batch2; p.rowgroup = rowgroup > 0 ? rowgroup : 1; p.act = act; p.alpha = alpha;
-    int cfg = g_split_cfg;
+    int cfg = k_split_cfg.get();
     // measured (scripts/gemm_split_bench.py): both shapes saturate near 158 TFLOP/s fp32-equivalent once >= 2 workgroups
     // share a CU; with fewer than 512 128x128 tiles (N = 1024 GEMMs at M = 4096) the 128x64 shape keeps 2+ per CU.
     if (cfg < 0) cfg = (psam_cdiv(M, 128) * psam_cdiv(N, 128) * (int64_t)batch1 * batch2 >= 512 && K > 256) ? 0 : 1;

@@ -213,17 +213,13 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
 // bound of the rows of a GEMM that consumes this output, e.g. |W_n . h + b_n| <= ||W_n|| t + |b_n| (psam_gemm_fuse_t.out_bound).
 // the instance the calling thread's last psam_layernorm* launched: NREG of layernorm_kernel (0 = streaming), 1000 + NV4 of layernorm_v4_kernel, + 100 when it
 // wrote the packed form; -1 after a refused call
-static thread_local int32_t t_layernorm_last = -1;
-PSAM_API int32_t psam_layernorm_last_instance(void) { return t_layernorm_last; }
-static int32_t layernorm_launched(int32_t inst) {
-    const int32_t rc = psam_launch_status("psam_layernorm: launch failed");
-    if (rc == PSAM_OK) t_layernorm_last = inst;
-    return rc;
-}
+static thread_local psam_launch_record<> t_layernorm;
+PSAM_API int32_t psam_layernorm_last_instance(void) { return t_layernorm.a; }
+static int32_t layernorm_launched(int32_t inst) { return t_layernorm.done("psam_layernorm: launch failed", inst); }
 PSAM_API int32_t psam_layernorm_ex2(const float* x, int64_t ldx, const float* res, int64_t ldr, const float* w, const float* b, float* y,
                                     int64_t ldy, int64_t rows, int32_t cols, float eps, int32_t act, float* row_scale, int32_t pack,
                                     float* row_bound, float c2, float c1, float c0, hipStream_t stream) {
-    t_layernorm_last = -1;
+    t_layernorm.reset();
     PSAM_REQUIRE(x && w && b && y, PSAM_EINVAL, "psam_layernorm: null pointer");
     PSAM_REQUIRE(!row_bound || pack, PSAM_EINVAL, "psam_layernorm: row_bound comes with the packed output");
     PSAM_REQUIRE(rows > 0 && cols > 0, PSAM_EINVAL, "psam_layernorm: bad shape");
@@ -337,11 +333,11 @@ __global__ __launch_bounds__(256) void swiglu_ln_kernel(const float* __restrict_
 }
 
 // NREG of the swiglu_ln_kernel instance the calling thread's last psam_swiglu_ln launched (0 = streaming); -1 after a refused call
-static thread_local int32_t t_swiglu_ln_last = -1;
-PSAM_API int32_t psam_swiglu_ln_last_instance(void) { return t_swiglu_ln_last; }
+static thread_local psam_launch_record<> t_swiglu_ln;
+PSAM_API int32_t psam_swiglu_ln_last_instance(void) { return t_swiglu_ln.a; }
 PSAM_API int32_t psam_swiglu_ln(const float* gx, int64_t ldg, int32_t xoff, const float* w, const float* b, float* out, int64_t ldo,
                                 int64_t rows, int32_t H, float eps, hipStream_t stream) {
-    t_swiglu_ln_last = -1;
+    t_swiglu_ln.reset();
     PSAM_REQUIRE(gx && w && b && out, PSAM_EINVAL, "psam_swiglu_ln: null pointer");
     PSAM_REQUIRE(rows > 0 && H > 0 && xoff >= H && ldo >= H && ldg >= xoff + H, PSAM_EINVAL, "psam_swiglu_ln: bad shape");
     const dim3 grid((unsigned)psam_cdiv(rows, 4)), block(256);
@@ -351,9 +347,7 @@ PSAM_API int32_t psam_swiglu_ln(const float* gx, int64_t ldg, int32_t xoff, cons
     else if (H <= 44 * 64) SG_LAUNCH(44);
     else SG_LAUNCH(0);
 #undef SG_LAUNCH
-    const int32_t rc = psam_launch_status("psam_swiglu_ln: launch failed");
-    if (rc == PSAM_OK) t_swiglu_ln_last = H <= 8 * 64 ? 8 : H <= 32 * 64 ? 32 : H <= 44 * 64 ? 44 : 0;
-    return rc;
+    return t_swiglu_ln.done("psam_swiglu_ln: launch failed", H <= 8 * 64 ? 8 : H <= 32 * 64 ? 32 : H <= 44 * 64 ? 44 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -681,17 +675,13 @@ __global__ __launch_bounds__(256) void interp3_c256_kernel(const float* __restri
 // scale_out [Z*N] != NULL (C == 256 only): out receives the g8-packed rows (A operand of psam_gemm_f16x3p) and scale_out their scales.
 // ln_gamma / ln_beta != NULL (C == 256 only): LayerNorm(ln_eps) + activation `act` (PSAM_ACT_NONE / GELU / RELU) of every interpolated row.
 // the kernel the calling thread's last psam_interp3* launched: 256 = interp3_c256_kernel, 0 = interp3_kernel (any other C); -1 after a refused call
-static thread_local int32_t t_interp3_last = -1;
-PSAM_API int32_t psam_interp3_last_instance(void) { return t_interp3_last; }
-static int32_t interp3_launched(int32_t inst) {
-    const int32_t rc = psam_launch_status("psam_interp3: launch failed");
-    if (rc == PSAM_OK) t_interp3_last = inst;
-    return rc;
-}
+static thread_local psam_launch_record<> t_interp3;
+PSAM_API int32_t psam_interp3_last_instance(void) { return t_interp3.a; }
+static int32_t interp3_launched(int32_t inst) { return t_interp3.done("psam_interp3: launch failed", inst); }
 PSAM_API int32_t psam_interp3_ex(const float* src, const int64_t* idx3, const float* w3, float* out, int32_t rep, int64_t Z, int32_t N, int32_t G,
                                  int32_t C, float* scale_out, const float* ln_gamma, const float* ln_beta, float ln_eps, int32_t act,
                                  hipStream_t stream) {
-    t_interp3_last = -1;
+    t_interp3.reset();
     PSAM_REQUIRE(src && idx3 && w3 && out && rep > 0 && Z > 0 && N > 0 && G > 0 && C > 0, PSAM_EINVAL, "psam_interp3: bad argument");
     PSAM_REQUIRE((C & 3) == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)out & 15) == 0, PSAM_EALIGN, "psam_interp3: C % 4 and 16B alignment");
     PSAM_REQUIRE(!scale_out || (C == 256 && ((uintptr_t)out & 31) == 0), PSAM_EINVAL, "psam_interp3: packed output needs C == 256 and 32-byte aligned rows");
@@ -902,21 +892,17 @@ __global__ __launch_bounds__(256) void attention_fewkeys_kernel(const float* __r
     for (int d = 0; d < HD4; ++d) *reinterpret_cast<float4*>(op + 4 * d) = make_float4(acc[d].x * invl, acc[d].y * invl, acc[d].z * invl, acc[d].w * invl);
 }
 
-static int g_attn_small_split = 1;      // test / A-B hook: 0 = always one wave per query
-PSAM_API void psam_attention_small_force_split(int32_t on) { g_attn_small_split = on; }
+static psam_knob k_attn_small_split(nullptr, 1);      // test / A-B hook: 0 = always one wave per query
+PSAM_API void psam_attention_small_force_split(int32_t on) { k_attn_small_split.force(on); }
 // the kernel the calling thread's last psam_attention_small launched: 0 = attention_small_kernel (one wave per query), 1 = attention_small_split_kernel,
 // 4 / 8 = attention_fewkeys_kernel<4> / <8>; -1 after a refused call
-static thread_local int32_t t_attn_small_last = -1;
-PSAM_API int32_t psam_attention_small_last_instance(void) { return t_attn_small_last; }
-static int32_t attn_small_launched(int32_t inst) {
-    const int32_t rc = psam_launch_status("psam_attention_small: launch failed");
-    if (rc == PSAM_OK) t_attn_small_last = inst;
-    return rc;
-}
+static thread_local psam_launch_record<> t_attn_small;
+PSAM_API int32_t psam_attention_small_last_instance(void) { return t_attn_small.a; }
+static int32_t attn_small_launched(int32_t inst) { return t_attn_small.done("psam_attention_small: launch failed", inst); }
 PSAM_API int32_t psam_attention_small(const float* q, int64_t ldq, int64_t sq, const float* k, int64_t ldk, int64_t sk, const float* v,
                                       int64_t ldv, int64_t sv, float* out, int64_t ldo, int64_t so, int64_t Z, int32_t H, int32_t Lq, int32_t Lk,
                                       int32_t hd, float scale, hipStream_t stream) {
-    t_attn_small_last = -1;
+    t_attn_small.reset();
     PSAM_REQUIRE(q && k && v && out && Z > 0 && H > 0 && Lq > 0 && Lk > 0 && hd > 0, PSAM_EINVAL, "psam_attention_small: bad argument");
     PSAM_REQUIRE((size_t)Lk * 16 <= 128 * 1024, PSAM_EINVAL, "psam_attention_small: Lk too large");
     const bool aligned = ((ldq | ldk | ldv | ldo | sq | sk | sv | so) & 3) == 0 && ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15) == 0);
@@ -927,7 +913,7 @@ PSAM_API int32_t psam_attention_small(const float* q, int64_t ldq, int64_t sq, c
         return attn_small_launched(hd == 16 ? 4 : 8);
     }
     const int64_t waves = Z * H * Lq;
-    if (g_attn_small_split && Lk >= 128 && waves <= 2048 && aligned && (hd & 3) == 0 && hd <= 64 && (64 % (hd >> 2)) == 0) {      // few queries, many keys: a workgroup per query
+    if (k_attn_small_split.get() && Lk >= 128 && waves <= 2048 && aligned && (hd & 3) == 0 && hd <= 64 && (64 % (hd >> 2)) == 0) {      // few queries, many keys: a workgroup per query
         hipLaunchKernelGGL(attention_small_split_kernel, dim3((unsigned)waves), dim3(256), (size_t)(((Lk + 3) & ~3) + 4 * 68) * 4, stream, q, ldq, sq, k, ldk, sk, v, ldv,
                            sv, out, ldo, so, H, Lq, Lk, hd, scale);
         return attn_small_launched(1);

@@ -594,26 +594,14 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_coop_pruned_kernel(const floa
     }
 }
 
-static int fps_num_cus() {
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    return cus;
-}
-
 // cooperative layout: groups of 4096 points, PPT4 of them per workgroup, W <= 64 workgroups per cloud, all B*W resident.  The hand-over
 // gets slower with W (1.0 us per iteration up to 16 workgroups on one XCD, 1.7 us at 32: profiles/r03/r03_fabric_probe.txt), the scan with
 // PPT4 (16 waves share four SIMDs).  Measured per iteration (profiles/r03/r03_fps_coop.txt, N = 131072): W = 16 x 8 points per thread 1.98 us,
 // W = 8 x 16 points 2.57 us, W = 32 x 4 points 2.98 us; N = 65536: W = 16 x 4 points 1.64 us, W = 8 x 8 points 1.85 us.  So: the fewest
 // points per thread that bring W down to 16, else as few workgroups as the registers allow (PPT4 <= 4).
 static int fps_coop_ppt4(int B, int N, int* W) {
-    static int ppt4_max = 0, min_groups = 0;      // tuning hooks (environment, read once)
-    if (!ppt4_max) {
-        const char* e = getenv("PSAM_FPS_COOP_PPT4"); ppt4_max = e && atoi(e) > 0 ? atoi(e) : 4;
-        const char* f = getenv("PSAM_FPS_COOP_MIN_GROUPS"); min_groups = f && atoi(f) > 0 ? atoi(f) : 8;
-    }
+    static psam_knob k_ppt4_max("PSAM_FPS_COOP_PPT4", 4), k_min_groups("PSAM_FPS_COOP_MIN_GROUPS", 8);      // tuning hooks (environment; a value <= 0: the default)
+    const int ppt4_max = k_ppt4_max.get_positive(), min_groups = k_min_groups.get_positive();
     const int64_t groups = fps_npad(N) / (4 * FPS_THREADS);
     if (groups < min_groups || N > (1 << 20) || B > 1024) return 0;      // the hand-over key holds a 20-bit index
     if (groups == 8) {
@@ -628,7 +616,7 @@ static int fps_coop_ppt4(int B, int N, int* W) {
     int best = 0;
     for (int ppt4 = 1; ppt4 <= 4 && ppt4 <= ppt4_max; ppt4 *= 2) {
         const int64_t w = groups / ppt4;
-        if (groups % ppt4 != 0 || w > 64 || (int64_t)B * w > fps_num_cus()) continue;
+        if (groups % ppt4 != 0 || w > 64 || (int64_t)B * w > psam_cu_count()) continue;
         best = ppt4; *W = (int)w;
         if (w <= 16) break;
     }
@@ -644,32 +632,22 @@ PSAM_API size_t psam_fps_workspace_bytes(int32_t B, int32_t N, int32_t G) {
     return (size_t)B * 4 * (size_t)fps_npad(N) * sizeof(float) + (size_t)B * (2 * 64 * sizeof(unsigned long long) + 16) + (size_t)B * (FPS_NCELL + 8) * sizeof(int);
 }
 
-static int g_fps_coop = 1;  // test hook: 0 forces the single-workgroup kernels, 2 the cooperative kernel without the one-XCD placement
-PSAM_API void psam_fps_set_cooperative(int32_t on) { g_fps_coop = on; }
-static int g_fps_prune = -1;      // -1: environment PSAM_FPS_PRUNE (default 1); 0 = the cooperative kernel scans every point in every iteration (A/B, tests)
-PSAM_API void psam_fps_set_pruning(int32_t mode) { g_fps_prune = mode; }
-static bool fps_prune_enabled() {
-    if (g_fps_prune >= 0) return g_fps_prune != 0;
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("PSAM_FPS_PRUNE"); on = e ? (atoi(e) != 0) : 1; }
-    return on != 0;
-}
+static psam_knob k_fps_coop(nullptr, 1);  // test hook: 0 forces the single-workgroup kernels, 2 the cooperative kernel without the one-XCD placement
+PSAM_API void psam_fps_set_cooperative(int32_t on) { k_fps_coop.force(on); }
+static psam_knob k_fps_prune("PSAM_FPS_PRUNE", 1);      // 0 = the cooperative kernel scans every point in every iteration (A/B, tests)
+PSAM_API void psam_fps_set_pruning(int32_t mode) { k_fps_prune.force(mode); }
 
 // the instance the calling thread's last psam_fps launched: kind * 100 + PPT4 (kind 0 = fps_kernel, PPT4 0 .. 8; 1 = fps_coop_kernel, 2 = fps_coop_pruned_kernel)
 // and the width of its grid (W * xs for the cooperative kinds, 0 for kind 0); -1 before the first launch and after a refused call.  Host-side bookkeeping only.
-static thread_local int32_t t_fps_last = -1, t_fps_grid_x = -1;
-PSAM_API int32_t psam_fps_last_instance(void) { return t_fps_last; }
-PSAM_API int32_t psam_fps_last_grid_x(void) { return t_fps_grid_x; }
-static int32_t fps_launched(int32_t code, int32_t grid_x) {
-    const int32_t rc = psam_launch_status("psam_fps: launch failed");
-    if (rc == PSAM_OK) { t_fps_last = code; t_fps_grid_x = grid_x; }
-    return rc;
-}
+static thread_local psam_launch_record<> t_fps;
+PSAM_API int32_t psam_fps_last_instance(void) { return t_fps.a; }
+PSAM_API int32_t psam_fps_last_grid_x(void) { return t_fps.b; }
+static int32_t fps_launched(int32_t code, int32_t grid_x) { return t_fps.done("psam_fps: launch failed", code, grid_x); }
 
 // xyz [B,N,3] f32 -> fps_idx [B,G] i64 (start index 0), centers [B,G,3] f32 (fused batch_index_select).
 PSAM_API int32_t psam_fps(const float* xyz, int32_t B, int32_t N, int32_t G, int64_t* fps_idx, float* centers, void* ws,
                           size_t ws_bytes, hipStream_t stream) {
-    t_fps_last = -1; t_fps_grid_x = -1;
+    t_fps.reset();
     PSAM_REQUIRE(xyz && fps_idx && centers && ws, PSAM_EINVAL, "psam_fps: null pointer");
     PSAM_REQUIRE(B > 0 && N > 0 && G > 0 && G <= N, PSAM_EINVAL, "psam_fps: need B>0, 0<G<=N");
     PSAM_REQUIRE((int64_t)N <= (int64_t)1 << 30, PSAM_EINVAL, "psam_fps: N too large");
@@ -679,15 +657,17 @@ PSAM_API int32_t psam_fps(const float* xyz, int32_t B, int32_t N, int32_t G, int
     float* soa = (float*)ws;
     float* mdg = soa + (int64_t)B * 3 * npad;
     int W = 0;
-    const int coop = g_fps_coop ? fps_coop_ppt4(B, N, &W) : 0;
-    if (!(coop && fps_prune_enabled()))      // (the pruned cooperative kernel builds its own, bucketed planes)
+    const int coop_mode = k_fps_coop.get();
+    const bool prune = k_fps_prune.get() != 0;
+    const int coop = coop_mode ? fps_coop_ppt4(B, N, &W) : 0;
+    if (!(coop && prune))      // (the pruned cooperative kernel builds its own, bucketed planes)
         hipLaunchKernelGGL(fps_soa_kernel, dim3((unsigned)psam_cdiv(npad, 256), B), dim3(256), 0, stream, xyz, N, npad, soa);
     if (coop) {
         unsigned long long* cand = (unsigned long long*)(mdg + (int64_t)B * npad);
         hipLaunchKernelGGL(fps_coop_reset_kernel, dim3((unsigned)psam_cdiv(B * 128, 256)), dim3(256), 0, stream, cand, B * 128);
         // one XCD (32 CUs) per cloud when its workgroups fit beside those of the other clouds dealt to the same XCD
-        const int xs = ((int64_t)W * psam_cdiv(B, 8) <= fps_num_cus() / 8 && g_fps_coop != 2) ? 8 : 1;
-        if (fps_prune_enabled()) {
+        const int xs = ((int64_t)W * psam_cdiv(B, 8) <= psam_cu_count() / 8 && coop_mode != 2) ? 8 : 1;
+        if (prune) {
             // counting sort of every cloud by grid cell (bounding box, histogram, scan, scatter) into the four planes of the workspace (x, y, z,
             // original index: the cooperative kernels keep the running minima in registers, the fourth plane is free), then the pruned kernel
             int* bbox = (int*)(cand + (int64_t)B * 128 + 2 * (int64_t)B);
@@ -1015,31 +995,24 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_band_kernel(const float* __re
     knn_sort_write(keys, K, out);
 }
 
-static int g_knn_band = -1;      // -1: environment PSAM_KNN_BAND (default 1); 0 = always the four-pass kernel (A/B, tests)
-PSAM_API void psam_knn_force_band(int32_t mode) { g_knn_band = mode; }
+static psam_knob k_knn_band("PSAM_KNN_BAND", 1);      // 0 = always the four-pass kernel (A/B, tests)
+PSAM_API void psam_knn_force_band(int32_t mode) { k_knn_band.force(mode); }
 // the kernel the calling thread's last psam_knn launched: 0 = knn_kernel, 1 = knn_band_kernel; -1 before the first launch and after a refused call
-static thread_local int32_t t_knn_last = -1;
-PSAM_API int32_t psam_knn_last_instance(void) { return t_knn_last; }
+static thread_local psam_launch_record<> t_knn;
+PSAM_API int32_t psam_knn_last_instance(void) { return t_knn.a; }
 
 // centers [B,G,3], xyz [B,N,3] -> knn_idx [B,G,K] i64 ascending by (squared distance, index).
 PSAM_API int32_t psam_knn(const float* centers, const float* xyz, int32_t B, int32_t G, int32_t N, int32_t K, int64_t* knn_idx,
                           hipStream_t stream) {
-    t_knn_last = -1;
+    t_knn.reset();
     PSAM_REQUIRE(centers && xyz && knn_idx, PSAM_EINVAL, "psam_knn: null pointer");
     PSAM_REQUIRE(B > 0 && G > 0 && N > 0 && K > 0 && K <= N, PSAM_EINVAL, "psam_knn: need 0<K<=N");
     PSAM_REQUIRE(K <= KNN_MAXK, PSAM_EINVAL, "psam_knn: K > 1024 unsupported");
     PSAM_REQUIRE(B <= 65535, PSAM_EINVAL, "psam_knn: B > 65535 unsupported");
-    int band = g_knn_band;
-    if (band < 0) {
-        static int env = -1;
-        if (env < 0) { const char* e = getenv("PSAM_KNN_BAND"); env = e ? atoi(e) : 1; }
-        band = env;
-    }
+    const int band = k_knn_band.get();
     if (!band) hipLaunchKernelGGL(knn_kernel, dim3(G, B), dim3(KNN_THREADS), 0, stream, centers, xyz, G, N, K, knn_idx);
     else hipLaunchKernelGGL(knn_band_kernel, dim3(G, B), dim3(KNN_THREADS), 0, stream, centers, xyz, G, N, K, knn_idx);
-    const int32_t rc = psam_launch_status("psam_knn: launch failed");
-    if (rc == PSAM_OK) t_knn_last = band ? 1 : 0;
-    return rc;
+    return t_knn.done("psam_knn: launch failed", band ? 1 : 0);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1091,12 +1064,7 @@ PSAM_API int32_t psam_three_nn(const float* xyz, const float* centers, int32_t B
         static unsigned long long attr_done = 0;
         int dev = 0;
         PSAM_REQUIRE(hipGetDevice(&dev) == hipSuccess, PSAM_EINVAL, "psam_three_nn: no device");
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(__atomic_load_n(&attr_done, __ATOMIC_ACQUIRE) & bit)) {
-            PSAM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&three_nn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) == hipSuccess,
-                         PSAM_EINVAL, "psam_three_nn: cannot reserve LDS");
-            __atomic_fetch_or(&attr_done, bit, __ATOMIC_RELEASE);
-        }
+        PSAM_REQUIRE(psam_reserve_lds(&three_nn_kernel, 144 * 1024, attr_done), PSAM_EINVAL, "psam_three_nn: cannot reserve LDS");
     }
     hipLaunchKernelGGL(three_nn_kernel, dim3((unsigned)psam_cdiv(N, 256), B), dim3(256), (size_t)G * 12, stream, xyz, centers, N, G,
                        eps, idx3, w3);
@@ -1240,12 +1208,12 @@ __global__ __launch_bounds__(256) void patch_l1_kernel(const float* __restrict__
 // W [128, Cin] (nn.Linear layout), Cin = 3 + C or 3 + 2C (centralize: center_idx [B, G] = the groups' FPS indices), bias/lnw/lnb [128];
 // out [B*rep*G*K, 128] fp32, or (scale_out != null) the g8-packed rows + their scales.  C in {1, 3}.
 // the patch_l1_kernel instance the calling thread's last psam_patch_l1* launched: CIN * 10 + PACK (CIN 4 / 6 plain, 5 / 9 centralised); -1 after a refused call
-static thread_local int32_t t_patch_l1_last = -1;
-PSAM_API int32_t psam_patch_l1_last_instance(void) { return t_patch_l1_last; }
+static thread_local psam_launch_record<> t_patch_l1;
+PSAM_API int32_t psam_patch_l1_last_instance(void) { return t_patch_l1.a; }
 PSAM_API int32_t psam_patch_l1_ex(const float* xyz, const float* feats, const float* centers, const int64_t* knn_idx, const int64_t* center_idx,
                                   const float* W, const float* bias, const float* lnw, const float* lnb, float eps, int32_t B, int32_t rep,
                                   int32_t N, int32_t G, int32_t K, int32_t C, float radius, float* out, float* scale_out, hipStream_t stream) {
-    t_patch_l1_last = -1;
+    t_patch_l1.reset();
     PSAM_REQUIRE(xyz && feats && centers && knn_idx && W && bias && lnw && lnb && out, PSAM_EINVAL, "psam_patch_l1: null pointer");
     PSAM_REQUIRE(B > 0 && rep > 0 && N > 0 && G > 0 && K > 0, PSAM_EINVAL, "psam_patch_l1: bad shape");
     PSAM_REQUIRE(C == 1 || C == 3, PSAM_EINVAL, "psam_patch_l1: C must be 1 (mask logit) or 3 (rgb)");
@@ -1264,9 +1232,7 @@ PSAM_API int32_t psam_patch_l1_ex(const float* xyz, const float* feats, const fl
     if (scale_out) L1_PICK(true); else L1_PICK(false);
 #undef L1_PICK
 #undef L1_LAUNCH
-    const int32_t rc = psam_launch_status("psam_patch_l1: launch failed");
-    if (rc == PSAM_OK) t_patch_l1_last = (center_idx ? 3 + 2 * C : 3 + C) * 10 + (scale_out ? 1 : 0);
-    return rc;
+    return t_patch_l1.done("psam_patch_l1: launch failed", (center_idx ? 3 + 2 * C : 3 + C) * 10 + (scale_out ? 1 : 0));
 }
 
 PSAM_API int32_t psam_patch_l1_r(const float* xyz, const float* feats, const float* centers, const int64_t* knn_idx, const float* W,

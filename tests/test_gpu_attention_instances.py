@@ -104,13 +104,13 @@ _KERNEL = r"([A-Za-z_]\w*_kernel)\s*(<[^<>()]*>)?"
 
 
 def launched_instances(text):
-    """Kernel instantiations named at launch sites (hipLaunchKernelGGL, and the FA_LAUNCH(HD8, DT) macro of the f32 family) and in hipFuncSetAttribute,
+    """Kernel instantiations named at launch sites (hipLaunchKernelGGL, and the FA_LAUNCH(HD8, DT) macro of the f32 family) and in the LDS opt-in (psam_reserve_lds),
     spelled without blanks: {"flash_attn_packed_kernel<4,2>", ...}.  The macro's own definition (template arguments that are names) is not an instance."""
     text = re.sub(r"//[^\n]*", "", text)
     found = set()
     for m in re.finditer(r"hipLaunchKernelGGL\(\s*\(?\s*" + _KERNEL, text):
         found.add(m.group(1) + (m.group(2) or "").replace(" ", ""))
-    for m in re.finditer(r"hipFuncSetAttribute\(\s*reinterpret_cast<const void\*>\(\s*&\s*" + _KERNEL, text):
+    for m in re.finditer(r"psam_reserve_lds\(\s*&\s*" + _KERNEL, text):
         found.add(m.group(1) + (m.group(2) or "").replace(" ", ""))
     macro = re.search(r"#define\s+FA_LAUNCH\(HD8, DT\)\s+hipLaunchKernelGGL\(\(" + _KERNEL, text)
     for m in re.finditer(r"\bFA_LAUNCH\(\s*(\d+)\s*,\s*(\d+)\s*\)", text):
@@ -146,7 +146,7 @@ def test_registry_matches_the_launch_sites():
     for k, i in INSTANCES.items():
         if i.family == "packed":
             spaced = re.escape(k).replace(",", r",\s*")
-            assert re.search(r"hipFuncSetAttribute\(reinterpret_cast<const void\*>\(&" + spaced + r"\)", body), k
+            assert re.search(r"psam_reserve_lds\(&" + spaced + r",", body), k
             assert re.search(r"hipLaunchKernelGGL\(\(?" + spaced + r"\)?,", body), k
             assert re.search(r"pa_launched\([^)]*\b%d\b" % i.code, body), (k, i.code)
             args = [int(a) for a in k[k.index("<") + 1:-1].split(",")]

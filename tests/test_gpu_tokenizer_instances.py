@@ -113,15 +113,15 @@ def pinned_constants(src):
 
     return {
         "fps_threads": num(r"constexpr int FPS_THREADS = (\d+);"),
-        "min_groups": num(r'getenv\("PSAM_FPS_COOP_MIN_GROUPS"\); min_groups = f && atoi\(f\) > 0 \? atoi\(f\) : (\d+);'),
-        "ppt4_max": num(r'getenv\("PSAM_FPS_COOP_PPT4"\); ppt4_max = e && atoi\(e\) > 0 \? atoi\(e\) : (\d+);'),
+        "min_groups": num(r'k_min_groups\("PSAM_FPS_COOP_MIN_GROUPS", (\d+)\); const int [^;]* min_groups = k_min_groups\.get_positive\(\);'),
+        "ppt4_max": num(r'k_ppt4_max\("PSAM_FPS_COOP_PPT4", (\d+)\), [^;]*; const int ppt4_max = k_ppt4_max\.get_positive\(\),'),
         "ppt4_loop": has("for (int ppt4 = 1; ppt4 <= 4 && ppt4 <= ppt4_max; ppt4 *= 2) {", "1..4 doubling"),
-        "w_max": num(r"if \(groups % ppt4 != 0 \|\| w > (\d+) \|\| \(int64_t\)B \* w > fps_num_cus\(\)\) continue;"),
+        "w_max": num(r"if \(groups % ppt4 != 0 \|\| w > (\d+) \|\| \(int64_t\)B \* w > psam_cu_count\(\)\) continue;"),
         "w_stop": num(r"best = ppt4; \*W = \(int\)w; if \(w <= (\d+)\) break;"),
         "groups8_max_b": num(r"if \(groups == 8\) \{ if \(B > (\d+) \|\| ppt4_max < 1\) return 0; \*W = 8; return 1; \}"),
         "n_max_shift": num(r"if \(groups < min_groups \|\| N > \(1 << (\d+)\) \|\| B > 1024\) return 0;"),
         "b_max": num(r"if \(groups < min_groups \|\| N > \(1 << 20\) \|\| B > (\d+)\) return 0;"),
-        "xs_rule": has("const int xs = ((int64_t)W * psam_cdiv(B, 8) <= fps_num_cus() / 8 && g_fps_coop != 2) ? 8 : 1;", "W * cdiv(B, 8) <= cus / 8 and mode != 2"),
+        "xs_rule": has("const int xs = ((int64_t)W * psam_cdiv(B, 8) <= psam_cu_count() / 8 && coop_mode != 2) ? 8 : 1;", "W * cdiv(B, 8) <= cus / 8 and mode != 2"),
         "single_max_groups": num(r"case (\d+): FPS_LAUNCH\(\d+\); break; default: FPS_LAUNCH\(0\); break;"),
         "knn_cand": num(r"constexpr int KNN_CAND = (\d+);"),
         "knn_maxk": num(r"constexpr int KNN_MAXK = (\d+);"),
@@ -176,15 +176,15 @@ def test_the_model_copies_the_constants_of_the_source():
     assert GROUP == 4 * MODEL["fps_threads"]
     assert "static inline int64_t fps_npad(int64_t N) { return psam_cdiv(N, 4 * FPS_THREADS) * (4 * FPS_THREADS); }" in src
     assert "const int64_t groups = fps_npad(N) / (4 * FPS_THREADS);" in src and "const int groups = (int)(npad / (4 * FPS_THREADS));" in src
-    assert "const int coop = g_fps_coop ? fps_coop_ppt4(B, N, &W) : 0;" in src
+    assert "const int coop_mode = k_fps_coop.get();" in src and "const int coop = coop_mode ? fps_coop_ppt4(B, N, &W) : 0;" in src
     assert "if (n_band > KNN_CAND) {" in src and "if (eq_total != need_eq) {" in src and "if (eq_total == need_eq) {" in src
     assert 'PSAM_REQUIRE(K <= KNN_MAXK, PSAM_EINVAL, "psam_knn: K > 1024 unsupported");' in src
     assert 'PSAM_REQUIRE((size_t)G * 12 <= 144 * 1024, PSAM_EINVAL, "psam_three_nn: G too large for LDS staging");' in src
     # the hand-over key: 12-bit tag above a 20-bit index field, slots reset to all ones
     assert "const unsigned tag = (unsigned)j & 0xFFFu;" in src and "if (i < n) cand[i] = ~0ull;" in src
-    for old, new in (("atoi(f) : 8;", "atoi(f) : 6;"), ("atoi(e) : 4;", "atoi(e) : 8;"), ("|| w > 64 ||", "|| w > 32 ||"), ("if (w <= 16) break;", "if (w <= 8) break;"),
+    for old, new in (('"PSAM_FPS_COOP_MIN_GROUPS", 8)', '"PSAM_FPS_COOP_MIN_GROUPS", 6)'), ('"PSAM_FPS_COOP_PPT4", 4)', '"PSAM_FPS_COOP_PPT4", 8)'), ("|| w > 64 ||", "|| w > 32 ||"), ("if (w <= 16) break;", "if (w <= 8) break;"),
                      ("if (B > 2 || ppt4_max < 1) return 0;", "if (B > 4 || ppt4_max < 1) return 0;"), ("N > (1 << 20)", "N > (1 << 19)"),
-                     ("<= fps_num_cus() / 8 && g_fps_coop != 2", "<= fps_num_cus() / 4 && g_fps_coop != 2"), ("KNN_CAND = 2048;", "KNN_CAND = 4096;"),
+                     ("<= psam_cu_count() / 8 && coop_mode != 2", "<= psam_cu_count() / 4 && coop_mode != 2"), ("KNN_CAND = 2048;", "KNN_CAND = 4096;"),
                      ("KNN_MAXK = 1024;", "KNN_MAXK = 2048;"), ("ppt4 <= 4 && ppt4 <= ppt4_max", "ppt4 <= 8 && ppt4 <= ppt4_max")):
         assert src.count(old) == 1, old
         assert pinned_constants(src.replace(old, new)) != MODEL, old

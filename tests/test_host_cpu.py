@@ -325,3 +325,73 @@ def test_library_keeps_no_stream_state_and_allocates_only_in_prepare():
         ops.use_counters(torch.zeros(4, dtype=torch.int32))
     from point_sam_amd.streams import pipeline_streams_report
     assert isinstance(pipeline_streams_report(), dict)
+
+
+def _csrc_sources():
+    """{path relative to csrc: text without comments} of every source under csrc/, experiments/ included."""
+    csrc = os.path.join(ROOT, "point_sam_amd", "csrc")
+    out = {}
+    for d, _, files in os.walk(csrc):
+        for f in files:
+            if f.endswith((".hip", ".h", ".cpp")):
+                text = open(os.path.join(d, f)).read()
+                out[os.path.relpath(os.path.join(d, f), csrc)] = re.sub(r"/\*.*?\*/", "", re.sub(r"//[^\n]*", "", text), flags=re.S)
+    return out
+
+
+def test_host_dispatch_mechanisms_have_one_copy():
+    """The environment is read in csrc/knob.h only (every switch is a psam_knob), the CU count and the LDS opt-in are asked in one file each (psam_cu_count,
+    psam_reserve_lds in csrc/common.h), and no hook variable is a plain int that one thread writes while others read it."""
+    srcs = _csrc_sources()
+    assert len(srcs) > 20 and "knob.h" in srcs and os.path.join("experiments", "twoway.hip") in srcs
+    assert [f for f, t in srcs.items() if "getenv(" in t] == ["knob.h"]
+    assert [f for f, t in srcs.items() if "hipDeviceAttributeMultiprocessorCount" in t] == ["common.h"]
+    assert [f for f, t in srcs.items() if "hipFuncAttributeMaxDynamicSharedMemorySize" in t] == ["common.h"]
+    for f, t in srcs.items():
+        assert not re.search(r"static int g_\w+", t), f
+    knob = srcs["knob.h"]      # host only: a CPU program includes it on its own (tests/host/knob_threads.cpp)
+    assert "hip" not in knob and set(re.findall(r"#include (\S+)", knob)) == {"<atomic>", "<climits>", "<cstdlib>"}
+
+
+_KEYSPLIT_SHAPE = (1, 16, 512, 512, 88, 4)      # one cloud of the giant encoder: 64 query units on 256 CUs (a real device, or the fallback without one)
+
+
+def test_switch_precedence_default_forced_environment():
+    """psam_knob through the real library, on host-only planning (psam_attention_f16x3_keysplit_ws_bytes): a forced value >= 0 beats the environment, the
+    environment beats the default, and force(-1) hands the switch back."""
+    import subprocess
+    import sys
+    lib = _lib.load()
+    ws = lambda: lib.psam_attention_f16x3_keysplit_ws_bytes(*_KEYSPLIT_SHAPE)
+    assert "PSAM_ATTN_KEYSPLIT" not in os.environ, "the suite runs with the library's defaults"
+    try:
+        default = ws()
+        assert default > 0
+        lib.psam_attention_f16x3_force_keysplit(0)
+        assert ws() == 0
+        lib.psam_attention_f16x3_force_keysplit(-1)
+        assert ws() == default
+    finally:
+        lib.psam_attention_f16x3_force_keysplit(-1)
+    code = f"""
+import ctypes
+lib = ctypes.CDLL({os.environ.get("PSAM_LIB_PATH", _lib.LIB_PATH)!r})
+lib.psam_attention_f16x3_keysplit_ws_bytes.restype = ctypes.c_size_t
+ws = lambda: lib.psam_attention_f16x3_keysplit_ws_bytes(*{_KEYSPLIT_SHAPE!r})
+out = [ws()]
+lib.psam_attention_f16x3_force_keysplit(1)
+out.append(ws())
+lib.psam_attention_f16x3_force_keysplit(-1)
+out.append(ws())
+print(*out)
+"""
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, PSAM_ATTN_KEYSPLIT="0"), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    env_off, forced_on, env_again = (int(v) for v in r.stdout.split())
+    assert env_off == 0 and forced_on > 0 and env_again == 0
+
+
+def test_a_refused_call_clears_the_launch_record():
+    lib = _lib.load()
+    assert lib.psam_knn(None, None, 1, 1, 1, 1, None, None) == -1
+    assert lib.psam_knn_last_instance() == -1

@@ -333,7 +333,8 @@ void psam_attention_packed_force_nw(int32_t nw);
 int32_t psam_attention_packed_last_instance(void);
 
 /* y [M, N] = act(x [M, K] W [N, K]^T + bias) + residual for M <= 64 rows (K % 16 == 0, rows 16-byte aligned; act: none / GELU / ReLU),
- * exact fp32 products.  The decoder's token-side nn.Linear calls (7 output tokens per prompt): transformer.py:109-236. */
+ * exact fp32 products.  The decoder's token-side nn.Linear calls (7 output tokens per prompt): transformer.py:109-236.  An inf or a NaN in a row of x
+ * reaches that row of y only (as NaN where K has a ragged last round of 128), and the ReLU of this entry and of the two below keeps a NaN, as torch.relu does. */
 int32_t psam_linear_skinny(const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, const float* residual, int64_t ldr,
                            float* y, int64_t ldy, int32_t M, int32_t N, int32_t K, int32_t act, psam_stream_t stream);
 

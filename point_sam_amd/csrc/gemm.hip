@@ -249,6 +249,9 @@ PSAM_API int32_t psam_linear(const float* x, int64_t ldx, const float* W, int64_
 // ------------------------------------------------------------------------------------------------
 typedef float sk_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int SK_CH = 8;      // float4 per operand per lane and round = 128 k
+// ReLU of the kernels below: a NaN stays a NaN, as torch.relu has it (fmaxf(NaN, 0) is 0).  A row of x that holds an inf comes out of a K with a ragged last
+// round as NaN -- its padded k-slots multiply slot 0 with a zeroed weight -- and must not pass for a row of zeros.
+__device__ __forceinline__ float sk_relu(float v) { return v < 0.f ? 0.f : v; }
 __global__ __launch_bounds__(256) void linear_skinny_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ W, int64_t ldw,
                                                             const float* __restrict__ bias, const float* __restrict__ res, int64_t ldr,
                                                             float* __restrict__ y, int64_t ldy, int M, int N, int K, int act) {
@@ -294,7 +297,7 @@ __global__ __launch_bounds__(256) void linear_skinny_kernel(const float* __restr
             if (orow < M) {
                 float val = acc[v] + bv;
                 if (act == 1) val = gelu_erf(val);
-                else if (act == 2) val = fmaxf(val, 0.f);
+                else if (act == 2) val = sk_relu(val);
                 if (res) val += res[(int64_t)orow * ldr + col];
                 y[(int64_t)orow * ldy + col] = val;
             }
@@ -348,7 +351,7 @@ __global__ __launch_bounds__(256) void linear_skinny_multi_kernel(const psam_ski
             if (orow < M) {
                 float val = acc[v] + bv;
                 if (jb.act == 1) val = gelu_erf(val);
-                else if (jb.act == 2) val = fmaxf(val, 0.f);
+                else if (jb.act == 2) val = sk_relu(val);
                 jb.y[(int64_t)orow * jb.ldy + col] = val;
             }
         }
@@ -420,7 +423,7 @@ __global__ __launch_bounds__(256) void linear_rows_multi_kernel(const psam_skinn
             if (orow < M) {
                 float val = acc[v] + bv;
                 if (jb.act == 1) val = gelu_erf(val);
-                else if (jb.act == 2) val = fmaxf(val, 0.f);
+                else if (jb.act == 2) val = sk_relu(val);
                 jb.y[(int64_t)orow * jb.ldy + col] = val;
             }
         }

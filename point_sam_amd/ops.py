@@ -962,28 +962,54 @@ def linear_skinny_ln(x, W, bias, ln_w, ln_b, eps, residual=None, out=None):
     return out
 
 
-def linear_rows_multi(x, jobs, xadd_rows_per_set=1, xadd_rep=1):
-    """[y_i] = [act_i((x + xadd_i) W_i^T + bias_i)] for jobs = [(W, bias | None, xadd | None, act), ..] over the same rows of x in ONE launch, exact fp32
-    products (csrc/gemm.hip linear_rows_multi_kernel: 32 x 64 tiles; a few hundred to a few thousand rows).  xadd_i: sets of xadd_rows_per_set rows, set
-    (row // (xadd_rep * xadd_rows_per_set)) is added to row `row` (the decoder's key_pe)."""
+def _skinny_jobs(what, x, jobs, outs):
+    """psam_skinny_jobs_t of jobs = [(W, bias | None, xadd | None, act), ..] over the rows of x -> (js, outs, ldx, ldxadd, ldw).  outs: None, or one
+    [M, N_i] row view per job to write into (any row stride)."""
     xp, ldx = _row_view(x, "x")
-    M, K = x.shape
+    M = x.shape[0]
+    if not 1 <= len(jobs) <= len(_lib.SkinnyJobs().job) or (outs is not None and len(outs) != len(jobs)):
+        raise ValueError(f"{what}: one to {len(_lib.SkinnyJobs().job)} jobs, and an output per job")
     js = _lib.SkinnyJobs()
     js.n = len(jobs)
-    outs, ldw, ldxa = [], None, ldx
+    ys, ldw, ldxa = [], None, None
     for i, (W, bias, xadd, act) in enumerate(jobs):
         wp, lw = _row_view(W, "W")
         if ldw not in (None, lw):
-            raise ValueError("linear_rows_multi: the weights must share their row stride")
+            raise ValueError(f"{what}: the weights must share their row stride")
         ldw = lw
-        y = torch.empty(M, W.shape[0], dtype=torch.float32, device=x.device)
-        outs.append(y)
+        y = torch.empty(M, W.shape[0], dtype=torch.float32, device=x.device) if outs is None else outs[i]
+        yp, ldy = _row_view(y, "out")
+        if tuple(y.shape) != (M, W.shape[0]):
+            raise ValueError(f"{what}: output {i} must be [{M}, {W.shape[0]}], got {tuple(y.shape)}")
+        ys.append(y)
         ap = 0
         if xadd is not None:
-            ap, ldxa = _row_view(xadd, "xadd")
-        js.job[i] = _lib.SkinnyJob(xp, ap, wp, _p(bias), y.data_ptr(), y.stride(0), W.shape[0], act)
+            ap, la = _row_view(xadd, "xadd")
+            if ldxa not in (None, la):
+                raise ValueError(f"{what}: the addends must share their row stride")
+            ldxa = la
+        js.job[i] = _lib.SkinnyJob(xp, ap, wp, _p(bias), yp, ldy, W.shape[0], act)
+    return js, ys, ldx, ldx if ldxa is None else ldxa, ldw
+
+
+def linear_rows_multi(x, jobs, xadd_rows_per_set=1, xadd_rep=1, outs=None):
+    """[y_i] = [act_i((x + xadd_i) W_i^T + bias_i)] for jobs = [(W, bias | None, xadd | None, act), ..] over the same rows of x in ONE launch, exact fp32
+    products (csrc/gemm.hip linear_rows_multi_kernel: 32 x 64 tiles; a few hundred to a few thousand rows).  xadd_i: sets of xadd_rows_per_set rows, set
+    (row // (xadd_rep * xadd_rows_per_set)) is added to row `row` (the decoder's key_pe).  outs: row views to write into instead of new tensors."""
+    js, ys, ldx, ldxa, ldw = _skinny_jobs("linear_rows_multi", x, jobs, outs)
+    M, K = x.shape
     check(_lib.load().psam_linear_rows_multi(ctypes.byref(js), ldx, ldxa, xadd_rows_per_set, xadd_rep, ldw, M, K, _stream()), "psam_linear_rows_multi")
-    return outs
+    return ys
+
+
+def linear_skinny_multi(x, jobs, outs=None):
+    """[y_i] = [act_i((x + xadd_i) W_i^T + bias_i)] for jobs = [(W, bias | None, xadd | None, act), ..] (linear_rows_multi's tuples; xadd_i [M, K], row for
+    row) over the same M <= 64 rows of x in ONE launch (csrc/gemm.hip linear_skinny_multi_kernel: the q / k / v projections of a decoder attention): per
+    job the bits of linear() on the pre-added input."""
+    js, ys, ldx, ldxa, ldw = _skinny_jobs("linear_skinny_multi", x, jobs, outs)
+    M, K = x.shape
+    check(_lib.load().psam_linear_skinny_multi(ctypes.byref(js), ldx, ldxa, ldw, M, K, _stream()), "psam_linear_skinny_multi")
+    return ys
 
 
 def linear_ln256(x, W, bias, ln_w, ln_b, eps, residual=None, out=None):

@@ -727,6 +727,33 @@ int32_t psam_interp_scene_rows(const float* src, int64_t src_ld, const int32_t* 
 int32_t psam_interp_scene_bits(const float* src, int64_t src_ld, const int32_t* idx3, const float* w3, int32_t K, int32_t Nw, int32_t M,
                                float thr, uint64_t* bits_f, int32_t* area_f, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- masks carried to another cloud */
+
+/* A radius-limited 3-NN search from the points of one cloud into ANOTHER cloud (point_sam_amd/transfer.py), written as a plan in the format of
+ * psam_interp_scene_plan: psam_interp_scene_rows / psam_interp_scene_bits apply it unchanged (Nw = N).  All arithmetic is fp32, every operation
+ * rounded on its own; every output is a function of the inputs alone.  No call allocates or synchronises with the host.
+ *
+ * src [N, 3] the sources, qry [M, 3] the queries, r the radius: h = r, inv_h = fl32(1 / r), r2 = fl32(r * r); origin: three floats in HOST memory
+ * (the Python host takes fl32(min of the sources per axis - r)); pose: NULL, or 12 floats in HOST memory, row-major 3 x 4, query frame -> source frame.
+ *     query coordinate  p = qry[i] bit for bit without a pose, else p_a = ((P[a][0] x + P[a][1] y) + P[a][2] z) + P[a][3]
+ *     cells             those of the voxel downsample with (origin, inv_h); a source without a cell (not finite, or outside [0, 2^21) on an axis) is
+ *                       never a candidate, a query without a cell has no candidates
+ *     candidates        every source j whose cell differs from cell(p) by at most 1 on every axis (cells outside [0, 2^21) hold nothing) and whose
+ *                       q_j = (dx dx + dy dy) + dz dz <= r2, d = p - src[j]; NaN compares false
+ *     selection, weights, exact hit (q_0 == 0 or a lone candidate: a copy), unused entries: psam_interp_scene_plan's, ordered by (q, j), eps its eps
+ *     no candidate      idx3 = (-1, -1, -1), w3 = (0, 0, 0)
+ * The 27-cell set IS the definition.  It equals the true radius-r search except where the fp32 rounding of (x - origin) * inv_h moves a point across
+ * a cell face while the two points lie at distance ~ r: a source with q <= r2 can then sit two cells away and is not seen.
+ *
+ * The index (workspace, 16-byte aligned, psam_transfer_index_workspace_bytes(N) bytes, 0 for N outside (0, 2^28]) belongs to (src, N, origin, inv_h):
+ * psam_transfer_plan must be given the same four.  Its layout is private; results do not depend on the order in which sources arrived in it.
+ * A null pointer, N or M outside (0, 2^28], inv_h, r2 or eps not finite and positive, an origin or pose that is not finite: -1; a misaligned
+ * pointer: -2; a short workspace: -3. */
+size_t psam_transfer_index_workspace_bytes(int32_t N);
+int32_t psam_transfer_index_build(const float* src, int32_t N, const float* origin, float inv_h, void* ws, size_t ws_bytes, psam_stream_t stream);
+int32_t psam_transfer_plan(const float* src, int32_t N, const void* ws, size_t ws_bytes, const float* origin, float inv_h, float r2,
+                           const float* qry, int32_t M, const float* pose, float eps, int32_t* idx3, float* w3, psam_stream_t stream);
+
 /* ---------------------------------------------------------------- connected components of masks */
 
 /* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel

@@ -145,6 +145,9 @@ SIGNATURES = {
     "psam_interp_scene_plan": (i32, [ptr, i32, ptr, ptr, ptr, i32, ptr, f32, f32, ptr, ptr, ptr]),
     "psam_interp_scene_rows": (i32, [ptr, i64, ptr, ptr, i32, i32, i32, f32, ptr, i64, ptr]),
     "psam_interp_scene_bits": (i32, [ptr, i64, ptr, ptr, i32, i32, i32, f32, ptr, ptr, ptr]),
+    "psam_transfer_index_workspace_bytes": (size_t, [i32]),
+    "psam_transfer_index_build": (i32, [ptr, i32, ptr, f32, ptr, size_t, ptr]),
+    "psam_transfer_plan": (i32, [ptr, i32, ptr, size_t, ptr, f32, f32, ptr, i32, ptr, f32, ptr, ptr, ptr]),
     "psam_region_neighbors_workspace_bytes": (size_t, [i32]),
     "psam_region_neighbors": (i32, [ptr, ptr, i32, ptr, f32, ptr, ptr, size_t, ptr]),
     "psam_region_labels_workspace_bytes": (size_t, [i32, i32, i32]),

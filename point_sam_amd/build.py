@@ -34,6 +34,9 @@ SOURCES = [
     ("regions.hip", ["-ffp-contract=off"]),    # the same cells as scene.hip (csrc/voxel_cell.h)
     ("crops.hip", ["-ffp-contract=off"]),      # membership, normalised coordinates and cells of a ball of the scan: every fp32 operation rounded on its own
     ("scene_interp.hip", ["-ffp-contract=off"]),      # 3-NN blend over the voxel neighbourhood: distances, weights and the blend rounded one operation at a time
+    # radius 3-NN into another cloud: the cells of scene.hip, the distances and weights of scene_interp.hip.  No SLP vectorisation, as for geometry.hip
+    # below: it packs two rows of the pose into a v_pk_mul_f32 that broadcasts one half of a register pair.
+    ("transfer.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # instance geometry: the extents' fp32 operations rounded one at a time, the moments' fp64 terms exact.  No SLP vectorisation: it packs the three
     # projections into v_pk_mul_f32 / v_pk_add_f32 that broadcast one half of a register pair, the form isa_lint.py refuses; the kernels are gather-bound.
     ("geometry.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

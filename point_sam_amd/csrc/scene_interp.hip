@@ -15,6 +15,7 @@
 // function of the inputs alone: no atomics, no hand-over between threads, no data-dependent loops.
 #include "common.h"
 #include "crop_coord.h"      // the crop's normalised coordinate: the same bits as the crop cloud's own points
+#include "interp_select.h"   // the ascending triple of (q, rank) and the weights: transfer.hip's too
 #include "row_popcount.h"    // the area pass of the packed masks
 #include "voxel_cell.h"      // VOXEL_MAX_POINTS, u64
 
@@ -23,25 +24,6 @@
 
 constexpr int INTERP_THREADS = 256;
 constexpr int INTERP_NBR = 26;                    // words of a voxel's row of nbr: 104 bytes, thirteen 8-byte loads
-
-struct InterpBest {
-    float q0, q1, q2;
-    int r0, r1, r2;
-};
-
-// (q, r) enters the ascending triple where it belongs; lexicographic, so a distance tie goes to the lower rank.  The unused entries are
-// (+inf, INT_MAX): nothing compares below them but a real candidate, and an unused candidate (the same pair) displaces nothing.
-__device__ __forceinline__ void interp_insert(InterpBest& b, float q, int r) {
-    const bool lt0 = q < b.q0 || (q == b.q0 && r < b.r0);
-    const bool lt1 = q < b.q1 || (q == b.q1 && r < b.r1);
-    const bool lt2 = q < b.q2 || (q == b.q2 && r < b.r2);
-    b.q2 = lt1 ? b.q1 : lt2 ? q : b.q2;
-    b.r2 = lt1 ? b.r1 : lt2 ? r : b.r2;
-    b.q1 = lt0 ? b.q0 : lt1 ? q : b.q1;
-    b.r1 = lt0 ? b.r0 : lt1 ? r : b.r1;
-    b.q0 = lt0 ? q : b.q0;
-    b.r0 = lt0 ? r : b.r0;
-}
 
 // A candidate rank outside [0, Nw) (-1: no occupied voxel there) reads the point's own representative again and is entered as unused.
 __device__ __forceinline__ void interp_candidate(InterpBest& b, const float* __restrict__ wxyz, int r, int own, int Nw, float px, float py, float pz) {
@@ -76,25 +58,14 @@ __global__ __launch_bounds__(INTERP_THREADS) void interp_plan_kernel(const float
     int2 n[INTERP_NBR / 2];
 #pragma unroll
     for (int o = 0; o < INTERP_NBR / 2; ++o) n[o] = row[o];
-    InterpBest b = {__builtin_inff(), __builtin_inff(), __builtin_inff(), INT_MAX, INT_MAX, INT_MAX};
+    InterpBest b = interp_none();
     interp_candidate(b, wxyz, v, v, Nw, p[0], p[1], p[2]);
 #pragma unroll
     for (int o = 0; o < INTERP_NBR / 2; ++o) {
         interp_candidate(b, wxyz, n[o].x, v, Nw, p[0], p[1], p[2]);
         interp_candidate(b, wxyz, n[o].y, v, Nw, p[0], p[1], p[2]);
     }
-    const bool two = b.r1 != INT_MAX, three = b.r2 != INT_MAX;
-    // the blend; an exact hit or a lone candidate is a copy instead
-    const float a0 = 1.0f / fmaxf(b.q0, eps), a1 = 1.0f / fmaxf(b.q1, eps), a2 = 1.0f / fmaxf(b.q2, eps);
-    float s = a0 + a1;
-    if (three) s = s + a2;
-    const bool copy = !two || b.q0 == 0.0f || b.r0 == INT_MAX;     // r0 == INT_MAX: only a non-finite coordinate gets here (q is NaN for every candidate)
-    oi[0] = b.r0 == INT_MAX ? -1 : b.r0;
-    oi[1] = copy ? -1 : b.r1;
-    oi[2] = copy || !three ? -1 : b.r2;
-    ow[0] = b.r0 == INT_MAX ? 0.0f : copy ? 1.0f : a0 / s;
-    ow[1] = copy ? 0.0f : a1 / s;
-    ow[2] = copy || !three ? 0.0f : a2 / s;
+    interp_finish(b, eps, oi, ow);
 }
 
 PSAM_API int32_t psam_interp_scene_plan(const float* xyz, int32_t M, const int64_t* inv, const float* wxyz, const int32_t* nbr, int32_t Nw,

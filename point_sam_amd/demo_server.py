@@ -15,6 +15,8 @@ POST /crop {center, radius} . POST /crop/clear (not in the reference): zoom into
 from the ball's own working cloud (predictor.set_crop), still per loaded point, until the crop is cleared or another cloud is loaded.
 POST /instances (not in the reference): /segment_all plus one box per kept mask (predictor.mask_geometry) . POST /crop/selection {margin}: zoom
 into the ball around the current /segment mask (predictor.set_crop_to_mask).
+POST /propagate {pointcloud, radius, pose?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
+there (predictor.snapshot / propagate).
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -76,6 +78,7 @@ class DemoSession:
         self.device = torch.device(device)
         self.lock = threading.Lock()          # the reference is single-threaded; requests are serialised here
         self.pc_xyz = self.pc_rgb = None
+        self.norm = None                       # (shift, scale) that normalised the loaded cloud; None for a client-side sampled one
         self.obj_path = None
         self.masks = []
         self._reset_prompts()
@@ -103,22 +106,33 @@ class DemoSession:
             self.pc_xyz = torch.from_numpy(pts).to(self.device).float()[None]
             self.pc_rgb = torch.from_numpy(col).to(self.device).float()[None]
             self.crop = None
+            self.norm = None
         return {"response": "success"}
 
     def load_pointcloud(self, path: str) -> dict:
         """Loads an ASCII PLY from models_dir, normalises it into the unit ball, rgb / 255 (app.py:111-141).  As in the
         reference, a configured --pointcloud overrides the requested name."""
+        loaded = self._read_pointcloud(path, None)
+        with self.lock:
+            return self._install_pointcloud(*loaded)
+
+    def _read_pointcloud(self, path: str, norm):
+        """-> (name, xyz, rgb, norm).  norm: None, or the (shift, scale) of another cloud to normalise this one with (/propagate)."""
         name = self.pointcloud or path
         pts = load_ply(safe_join(self.models_dir, name))
         xyz, rgb = pts[:, :3], pts[:, 3:6] / 255
-        shift = xyz.mean(0)
-        scale = np.linalg.norm(xyz - shift, axis=-1).max()
-        xyz = (xyz - shift) / scale
-        with self.lock:
-            self.obj_path = name
-            self.pc_xyz = torch.from_numpy(xyz).to(self.device).float()[None]
-            self.pc_rgb = torch.from_numpy(rgb).to(self.device).float()[None]
-            self.crop = None
+        if norm is None:
+            shift = xyz.mean(0)
+            norm = (shift, np.linalg.norm(xyz - shift, axis=-1).max())
+        return name, (xyz - norm[0]) / norm[1], rgb, norm
+
+    def _install_pointcloud(self, name, xyz, rgb, norm) -> dict:
+        """The caller holds the lock."""
+        self.obj_path = name
+        self.pc_xyz = torch.from_numpy(xyz).to(self.device).float()[None]
+        self.pc_rgb = torch.from_numpy(rgb).to(self.device).float()[None]
+        self.crop = None
+        self.norm = norm
         return {"xyz": xyz.flatten().tolist(), "rgb": rgb.flatten().tolist()}
 
     def static_file(self, rel: str):
@@ -187,6 +201,53 @@ class DemoSession:
                     bits, _, _ = self.predictor.clean_masks(logits[:1, best:best + 1], cfg, pts, lab)
                 self.segment_mask = ops.mask_unpack(bits, mask.shape[-1])[0]
             return {"seg": self.segment_mask.cpu().numpy().tolist()}
+
+    def propagate(self, data: dict) -> dict:
+        """The next scan of a sequence: {"pointcloud": name, "radius": r, "pose": 3 x 4 or 4 x 4 rows (optional)}.  The kept masks (/next) plus the
+        current /segment mask become a snapshot of the loaded cloud (a mask's logits are +1 inside, -1 outside: the session keeps masks, not logits);
+        the named cloud is loaded as /pointcloud/ does, but normalised with the SAME shift and scale as the cloud it follows (a transfer compares
+        coordinates; a point that leaves the unit ball is the model's ValueError), and predictor.propagate re-segments every object there.  radius
+        and pose are in those normalised coordinates, pose from the new cloud to the previous one.  -> {"xyz", "rgb" (the new cloud, as
+        /pointcloud/), "objects": [{"seg": [...]} per object, /segment's format], "lost": [bool per object], "scores": [float or null]}.  The
+        propagated masks replace the kept ones, the click state is reset and a crop dropped.  Before any mask, or with a bad value: a 400 that
+        leaves the previous state."""
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/propagate before a point cloud was set")
+            masks = list(self.masks) + ([self.segment_mask.cpu().numpy()] if self.segment_mask is not None else [])
+            if not masks:
+                raise ValueError("/propagate before any /segment: there is no mask to carry over")
+            if not isinstance(data, dict) or not {"pointcloud", "radius"} <= set(data) or set(data) - {"pointcloud", "radius", "pose"}:
+                raise ValueError('/propagate takes {"pointcloud": name, "radius": r, "pose": rows (optional)}')
+            name, radius, pose = data["pointcloud"], data["radius"], data.get("pose")
+            if not isinstance(name, str) or not name:
+                raise ValueError("pointcloud must be a file name")
+            if isinstance(radius, bool) or not isinstance(radius, (int, float)) or not 0 < radius < float("inf"):
+                raise ValueError("radius must be a finite positive number")
+            from . import ops
+            ops.transfer_pose(pose)                # a bad pose is refused before anything is loaded
+            if any(m.shape != (self.pc_xyz.shape[1],) for m in masks):
+                raise ValueError("/propagate: a kept mask does not belong to the loaded cloud")
+            before = (self.pc_xyz, self.pc_rgb, self.obj_path, self.crop, self.norm)
+            try:
+                with torch.no_grad():
+                    self.crop = None
+                    self._set_cloud()
+                    inside = torch.from_numpy(np.stack(masks).astype(bool)).to(self.device)
+                    snap = self.predictor.snapshot(torch.where(inside, 1.0, -1.0).float())
+                    cloud = self._install_pointcloud(*self._read_pointcloud(name, self.norm))
+                    self._set_cloud()
+                    res = self.predictor.propagate(snap, float(radius), pose)
+            except Exception:
+                self.pc_xyz, self.pc_rgb, self.obj_path, self.crop, self.norm = before
+                raise
+            segs = (res.logits > 0).cpu().numpy()
+            scores = res.scores.cpu().numpy().astype(float)
+            self.masks = [m for m in segs]
+            self._reset_prompts()
+            self.segment_mask = None
+            return dict(cloud, objects=[{"seg": m.tolist()} for m in segs], lost=res.lost.cpu().numpy().astype(bool).tolist(),
+                        scores=[float(v) if np.isfinite(v) else None for v in scores])
 
     def set_crop(self, data: dict) -> dict:
         """Zoom: {"center": [x, y, z], "radius": r} in the loaded cloud's coordinates.  The crop is built (and its cloud encoded) now, so an empty
@@ -366,7 +427,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
             except json.JSONDecodeError as e:
                 return self._send(400, {"error": f"bad JSON: {e}"})
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
-                      "/segment_all": lambda: session.segment_all(data),
+                      "/segment_all": lambda: session.segment_all(data), "/propagate": lambda: session.propagate(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/instances": lambda: session.instances(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}

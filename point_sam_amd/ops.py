@@ -1487,6 +1487,120 @@ def scene_interp_bits(src: torch.Tensor, idx3: torch.Tensor, w3: torch.Tensor, t
     return bits_f, area_f
 
 
+# ------------------------------------------------------------------------------------------ masks carried to another cloud (csrc/transfer.hip)
+class TransferIndex:
+    """The sources of a radius search, indexed by cells of the radius' size (transfer_index): `ws` is the library's workspace (layout private),
+    `src_xyz` [N, 3] the sources it was built from (kept alive: the plan reads them), `radius`, `inv_h` = fl32(1 / radius) and `r2` =
+    fl32(radius * radius) fp32 values, `origin` three fp32 values."""
+    __slots__ = ("ws", "src_xyz", "radius", "inv_h", "r2", "origin")
+
+    def __init__(self, ws, src_xyz, radius, inv_h, r2, origin):
+        self.ws, self.src_xyz, self.radius, self.inv_h, self.r2, self.origin = ws, src_xyz, radius, inv_h, r2, origin
+
+    @property
+    def num_source(self) -> int:
+        return self.src_xyz.shape[0]
+
+
+def transfer_radius(radius):
+    """-> (r, inv_h, r2) as fp32 values: r = fl32(radius), inv_h = fl32(1 / r), r2 = fl32(r * r).  ValueError unless all three are finite and positive."""
+    import numpy as np
+    if isinstance(radius, bool) or not isinstance(radius, (int, float, np.floating, np.integer)):
+        raise ValueError(f"transfer: radius must be a number, got {radius!r}")
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        r = np.float32(radius)
+        inv_h = np.float32(1) / r
+        r2 = np.float32(r * r)
+    if not (np.isfinite(r) and r > 0 and np.isfinite(inv_h) and inv_h > 0 and np.isfinite(r2) and r2 > 0):
+        raise ValueError(f"transfer: radius must be finite and positive with a finite positive fp32 inverse and square, got {radius!r}")
+    return r, inv_h, r2
+
+
+def transfer_pose(pose):
+    """A 3 x 4 or 4 x 4 array-like (query frame -> source frame) -> its twelve fp32 words, row-major 3 x 4; None stays None.  ValueError for another
+    shape, a value that is not finite, or a 4 x 4 whose last row is not (0, 0, 0, 1)."""
+    import numpy as np
+    if pose is None:
+        return None
+    if isinstance(pose, torch.Tensor):
+        pose = pose.detach().cpu().numpy()
+    try:
+        P = np.asarray(pose, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"transfer: pose must be a 3 x 4 or 4 x 4 array of numbers, got {pose!r}") from None
+    if P.shape not in ((3, 4), (4, 4)):
+        raise ValueError(f"transfer: pose must be 3 x 4 or 4 x 4, got shape {P.shape}")
+    if P.shape == (4, 4) and not np.array_equal(P[3], [0.0, 0.0, 0.0, 1.0]):
+        raise ValueError(f"transfer: the last row of a 4 x 4 pose must be (0, 0, 0, 1), got {P[3].tolist()}")
+    with np.errstate(over="ignore"):
+        words = P[:3].astype(np.float32).reshape(12)
+    if not np.isfinite(words).all():
+        raise ValueError("transfer: pose must be finite in fp32")
+    return words
+
+
+def _transfer_cloud(xyz, what: str):
+    if not isinstance(xyz, torch.Tensor):
+        raise TypeError(f"{what} must be a tensor, got {type(xyz).__name__}")
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or not 1 <= xyz.shape[0] <= 1 << 28:
+        raise ValueError(f"{what} must be [n, 3] with 1 <= n <= 2^28, got {tuple(xyz.shape)}")
+    if xyz.dtype != torch.float32:
+        raise TypeError(f"{what}: expected {torch.float32}, got {xyz.dtype}")
+    return xyz
+
+
+def transfer_index(src_xyz: torch.Tensor, radius) -> TransferIndex:
+    """src_xyz [N, 3] f32, radius -> a TransferIndex for transfer_plan: the sources in cells of size `radius` from origin = fl32(min of the sources per
+    axis - radius) (include/pointsam_hip.h: masks carried to another cloud).  One device reduction and one host read (the sources' bounds).
+    ValueError for sources that are not finite, a bad radius (transfer_radius), or an extent of 2^21 cells or more on an axis."""
+    import numpy as np
+    src_xyz = _transfer_cloud(src_xyz, "transfer_index: src_xyz")
+    r, inv_h, r2 = transfer_radius(radius)
+    lo, hi = torch.aminmax(src_xyz, dim=0)                     # a NaN propagates into both, an infinity into one
+    bounds = torch.stack([lo, hi]).cpu().numpy()
+    if not np.isfinite(bounds).all():
+        raise ValueError("transfer_index: src_xyz must be finite")
+    if ((bounds[1].astype(np.float64) - bounds[0].astype(np.float64)) / float(r) + 3 >= float(1 << 21)).any():
+        raise ValueError(f"transfer_index: the sources span {bounds[0].tolist()} .. {bounds[1].tolist()}: 2^21 cells of size {float(r)} or more on an axis")
+    with np.errstate(over="ignore"):
+        origin = (bounds[0] - r).astype(np.float32)
+    if not np.isfinite(origin).all():
+        raise ValueError("transfer_index: min - radius is not finite in fp32")
+    _chk(src_xyz, name="src_xyz")
+    N = src_xyz.shape[0]
+    L = _lib.load()
+    ws = torch.empty(L.psam_transfer_index_workspace_bytes(N) // 8 + 2, dtype=torch.int64, device=src_xyz.device)      # torch allocations are at least 16-byte aligned
+    org = (ctypes.c_float * 3)(*[float(v) for v in origin])
+    check(L.psam_transfer_index_build(src_xyz.data_ptr(), N, ctypes.addressof(org), float(inv_h), ws.data_ptr(), ws.numel() * 8, _stream()),
+          "psam_transfer_index_build")
+    return TransferIndex(ws, src_xyz, r, inv_h, r2, tuple(float(v) for v in origin))
+
+
+def transfer_plan(index: TransferIndex, xyz: torch.Tensor, pose=None, eps: float = 1e-8):
+    """index (transfer_index), xyz [M, 3] f32 (the queries), pose (3 x 4 or 4 x 4 array-like, query frame -> source frame, or None) -> (idx3 [M, 3]
+    int32, w3 [M, 3] f32) in scene_interp_plan's format: per query the up to three sources nearest to pose(xyz), by (squared distance, index), among
+    those within the radius in its own and the 26 surrounding cells; a query without one gets idx3 = -1, w3 = 0.  scene_interp_rows /
+    scene_interp_bits apply the plan.  No host synchronisation."""
+    if not isinstance(index, TransferIndex):
+        raise TypeError(f"transfer_plan: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
+    xyz = _transfer_cloud(xyz, "transfer_plan: xyz")
+    words = transfer_pose(pose)
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 < eps < float("inf"):
+        raise ValueError(f"transfer_plan: eps must be finite and positive, got {eps!r}")
+    _chk(xyz, name="xyz")
+    M, N, dev = xyz.shape[0], index.num_source, xyz.device
+    idx3 = torch.empty(M, 3, dtype=torch.int32, device=dev)
+    w3 = torch.empty(M, 3, dtype=torch.float32, device=dev)
+    org = (ctypes.c_float * 3)(*index.origin)
+    P = None if words is None else (ctypes.c_float * 12)(*[float(v) for v in words])
+    check(_lib.load().psam_transfer_plan(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org),
+                                         float(index.inv_h), float(index.r2), xyz.data_ptr(), M, None if P is None else ctypes.addressof(P), float(eps),
+                                         idx3.data_ptr(), w3.data_ptr(), _stream()), "psam_transfer_plan")
+    return idx3, w3
+
+
 # ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)
 def _region_ws(nbytes: int, dev, what: str):
     if nbytes == 0:

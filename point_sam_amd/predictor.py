@@ -187,6 +187,11 @@ class PointSAMPredictor:
         (set_scene / set_crop smooth=True) the logits are the 3-NN blend of the working cloud's; at the representatives they are the working
         cloud's bit for bit, so they serve as the next click's prompt_mask exactly like the working-width logits."""
         logits, scores, sc, crop = self._decode(prompt_points, prompt_labels, prompt_mask, multimask_output)
+        logits = self._expand_logits(logits, sc, crop)
+        return logits, scores, logits
+
+    def _expand_logits(self, logits, sc, crop):
+        """Working-width logits [..., num_working] -> the scan's width [..., M] through the active mapping `sc` (None after set_pointcloud: unchanged)."""
         plan = self._interp_plan()
         if plan is not None:
             logits = ops.scene_interp_rows(logits, plan.idx3, plan.w3, float("-inf") if crop else None)      # [M', C, num_working] -> [M', C, M]
@@ -194,7 +199,7 @@ class PointSAMPredictor:
             logits = ops.crop_expand_rows(logits, sc.inv, float("-inf"))      # [M', C, num_working] -> [M', C, M]; -inf off the ball
         elif sc is not None and not sc.identity:
             logits = ops.scene_expand_rows(logits, sc.inv)       # [M', C, num_working] -> [M', C, M]: each point takes its representative's logit
-        return logits, scores, logits
+        return logits
 
     @torch.no_grad()
     def predict_mask_bits(self, prompt_points=None, prompt_labels=None, prompt_mask=None, multimask_output: bool = True, threshold: float = 0.0):
@@ -214,6 +219,96 @@ class PointSAMPredictor:
         elif sc is not None and not sc.identity:
             bits, area = ops.scene_expand_bits(bits, sc.inv, sc.num_working)
         return bits, area, scores
+
+    # -- from one scan to the next (point_sam_amd/transfer.py) ------------------------------------------------
+    def _transfer_cloud(self, what: str):
+        """(encoder state, scene or None) of the one cloud that snapshot / transfer_masks / propagate work on."""
+        if self._state is None:
+            raise RuntimeError(f"{what}: call set_scene() or set_pointcloud() first")
+        if self.crop is not None:
+            raise RuntimeError(f"{what}: not under a crop (crops are neither source nor destination of a transfer): call clear_crop() first")
+        if self._state.coords.shape[0] != 1:
+            raise ValueError(f"{what}: one cloud at a time, the cached batch holds {self._state.coords.shape[0]}")
+        return self._state, self.scene
+
+    @torch.no_grad()
+    def snapshot(self, logits: torch.Tensor):
+        """What the next scan needs of this one: -> transfer.Snapshot of the working cloud's coordinates as encoded and the K objects' logits at working
+        width.  logits [K, n] f32, n the scan's or the working cloud's width; of a scan-width row the representatives' own words are kept (exact, as
+        for a prompt_mask).  RuntimeError before any cloud is set and under an active crop."""
+        from . import transfer as T
+        from .scene import reduce_prompt_mask
+        state, sc = self._transfer_cloud("snapshot")
+        Nw = state.coords.shape[1]
+        logits = T.check_snapshot_logits(logits, (Nw,) if sc is None else (Nw, sc.num_points), "snapshot")
+        if sc is not None:
+            logits = reduce_prompt_mask(sc, logits)
+        return T.Snapshot(state.coords[0].contiguous(), logits.to(self.model.device).contiguous(), logits.shape[0])
+
+    def _scan_xyz(self, state, sc):
+        return state.coords[0].contiguous() if sc is None else self._keepalive[0]
+
+    @torch.no_grad()
+    def transfer_masks(self, snap, radius: float, pose=None, threshold: float = 0.0):
+        """The snapshot's masks at every point of the CURRENT cloud (after set_scene / set_pointcloud of the next scan), without the model: each point
+        receives the inverse-distance blend of the up to three snapshot points within `radius` of it (a lone one or an exact hit is copied), a point
+        with none is off.  -> (bits [K, W] int64 words of ``blend > threshold`` in mask_pack's layout, W = ceil(M / 64); area [K] int32;
+        covered_count, a 0-d int64 device tensor: the points with a snapshot point in reach).  pose: 3 x 4 or 4 x 4, this scan's coordinates -> the
+        snapshot's; both scans normalised with the same centre and scale.  No host synchronisation beyond the index build's read of the bounds."""
+        from . import transfer as T
+        T.check_snapshot(snap, "transfer_masks")
+        threshold = T.check_threshold(threshold, "transfer_masks")
+        state, sc = self._transfer_cloud("transfer_masks")
+        plan = T.build_plan(snap.coords, self._scan_xyz(state, sc), radius, pose)
+        bits, area = T.transfer_bits(plan, snap.logits, threshold)
+        return bits, area, T.covered(plan).sum()
+
+    @torch.no_grad()
+    def propagate(self, snap, radius: float, pose=None, clicks: int = 1, fill=None):
+        """The model re-segments every snapshot object in the CURRENT cloud -> transfer.Propagated.  The carried logits (`prior`: the blend of the
+        snapshot's logits at this working cloud's points; where no snapshot point is within `radius`, `fill`, or with fill=None the object's own
+        minimum snapshot logit -- the model's "most certainly background" for that object) serve as the mask prompt and, thresholded at 0, in place of
+        the ground truth of the reference's evaluation loop (pc_sam.py:139-194): click 0 is the deepest point of the carried mask, click i > 0 the
+        deepest point of the error of the previous output against it; every decode sees all clicks so far and the previous output (the prior for the
+        first) as mask prompt, single-mask output.  An object whose carried mask is empty is `lost`: -inf logits, NaN score, no part in the decode.
+        One host read (K + 1 counts) besides the index build's.  pose and normalisation as for transfer_masks.  Nothing here has been tuned on a
+        trained checkpoint (none exists offline)."""
+        from . import transfer as T
+        T.check_snapshot(snap, "propagate")
+        T.check_propagate_arguments(clicks, fill)
+        state, sc = self._transfer_cloud("propagate")
+        model, dev = self.model, self.model.device
+        K, Nw = snap.num_masks, state.coords.shape[1]
+        plan = T.build_plan(snap.coords, state.coords[0].contiguous(), radius, pose)
+        cov = T.covered(plan)
+        prior = T.transfer_rows(plan, snap.logits, 0.0)
+        outside = snap.logits.amin(dim=1, keepdim=True) if fill is None else torch.full((K, 1), float(fill), dtype=torch.float32, device=dev)
+        prior = torch.where(cov[None, :], prior, outside).contiguous()
+        gt = prior > 0
+        counts = torch.cat([gt.sum(1), cov.sum()[None]]).cpu()                     # the one host read
+        prior_area, lost = counts[:K].to(dev), (counts[:K] == 0).to(dev)
+        keep = torch.nonzero(counts[:K] > 0)[:, 0].to(dev)
+        M = Nw if sc is None else sc.num_points
+        out = torch.full((K, M), float("-inf"), dtype=torch.float32, device=dev)
+        scores = torch.full((K,), float("nan"), dtype=torch.float32, device=dev)
+        points = torch.full((K, clicks, 3), float("nan"), dtype=torch.float32, device=dev)
+        labels = torch.zeros(K, clicks, dtype=torch.bool, device=dev)
+        if keep.numel() > 0:
+            Z = keep.numel()
+            truth = gt.index_select(0, keep)[None]                                 # [1, Z, Nw]
+            prompt_mask, previous = prior.index_select(0, keep), None
+            pc = torch.empty(Z, 0, 3, dtype=torch.float32, device=dev)
+            pl = torch.empty(Z, 0, dtype=torch.bool, device=dev)
+            for _ in range(clicks):
+                nc, nl = model.sample_prompts(state.coords, truth, previous)
+                pc, pl = torch.cat([pc, nc], dim=1), torch.cat([pl, nl], dim=1)
+                masks, iou = model.decode(state, pc, pl, prompt_mask, multimask_output=False)
+                prompt_mask = previous = masks[:, 0].contiguous()
+            model.check_coordinate_range()
+            out[keep] = self._expand_logits(previous, sc, False)
+            scores[keep] = iou[:, 0].float()
+            points[keep], labels[keep] = pc, pl
+        return T.Propagated(out, scores, lost, prior_area, float(counts[K]) / Nw, points, labels)
 
     @torch.no_grad()
     def generate_masks(self, cfg=None, crops=None):

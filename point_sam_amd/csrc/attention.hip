@@ -11,7 +11,7 @@
 //                    for register, the B operand of the second (key(r,h) = (r&3)+8*(r>>2)+4*h on both sides).
 // K/V tiles of 64 keys are staged in LDS (K rows padded by 4 floats: conflict-free ds_read_b128), double
 // buffered with a register prefetch; Q stays in registers, pre-scaled by scale*log2(e) so softmax uses v_exp_f32.
-#include "common.h"
+#include "g8_pack.h"
 #include <math.h>
 #include <utility>
 #include <cstdlib>
@@ -255,18 +255,8 @@ PSAM_API int32_t psam_attention_f32(const float* q, int64_t ldq, int64_t sq, con
 //         rides on the online-softmax rescale that exists anyway.
 // LDS rows are 128 bytes with the 16-byte chunk XOR-swizzled by (row>>1)&7: conflict-free ds_read_b128 fragments.
 typedef _Float16 fa_f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 fa_f16x2 __attribute__((ext_vector_type(2)));
 typedef float fa_f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned fa_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned fa_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void fa_split2(const fa_f32x2 xs, unsigned& hi, unsigned& lo) {   // xs already scaled
-    const fa_f16x2 h = __builtin_convertvector(xs, fa_f16x2);
-    const fa_f32x2 r = xs - __builtin_convertvector(h, fa_f32x2);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, fa_f16x2));
-}
-__device__ __forceinline__ float fa_inv_pow2(float s) { return __builtin_bit_cast(float, (254u << 23) - __builtin_bit_cast(unsigned, s)); }
 
 // HD: head dim of the LDS layout, 64 or 128.  HDA <= HD (a multiple of 32): the channels that can be non-zero -- a head dim of 88 runs on the 128-wide layout
 // (power-of-two index maps) but issues the MFMAs, fragment reads and conversions of 96 channels only (round 6: the products with the zero padding add exact
@@ -367,8 +357,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
             if (HDA < HD && c4 * 4 >= HDA) continue;      // padding channels: never read (the k16 steps beyond HDA are not issued)
             unsigned h0, l0, h1, l1;
             // K planes: row-major, chunk (c4>>1) of the row swizzled
-            fa_split2(fa_f32x2{rk[i][0], rk[i][1]} * sk, h0, l0);
-            fa_split2(fa_f32x2{rk[i][2], rk[i][3]} * sk, h1, l1);
+            g8_split2_scaled(fa_f32x2{rk[i][0], rk[i][1]} * sk, h0, l0);
+            g8_split2_scaled(fa_f32x2{rk[i][2], rk[i][3]} * sk, h1, l1);
             const int koff = row * KROW + ((((c4 >> 1) ^ ((row >> 1) & KSW)) << 4) | ((c4 & 1) << 3));
             *reinterpret_cast<fa_u32x2*>(st + koff) = fa_u32x2{h0, h1};
             *reinterpret_cast<fa_u32x2*>(st + KPLANE + koff) = fa_u32x2{l0, l1};
@@ -383,8 +373,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
             for (int e = 0; e < 4; ++e) {
                 const int d = vc4 * 4 + e;
                 unsigned h0, l0, h1, l1;
-                fa_split2(fa_f32x2{rv[4 * ps][e], rv[4 * ps + 1][e]} * sv, h0, l0);
-                fa_split2(fa_f32x2{rv[4 * ps + 2][e], rv[4 * ps + 3][e]} * sv, h1, l1);
+                g8_split2_scaled(fa_f32x2{rv[4 * ps][e], rv[4 * ps + 1][e]} * sv, h0, l0);
+                g8_split2_scaled(fa_f32x2{rv[4 * ps + 2][e], rv[4 * ps + 3][e]} * sv, h1, l1);
                 const int voff = 2 * KPLANE + d * ROWB + ((((pos >> 3) ^ ((d >> 1) & 7)) << 4) | ((pos & 7) << 1));
                 *reinterpret_cast<fa_u32x2*>(st + voff) = fa_u32x2{h0, h1};
                 *reinterpret_cast<fa_u32x2*>(st + VPLANE + voff) = fa_u32x2{l0, l1};
@@ -428,17 +418,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
             }
         amax = fmaxf(amax, __shfl_xor(amax, 32, 64));
         const float sq = f16_row_scale(amax);
-        q_inv = fa_inv_pow2(sq);
+        q_inv = inv_pow2(sq);
 #pragma unroll
         for (int s = 0; s < KSA; ++s) {
             unsigned hi[4], lo[4];
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-                fa_split2(fa_f32x2{t[s][e][0], t[s][e][1]} * sq, hi[2 * e], lo[2 * e]);
-                fa_split2(fa_f32x2{t[s][e][2], t[s][e][3]} * sq, hi[2 * e + 1], lo[2 * e + 1]);
+                g8_split2_scaled(fa_f32x2{t[s][e][0], t[s][e][1]} * sq, hi[2 * e], lo[2 * e]);
+                g8_split2_scaled(fa_f32x2{t[s][e][2], t[s][e][3]} * sq, hi[2 * e + 1], lo[2 * e + 1]);
             }
-            qh[s] = __builtin_bit_cast(fa_f16x8, fa_u32x4{hi[0], hi[1], hi[2], hi[3]});
-            ql[s] = __builtin_bit_cast(fa_f16x8, fa_u32x4{lo[0], lo[1], lo[2], lo[3]});
+            qh[s] = __builtin_bit_cast(fa_f16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+            ql[s] = __builtin_bit_cast(fa_f16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
         }
     }
 
@@ -451,7 +441,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
         const int buf = (t - t_first) & 1;
         const unsigned char* st_base = smem + buf * STAGE;
         if (t + 1 < ntiles && !FA_ABL(2)) load_tile((t + 1) * FA_BKV);
-        const float c_s = p.scale_log2e * q_inv * fa_inv_pow2(sk_cur);     // S_scaled -> log2-domain logits
+        const float c_s = p.scale_log2e * q_inv * inv_pow2(sk_cur);     // S_scaled -> log2-domain logits
 #pragma unroll
         for (int kt = 0; kt < FA_BKV / 32; ++kt) {
             const int key_base = t * FA_BKV + kt * 32;
@@ -494,7 +484,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
             l_run = l_run * alpha + ps;
             m_run = m_new;
             // rescale O into the domain of this tile's V scale (ratio of powers of two) and the new running max
-            const float fo = alpha * (sv_cur * fa_inv_pow2(sv_acc));
+            const float fo = alpha * (sv_cur * inv_pow2(sv_acc));
             sv_acc = sv_cur;
             if (__builtin_amdgcn_ballot_w64(fo != 1.f) != 0) {
 #pragma unroll
@@ -510,10 +500,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (FA_ABL(4)) { hi[e] = __builtin_bit_cast(unsigned, st[8 * s2 + 2 * e]); lo[e] = __builtin_bit_cast(unsigned, st[8 * s2 + 2 * e + 1]); }
-                    else fa_split2(fa_f32x2{st[8 * s2 + 2 * e], st[8 * s2 + 2 * e + 1]}, hi[e], lo[e]);
+                    else g8_split2_scaled(fa_f32x2{st[8 * s2 + 2 * e], st[8 * s2 + 2 * e + 1]}, hi[e], lo[e]);
                 }
-                ph[s2] = __builtin_bit_cast(fa_f16x8, fa_u32x4{hi[0], hi[1], hi[2], hi[3]});
-                pl[s2] = __builtin_bit_cast(fa_f16x8, fa_u32x4{lo[0], lo[1], lo[2], lo[3]});
+                ph[s2] = __builtin_bit_cast(fa_f16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+                pl[s2] = __builtin_bit_cast(fa_f16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2)
@@ -545,14 +535,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
         // split-K fix-up (gemm_f16x3p.hip).  The last arrival re-reads ALL partials, its own too, and adds them in split order.
         constexpr int SC1 = 16, QUADS = DT * 4, SPLIT_BYTES = (QUADS * 256 + 128) * 16;      // + 256 x (m, l) pairs
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(p.sk_part + (int64_t)bid * p.ksplit * (SPLIT_BYTES / 4)), 0, 0x7fffffff, 0x00020000);
-        const float isv = fa_inv_pow2(sv_acc);
+        const float isv = inv_pow2(sv_acc);
 #pragma unroll
         for (int d = 0; d < DT; ++d)
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const float a0 = oacc[d][4 * r4] * isv, a1 = oacc[d][4 * r4 + 1] * isv, a2 = oacc[d][4 * r4 + 2] * isv, a3 = oacc[d][4 * r4 + 3] * isv;
                 const f32x4 vf = {a0, a1, a2, a3};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fa_u32x4, vf), rs, split * SPLIT_BYTES + ((d * 4 + r4) * 256 + tid) * 16, 0, SC1);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vf), rs, split * SPLIT_BYTES + ((d * 4 + r4) * 256 + tid) * 16, 0, SC1);
             }
         {
             const fa_f32x2 ml = {m_run, l_tot};
@@ -597,7 +587,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
         }
         sv_acc = 1.f;
     }
-    const float inv = fa_inv_pow2(sv_acc) / l_tot;                  // (oacc / (2^14 sv)) / (l_tot / 2^14)
+    const float inv = inv_pow2(sv_acc) / l_tot;                  // (oacc / (2^14 sv)) / (l_tot / 2^14)
     const int qrow = q0 + r32;
     if (p.o_scale) {
         // g8-packed rows: this lane holds channels d0..d0+3 of its query row, lane ^ 32 the other four of the same group of 8: the
@@ -609,11 +599,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HD == 64 ? 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d0 = d * 32 + 8 * g + 4 * h;
-                unsigned h0, l0, h1, l1;
-                fa_split2(fa_f32x2{oacc[d][4 * g] * inv, oacc[d][4 * g + 1] * inv} * out_scale, h0, l0);
-                fa_split2(fa_f32x2{oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv} * out_scale, h1, l1);
-                const unsigned r0 = __shfl_xor(h ? h0 : l0, 32, 64), r1 = __shfl_xor(h ? h1 : l1, 32, 64);
-                if (qrow < p.Lq && d0 < hd) *reinterpret_cast<fa_u32x4*>(op + d0) = h ? fa_u32x4{r0, r1, l0, l1} : fa_u32x4{h0, h1, r0, r1};
+                const u32x4 chunk = g8_chunk_scaled<32>(fa_f32x2{oacc[d][4 * g] * inv, oacc[d][4 * g + 1] * inv} * out_scale,
+                                                        fa_f32x2{oacc[d][4 * g + 2] * inv, oacc[d][4 * g + 3] * inv} * out_scale, lane);
+                if (qrow < p.Lq && d0 < hd) *reinterpret_cast<u32x4*>(op + d0) = chunk;
             }
         return;
     }
@@ -844,7 +832,7 @@ __global__ __launch_bounds__(64 * NW, RING == 2 ? 2 : 1) void flash_attn_packed_
             ql[u][s] = *reinterpret_cast<const fa_f16x8*>(qp + (2 * s + h) * 32 + 16);
         }
     }
-    const float inv_su = fa_inv_pow2(s_u);
+    const float inv_su = inv_pow2(s_u);
     const float c_s = p.scale_log2e * inv_su * inv_su;          // scaled-domain S -> log2-domain logits
 
     f32x16 oacc[QB][DT];
@@ -975,9 +963,9 @@ __global__ __launch_bounds__(64 * NW, RING == 2 ? 2 : 1) void flash_attn_packed_
             for (int s2 = 0; s2 < 2; ++s2) {
                 unsigned hi[4], lo[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) fa_split2(fa_f32x2{st[u][kt][8 * s2 + 2 * e], st[u][kt][8 * s2 + 2 * e + 1]}, hi[e], lo[e]);
-                const fa_f16x8 ph = __builtin_bit_cast(fa_f16x8, fa_u32x4{hi[0], hi[1], hi[2], hi[3]});
-                const fa_f16x8 pl = __builtin_bit_cast(fa_f16x8, fa_u32x4{lo[0], lo[1], lo[2], lo[3]});
+                for (int e = 0; e < 4; ++e) g8_split2_scaled(fa_f32x2{st[u][kt][8 * s2 + 2 * e], st[u][kt][8 * s2 + 2 * e + 1]}, hi[e], lo[e]);
+                const fa_f16x8 ph = __builtin_bit_cast(fa_f16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
+                const fa_f16x8 pl = __builtin_bit_cast(fa_f16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
 #pragma unroll
                 for (int d = 0; d < DT; ++d) oacc[u][d] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh[s2][d], pl, oacc[u][d], 0, 0, 0);      // the two channel tiles alternate
 #pragma unroll
@@ -1003,11 +991,9 @@ __global__ __launch_bounds__(64 * NW, RING == 2 ? 2 : 1) void flash_attn_packed_
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int d0 = d * 32 + 8 * g + 4 * h;
-                unsigned h0, l0, h1, l1;
-                fa_split2(fa_f32x2{oacc[u][d][4 * g] * inv, oacc[u][d][4 * g + 1] * inv} * out_scale, h0, l0);
-                fa_split2(fa_f32x2{oacc[u][d][4 * g + 2] * inv, oacc[u][d][4 * g + 3] * inv} * out_scale, h1, l1);
-                const unsigned r0 = __shfl_xor(h ? h0 : l0, 32, 64), r1 = __shfl_xor(h ? h1 : l1, 32, 64);
-                if (qrow[u] < p.L) *reinterpret_cast<fa_u32x4*>(op + d0) = h ? fa_u32x4{r0, r1, l0, l1} : fa_u32x4{h0, h1, r0, r1};
+                const u32x4 chunk = g8_chunk_scaled<32>(fa_f32x2{oacc[u][d][4 * g] * inv, oacc[u][d][4 * g + 1] * inv} * out_scale,
+                                                        fa_f32x2{oacc[u][d][4 * g + 2] * inv, oacc[u][d][4 * g + 3] * inv} * out_scale, lane);
+                if (qrow[u] < p.L) *reinterpret_cast<u32x4*>(op + d0) = chunk;
             }
     }
 }

@@ -25,11 +25,10 @@
 #include <string>
 #include <utility>
 #include <vector>
-#include "common.h"      // brings in include/pointsam_hip.h
+#include "g8_pack.h"     // kpad32; brings in common.h and with it include/pointsam_hip.h
 
 namespace {
 constexpr int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-inline int kpad(int k) { return (k + 31) / 32 * 32; }
 
 struct Carve {      // bump allocator over a caller-provided buffer; on a null base it only counts (`off` is then the size of the layout it walked)
     char* base; int64_t off = 0;
@@ -39,9 +38,9 @@ struct Carve {      // bump allocator over a caller-provided buffer; on a null b
 };
 template <typename F> size_t carved_bytes(F&& layout) { Carve cv(nullptr); layout(cv); return (size_t)cv.off; }      // the size of a layout
 
-// A weight [rows, K] as the packed-operand GEMMs read it: g8-packed hi|lo fp16 rows (kpad(K) floats each) and their power-of-two row scales
+// A weight [rows, K] as the packed-operand GEMMs read it: g8-packed hi|lo fp16 rows (kpad32(K) floats each) and their power-of-two row scales
 struct Packed { float* w; float* s; };
-Packed take_packed(Carve& cv, int64_t rows, int K) { float* w = cv.take<float>(rows * kpad(K)); return {w, cv.take<float>(rows)}; }
+Packed take_packed(Carve& cv, int64_t rows, int K) { float* w = cv.take<float>(rows * kpad32(K)); return {w, cv.take<float>(rows)}; }
 void put_offsets(const Carve& cv, const Packed& p, int64_t* o_w, int64_t* o_s) { *o_w = cv.offset_of(p.w); *o_s = cv.offset_of(p.s); }
 
 int32_t fail(const char* who, const char* what) { psam_set_error((std::string(who) + ": " + what).c_str()); return PSAM_EINVAL; }
@@ -50,7 +49,7 @@ int32_t fail(const char* who, const char* what) { psam_set_error((std::string(wh
 int32_t pack_weight(const char* who, const float* w, int64_t ldw, int rows, int K, const Packed& dst, hipStream_t stream) {
     if (!w) return fail(who, "null weight pointer");
     int32_t rc = psam_row_scale_f16(w, ldw, rows, K, dst.s, stream);
-    if (!rc) rc = psam_pack_rows_f16x2_g8(w, ldw, dst.s, rows, K, dst.w, kpad(K), stream);
+    if (!rc) rc = psam_pack_rows_f16x2_g8(w, ldw, dst.s, rows, K, dst.w, kpad32(K), stream);
     return rc;
 }
 int32_t packing_done(const char* who, int32_t rc, hipStream_t stream) {      // the end of every _prepare: the blob is complete when it returns
@@ -107,7 +106,7 @@ int32_t host_linear(const Lin& l, const float* x, int64_t M, float* y, int act, 
         return psam_linear_rows_multi(&jobs, l.K, l.K, 1, 1, l.ldw, M, l.K, stream);
     }
     if (M >= 256 && l.packed) {
-        const int kp = kpad(l.K);
+        const int kp = kpad32(l.K);
         int32_t rc = psam_scale_pack_rows_g8(x, l.K, (int32_t)M, l.K, pack_buf, kp, scale_buf, stream);
         if (rc) return rc;
         return psam_gemm_f16x3p_ex(pack_buf, kp, scale_buf, l.packed, kp, l.scales, y, l.N, l.b, nullptr, 0, nullptr, 0, 0, (int32_t)M, l.N, kp, 1.f, act, nullptr, stream);
@@ -123,7 +122,7 @@ inline const float* at(const void* prepared, int64_t off) { return reinterpret_c
 namespace {
 struct EvaPrepared { Packed qkv; float* bqkv; Packed proj; Packed w1; float* b1; Packed w2g; float *lnc, *lnd; };
 EvaPrepared eva_prepared(Carve& cv, int dim, int hidden) {
-    const int D = dim, Hp = kpad(hidden);
+    const int D = dim, Hp = kpad32(hidden);
     EvaPrepared p;
     p.qkv = take_packed(cv, 3 * D, D); p.bqkv = cv.take<float>(3 * D);      // q | k | v, their bias
     p.proj = take_packed(cv, D, D);
@@ -134,7 +133,7 @@ EvaPrepared eva_prepared(Carve& cv, int dim, int hidden) {
 
 struct EvaWs { float *h, *rs, *ub, *so, *qkv, *sq, *o, *u, *su, *st, *mean, *rstd; };
 EvaWs eva_ws(Carve& cv, int64_t M, int dim, int hidden) {
-    const int64_t D = dim, Dp = kpad(dim), Hp = kpad(hidden), segs = psam_gemm_f16x3p_stat_segs((int32_t)(2 * Hp));
+    const int64_t D = dim, Dp = kpad32(dim), Hp = kpad32(hidden), segs = psam_gemm_f16x3p_stat_segs((int32_t)(2 * Hp));
     EvaWs w;
     w.h = cv.take<float>(M * Dp);                                                    // LayerNorm output, packed
     w.rs = cv.take<float>(M); w.ub = cv.take<float>(M); w.so = cv.take<float>(M);    // its row scales, the gated rows' bound, attention output scales
@@ -162,7 +161,7 @@ PSAM_API int32_t psam_eva_block_prepare(const psam_eva_block_weights_t* wt, psam
     const int D = wt->dim, H = wt->hidden, heads = wt->heads;
     PSAM_REQUIRE(D > 0 && H > 0 && heads > 0 && D % heads == 0 && D / heads == 64 && D % 32 == 0, PSAM_EINVAL,
                  WHO ": head dim must be 64 and dim % 32 == 0 (the packed-operand attention)");
-    const int Hp = kpad(H);
+    const int Hp = kpad32(H);
     PSAM_REQUIRE(Hp % 64 == 0, PSAM_EINVAL, WHO ": hidden rounded up to 32 must be a multiple of 64 (fused SwiGLU epilogue)");
     PSAM_REQUIRE(prepared_bytes >= psam_eva_block_prepared_bytes(D, H), PSAM_EWORKSPACE, WHO ": prepared buffer too small");
     const float* ptrs[] = {wt->norm1_w, wt->norm1_b, wt->q_w, wt->q_b, wt->k_w, wt->v_w, wt->v_b, wt->proj_w, wt->proj_b, wt->norm2_w, wt->norm2_b,
@@ -265,7 +264,7 @@ PSAM_API size_t psam_eva_block_ws_bytes(int64_t M, int32_t dim, int32_t hidden) 
 // x [B*L, dim] (fp32, updated in place) <- block(x).  M = B * L must be a multiple of 256 (the fused GEMM epilogues work on whole tiles).
 PSAM_API int32_t psam_eva_block(const psam_eva_block_plan_t* plan, const void* prepared, float* x, int32_t B, int32_t L, void* ws, size_t ws_bytes, hipStream_t stream) {
     PSAM_REQUIRE(plan && prepared && x && ws, PSAM_EINVAL, "psam_eva_block: null pointer");
-    const int D = plan->dim, H = plan->hidden, Hp = plan->hidden_pad, heads = plan->heads, Dp = kpad(D);
+    const int D = plan->dim, H = plan->hidden, Hp = plan->hidden_pad, heads = plan->heads, Dp = kpad32(D);
     const int64_t M = (int64_t)B * L;
     PSAM_REQUIRE(B > 0 && L > 0 && M % 256 == 0 && M < ((int64_t)1 << 31), PSAM_EINVAL, "psam_eva_block: B * L must be a positive multiple of 256");
     PSAM_REQUIRE(ws_bytes >= psam_eva_block_ws_bytes(M, D, H), PSAM_EWORKSPACE, "psam_eva_block: workspace too small");
@@ -316,7 +315,7 @@ GeluPrepared gelu_prepared(Carve& cv, int dim, int hidden) {
 constexpr int64_t GELU_KS_WS_BYTES = (int64_t)32 << 20;
 struct GeluWs { float *h, *rs, *ub, *so, *sg, *qkv, *o, *g, *gp, *planes; char* ks_ws; };
 GeluWs gelu_ws(Carve& cv, int64_t M, int dim, int hidden) {
-    const int64_t D = dim, Dp = kpad(dim), Hp = kpad(hidden), widest = std::max(3 * D, Hp);
+    const int64_t D = dim, Dp = kpad32(dim), Hp = kpad32(hidden), widest = std::max(3 * D, Hp);
     GeluWs w;
     w.h = cv.take<float>(M * Dp);                                  // packed LayerNorm rows
     w.rs = cv.take<float>(M); w.ub = cv.take<float>(M); w.so = cv.take<float>(M); w.sg = cv.take<float>(M);      // its scales, the fc1 bound, attention-output scales, fc2-input scales
@@ -386,7 +385,7 @@ PSAM_API size_t psam_eva_gelu_block_ws_bytes(int64_t M, int32_t dim, int32_t hid
 PSAM_API int32_t psam_eva_gelu_block(const psam_eva_gelu_block_plan_t* plan, const void* prepared, float* x, int32_t B, int32_t L, void* ws, size_t ws_bytes,
                                      int32_t* counters, hipStream_t stream) {
     PSAM_REQUIRE(plan && prepared && x && ws, PSAM_EINVAL, "psam_eva_gelu_block: null pointer");
-    const int D = plan->dim, H = plan->hidden, heads = plan->heads, Dp = kpad(D), Hp = kpad(H), hd = D / heads;
+    const int D = plan->dim, H = plan->hidden, heads = plan->heads, Dp = kpad32(D), Hp = kpad32(H), hd = D / heads;
     const int64_t M = (int64_t)B * L;
     PSAM_REQUIRE(B > 0 && L > 0 && M >= 256 && M < ((int64_t)1 << 31), PSAM_EINVAL, "psam_eva_gelu_block: B * L must be at least 256 (the packed-operand GEMMs)");
     PSAM_REQUIRE(ws_bytes >= psam_eva_gelu_block_ws_bytes(M, D, H), PSAM_EWORKSPACE, "psam_eva_gelu_block: workspace too small");
@@ -450,7 +449,7 @@ PatchPrepared patch_prepared(Carve& cv, int h0, int h1, int cout) {
 
 struct PatchWs { float *x1, *x2, *s1, *s2, *rs, *y1, *y1p, *sy, *g1, *x3; };
 PatchWs patch_ws(Carve& cv, int64_t rows, int64_t groups, int h0, int h1) {
-    const int64_t a = kpad(h0), b = kpad(h1);
+    const int64_t a = kpad32(h0), b = kpad32(h1);
     PatchWs w;
     w.x1 = cv.take<float>(rows * a); w.x2 = cv.take<float>(rows * a);                                    // conv1.1 and conv1.3 rows, packed
     w.s1 = cv.take<float>(rows); w.s2 = cv.take<float>(rows); w.rs = cv.take<float>(rows);               // their scales, conv2.1's
@@ -511,7 +510,7 @@ PSAM_API int32_t psam_patch_encoder(const psam_patch_encoder_plan_t* plan, const
                                     const int64_t* knn_idx, const int64_t* center_idx, int32_t B, int32_t rep, int32_t N, int32_t G, int32_t K, int32_t C,
                                     float radius, float* out, void* ws, size_t ws_bytes, hipStream_t stream) {
     PSAM_REQUIRE(plan && prepared && xyz && feats && centers && knn_idx && out && ws, PSAM_EINVAL, "psam_patch_encoder: null pointer");
-    const int h0 = plan->h0, h1 = plan->h1, cout = plan->cout, a = kpad(h0), b = kpad(h1);
+    const int h0 = plan->h0, h1 = plan->h1, cout = plan->cout, a = kpad32(h0), b = kpad32(h1);
     const int64_t groups = (int64_t)B * rep * G, rows = groups * K;
     PSAM_REQUIRE(B > 0 && rep > 0 && N > 0 && G > 0 && (K == 32 || (K > 0 && K % 64 == 0)) && rows % 256 == 0 && rows < ((int64_t)1 << 31), PSAM_EINVAL,
                  "psam_patch_encoder: group size must be 32 or a multiple of 64, and B * rep * G * K a multiple of 256");
@@ -568,7 +567,7 @@ UpscalePrepared upscale_prepared(Carve& cv, int dim) { return {take_packed(cv, d
 
 struct UpscaleWs { float *kp, *k1, *sk, *up, *s1, *parts; };
 UpscaleWs upscale_ws(Carve& cv, int64_t Z, int N, int G, int C, int dim) {
-    const int64_t a = kpad(dim), planes = psam_gemm_f16x3p_hyper_planes(dim, 0);
+    const int64_t a = kpad32(dim), planes = psam_gemm_f16x3p_hyper_planes(dim, 0);
     UpscaleWs w;
     w.kp = cv.take<float>(Z * G * a); w.k1 = cv.take<float>(Z * G * a); w.sk = cv.take<float>(Z * G);      // the patch rows packed, after the first Linear, their scales
     w.up = cv.take<float>(Z * N * a); w.s1 = cv.take<float>(Z * N);                                        // interpolated rows after LayerNorm + GELU, packed, their scales
@@ -610,7 +609,7 @@ PSAM_API int32_t psam_upscale_masks(const psam_upscale_plan_t* plan, const void*
                                     const float* hyper, int32_t rep, int64_t Z, int32_t N, int32_t G, int32_t C, float* masks, void* ws, size_t ws_bytes,
                                     hipStream_t stream) {
     PSAM_REQUIRE(plan && prepared && keys && idx3 && w3 && hyper && masks && ws, PSAM_EINVAL, "psam_upscale_masks: null pointer");
-    const int E = plan->dim, a = kpad(E);
+    const int E = plan->dim, a = kpad32(E);
     PSAM_REQUIRE(rep > 0 && Z > 0 && Z % rep == 0 && N > 0 && G > 0 && C > 0 && C <= 4 && (Z * N) % 256 == 0 && N % 32 == 0 && Z * N < ((int64_t)1 << 31), PSAM_EINVAL,
                  "psam_upscale_masks: need Z * N % 256 == 0, N % 32 == 0, C <= 4");
     PSAM_REQUIRE(ws_bytes >= psam_upscale_masks_ws_bytes(Z, N, G, C, E), PSAM_EWORKSPACE, "psam_upscale_masks: workspace too small");
@@ -701,10 +700,10 @@ TwWs tw_ws(Carve& cv, int64_t Z, int T, int G, int dim, int mlp) {
     b.ta = cv.take<float>(R * E); b.ty = cv.take<float>(R * E); b.tm = cv.take<float>(R * mlp);                                // attention output, Linear output, MLP hidden rows
     b.k = cv.take<float>(I * E); b.ik = cv.take<float>(I * E); b.iv = cv.take<float>(I * E); b.iq = cv.take<float>(I * E);      // patch rows: keys + key_pe, projections
     b.ia = cv.take<float>(I * E); b.iy = cv.take<float>(I * E);
-    b.pack_buf = cv.take<float>(big * kpad(std::max(mlp, dim))); b.scale_buf = cv.take<float>(big);                            // host_linear's packed input rows
-    b.kin_p = cv.take<float>(I * kpad(dim)); b.kin_s = cv.take<float>(I);      // the packed keys + key_pe rows (shared by two projections per layer) and their scales
+    b.pack_buf = cv.take<float>(big * kpad32(std::max(mlp, dim))); b.scale_buf = cv.take<float>(big);                            // host_linear's packed input rows
+    b.kin_p = cv.take<float>(I * kpad32(dim)); b.kin_s = cv.take<float>(I);      // the packed keys + key_pe rows (shared by two projections per layer) and their scales
     b.nq = cv.take<float>(R * E); b.nk = cv.take<float>(R * E); b.nv = cv.take<float>(R * E); b.lntmp = cv.take<float>(8 * R * 256);      // regrouped sequence: next projections, Linear + LN scratch
-    b.kv_p = cv.take<float>(I * kpad(dim)); b.kv_s = cv.take<float>(I);        // regrouped sequence: the packed keys rows
+    b.kv_p = cv.take<float>(I * kpad32(dim)); b.kv_s = cv.take<float>(I);        // regrouped sequence: the packed keys rows
     return b;
 }
 
@@ -770,7 +769,7 @@ PSAM_API int32_t psam_twoway_decoder_prepare(const psam_twoway_weights_t* wt, ps
     plan->weights = *wt;
     for (int i = 0; i < wt->depth; ++i) plan->layers[i] = wt->layers[i];
     plan->weights.layers = nullptr;      // the plan carries its own copy of the per-layer pointer blocks
-    const int E = wt->dim, IX = wt->dim / wt->downsample, kp = kpad(E);
+    const int E = wt->dim, IX = wt->dim / wt->downsample, kp = kpad32(E);
     Carve cv(prepared);
     const TwPrepared p = tw_prepared(cv, *wt);
     int32_t rc = PSAM_OK;
@@ -834,11 +833,11 @@ PSAM_API int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void*
         return psam_linear_skinny_multi(&jobs, E, E, E, (int32_t)R, E, stream);
     };
     auto gemm_packed = [&](const Lin& l, const float* xp, const float* sx, int64_t M, float* y, hipStream_t s) -> int32_t {
-        const int kp = kpad(l.K);
+        const int kp = kpad32(l.K);
         return psam_gemm_f16x3p_ex(xp, kp, sx, l.packed, kp, l.scales, y, l.N, l.b, nullptr, 0, nullptr, 0, 0, (int32_t)M, l.N, kp, 1.f, 0, nullptr, s);
     };
     // k_in = keys + pos, packed: shared by every projection of the layer that reads it (needs I >= 256 and packed weights)
-    auto pack_kin = [&](hipStream_t s) -> int32_t { return psam_scale_pack_rows_g8_add(keys, E, pos, E, G, rep, (int32_t)I, E, b.kin_p, kpad(E), b.kin_s, s); };
+    auto pack_kin = [&](hipStream_t s) -> int32_t { return psam_scale_pack_rows_g8_add(keys, E, pos, E, G, rep, (int32_t)I, E, b.kin_p, kpad32(E), b.kin_s, s); };
     // softmax(q k^T / sqrt(hd)) v of projected rows (row strides ldq / ldk / ldv; out dense)
     auto sattn = [&](int inner, const float* oq, int64_t ldq, const float* ok, int64_t ldk, const float* ov, int64_t ldv, float* out, int Lq, int Lk) -> int32_t {
         return psam_attention_small(oq, ldq, Lq * ldq, ok, ldk, Lk * ldk, ov, ldv, Lk * ldv, out, inner, (int64_t)Lq * inner, Z, H, Lq, Lk, inner / H,
@@ -869,7 +868,7 @@ PSAM_API int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void*
             const psam_skinny_jobs_t jobs = skinny_jobs(js);
             return psam_linear_rows_multi(&jobs, E, E, G, rep, E, I, E, stream);
         };
-        auto dual_pack = [&]() -> int32_t { return psam_scale_pack_rows_g8_add_dual(keys, E, pos, E, G, rep, (int32_t)I, E, b.kin_p, b.kin_s, b.kv_p, b.kv_s, kpad(E), stream); };
+        auto dual_pack = [&]() -> int32_t { return psam_scale_pack_rows_g8_add_dual(keys, E, pos, E, G, rep, (int32_t)I, E, b.kin_p, b.kin_s, b.kv_p, b.kv_s, kpad32(E), stream); };
         float *aq = b.pq, *ak = b.pk, *av = b.pv;      // self-attention projections of the layer at hand
         float *cqo = b.nq, *jko = b.nk, *jvo = b.nv;   // q of tokens -> patches (and of the final attention); k / v of patches -> tokens
         {   // first layer: q = k = v = the tokens, no positional encoding (skip_first_layer_pe)

@@ -92,17 +92,9 @@ __device__ __forceinline__ float f16_row_scale(float amax) {
     return __builtin_bit_cast(float, (unsigned)(127 + 14 - e) << 23);
 }
 
-// (x0, x1) * s (s = power-of-two row scale) -> packed fp16 pairs hi = RNE(s*x), lo = RNE(s*x - hi): the f16x3 operand split
-// (gemm_f16x3.hip); the residual is exact (one FMA).
-typedef float psam_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 psam_f16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void psam_split2_f16(float x0, float x1, float s, unsigned& hi, unsigned& lo) {
-    const psam_f32x2 xs = psam_f32x2{x0, x1} * s;
-    const psam_f16x2 h = __builtin_convertvector(xs, psam_f16x2);
-    const psam_f32x2 r = xs - __builtin_convertvector(h, psam_f32x2);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, psam_f16x2));
-}
+// 1/s for a power-of-two scale s in [2^-126, 2^126] (exact): exponent field 254 - E
+__device__ __forceinline__ float inv_pow2(float s) { return __builtin_bit_cast(float, (254u << 23) - __builtin_bit_cast(unsigned, s)); }
+// (the operand split and the packed-row format built on these scales: g8_pack.h)
 
 // Reductions on the VALU's data-parallel-primitive path instead of ds_bpermute (an LDS round trip, ~100+ cycles per step, six steps for a
 // wave): quad_perm xor 1 / xor 2, row_half_mirror, row_mirror leave every lane of a 16-lane row with the row's result in four
@@ -112,6 +104,14 @@ __device__ __forceinline__ int dpp_i32(int v) { return __builtin_amdgcn_update_d
 template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float v) { return __builtin_bit_cast(float, dpp_i32<CTRL>(__builtin_bit_cast(int, v))); }
 constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E, DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;
+// Half-wave exchange (v_permlane32_swap): lanes 32-63 of a <-> lanes 0-31 of b.  Whole wave must be active.
+__device__ __forceinline__ void psam_swap32(unsigned& a, unsigned& b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef unsigned swap_u32x2 __attribute__((ext_vector_type(2)));
+    const swap_u32x2 r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = r[0]; b = r[1];
+#endif
+}
 __device__ __forceinline__ float row16_max(float v) {
     v = fmaxf(v, dpp_f32<DPP_XOR1>(v)); v = fmaxf(v, dpp_f32<DPP_XOR2>(v));
     v = fmaxf(v, dpp_f32<DPP_HALF_MIRROR>(v)); v = fmaxf(v, dpp_f32<DPP_MIRROR>(v));

@@ -238,7 +238,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16x3s_kernel(const F16SArgs a) {
                         for (int r4 = 0; r4 < 4; ++r4) {
                             const float a0 = acc[i][j][4 * r4], a1 = acc[i][j][4 * r4 + 1], a2 = acc[i][j][4 * r4 + 2], a3 = acc[i][j][4 * r4 + 3];
                             const ep_f32x4 vf = {a0, a1, a2, a3};
-                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4, vf), rs, ((i * 2 + j) * 4 + r4) * (SK_NW * 64 * 16) + lane_off, 0, SC1);
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vf), rs, ((i * 2 + j) * 4 + r4) * (SK_NW * 64 * 16) + lane_off, 0, SC1);
                         }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's part is acknowledged by the memory side

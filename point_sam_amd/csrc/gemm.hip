@@ -19,7 +19,6 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct GemmArgs {
     const float* A; const float* W; float* C;
@@ -516,15 +515,14 @@ __global__ __launch_bounds__(256) void linear_skinny_ln_kernel(const float* __re
     __syncthreads();
     if (flag != (int)(gridDim.x * gridDim.y) - 1) return;
     if (threadIdx.x == 0) __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    typedef unsigned sk_u32x4 __attribute__((ext_vector_type(4)));
     const float inv = 1.0f / (float)N;
     const sk_f32x4 w4 = *reinterpret_cast<const sk_f32x4*>(lnw + lane * 4), b4 = *reinterpret_cast<const sk_f32x4*>(lnb + lane * 4);
     const sk_f32x4 bv = bias ? *reinterpret_cast<const sk_f32x4*>(bias + lane * 4) : sk_f32x4{0.f, 0.f, 0.f, 0.f};
     const int ksplit = (int)gridDim.y;
     for (int orow = wave; orow < M; orow += 4) {
-        sk_f32x4 v = __builtin_bit_cast(sk_f32x4, (sk_u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, (orow * N + lane * 4) * 4, 0, SC1));
+        sk_f32x4 v = __builtin_bit_cast(sk_f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, (orow * N + lane * 4) * 4, 0, SC1));
         for (int ks = 1; ks < ksplit; ++ks)
-            v += __builtin_bit_cast(sk_f32x4, (sk_u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, (ks * plane + orow * N + lane * 4) * 4, 0, SC1));
+            v += __builtin_bit_cast(sk_f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, (ks * plane + orow * N + lane * 4) * 4, 0, SC1));
         v += bv;
         if (res) v += *reinterpret_cast<const sk_f32x4*>(res + (int64_t)orow * ldr + lane * 4);
         const float s = (v[0] + v[1]) + (v[2] + v[3]);

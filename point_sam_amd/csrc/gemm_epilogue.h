@@ -12,7 +12,7 @@
 // C/D layout of v_mfma_f32_32x32x*: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 #pragma once
 #include <type_traits>
-#include "common.h"
+#include "g8_pack.h"
 
 typedef float ep_f32x16 __attribute__((ext_vector_type(16)));
 typedef float ep_f32x4 __attribute__((ext_vector_type(4)));
@@ -20,8 +20,6 @@ typedef float ep_f32x4 __attribute__((ext_vector_type(4)));
 template <int TN>
 constexpr int gemm_epilogue_lds_floats_per_wave() { return 32 * (TN * 32 + 4); }
 
-// 1/s for a power-of-two scale s in [2^-126, 2^126] (exact): exponent field 254 - E
-__device__ __forceinline__ float inv_pow2(float s) { return __builtin_bit_cast(float, (254u << 23) - __builtin_bit_cast(unsigned, s)); }
 __device__ __forceinline__ ep_f32x4 ep_load4(const float* q) { return *reinterpret_cast<const ep_f32x4*>(q); }
 __device__ __forceinline__ float ep_act(float v, int act) { return act == 1 ? gelu_erf(v) : (act == 2 ? fmaxf(v, 0.f) : v); }
 // Every DS operation in flight completes here.  Added in round 3 as the presumed cure of 1e-2 wrong fc2 outputs in multi-stream runs (a DS
@@ -295,15 +293,8 @@ __device__ __forceinline__ void gemm_store_tile(const ArgsT& p, ep_f32x16 (&acc)
                             const float bnd = p.out_k1 * rsq + p.out_k2;          // rsq = 1 / scaleA[row]
                             const float so = f16_row_scale(o_bnd ? obnd : (o_swiglu ? bnd * bnd : bnd));
                             if (c4 == 0 && col_base == 0) p.out_scale[row] = so;
-                            unsigned h0, l0, h1, l1;
-                            psam_split2_f16(v[0], v[1], so, h0, l0);
-                            psam_split2_f16(v[2], v[3], so, h1, l1);
-                            const bool odd = lane & 1;
-                            // lane ^ 1 exchange on the VALU's DPP path (quad_perm), not through the LDS crossbar (ds_bpermute): every lane is active
-                            // here (packing exists for the two-tile-wide wave tiles only)
-                            const unsigned r0 = (unsigned)dpp_i32<DPP_XOR1>((int)(odd ? h0 : l0)), r1 = (unsigned)dpp_i32<DPP_XOR1>((int)(odd ? h1 : l1));
-                            typedef unsigned ep_u32x4 __attribute__((ext_vector_type(4)));
-                            *reinterpret_cast<ep_u32x4*>(C + (int64_t)row * p.ldc + ocol) = odd ? ep_u32x4{r0, r1, l0, l1} : ep_u32x4{h0, h1, r0, r1};
+                            // every lane is active here (packing exists for the two-tile-wide wave tiles only)
+                            *reinterpret_cast<u32x4*>(C + (int64_t)row * p.ldc + ocol) = g8_chunk<1>(v, so, lane);
                             stored = true;
                         }
                     }

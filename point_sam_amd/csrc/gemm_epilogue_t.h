@@ -23,8 +23,6 @@
 #pragma once
 #include "gemm_epilogue.h"
 
-typedef unsigned ept_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned ept_u32x2 __attribute__((ext_vector_type(2)));
 
 // Scheduling fence between the tiles of an epilogue: without it the pre-RA scheduler hoists every tile's constant / residual loads to the top
 // (latency hiding the epilogue does not need at two waves per SIMD) and the 128-register accumulator tiles of the ping-pong kernels spill.
@@ -33,16 +31,9 @@ __device__ __forceinline__ void ept_fence() {
     __builtin_amdgcn_sched_barrier(0);
 #endif
 }
-// lanes 32-63 of a <-> lanes 0-31 of b
-__device__ __forceinline__ void ept_swap32(unsigned& a, unsigned& b) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const ept_u32x2 r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
-    a = r[0]; b = r[1];
-#endif
-}
 __device__ __forceinline__ void ept_swap32f(float& a, float& b) {
     unsigned x = __builtin_bit_cast(unsigned, a), y = __builtin_bit_cast(unsigned, b);
-    ept_swap32(x, y);
+    psam_swap32(x, y);
     a = __builtin_bit_cast(float, x); b = __builtin_bit_cast(float, y);
 }
 // s[g] = this lane's partial over run g (columns 8 g + 4 h .. + 3 of a 32-column segment): returns, in every lane, the segment's total in the
@@ -236,16 +227,9 @@ __device__ __forceinline__ void gemm_store_tile_t_impl(const ArgsT& p, ep_f32x16
                 // runs (2 g', 2 g' + 1) of the two half-waves -> column groups 8 (2 g' + h) .. + 7 of this lane: [hi x 8 | lo x 8] = 32 contiguous bytes
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
-                    unsigned xh[2], xl[2], yh[2], yl[2];
-                    psam_split2_f16(v[2 * gp][0], v[2 * gp][1], so[i], xh[0], xl[0]);
-                    psam_split2_f16(v[2 * gp][2], v[2 * gp][3], so[i], xh[1], xl[1]);
-                    psam_split2_f16(v[2 * gp + 1][0], v[2 * gp + 1][1], so[i], yh[0], yl[0]);
-                    psam_split2_f16(v[2 * gp + 1][2], v[2 * gp + 1][3], so[i], yh[1], yl[1]);
-                    ept_swap32(xh[0], yh[0]); ept_swap32(xh[1], yh[1]); ept_swap32(xl[0], yl[0]); ept_swap32(xl[1], yl[1]);
-                    // x = columns 0-3, y = columns 4-7 of group 2 gp + h (relative to the tile: 16 gp + 8 h)
-                    unsigned* dst = reinterpret_cast<unsigned*>(C) + (int64_t)row * p.ldc + (ocol - 4 * h) + 16 * gp + 8 * h;
-                    *reinterpret_cast<ept_u32x4*>(dst) = ept_u32x4{xh[0], xh[1], yh[0], yh[1]};
-                    *reinterpret_cast<ept_u32x4*>(dst + 4) = ept_u32x4{xl[0], xl[1], yl[0], yl[1]};
+                    const g8_group grp = g8_halfwave_group(v[2 * gp], v[2 * gp + 1], so[i]);
+                    // group 2 gp + h of the tile (containers 16 gp + 8 h ..)
+                    g8_store_group(reinterpret_cast<unsigned*>(C) + (int64_t)row * p.ldc + (ocol - 4 * h) + 16 * gp + 8 * h, grp);
                 }
             } else {
 #pragma unroll
@@ -412,15 +396,8 @@ __device__ __forceinline__ void gemm_store_tile_t_rowln(const ArgsT& p, ep_f32x1
             if (p.pack_out) {
 #pragma unroll
                 for (int gp = 0; gp < 2; ++gp) {
-                    unsigned xh[2], xl[2], yh[2], yl[2];
-                    psam_split2_f16(v[2 * gp][0], v[2 * gp][1], so, xh[0], xl[0]);
-                    psam_split2_f16(v[2 * gp][2], v[2 * gp][3], so, xh[1], xl[1]);
-                    psam_split2_f16(v[2 * gp + 1][0], v[2 * gp + 1][1], so, yh[0], yl[0]);
-                    psam_split2_f16(v[2 * gp + 1][2], v[2 * gp + 1][3], so, yh[1], yl[1]);
-                    ept_swap32(xh[0], yh[0]); ept_swap32(xh[1], yh[1]); ept_swap32(xl[0], yl[0]); ept_swap32(xl[1], yl[1]);
-                    unsigned* dst = reinterpret_cast<unsigned*>(C) + (int64_t)row * p.ldc + col_base + j * 32 + 16 * gp + 8 * h;
-                    *reinterpret_cast<ept_u32x4*>(dst) = ept_u32x4{xh[0], xh[1], yh[0], yh[1]};
-                    *reinterpret_cast<ept_u32x4*>(dst + 4) = ept_u32x4{xl[0], xl[1], yl[0], yl[1]};
+                    const g8_group grp = g8_halfwave_group(v[2 * gp], v[2 * gp + 1], so);
+                    g8_store_group(reinterpret_cast<unsigned*>(C) + (int64_t)row * p.ldc + col_base + j * 32 + 16 * gp + 8 * h, grp);
                 }
             } else {
 #pragma unroll

@@ -23,7 +23,7 @@
 // Tile shapes (waves WM x WN, each TM x TN accumulator tiles of 32x32) and S are template parameters; the host picks per shape.
 #include <type_traits>
 #include <cstdlib>
-#include "common.h"
+#include "g8_pack.h"
 #include <utility>
 #include "gemm_f16x3p_args.h"
 #include "gemm_epilogue.h"
@@ -278,7 +278,7 @@ __global__ __launch_bounds__(64 * WM * WN, (TR && WM * WN == 4) ? 2 : 1) void ge
                     // (element by element into floats first: __builtin_bit_cast applied to a vector ELEMENT expression read element 0 every time)
                     const float a0 = acc[i][j][4 * r4], a1 = acc[i][j][4 * r4 + 1], a2 = acc[i][j][4 * r4 + 2], a3 = acc[i][j][4 * r4 + 3];
                     const ep_f32x4 vf = {a0, a1, a2, a3};
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pu32x4, vf), rs, (split * QUADS + (i * TN + j) * 4 + r4) * (NW * 64 * 16) + lane_off, 0, SC1);
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, vf), rs, (split * QUADS + (i * TN + j) * 4 + r4) * (NW * 64 * 16) + lane_off, 0, SC1);
                 }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's partials are acknowledged by the memory side
         __syncthreads();
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(256) void row_scale_f16_kernel(const float* __restr
         const int c4 = cols >> 2;
         for (int c = lane; c < c4; c += 64) {
             const rs_f32x4 v = *reinterpret_cast<const rs_f32x4*>(x + c * 4);
-            m = fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+            m = g8_absmax4(m, v);
         }
         for (int c = (c4 << 2) + lane; c < cols; c += 64) m = fmaxf(m, fabsf(x[c]));
     } else {
@@ -369,19 +369,14 @@ __global__ __launch_bounds__(256) void pack_rows_g8_kernel(const float* __restri
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = g * 8 + e < K ? x[e] : 0.f;
-    const float s = scale[r];
-    unsigned hi[4], lo[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) psam_split2_f16(v[2 * e], v[2 * e + 1], s, hi[e], lo[e]);
-    unsigned* o = P + (int64_t)r * ldp + g * 8;
-    *reinterpret_cast<pu32x4*>(o) = pu32x4{hi[0], hi[1], hi[2], hi[3]};
-    *reinterpret_cast<pu32x4*>(o + 4) = pu32x4{lo[0], lo[1], lo[2], lo[3]};
+    const g8_group grp = g8_whole_group(v, scale[r]);
+    g8_store_group(P + (int64_t)r * ldp + g * 8, grp);
 }
 
 PSAM_API int32_t psam_pack_rows_f16x2_g8(const float* X, int64_t ldx, const float* scale, int32_t rows, int32_t K, void* P, int64_t ldp,
                                          hipStream_t stream) {
     PSAM_REQUIRE(X && scale && P, PSAM_EINVAL, "psam_pack_rows_f16x2_g8: null pointer");
-    const int Kp = (K + 31) / 32 * 32;
+    const int Kp = kpad32(K);
     PSAM_REQUIRE(rows > 0 && K > 0 && ldx >= K && ldp >= Kp, PSAM_EINVAL, "psam_pack_rows_f16x2_g8: bad shape (ldp >= K rounded up to 32)");
     PSAM_REQUIRE((ldp & 7) == 0 && ((uintptr_t)P & 31) == 0, PSAM_EALIGN, "psam_pack_rows_f16x2_g8: packed rows must be 32-byte aligned");
     PSAM_REQUIRE((const void*)X != (const void*)P || (ldx == ldp && (K & 7) == 0), PSAM_EINVAL, "psam_pack_rows_f16x2_g8: in place needs ldp == ldx, K % 8 == 0");
@@ -413,35 +408,26 @@ __global__ __launch_bounds__(256) void scale_pack_rows_g8_kernel(const float* __
         v[i] = xr[c < c4n ? c : c4n - 1];                       // unconditional (clamped) loads
         if (ar) v[i] = ar[c < c4n ? c : c4n - 1] + v[i];
         if (c >= c4n) v[i] = sp_f32x4{0.f, 0.f, 0.f, 0.f};
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(v[i][0]), fabsf(v[i][1]))), fmaxf(fabsf(v[i][2]), fabsf(v[i][3])));
+        amax = g8_absmax4(amax, v[i]);
     }
-    amax = wave_max(amax);
-    const float sc = f16_row_scale(amax);
+    const float sc = g8_row_scale(amax);
     if (lane == 0) scale[row] = sc;
-    const int klim = (K + 31) & ~31;
-    const bool odd = lane & 1;
+    const int klim = kpad32(K);
     unsigned* prow = P + (int64_t)row * ldp;
 #pragma unroll
     for (int i = 0; i < NV4; ++i) {
         const int c = i * 64 + lane;
-        unsigned h0, l0, h1, l1;
-        psam_split2_f16(v[i][0], v[i][1], sc, h0, l0);
-        psam_split2_f16(v[i][2], v[i][3], sc, h1, l1);
-        const unsigned r0 = __shfl_xor(odd ? h0 : l0, 1, 64), r1 = __shfl_xor(odd ? h1 : l1, 1, 64);
-        if (c * 4 < klim) *reinterpret_cast<pu32x4*>(prow + c * 4) = odd ? pu32x4{r0, r1, l0, l1} : pu32x4{h0, h1, r0, r1};
+        const u32x4 chunk = g8_chunk<1, true>(v[i], sc, lane);      // the exchange: every lane, also those past the row
+        if (c * 4 < klim) *reinterpret_cast<u32x4*>(prow + c * 4) = chunk;
     }
 }
 
-// scale[r] = f16 row scale of X[r, :K]; P[r, :] = g8-packed scale[r] * X[r, :K], zero-padded to K rounded up to 32 (ldp >= that).
-PSAM_API int32_t psam_scale_pack_rows_g8(const float* X, int64_t ldx, int32_t rows, int32_t K, void* P, int64_t ldp, float* scale, hipStream_t stream) {
-    PSAM_REQUIRE(X && P && scale, PSAM_EINVAL, "psam_scale_pack_rows_g8: null pointer");
-    const int Kp = (K + 31) / 32 * 32;
-    PSAM_REQUIRE(rows > 0 && K > 0 && K <= 6144 && (K & 3) == 0 && ldx >= K && ldp >= Kp, PSAM_EINVAL,
-                 "psam_scale_pack_rows_g8: bad shape (K % 4 == 0, K <= 6144, ldp >= K rounded up to 32)");
-    PSAM_REQUIRE((ldx & 3) == 0 && ((uintptr_t)X & 15) == 0 && (ldp & 7) == 0 && ((uintptr_t)P & 31) == 0, PSAM_EALIGN,
-                 "psam_scale_pack_rows_g8: rows of X 16-byte, of P 32-byte aligned");
+// The one launch of scale_pack_rows_g8_kernel: NV4 float4s per lane by the padded width.  add == nullptr: no addend.
+static void scale_pack_launch(const float* X, int64_t ldx, int32_t rows, int32_t K, void* P, int64_t ldp, float* scale, const float* add, int64_t ldadd,
+                              int32_t rows_per_set, int32_t rep, hipStream_t stream) {
     const dim3 grid((unsigned)psam_cdiv(rows, 4)), block(256);
-#define SP_LAUNCH(R) hipLaunchKernelGGL(scale_pack_rows_g8_kernel<R>, grid, block, 0, stream, X, ldx, rows, K, (unsigned*)P, ldp, scale, (const float*)nullptr, (int64_t)0, 1, 1)
+    const int Kp = kpad32(K);
+#define SP_LAUNCH(R) hipLaunchKernelGGL(scale_pack_rows_g8_kernel<R>, grid, block, 0, stream, X, ldx, rows, K, (unsigned*)P, ldp, scale, add, ldadd, rows_per_set, rep)
     if (Kp <= 256) SP_LAUNCH(1);
     else if (Kp <= 512) SP_LAUNCH(2);
     else if (Kp <= 1024) SP_LAUNCH(4);
@@ -449,26 +435,29 @@ PSAM_API int32_t psam_scale_pack_rows_g8(const float* X, int64_t ldx, int32_t ro
     else if (Kp <= 4096) SP_LAUNCH(16);
     else SP_LAUNCH(24);
 #undef SP_LAUNCH
+}
+
+// scale[r] = f16 row scale of X[r, :K]; P[r, :] = g8-packed scale[r] * X[r, :K], zero-padded to K rounded up to 32 (ldp >= that).
+PSAM_API int32_t psam_scale_pack_rows_g8(const float* X, int64_t ldx, int32_t rows, int32_t K, void* P, int64_t ldp, float* scale, hipStream_t stream) {
+    PSAM_REQUIRE(X && P && scale, PSAM_EINVAL, "psam_scale_pack_rows_g8: null pointer");
+    const int Kp = kpad32(K);
+    PSAM_REQUIRE(rows > 0 && K > 0 && K <= 6144 && (K & 3) == 0 && ldx >= K && ldp >= Kp, PSAM_EINVAL,
+                 "psam_scale_pack_rows_g8: bad shape (K % 4 == 0, K <= 6144, ldp >= K rounded up to 32)");
+    PSAM_REQUIRE((ldx & 3) == 0 && ((uintptr_t)X & 15) == 0 && (ldp & 7) == 0 && ((uintptr_t)P & 31) == 0, PSAM_EALIGN,
+                 "psam_scale_pack_rows_g8: rows of X 16-byte, of P 32-byte aligned");
+    scale_pack_launch(X, ldx, rows, K, P, ldp, scale, nullptr, 0, 1, 1, stream);
     return psam_launch_status("psam_scale_pack_rows_g8: launch failed");
 }
 
 PSAM_API int32_t psam_scale_pack_rows_g8_add(const float* X, int64_t ldx, const float* add, int64_t ldadd, int32_t rows_per_set, int32_t rep, int32_t rows, int32_t K,
                                              void* P, int64_t ldp, float* scale, hipStream_t stream) {
     PSAM_REQUIRE(X && add && P && scale, PSAM_EINVAL, "psam_scale_pack_rows_g8_add: null pointer");
-    const int Kp = (K + 31) / 32 * 32;
+    const int Kp = kpad32(K);
     PSAM_REQUIRE(rows > 0 && K > 0 && K <= 6144 && (K & 3) == 0 && ldx >= K && ldadd >= K && ldp >= Kp && rows_per_set > 0 && rep > 0, PSAM_EINVAL,
                  "psam_scale_pack_rows_g8_add: bad shape (K % 4 == 0, K <= 6144, ldp >= K rounded up to 32)");
     PSAM_REQUIRE(((ldx | ldadd) & 3) == 0 && (((uintptr_t)X | (uintptr_t)add) & 15) == 0 && (ldp & 7) == 0 && ((uintptr_t)P & 31) == 0, PSAM_EALIGN,
                  "psam_scale_pack_rows_g8_add: rows of X / add 16-byte, of P 32-byte aligned");
-    const dim3 grid((unsigned)psam_cdiv(rows, 4)), block(256);
-#define SPA_LAUNCH(R) hipLaunchKernelGGL(scale_pack_rows_g8_kernel<R>, grid, block, 0, stream, X, ldx, rows, K, (unsigned*)P, ldp, scale, add, ldadd, rows_per_set, rep)
-    if (Kp <= 256) SPA_LAUNCH(1);
-    else if (Kp <= 512) SPA_LAUNCH(2);
-    else if (Kp <= 1024) SPA_LAUNCH(4);
-    else if (Kp <= 2048) SPA_LAUNCH(8);
-    else if (Kp <= 4096) SPA_LAUNCH(16);
-    else SPA_LAUNCH(24);
-#undef SPA_LAUNCH
+    scale_pack_launch(X, ldx, rows, K, P, ldp, scale, add, ldadd, rows_per_set, rep, stream);
     return psam_launch_status("psam_scale_pack_rows_g8_add: launch failed");
 }
 
@@ -485,26 +474,19 @@ __global__ __launch_bounds__(256) void scale_pack_rows_g8_dual_kernel(const floa
     sp_f32x4 x = reinterpret_cast<const sp_f32x4*>(X + (int64_t)row * ldx)[c];
     sp_f32x4 v = reinterpret_cast<const sp_f32x4*>(add + ((int64_t)(row / (rep * rows_per_set)) * rows_per_set + row % rows_per_set) * ldadd)[c] + x;
     if (lane >= c4n) { x = sp_f32x4{0.f, 0.f, 0.f, 0.f}; v = x; }
-    const float scs = f16_row_scale(wave_max(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])))));
-    const float scx = f16_row_scale(wave_max(fmaxf(fmaxf(fabsf(x[0]), fabsf(x[1])), fmaxf(fabsf(x[2]), fabsf(x[3])))));
+    const float scs = g8_row_scale(g8_absmax4(v)), scx = g8_row_scale(g8_absmax4(x));
     if (lane == 0) { ss[row] = scs; sx[row] = scx; }
-    const int klim = (K + 31) & ~31;
-    const bool odd = lane & 1;
-    auto put = [&](const sp_f32x4& t, float sc, unsigned* prow) {
-        unsigned h0, l0, h1, l1;
-        psam_split2_f16(t[0], t[1], sc, h0, l0);
-        psam_split2_f16(t[2], t[3], sc, h1, l1);
-        const unsigned r0 = __shfl_xor(odd ? h0 : l0, 1, 64), r1 = __shfl_xor(odd ? h1 : l1, 1, 64);
-        if (lane * 4 < klim) *reinterpret_cast<pu32x4*>(prow + lane * 4) = odd ? pu32x4{r0, r1, l0, l1} : pu32x4{h0, h1, r0, r1};
-    };
-    put(v, scs, Ps + (int64_t)row * ldp);
-    put(x, scx, Px + (int64_t)row * ldp);
+    const u32x4 cs = g8_chunk<1>(v, scs, lane), cx = g8_chunk<1>(x, scx, lane);      // the exchanges: every lane
+    if (lane * 4 < kpad32(K)) {
+        *reinterpret_cast<u32x4*>(Ps + (int64_t)row * ldp + lane * 4) = cs;
+        *reinterpret_cast<u32x4*>(Px + (int64_t)row * ldp + lane * 4) = cx;
+    }
 }
 
 PSAM_API int32_t psam_scale_pack_rows_g8_add_dual(const float* X, int64_t ldx, const float* add, int64_t ldadd, int32_t rows_per_set, int32_t rep, int32_t rows, int32_t K,
                                                   void* P_sum, float* scale_sum, void* P_x, float* scale_x, int64_t ldp, hipStream_t stream) {
     PSAM_REQUIRE(X && add && P_sum && scale_sum && P_x && scale_x, PSAM_EINVAL, "psam_scale_pack_rows_g8_add_dual: null pointer");
-    const int Kp = (K + 31) / 32 * 32;
+    const int Kp = kpad32(K);
     PSAM_REQUIRE(rows > 0 && K > 0 && K <= 256 && (K & 3) == 0 && ldx >= K && ldadd >= K && ldp >= Kp && rows_per_set > 0 && rep > 0, PSAM_EINVAL,
                  "psam_scale_pack_rows_g8_add_dual: bad shape (K % 4 == 0, K <= 256, ldp >= K rounded up to 32)");
     PSAM_REQUIRE(((ldx | ldadd) & 3) == 0 && (((uintptr_t)X | (uintptr_t)add) & 15) == 0 && (ldp & 7) == 0 && (((uintptr_t)P_sum | (uintptr_t)P_x) & 31) == 0, PSAM_EALIGN,

@@ -1,11 +1,10 @@
 // Shared by the two packed-operand GEMM translation units (gemm_f16x3p.hip: lock-step ring kernels; gemm_f16x3pp.hip: the
 // ping-pong kernel): argument block, LDS-DMA macro, tile-order panel model.
 #pragma once
-#include "common.h"
+#include "g8_pack.h"      // u32x4, kpad32
 
 typedef float pf32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 pf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned pu32x4 __attribute__((ext_vector_type(4)));
 
 struct F16PArgs {
     const unsigned char* A; const unsigned char* W; float* C;

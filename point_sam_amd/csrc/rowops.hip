@@ -2,7 +2,7 @@
 // gate with inner LayerNorm, per-group max-pool, positional encodings, token assembly, 3-NN feature interpolation
 // and the small prompt-token attentions of the two-way decoder.  All memory-bound: one wave per row, lane-consecutive
 // (coalesced) accesses, shuffle reductions.
-#include "common.h"
+#include "g8_pack.h"
 #include <math.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -134,11 +134,9 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
     const float r = 1.0f / sqrtf(wave_sum(q) * inv + eps);
     const int cfull = cols >> 2;    // float4 groups entirely inside the row (cols >= 256 on this path, so cfull >= 64)
     if (pack) {
-        // g8-packed output for the f16x3p GEMM (gemm_f16x3p.hip): the outputs stay in registers until the row maximum (hence the row
-        // scale) is known; then every group of 8 columns is written as [hi x8 | lo x8] fp16.  A lane holds 4 columns (hi: 8 B, lo: 8 B),
-        // its neighbour lane ^ 1 the other 4 of the group: the even lane collects the 16-byte hi chunk, the odd lane the lo chunk (one
-        // exchange), so consecutive lanes still write consecutive 16-byte chunks.  Columns cols .. round_up(cols, 32) - 1 (the GEMM's
-        // K padding) are written as zeros when the row stride has room for them.
+        // g8-packed output for the f16x3p GEMM (g8_pack.h): the outputs stay in registers until the row maximum (hence the row scale) is
+        // known; then every lane writes its 16-byte chunk.  Columns cols .. kpad32(cols) - 1 (the GEMM's K padding) are written as zeros
+        // when the row stride has room for them.
 #pragma unroll
         for (int i = 0; i < NV4; ++i) {
             const int c = i * 64 + lane;
@@ -153,7 +151,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
 #pragma unroll
             for (int e = 0; e < 4; ++e) if (c * 4 + e >= cols) o[e] = 0.f;
             v[i] = o;
-            amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
+            amax = g8_absmax4(amax, o);
         }
         if (rbound) {      // bc2 t^2 + bc1 t + bc0 with t = ||output row||_2: what the consuming GEMM's epilogue bounds ITS output rows with (psam_gemm_fuse_t.out_bound)
             float n2 = 0.f;
@@ -162,22 +160,15 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
             const float t = sqrtf(wave_sum(n2)) * 1.0001f;
             if (lane == 0) rbound[row] = (bc2 * t + bc1) * t + bc0;
         }
-        amax = wave_max(amax);
-        const float sc = f16_row_scale(amax);
+        const float sc = g8_row_scale(amax);
         if (lane == 0) rscale[row] = sc;
-        typedef unsigned ln_u32x4 __attribute__((ext_vector_type(4)));
-        const int kp = (cols + 31) & ~31;
+        const int kp = kpad32(cols);
         const int klim = kp <= ldy ? kp : (cols + 7) & ~7;      // columns to write (multiple of 8)
-        const bool odd = lane & 1;
 #pragma unroll
         for (int i = 0; i < NV4; ++i) {
             const int c = i * 64 + lane;
-            unsigned h0, l0, h1, l1;
-            psam_split2_f16(v[i][0], v[i][1], sc, h0, l0);
-            psam_split2_f16(v[i][2], v[i][3], sc, h1, l1);
-            // even lane keeps its hi and receives the neighbour's hi; odd lane keeps its lo and receives the neighbour's lo
-            const unsigned r0 = __shfl_xor(odd ? h0 : l0, 1, 64), r1 = __shfl_xor(odd ? h1 : l1, 1, 64);
-            if (c * 4 < klim) *reinterpret_cast<ln_u32x4*>(yrow + c * 4) = odd ? ln_u32x4{r0, r1, l0, l1} : ln_u32x4{h0, h1, r0, r1};
+            const u32x4 chunk = g8_chunk<1>(v[i], sc, lane);      // the exchange: every lane, also those past the row
+            if (c * 4 < klim) *reinterpret_cast<u32x4*>(yrow + c * 4) = chunk;
         }
         return;
     }
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
             f32x4 o = (v[i] - mean) * r * w4 + b4;
             if (act == 1) { o[0] = gelu_erf(o[0]); o[1] = gelu_erf(o[1]); o[2] = gelu_erf(o[2]); o[3] = gelu_erf(o[3]); }
             *reinterpret_cast<f32x4*>(yrow + c * 4) = o;
-            amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
+            amax = g8_absmax4(amax, o);
         } else if (c * 4 < cols) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -231,22 +222,20 @@ PSAM_API int32_t psam_layernorm_ex2(const float* x, int64_t ldx, const float* re
     PSAM_REQUIRE(!pack || (vec && row_scale && (ldy & 7) == 0 && ((uintptr_t)y & 31) == 0 && ldy >= ((cols + 7) & ~7)), PSAM_EINVAL,
                  "psam_layernorm: packed output needs row_scale, the float4 path (256 <= cols <= 4096, aligned) and 32-byte aligned output rows");
     if (vec) {
-#define LNV_LAUNCH(R) hipLaunchKernelGGL(layernorm_v4_kernel<R>, grid, block, 0, stream, x, ldx, res, ldr, w, b, y, ldy, rows, cols, eps, act, row_scale, pack, row_bound, c2, c1, c0)
-        const int span = pack ? ((cols + 31) & ~31) : cols;     // the packed form also writes the zero padding up to the 32-k slab
-        if (span <= 256) LNV_LAUNCH(1);
-        else if (span <= 512) LNV_LAUNCH(2);
-        else if (span <= 1024) LNV_LAUNCH(4);
-        else if (span <= 2048) LNV_LAUNCH(8);
-        else LNV_LAUNCH(16);
-        if ((psam_ablate_repeat() & 2) && x != y && res != y) {
+        const int span = pack ? kpad32(cols) : cols;     // the packed form also writes the zero padding up to the 32-k slab
+        int nv4 = 0;      // float4s per lane: picked once, by the one chain below, for the launch, the repeat launch and the recorded instance
+#define LNV_LAUNCH(R) do { nv4 = R; hipLaunchKernelGGL(layernorm_v4_kernel<R>, grid, block, 0, stream, x, ldx, res, ldr, w, b, y, ldy, rows, cols, eps, act, row_scale, pack, row_bound, c2, c1, c0); } while (0)
+        auto launch = [&] {
             if (span <= 256) LNV_LAUNCH(1);
             else if (span <= 512) LNV_LAUNCH(2);
             else if (span <= 1024) LNV_LAUNCH(4);
             else if (span <= 2048) LNV_LAUNCH(8);
             else LNV_LAUNCH(16);
-        }
+        };
 #undef LNV_LAUNCH
-        return layernorm_launched(1000 + (span <= 256 ? 1 : span <= 512 ? 2 : span <= 1024 ? 4 : span <= 2048 ? 8 : 16) + (pack ? 100 : 0));
+        launch();
+        if ((psam_ablate_repeat() & 2) && x != y && res != y) launch();
+        return layernorm_launched(1000 + nv4 + (pack ? 100 : 0));
     }
 #define LN_LAUNCH(R) hipLaunchKernelGGL(layernorm_kernel<R>, grid, block, 0, stream, x, ldx, res, ldr, w, b, y, ldy, rows, cols, eps, act, row_scale)
     if (cols <= 128) LN_LAUNCH(2);
@@ -585,15 +574,9 @@ __global__ __launch_bounds__(256) void interp3_kernel(const float* __restrict__ 
             else if (act == 2) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
         }
         if (scale_out) {      // C == 256 (host-checked): the whole row is in this wave -> g8-packed row + its scale (gemm_f16x3p.hip)
-            const float sc = f16_row_scale(wave_max(fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])))));
+            const float sc = g8_row_scale(g8_absmax4(v));
             if (lane == 0) scale_out[z * N + n] = sc;
-            unsigned h0, l0, h1, l1;
-            psam_split2_f16(v[0], v[1], sc, h0, l0);
-            psam_split2_f16(v[2], v[3], sc, h1, l1);
-            const bool odd = lane & 1;
-            const unsigned r0 = __shfl_xor(odd ? h0 : l0, 1, 64), r1 = __shfl_xor(odd ? h1 : l1, 1, 64);
-            typedef unsigned ip_u32x4 __attribute__((ext_vector_type(4)));
-            *reinterpret_cast<ip_u32x4*>(out + (z * N + n) * C + c) = odd ? ip_u32x4{r0, r1, l0, l1} : ip_u32x4{h0, h1, r0, r1};
+            *reinterpret_cast<u32x4*>(out + (z * N + n) * C + c) = g8_chunk<1>(v, sc, lane);      // C == 256: every lane is in this one trip
         } else {
             *reinterpret_cast<f32x4*>(out + (z * N + n) * C + c) = v;
         }
@@ -651,18 +634,13 @@ __global__ __launch_bounds__(256) void interp3_c256_kernel(const float* __restri
     if (scale_out) {
         float sc[R];
 #pragma unroll
-        for (int r = 0; r < R; ++r) sc[r] = f16_row_scale(wave_max(fmaxf(fmaxf(fabsf(v[r][0]), fabsf(v[r][1])), fmaxf(fabsf(v[r][2]), fabsf(v[r][3])))));
+        for (int r = 0; r < R; ++r) sc[r] = g8_row_scale(g8_absmax4(v[r]));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            unsigned h0, l0, h1, l1;
-            psam_split2_f16(v[r][0], v[r][1], sc[r], h0, l0);
-            psam_split2_f16(v[r][2], v[r][3], sc[r], h1, l1);
-            const bool odd = lane & 1;
-            const unsigned r0 = __shfl_xor(odd ? h0 : l0, 1, 64), r1 = __shfl_xor(odd ? h1 : l1, 1, 64);
-            typedef unsigned ip_u32x4 __attribute__((ext_vector_type(4)));
+            const u32x4 chunk = g8_chunk<1, true>(v[r], sc[r], lane);      // the exchange: every lane, also for a clamped duplicate row
             if (row0 + r < total) {
                 if (lane == 0) scale_out[rows[r]] = sc[r];
-                *reinterpret_cast<ip_u32x4*>(out + rows[r] * C + c) = odd ? ip_u32x4{r0, r1, l0, l1} : ip_u32x4{h0, h1, r0, r1};
+                *reinterpret_cast<u32x4*>(out + rows[r] * C + c) = chunk;
             }
         }
     } else {
@@ -952,7 +930,6 @@ __device__ __forceinline__ void mlp3_body(const float* __restrict__ x, int64_t l
             // buffer loads: the row offset is a scalar (soffset), the lane's k offset the one address register of all MLP3_OB loads.  The scalar offset
             // is NOT covered by the resource's bounds check, so rows past `no` are clamped to the last row (their sums are never stored) and k past `ni`
             // to the row's last chunk (it meets a zero of the input: LDS holds zeros beyond ni) -- no load leaves the matrix.
-            typedef unsigned m3_u32x4 __attribute__((ext_vector_type(4)));
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, no * ni * 4, 0x00020000);
             const int obu = __builtin_amdgcn_readfirstlane(ob);
             for (int kc = 0; kc < ni; kc += 256) {
@@ -965,7 +942,7 @@ __device__ __forceinline__ void mlp3_body(const float* __restrict__ x, int64_t l
 #pragma unroll
                 for (int o = 0; o < MLP3_OB; ++o) {
                     const int row = obu + o < no ? obu + o : no - 1;
-                    const f32x4 wv = __builtin_bit_cast(f32x4, (m3_u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, kw * 4, row * ni * 4, 0));
+                    const f32x4 wv = __builtin_bit_cast(f32x4, (u32x4)__builtin_amdgcn_raw_buffer_load_b128(rs, kw * 4, row * ni * 4, 0));
                     part[o] = fmaf(x3, wv[3], fmaf(x2, wv[2], fmaf(x1, wv[1], fmaf(x0, wv[0], part[o]))));      // one chain per output (16 independent chains): nothing to pair
                 }
             }

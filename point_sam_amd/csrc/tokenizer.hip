@@ -10,7 +10,7 @@
 // Numerical spec = oracle/tokenizer_oracle.c: fp32 d = (dx*dx + dy*dy) + dz*dz without FMA contraction,
 // ties broken by lowest index.  This file is compiled with -ffp-contract=off and additionally uses the
 // explicitly rounded intrinsics in dist2_exact().
-#include "common.h"
+#include "g8_pack.h"
 #include <math.h>
 
 // ------------------------------------------------------------------------------------------------
@@ -20,7 +20,6 @@
 // are held on chip as well (registers + LDS), see fps_kernel.
 // ------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int FPS_THREADS = 1024;
 constexpr int FPS_WAVES = FPS_THREADS / WAVE;
 
@@ -1193,11 +1192,7 @@ __global__ __launch_bounds__(256) void patch_l1_kernel(const float* __restrict__
             if (row >= rows) break;
             if (PACK) {
                 if (lane == 0) scale_out[row] = sc[q];
-                unsigned hi, lo;
-                psam_split2_f16(o0[q], o1[q], sc[q], hi, lo);
-                unsigned* orow = reinterpret_cast<unsigned*>(out) + row * 128 + (lane >> 2) * 8 + (lane & 3);   // group of 8 channels = 4 lanes
-                orow[0] = hi;
-                orow[4] = lo;
+                g8_store_pair(reinterpret_cast<unsigned*>(out), row, 128, lane, o0[q], o1[q], sc[q]);
             } else {
                 *reinterpret_cast<psam_f32x2*>(out + row * 128 + 2 * lane) = psam_f32x2{o0[q], o1[q]};
             }

@@ -302,13 +302,6 @@ def _header(title):
     print(f"\n{title}\n| case | kernel err | fp32 evaluation err | bound | kernel err / tensor max | worst (cloud, head) |\n|---|---|---|---|---|---|")
 
 
-def _unpack_g8(p, scale, K):
-    """[rows, Kp] g8-packed containers -> (hi + lo) / scale as fp64 [rows, K] (the inverse of the packing)."""
-    rows, Kp = p.shape
-    h = p.contiguous().view(torch.float16).view(rows, Kp // 8, 2, 8).double()
-    return ((h[:, :, 0] + h[:, :, 1]).reshape(rows, Kp) / scale.double()[:, None])[:, :K]
-
-
 def onehot_inputs(B, H, Lq, Lk, hd, seed, gain=48.0):
     """One-hot selection inputs: (q, k, v [B, L, H hd] fp32, pi [B, H, Lq], scale).  Keys: unit-norm random rows times 8; q_i = k_pi(i) with pi drawn per (cloud,
     head) -- a permutation where Lq == Lk, else a random map; V: 11 significant bits, +-(1024 + randint(1024)) / 1024 * 2^randint(-3, 4), distinct per (cloud,
@@ -375,6 +368,7 @@ def test_onehot_preconditions_hold_for_every_case():
 # ------------------------------------------------------------------------------------------------ GPU plumbing
 try:
     import torch
+    from g8_reference import unpack_g8
 except ImportError:      # pragma: no cover
     torch = None
 
@@ -425,7 +419,7 @@ class PackedProblem:
         self.big = torch.full((B * L, self.ld), float("nan"), device="cuda")
         self.xp = self.big[:, self.off:self.off + 3 * D]
         ops.pack_rows_g8(x.cuda(), self.sc, out=self.xp)
-        dec = _unpack_g8(self.xp.contiguous().cpu(), self.sc.cpu(), 3 * D)
+        dec = unpack_g8(self.xp.contiguous().cpu(), self.sc.cpu(), 3 * D)
         self.q, self.k, self.v = (dec[:, i * D:(i + 1) * D].reshape(B, L, D) for i in range(3))      # fp64, exactly what the kernel reads
         self.v_bound = float(self.v.abs().max()) * 1.01
 
@@ -447,7 +441,7 @@ class PackedProblem:
         return out.contiguous(), so
 
     def decode(self, out, so):
-        return _unpack_g8(out.cpu(), so.cpu(), self.D).view(self.B, self.L, self.D)
+        return unpack_g8(out.cpu(), so.cpu(), self.D).view(self.B, self.L, self.D)
 
 
 def _packed_random(ops, c):

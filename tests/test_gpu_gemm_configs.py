@@ -556,15 +556,9 @@ def _perm(n):
     return [(i * 37 + 11) % n for i in range(n)]      # 37 is prime to 2752: a permutation of 0 .. n-1
 
 
-def _unpack_g8(p, scale, K):
-    """[rows, Kp] g8-packed containers -> (hi + lo) / scale as fp64 [rows, K] (the inverse of the packing)."""
-    rows, Kp = p.shape
-    h = p.contiguous().view(torch.float16).view(rows, Kp // 8, 2, 8).double()
-    return ((h[:, :, 0] + h[:, :, 1]).reshape(rows, Kp) / scale.double()[:, None])[:, :K]
-
-
 @pytest.fixture(scope="module")
 def sel(ops):
+    from g8_reference import unpack_g8      # imports torch: here, like every use of torch in this module
     g = torch.Generator().manual_seed(5)
     K, R = SEL_K, 300
     pi = torch.tensor(_perm(K))
@@ -573,8 +567,8 @@ def sel(ops):
     # random operand with 20 binary orders of magnitude along k: the lo plane holds fp16 subnormals
     dense = torch.randn(R, K, generator=g) * 2.0 ** -torch.randint(0, 21, (R, K), generator=g).float()
     oh, dn = _pack(ops, onehot.cuda(), K), _pack(ops, dense.cuda(), K)
-    dec = _unpack_g8(dn[0], dn[1], K)                     # exact values of the packed dense operand
-    assert (oh[1] == 2.0 ** 14).all() and (_unpack_g8(oh[0], oh[1], K) == onehot.cuda().double()).all()
+    dec = unpack_g8(dn[0], dn[1], K)                     # exact values of the packed dense operand
+    assert (oh[1] == 2.0 ** 14).all() and (unpack_g8(oh[0], oh[1], K) == onehot.cuda().double()).all()
     pic = pi.cuda()
     return dict(K=K, R=R, pi=pi, oh=oh, dn=dn, want_a=dec[:, pic].T.contiguous(), want_w=dec[:, pic].contiguous())
 

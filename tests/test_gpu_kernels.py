@@ -8,6 +8,7 @@ import torch
 import torch.nn.functional as F
 
 from oracle import pointsam_oracle as O
+from g8_reference import pack_g8, unpack_g8
 
 pytestmark = pytest.mark.gpu
 
@@ -395,27 +396,22 @@ def test_layernorm_emits_f16x3_row_scale(ops, cols):
         assert torch.equal(y, ops.layernorm(x, w, b, 1e-5, act=act))
 
 
-def _unpack_g8(p, scale, K):
-    """[rows, Kp] g8-packed containers -> (hi + lo) / scale as fp64 [rows, K] (test helper: the inverse of the packing)."""
-    rows, Kp = p.shape
-    h = p.contiguous().view(torch.float16).view(rows, Kp // 8, 2, 8).double()        # [rows, group, hi|lo, 8]
-    return ((h[:, :, 0] + h[:, :, 1]).reshape(rows, Kp) / scale.double()[:, None])[:, :K]
-
-
 @pytest.mark.parametrize("M,K", [(300, 128), (256, 516), (1000, 1024), (77, 2752), (130, 6144), (64, 36)])
 def test_g8_packing(ops, M, K):
     """pack_rows_g8 (static weights) and scale_pack_rows_g8 (activations, one pass): identical bits; the decoded value is the input to
-    2^-21 relative (hi + lo = 22 significand bits); the K padding up to the 32-k slab is zero."""
+    2^-21 relative (hi + lo = 22 significand bits); the K padding up to the 32-k slab is zero.  pack_rows_g8's words equal the host packer's
+    (tests/g8_reference.py), the one expectation here that no device code of the project produced."""
     g = torch.Generator().manual_seed(M + K)
     x = (torch.randn(M, K, generator=g) * torch.exp(2 * torch.randn(M, 1, generator=g))).cuda()
     s = ops.row_scale_f16(x)
     p = ops.pack_rows_g8(x, s)
     Kp = (K + 31) // 32 * 32
     assert p.shape == (M, Kp)
-    dec = _unpack_g8(p, s, Kp)
+    dec = unpack_g8(p, s, Kp)
     assert (dec[:, K:] == 0).all()
     rel = ((dec[:, :K] - x.double()).abs() / x.double().abs().amax(1, keepdim=True)).max().item()
     assert rel < 2.0 ** -21, rel
+    assert torch.equal(p.view(torch.int32).cpu(), pack_g8(x, s))
     if K % 4 == 0:
         p2, s2 = ops.scale_pack_rows_g8(x)
         assert torch.equal(s2, s) and torch.equal(p2.view(torch.int32), p.view(torch.int32))
@@ -516,7 +512,7 @@ def test_layernorm_packed_output(ops, cols, ld):
         g8 = (cols // 8) * 8
         assert torch.equal(got[:, :g8], want.view(torch.int32)[:, :g8])
         assert torch.equal(got[:, g8 + 8:], want.view(torch.int32)[:, g8 + 8:])
-        dec = _unpack_g8(xin[:, :Kp], rs, Kp)
+        dec = unpack_g8(xin[:, :Kp], rs, Kp)
         assert torch.allclose(dec[:, g8:cols].float(), y[:, g8:], rtol=2e-6, atol=1e-7) and (dec[:, cols:] == 0).all()
     rs2 = torch.empty(300, device="cuda")
     out = ops.layernorm(x[:, :cols], w, b, 1e-6, scale_out=rs2, pack=True)                      # out of place: a [rows, Kp] buffer
@@ -595,7 +591,7 @@ def test_fused_mlp_two_gemms(ops, M, D, H):
         mean, rstd = ops.ln_stats_finalize(st, H, eps)
         y1 = ops.linear(up, fw2g, ln_d, residual=cu(res), x_scale=su, x_packed=True, ln_fold=(mean, rstd, ln_c))
     # the packed gated rows decode to u (fp32-grade), with power-of-two scales that keep every element below 2^15
-    dec = _unpack_g8(up, su, Hp)
+    dec = unpack_g8(up, su, Hp)
     assert (dec[:, H:] == 0).all()
     assert ((dec[:, :H].cpu() - u64).abs().max(1).values / u64.abs().max(1).values.clamp_min(1e-30)).max().item() < 1e-5
     assert (torch.log2(su) == torch.log2(su).round()).all() and (u64.abs().max(1).values * su.cpu().double() < 2.0 ** 15).all()
@@ -883,7 +879,7 @@ def test_gemm_row_ln_512(ops):
             plain = ops.linear(xp, fw, None, act=ops.ACT_GELU, rowbias=cu(rb), rowgroup=grp, x_scale=sx, x_packed=True, row_ln=(cu(gam), cu(bet), eps))
     finally:
         L.psam_gemm_f16x3p_force_epilogue(-1)
-    dec = _unpack_g8(out, so, N).cpu().double()
+    dec = unpack_g8(out, so, N).cpu().double()
     assert (torch.log2(so) == torch.log2(so).round()).all() and (want.abs().max(1).values * so.cpu().double() < 2.0 ** 15).all()
     e_pack = ((dec - want).abs().max() / want.abs().max()).item()
     e_plain = ((plain.cpu().double() - want).abs().max() / want.abs().max()).item()
@@ -915,7 +911,7 @@ def test_gemm_row_epilogues_upscaling_chain(ops):
         masks = torch.empty(Z, C, Npts, device="cuda")
         ops.linear(u1p, fw3, cu(b3), act=ops.ACT_GELU, x_scale=s1, x_packed=True, hyper=(cu(hyper), masks, Npts), no_store=True)
         full = ops.linear(u1p, fw3, cu(b3), act=ops.ACT_GELU, x_scale=s1, x_packed=True)      # the same GEMM with its output stored
-    dec = _unpack_g8(u1p, s1, E).cpu()
+    dec = unpack_g8(u1p, s1, E).cpu()
     assert ((dec - u1).abs().max() / u1.abs().max()).item() < 2e-6
     m = u1.abs().max(1).values * s1.cpu().double()
     assert (s1 == s1[0]).all() and 2.0 ** 14 <= bound * s1[0].item() < 2.0 ** 15 and (m < 2.0 ** 15).all(), "scale from the LayerNorm bound"
@@ -1034,7 +1030,7 @@ def test_group_max_pos_fourier_addbcast_interp(ops):
     _close(out, want_ln, 1e-5, what="interp3 + LN + GELU")
     sc = torch.empty(4 * 300, device="cuda")
     ops.interp3(cu(src), cu(idx), cu(w3), out, 2, scale_out=sc, ln=(cu(gam), cu(bet), 1e-5), act=ops.ACT_GELU)
-    dec = _unpack_g8(out.view(-1, 256), sc, 256).cpu()
+    dec = unpack_g8(out.view(-1, 256), sc, 256).cpu()
     assert ((dec - want_ln.view(-1, 256)).abs().max() / want_ln.abs().max()).item() < 2e-6, "packed interp3 + LN + GELU"
 
 
@@ -1158,7 +1154,7 @@ def test_attention_packed_operands(ops, H, L, B, spike):
         with ops.gemm_mode("f16x3"):
             ops.attention_packed(xp, sc, out, so, B, H, L, hd, scale, vmax * 1.01)
         assert (so == so[0]).all() and float(torch.log2(so[0])) == round(float(torch.log2(so[0]))) and vmax * float(so[0]) < 2.0 ** 15
-        got = _unpack_g8(out, so, D).cpu().view(B, L, D)
+        got = unpack_g8(out, so, D).cpu().view(B, L, D)
         err = (got - want).abs().max().item() / want.abs().max().item()
         print(f"\n[packed-operand attention H={H} L={L} B={B} bound x{slack:g}] rel err {err:.2e}")
         assert err < 2e-6, err

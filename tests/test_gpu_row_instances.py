@@ -21,6 +21,8 @@ import torch
 import torch.nn.functional as F
 
 from oracle import pointsam_oracle as O
+import g8_reference
+from g8_reference import unpack_g8
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "point_sam_amd", "csrc")
@@ -194,7 +196,7 @@ def test_registry_matches_the_launch_sites():
     assert dispatch_chain(row, "LN_LAUNCH", "cols") == LN_CHAIN
     assert dispatch_chain(row, "LNV_LAUNCH", "span") == LNV_CHAIN
     assert dispatch_chain(row, "SG_LAUNCH", "H") == SG_CHAIN
-    assert "const int span = pack ? ((cols + 31) & ~31) : cols;" in row
+    assert "const int span = pack ? kpad32(cols) : cols;" in row and "int kpad32(int k) { return (k + 31) & ~31; }" in _read("g8_pack.h")
     assert "if (C == 256) {" in re.sub(r"\s+", " ", row[row.index("PSAM_API int32_t psam_interp3_ex("):])
     for k, i in INSTANCES.items():
         args = k[k.index("<") + 1:-1].split(",") if "<" in k else []
@@ -276,6 +278,7 @@ SWIGLU_ROWS = (1, 9)
 INTERP_G = 20
 INTERP_GENERIC_C = (64, 128, 320, 512)      # 320: the second trip of the 256-column loop with idle lanes
 INTERP_SHAPES = [(1, 1, 1), (3, 101, 3), (2, 6, 1), (4, 300, 2)]      # (Z, N, rep): 1, 303, 12, 1200 rows -> tails of 1, 3, 0, 0 rows of the 4-row wave
+INTERP_FIVE_ROWS = (1, 5, 1)      # a full wave, then a second one that holds one row and three clamped duplicates (computed, exchanged, not stored)
 
 
 def test_cases_reach_every_instance():
@@ -350,14 +353,6 @@ class Guarded:
         assert (g == SENTINEL).all(), f"{what}: {int((g != SENTINEL).sum())} floats outside the output window were written"
 
 
-def _unpack_g8(p, scale, K):
-    """[rows, Kp] g8-packed containers -> (hi + lo) / scale as fp64 [rows, K] (the inverse of the packing)."""
-    p, scale = p.detach().cpu(), scale.detach().cpu()
-    rows, Kp = p.shape
-    h = p.contiguous().view(torch.float16).view(rows, Kp // 8, 2, 8).double()
-    return ((h[:, :, 0] + h[:, :, 1]).reshape(rows, Kp) / scale.double()[:, None])[:, :K]
-
-
 def _same_words(a, b):
     return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
 
@@ -371,6 +366,18 @@ def _packed_is_the_packing_of(ops, words, scales, y, what):
     print(f"| {what} | words differing {nw}/{want_w.numel()} | scales differing {ns}/{want_s.numel()} |")
     assert ns == 0, f"{what}: {ns} row scales differ from row_scale_f16 of the unpacked output"
     assert nw == 0, f"{what}: {nw} packed words differ from pack_rows_g8 of the unpacked output"
+    _is_the_host_packing_of(words, scales, y, what)
+
+
+def _is_the_host_packing_of(words, scales, y, what):
+    """The same two equalities against tests/g8_reference.py: torch on the CPU, no device code of the project in the expectation."""
+    host_s = g8_reference.row_scale_f16(y)
+    host_w = g8_reference.pack_g8(y, host_s)
+    nw = int((words.contiguous().view(torch.int32).cpu() != host_w).sum())
+    ns = int((scales.cpu() != host_s).sum())
+    print(f"| {what}, host packer | words differing {nw}/{host_w.numel()} | scales differing {ns}/{host_s.numel()} |")
+    assert ns == 0, f"{what}: {ns} row scales differ from g8_reference.row_scale_f16 of the unpacked output"
+    assert nw == 0, f"{what}: {nw} packed words differ from g8_reference.pack_g8 of the unpacked output"
 
 
 def _one_ulp(a, b):
@@ -429,7 +436,7 @@ def test_patch_l1_instances(ops, s, C, central, radius):
     _confirm(ops, "patch_l1", patch_code(C, central, True), what + " packed")
     pk.untouched(what + " packed"); sc.untouched(what + " scales")
     scales = sc.win[:, 0].contiguous()
-    _err(_unpack_g8(pk.win, scales, 128), ref, 2e-5, "patch_l1 packed", what + " packed, decoded", rowmax_term=2.0 ** -21)
+    _err(unpack_g8(pk.win, scales, 128), ref, 2e-5, "patch_l1 packed", what + " packed, decoded", rowmax_term=2.0 ** -21)
     _packed_is_the_packing_of(ops, pk.win, scales, out.win, what + " packed")
 
 
@@ -561,7 +568,47 @@ def test_layernorm_packed_instances(ops, cols, ld):
             y, words, scales, _, ref = _ln_packed_runs(ops, cols, ld, rows, act)
             what = f"LN packed rows={rows} cols={cols} act={act}"
             _packed_is_the_packing_of(ops, words, scales, y, what)
-            _err(_unpack_g8(words, scales, cols), ref, 2e-5, "layernorm packed", what + ", decoded", rowmax_term=2.0 ** -21)
+            _err(unpack_g8(words, scales, cols), ref, 2e-5, "layernorm packed", what + ", decoded", rowmax_term=2.0 ** -21)
+
+
+@gpu
+def test_layernorm_packed_last_lane_pairs_with_a_zero_lane(ops):
+    """cols = 260 = 4 (mod 8) on a row stride of packed_cols(260) = 288: the last float4 of the row shares its group with a lane that holds zeros, and the 28
+    padding columns are written as zeros over the 7.0 they held.  Five rows: a workgroup of four waves, then a ragged one."""
+    cols, ld, rows = 260, ops.packed_cols(260), 5
+    assert ld == 288
+    for act in (ops.ACT_NONE, ops.ACT_GELU):
+        y, words, scales, _, ref = _ln_packed_runs(ops, cols, ld, rows, act)
+        what = f"LN packed rows={rows} cols={cols} ld={ld} act={act}"
+        assert words.shape == (rows, ld)
+        _packed_is_the_packing_of(ops, words, scales, y, what)
+        _err(unpack_g8(words, scales, cols), ref, 2e-5, "layernorm packed", what + ", decoded", rowmax_term=2.0 ** -21)
+
+
+@gpu
+@pytest.mark.parametrize("K", [36, 64])
+def test_scale_pack_writers_at_the_pairing_edges(ops, K):
+    """psam_scale_pack_rows_g8, _add and _add_dual on five rows (four waves, then a ragged workgroup).  K = 36 = 4 (mod 8): the last real lane's partner is a
+    zero lane and columns 36 .. 63 are padding, written as zeros.  K = 64 with ld == K: the row is full, nothing is written past it (guard rows and the floats
+    outside the windows keep their sentinel).  Words and scales equal, bit for bit, pack_rows_g8 of the fp32 rows and the host packer of g8_reference."""
+    L, check = ops._lib.load(), ops._lib.check
+    rows, Kp = 5, ops.packed_cols(K)
+    g = torch.Generator().manual_seed(K)
+    x = (torch.randn(rows, K, generator=g) * torch.exp(2 * torch.randn(rows, 1, generator=g))).cuda()
+    pos = torch.randn(rows, K, generator=g).cuda()
+    total = pos + x              # one fp32 addition per element, as the kernels form it
+    stream = torch.cuda.current_stream().cuda_stream
+    win = lambda: (Guarded(rows, Kp), Guarded(rows, 1))
+    (p1, s1), (p2, s2), (p3, s3), (p4, s4) = win(), win(), win(), win()
+    check(L.psam_scale_pack_rows_g8(x.data_ptr(), K, rows, K, p1.win.data_ptr(), Kp, s1.win.data_ptr(), stream), "scale_pack")
+    check(L.psam_scale_pack_rows_g8_add(x.data_ptr(), K, pos.data_ptr(), K, rows, 1, rows, K, p2.win.data_ptr(), Kp, s2.win.data_ptr(), stream), "add")
+    check(L.psam_scale_pack_rows_g8_add_dual(x.data_ptr(), K, pos.data_ptr(), K, rows, 1, rows, K, p3.win.data_ptr(), s3.win.data_ptr(), p4.win.data_ptr(),
+                                             s4.win.data_ptr(), Kp, stream), "dual")
+    torch.cuda.synchronize()
+    for name, p, sc, y in (("scale_pack", p1, s1, x), ("add", p2, s2, total), ("dual, sum", p3, s3, total), ("dual, x", p4, s4, x)):
+        what = f"{name} rows={rows} K={K}"
+        p.untouched(what); sc.untouched(what + ": scales")
+        _packed_is_the_packing_of(ops, p.win, sc.win[:, 0].contiguous(), y, what)
 
 
 @gpu
@@ -573,8 +620,8 @@ def test_layernorm_row_bound(ops, cols, ld):
     rows = 37
     for act in (ops.ACT_NONE, ops.ACT_GELU):
         y, words0, scales0, _, ref = _ln_packed_runs(ops, cols, ld, rows, act)
-        _err(_unpack_g8(words0, scales0, cols), ref, 2e-5, "layernorm packed", f"LN packed cols={cols} ld={ld} act={act}, decoded", rowmax_term=2.0 ** -21)
-        assert (_unpack_g8(words0, scales0, _kpad(cols))[:, cols:] == 0).all(), "K padding not zero"
+        _err(unpack_g8(words0, scales0, cols), ref, 2e-5, "layernorm packed", f"LN packed cols={cols} ld={ld} act={act}, decoded", rowmax_term=2.0 ** -21)
+        assert (unpack_g8(words0, scales0, _kpad(cols))[:, cols:] == 0).all(), "K padding not zero"
         t0 = y.cpu().double().norm(dim=1)
         for c2, c1, c0 in LN_BOUND_COEFFS:
             _, words, scales, got, _ = _ln_packed_runs(ops, cols, ld, rows, act, bound=(c2, c1, c0))
@@ -657,7 +704,7 @@ def test_interp3_generic_kernel(ops, C):
 
 
 @gpu
-@pytest.mark.parametrize("Z,N,rep", INTERP_SHAPES)
+@pytest.mark.parametrize("Z,N,rep", INTERP_SHAPES + [INTERP_FIVE_ROWS])
 def test_interp3_c256_kernel(ops, Z, N, rep):
     """interp3_c256_kernel<4>, four rows per wave, at row counts with a tail of 1, 3 and 0 rows: plain; LayerNorm + GELU; LayerNorm + ReLU; LayerNorm + GELU
     packed -- each within 1e-5 of fp64 (packed: decoded, + 2^-21 rowmax), guard rows and scale_out beyond Z N untouched, and the packed rows bit for bit the
@@ -684,7 +731,7 @@ def test_interp3_c256_kernel(ops, Z, N, rep):
     _confirm(ops, "interp3", 256, what)
     out.untouched(what); sc.untouched(what + ": scale_out beyond Z N")
     scales = sc.win[:, 0].contiguous()
-    _err(_unpack_g8(out.win, scales, C), F.gelu(ln).view(-1, C), 1e-5, "interp3 packed", what + ", decoded", rowmax_term=2.0 ** -21)
+    _err(unpack_g8(out.win, scales, C), F.gelu(ln).view(-1, C), 1e-5, "interp3 packed", what + ", decoded", rowmax_term=2.0 ** -21)
     _packed_is_the_packing_of(ops, out.win, scales, y, what)
 
 

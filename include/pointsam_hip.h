@@ -754,6 +754,49 @@ int32_t psam_transfer_index_build(const float* src, int32_t N, const float* orig
 int32_t psam_transfer_plan(const float* src, int32_t N, const void* ws, size_t ws_bytes, const float* origin, float inv_h, float r2,
                            const float* qry, int32_t M, const float* pose, float eps, int32_t* idx3, float* w3, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- camera views */
+
+/* A picture of a cloud and the way back from it (point_sam_amd/views.py): a z-buffer of point splats, the point under a pixel, packed masks painted
+ * into the image, image masks lifted to packed masks of the points visible in the view.  All arithmetic is fp32, every operation rounded on its own,
+ * division IEEE; every output is a function of the inputs alone.  No call allocates, creates a stream or an event, or synchronises with the host.
+ *
+ * Camera.  pose: 12 floats in HOST memory, row-major 3 x 4, from the cloud's frame to the camera's (the convention of psam_transfer_plan's pose);
+ *   fx, fy finite and > 0, cx, cy finite; width, height in [1, 8192]; near finite and > 0.  The camera looks along +z of its frame.
+ * Projection of point i = (x, y, z):
+ *     c_a = ((P[a][0] x + P[a][1] y) + P[a][2] z) + P[a][3]
+ *     u = fx (c_x / c_z) + cx,  v = fy (c_y / c_z) + cy
+ *     in view   iff c_z >= near, c_z is finite, 0 <= u < width and 0 <= v < height: fp32 compares, a NaN is false everywhere, and the compares come
+ *               before any conversion to an integer (u = -0.0 is in pixel 0, u == width is out, u ~ 1e30 is out)
+ *     pixel     (floorf(u), floorf(v)), p = y * width + x
+ *     key_i     (bits(c_z) << 32) | i as an unsigned 64-bit word; c_z > 0, so the bit order is the value order.  0 < N <= 2^28
+ * Splat with footprint s in 0 .. 3: point i offers key_i to every pixel (px + dx, py + dy), |dx|, |dy| <= s, inside the image.  keys [height, width]
+ *   uint64 holds the minimum key offered to each pixel, all ones where none was: the low word is the winner's index (-1 if empty), the high word its
+ *   depth as a float (a NaN pattern if empty: read it as +inf).  The minimum of a set does not depend on the order of arrival and equal depths go to
+ *   the lower index, so keys depends on (points, camera, s) alone.
+ * Pick with window w in 0 .. 16: for a click at integer pixel (qx, qy) (pixels [P, 2] int32, x first; may lie outside the image), among the non-empty
+ *   pixels (qx + dx, qy + dy), |dx|, |dy| <= w, inside the image the one lowest in (dx dx + dy dy, key); point_index [P] = its point index, -1 if none.
+ * Paint, bits [K, ceil(N / 64)] in the layout of psam_mask_pack: a pixel whose key is empty or whose index is not below N (checked before a bit word is
+ *   read: keys of another cloud give a wrong picture, not a wild load) has no point.
+ *     ids [height, width] int32            the lowest row k whose bit for the pixel's point is set (proposals are best first), -1 if none or no point
+ *     rows [K, height, width] uint8        that bit of row k, 0 without a point
+ * Lift, img [K, height, width] uint8 and tau >= 0 (+inf allowed): bit i of row k of bits [K, ceil(N / 64)] iff point i is in view with centre pixel p,
+ *   keys[p] is not empty, c_z <= depth(keys[p]) + tau (one rounded add) and img[k, p] != 0.  img == NULL: K must be 1, every pixel counts as set -- the
+ *   VISIBLE SET of the view.  Bits past N are zero; area [K] (may be NULL) = the rows' popcounts.  keys must be psam_view_splat's for the same points
+ *   and camera (any s).
+ * A null pointer, N outside (0, 2^28], a side outside [1, 8192], s outside 0 .. 3, w outside 0 .. 16, fx, fy or near not finite and positive, cx, cy or
+ * a pose entry not finite, tau negative or NaN, K or P < 1: -1, before any launch; a misaligned pointer: -2. */
+int32_t psam_view_splat(const float* xyz, int32_t N, const float* pose, float fx, float fy, float cx, float cy, int32_t width, int32_t height,
+                        float znear, int32_t s, uint64_t* keys, psam_stream_t stream);
+int32_t psam_view_pick(const uint64_t* keys, int32_t width, int32_t height, const int32_t* pixels, int32_t P, int32_t w, int32_t* point_index,
+                       psam_stream_t stream);
+int32_t psam_view_paint_ids(const uint64_t* keys, int32_t width, int32_t height, const uint64_t* bits, int32_t K, int32_t N, int32_t* ids,
+                            psam_stream_t stream);
+int32_t psam_view_paint_rows(const uint64_t* keys, int32_t width, int32_t height, const uint64_t* bits, int32_t K, int32_t N, uint8_t* rows,
+                             psam_stream_t stream);
+int32_t psam_view_lift_bits(const float* xyz, int32_t N, const float* pose, float fx, float fy, float cx, float cy, int32_t width, int32_t height,
+                            float znear, const uint64_t* keys, const uint8_t* img, int32_t K, float tau, uint64_t* bits, int32_t* area,
+                            psam_stream_t stream);
+
 /* ---------------------------------------------------------------- connected components of masks */
 
 /* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel

@@ -37,6 +37,9 @@ SOURCES = [
     # radius 3-NN into another cloud: the cells of scene.hip, the distances and weights of scene_interp.hip.  No SLP vectorisation, as for geometry.hip
     # below: it packs two rows of the pose into a v_pk_mul_f32 that broadcasts one half of a register pair.
     ("transfer.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # camera views: the projection's fp32 operations rounded one at a time; the pose is transfer.hip's (csrc/rigid_pose.h), and so is the reason for
+    # leaving SLP vectorisation off.
+    ("views.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # instance geometry: the extents' fp32 operations rounded one at a time, the moments' fp64 terms exact.  No SLP vectorisation: it packs the three
     # projections into v_pk_mul_f32 / v_pk_add_f32 that broadcast one half of a register pair, the form isa_lint.py refuses; the kernels are gather-bound.
     ("geometry.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

@@ -21,6 +21,7 @@
 // Every fp32 operation is rounded on its own (-ffp-contract=off).  Caller-owned workspace; no allocation, no host synchronisation.
 #include "common.h"
 #include "interp_select.h"
+#include "rigid_pose.h"      // the pose and its arithmetic, shared with views.hip
 #include "voxel_table.h"
 
 #include <cmath>
@@ -61,27 +62,19 @@ __global__ __launch_bounds__(TRANSFER_THREADS) void transfer_insert_kernel(const
     next[j] = after;
 }
 
-struct TransferPose {
-    float m[12];          // row-major 3 x 4, query frame -> source frame
-};
-
 // One thread per query: 27 look-ups in the finished table, each followed by a walk along the cell's chain.
 template <bool POSE>
 __global__ __launch_bounds__(TRANSFER_THREADS) void transfer_plan_kernel(const float* __restrict__ src, int N, const u64* __restrict__ keys,
                                                                        const unsigned* __restrict__ head, const unsigned* __restrict__ next, int capacity,
                                                                        float ox, float oy, float oz, float inv_h, float r2,
-                                                                       const float* __restrict__ qry, int M, TransferPose P, float eps,
+                                                                       const float* __restrict__ qry, int M, RigidPose P, float eps,
                                                                        int* __restrict__ idx3, float* __restrict__ w3) {
 #pragma clang fp contract(off)
     const int i = blockIdx.x * TRANSFER_THREADS + threadIdx.x;
     if (i >= M) return;
     const float x = qry[(int64_t)i * 3 + 0], y = qry[(int64_t)i * 3 + 1], z = qry[(int64_t)i * 3 + 2];
     float px = x, py = y, pz = z;
-    if (POSE) {
-        px = ((P.m[0] * x + P.m[1] * y) + P.m[2] * z) + P.m[3];
-        py = ((P.m[4] * x + P.m[5] * y) + P.m[6] * z) + P.m[7];
-        pz = ((P.m[8] * x + P.m[9] * y) + P.m[10] * z) + P.m[11];
-    }
+    if (POSE) pose_apply(P, x, y, z, px, py, pz);                  // query frame -> source frame
     InterpBest b = interp_none();
     u64 cx, cy, cz;
     if (transfer_cell(px, py, pz, ox, oy, oz, inv_h, cx, cy, cz)) {
@@ -146,12 +139,9 @@ PSAM_API int32_t psam_transfer_plan(const float* src, int32_t N, const void* ws,
     const TransferWs w = transfer_layout(const_cast<void*>(ws), N);
     const dim3 grid((unsigned)psam_cdiv(M, TRANSFER_THREADS)), block(TRANSFER_THREADS);
     const int capacity = (int)voxel_capacity(N);
-    TransferPose P = {};
+    RigidPose P = {};
     if (pose) {
-        for (int a = 0; a < 12; ++a) {
-            PSAM_REQUIRE(std::isfinite(pose[a]), PSAM_EINVAL, "psam_transfer_plan: pose must be finite");
-            P.m[a] = pose[a];
-        }
+        PSAM_REQUIRE(pose_load(pose, P), PSAM_EINVAL, "psam_transfer_plan: pose must be finite");
         hipLaunchKernelGGL(transfer_plan_kernel<true>, grid, block, 0, stream, src, (int)N, (const u64*)w.table.keys, (const unsigned*)w.table.low,
                            (const unsigned*)w.next, capacity, origin[0], origin[1], origin[2], inv_h, r2, qry, (int)M, P, eps, (int*)idx3, w3);
     } else {

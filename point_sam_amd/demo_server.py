@@ -17,6 +17,8 @@ POST /instances (not in the reference): /segment_all plus one box per kept mask 
 into the ball around the current /segment mask (predictor.set_crop_to_mask).
 POST /propagate {pointcloud, radius, pose?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
 there (predictor.snapshot / propagate).
+POST /view {camera, splat?} (not in the reference): the loaded cloud as a camera sees it, a z-buffered point-splat image (predictor.render_view) .
+POST /click_pixel {pixel, label, window?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -83,6 +85,7 @@ class DemoSession:
         self.masks = []
         self._reset_prompts()
         self.segment_mask = None
+        self.view = None                       # the last /view of the loaded cloud (views.View); another cloud drops it
 
     def _set_cloud(self):
         smooth = {"smooth": True} if self.smooth_edges else {}
@@ -107,6 +110,7 @@ class DemoSession:
             self.pc_rgb = torch.from_numpy(col).to(self.device).float()[None]
             self.crop = None
             self.norm = None
+            self.view = None
         return {"response": "success"}
 
     def load_pointcloud(self, path: str) -> dict:
@@ -133,6 +137,7 @@ class DemoSession:
         self.pc_rgb = torch.from_numpy(rgb).to(self.device).float()[None]
         self.crop = None
         self.norm = norm
+        self.view = None
         return {"xyz": xyz.flatten().tolist(), "rgb": rgb.flatten().tolist()}
 
     def static_file(self, rel: str):
@@ -177,30 +182,85 @@ class DemoSession:
         with self.lock:
             if self.pc_xyz is None:
                 raise ValueError("/segment before a point cloud was set")
-            # the click joins the session only after the predictor accepted it: a malformed point must not poison every later click
-            point = np.asarray(data["prompt_point"], dtype=np.float32)
-            label = int(data["prompt_label"])
-            if point.shape != (3,) or not np.isfinite(point).all():
-                raise ValueError("prompt_point must be three finite numbers")
-            prompts, labels = self.prompts + [point.tolist()], self.labels + [label]
-            pts = torch.from_numpy(np.array(prompts, dtype=np.float32)).to(self.device).float()[None]
-            lab = torch.from_numpy(np.array(labels)).to(self.device)[None]
+            return self._segment(data)
+
+    def _segment(self, data: dict) -> dict:
+        """/segment's work; the caller holds the lock and has checked that a cloud is loaded."""
+        # the click joins the session only after the predictor accepted it: a malformed point must not poison every later click
+        point = np.asarray(data["prompt_point"], dtype=np.float32)
+        label = int(data["prompt_label"])
+        if point.shape != (3,) or not np.isfinite(point).all():
+            raise ValueError("prompt_point must be three finite numbers")
+        prompts, labels = self.prompts + [point.tolist()], self.labels + [label]
+        pts = torch.from_numpy(np.array(prompts, dtype=np.float32)).to(self.device).float()[None]
+        lab = torch.from_numpy(np.array(labels)).to(self.device)[None]
+        with torch.no_grad():
+            self._set_cloud()
+            mask, scores, logits = self.predictor.predict_masks(pts, lab, self.prompt_mask, self.prompt_mask is None)
+        self.prompts, self.labels = prompts, labels
+        best = torch.argmax(scores[0])
+        self.prompt_mask = logits[0][best][None]
+        if self.clean_min_points is None:
+            self.segment_mask = mask[0][best] > 0
+        else:
+            from . import ops
+            from .regions import RegionConfig
+            cfg = RegionConfig(min_island=self.clean_min_points, min_hole=self.clean_min_points, keep_clicked=True)
+            with torch.no_grad():
+                bits, _, _ = self.predictor.clean_masks(logits[:1, best:best + 1], cfg, pts, lab)
+            self.segment_mask = ops.mask_unpack(bits, mask.shape[-1])[0]
+        return {"seg": self.segment_mask.cpu().numpy().tolist()}
+
+    def render_view(self, data: dict) -> dict:
+        """The loaded cloud as a camera sees it: {"camera": {...}, "splat": s (optional, 0 .. 3, default 1)}; the camera is either {"pose": 3 x 4 or
+        4 x 4 rows (cloud -> camera), "fx", "fy", "cx", "cy", "width", "height", "near" (optional)} or {"eye", "target", "up", "fov_y_degrees",
+        "width", "height", "near" (optional)}, in the loaded cloud's normalised coordinates.  -> {"width", "height", "rgb": the image's
+        height * width * 3 bytes, row-major RGB, base64; an empty pixel is black}.  The view is kept for /click_pixel until another cloud is loaded."""
+        import base64
+        from .views import Camera
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/view before a point cloud was set")
+            if not isinstance(data, dict) or "camera" not in data or set(data) - {"camera", "splat"} or not isinstance(data["camera"], dict):
+                raise ValueError('/view takes {"camera": {...}, "splat": s (optional)}')
+            spec, splat = data["camera"], data.get("splat", 1)
+            if isinstance(splat, bool) or not isinstance(splat, int) or not 0 <= splat <= 3:
+                raise ValueError("splat must be an integer in 0 .. 3")
+            explicit, aimed = {"pose", "fx", "fy", "cx", "cy", "width", "height"}, {"eye", "target", "up", "fov_y_degrees", "width", "height"}
+            if set(spec) - {"near"} == explicit:
+                camera = Camera(**spec)
+            elif set(spec) - {"near"} == aimed:
+                camera = Camera.look_at(**spec)
+            else:
+                raise ValueError(f"camera takes {sorted(explicit)} or {sorted(aimed)}, and optionally near")
             with torch.no_grad():
                 self._set_cloud()
-                mask, scores, logits = self.predictor.predict_masks(pts, lab, self.prompt_mask, self.prompt_mask is None)
-            self.prompts, self.labels = prompts, labels
-            best = torch.argmax(scores[0])
-            self.prompt_mask = logits[0][best][None]
-            if self.clean_min_points is None:
-                self.segment_mask = mask[0][best] > 0
-            else:
-                from . import ops
-                from .regions import RegionConfig
-                cfg = RegionConfig(min_island=self.clean_min_points, min_hole=self.clean_min_points, keep_clicked=True)
-                with torch.no_grad():
-                    bits, _, _ = self.predictor.clean_masks(logits[:1, best:best + 1], cfg, pts, lab)
-                self.segment_mask = ops.mask_unpack(bits, mask.shape[-1])[0]
-            return {"seg": self.segment_mask.cpu().numpy().tolist()}
+                view = self.predictor.render_view(camera, splat)
+                img = (view.colour(self.pc_rgb[0], 0.0).clamp(0, 1) * 255).round().to(torch.uint8)
+            self.view = view
+            return {"width": camera.width, "height": camera.height, "rgb": base64.b64encode(img.cpu().numpy().tobytes()).decode("ascii")}
+
+    def click_pixel(self, data: dict) -> dict:
+        """A click on the last /view: {"pixel": [x, y], "label": l, "window": w (optional, 0 .. 16, default 2)}.  The point shown nearest to the pixel
+        within the window (predictor.click_pixels) becomes the prompt, and the answer is /segment's for that point, bit for bit; a pixel that shows
+        nothing is a 400 that leaves the click state alone."""
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/click_pixel before a point cloud was set")
+            if self.view is None:
+                raise ValueError("/click_pixel before any /view of this point cloud")
+            if not isinstance(data, dict) or not {"pixel", "label"} <= set(data) or set(data) - {"pixel", "label", "window"}:
+                raise ValueError('/click_pixel takes {"pixel": [x, y], "label": l, "window": w (optional)}')
+            pixel, window = data["pixel"], data.get("window", 2)
+            if not isinstance(pixel, list) or len(pixel) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in pixel):
+                raise ValueError("pixel must be two integers [x, y]")
+            if isinstance(window, bool) or not isinstance(window, int) or not 0 <= window <= 16:
+                raise ValueError("window must be an integer in 0 .. 16")
+            label = int(data["label"])
+            with torch.no_grad():
+                self._set_cloud()
+                pts, _ = self.predictor.click_pixels(self.view, [pixel], [label], window)
+            return self._segment({"prompt_point": pts[0, 0].cpu().numpy().tolist(), "prompt_label": label})
 
     def propagate(self, data: dict) -> dict:
         """The next scan of a sequence: {"pointcloud": name, "radius": r, "pose": 3 x 4 or 4 x 4 rows (optional)}.  The kept masks (/next) plus the
@@ -428,6 +488,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
                 return self._send(400, {"error": f"bad JSON: {e}"})
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
                       "/segment_all": lambda: session.segment_all(data), "/propagate": lambda: session.propagate(data),
+                      "/view": lambda: session.render_view(data), "/click_pixel": lambda: session.click_pixel(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/instances": lambda: session.instances(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}

@@ -1601,6 +1601,126 @@ def transfer_plan(index: TransferIndex, xyz: torch.Tensor, pose=None, eps: float
     return idx3, w3
 
 
+# ------------------------------------------------------------------------------------------ camera views (csrc/views.hip)
+VIEW_MAX_SIDE, VIEW_MAX_SPLAT, VIEW_MAX_WINDOW = 8192, 3, 16
+
+
+def _view_int(value, lo: int, hi: int, what: str) -> int:
+    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
+        raise ValueError(f"{what} must be an integer in {lo} .. {hi}, got {value!r}")
+    return value
+
+
+def _view_camera(camera, what: str):
+    """-> (the pose's ctypes words, kept alive by the caller for the call; the nine camera arguments of the C entry points).  camera: a views.Camera, or
+    anything with its attributes (pose_words: twelve fp32 words, fx, fy, cx, cy, width, height, near)."""
+    try:
+        words = [float(v) for v in camera.pose_words]
+        args = (float(camera.fx), float(camera.fy), float(camera.cx), float(camera.cy), int(camera.width), int(camera.height), float(camera.near))
+    except (AttributeError, TypeError):
+        raise TypeError(f"{what}: camera must be a views.Camera, got {type(camera).__name__}") from None
+    if len(words) != 12:
+        raise ValueError(f"{what}: the camera's pose must have twelve words, got {len(words)}")
+    P = (ctypes.c_float * 12)(*words)
+    return P, (ctypes.addressof(P),) + args
+
+
+def _view_keys(keys, what: str):
+    """The shape of a view's keys; whether they live on the GPU is the caller's last check (_chk), after every check of a value."""
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
+        raise TypeError(f"{what}: keys must be an int64 tensor (view_splat), got {getattr(keys, 'dtype', type(keys).__name__)}")
+    if keys.dim() != 2 or not (1 <= keys.shape[0] <= VIEW_MAX_SIDE and 1 <= keys.shape[1] <= VIEW_MAX_SIDE):
+        raise ValueError(f"{what}: keys must be [height, width] with sides in 1 .. {VIEW_MAX_SIDE}, got {tuple(keys.shape)}")
+    return keys.shape[0], keys.shape[1]
+
+
+def _view_bits(keys, bits, N: int, what: str):
+    H, W = _view_keys(keys, what)
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64:
+        raise TypeError(f"{what}: bits must be an int64 tensor, got {getattr(bits, 'dtype', type(bits).__name__)}")
+    if isinstance(N, bool) or not isinstance(N, int) or not 1 <= N <= 1 << 28:
+        raise ValueError(f"{what}: N must be an integer in 1 .. 2^28, got {N!r}")
+    if bits.dim() != 2 or bits.shape[0] < 1 or bits.shape[1] != mask_words(N):
+        raise ValueError(f"{what}: bits {tuple(bits.shape)} for N = {N}: need [K >= 1, {mask_words(N)}]")
+    if bits.device != keys.device:
+        raise ValueError(f"{what}: keys are on {keys.device}, bits on {bits.device}")
+    _chk(keys, torch.int64, "keys"); _chk(bits, torch.int64, "bits")
+    return H, W, bits.shape[0]
+
+
+def view_splat(xyz: torch.Tensor, camera, splat: int = 1) -> torch.Tensor:
+    """xyz [N, 3] (or [1, N, 3]) f32, camera (views.Camera), footprint `splat` in 0 .. 3 -> keys [height, width] int64 words: per pixel the minimum
+    (bits(depth) << 32) | index over the in-view points whose pixel lies within `splat` of it on both axes, all ones (-1) where there is none
+    (include/pointsam_hip.h: camera views).  Exact and independent of the order the points arrive in.  No host synchronisation."""
+    xyz = _transfer_cloud(xyz, "view_splat: xyz")
+    s = _view_int(splat, 0, VIEW_MAX_SPLAT, "view_splat: splat")
+    P, cam = _view_camera(camera, "view_splat")
+    _chk(xyz, name="xyz")
+    keys = torch.empty(cam[6], cam[5], dtype=torch.int64, device=xyz.device)
+    check(_lib.load().psam_view_splat(xyz.data_ptr(), xyz.shape[0], *cam, s, keys.data_ptr(), _stream()), "psam_view_splat")
+    return keys
+
+
+def view_pick(keys: torch.Tensor, pixels: torch.Tensor, window: int = 2) -> torch.Tensor:
+    """keys [H, W] int64 (view_splat), pixels [P, 2] int32 (x, y) -> point_index [P] int32: the point of the non-empty pixel nearest to each click within
+    `window` (0 .. 16) pixels on both axes, by (squared pixel distance, key); -1 where the window is empty.  No host synchronisation."""
+    H, W = _view_keys(keys, "view_pick")
+    w = _view_int(window, 0, VIEW_MAX_WINDOW, "view_pick: window")
+    if not isinstance(pixels, torch.Tensor) or pixels.dim() != 2 or pixels.shape[1] != 2 or pixels.shape[0] < 1:
+        raise ValueError(f"view_pick: pixels must be a tensor [P, 2] with P >= 1, got {tuple(getattr(pixels, 'shape', ()))}")
+    _chk(keys, torch.int64, "keys"); _chk(pixels, torch.int32, "pixels")
+    out = torch.empty(pixels.shape[0], dtype=torch.int32, device=keys.device)
+    check(_lib.load().psam_view_pick(keys.data_ptr(), W, H, pixels.data_ptr(), pixels.shape[0], w, out.data_ptr(), _stream()), "psam_view_pick")
+    return out
+
+
+def view_paint_ids(keys: torch.Tensor, bits: torch.Tensor, N: int) -> torch.Tensor:
+    """keys [H, W] int64 (view_splat of a cloud of N points), bits [K, ceil(N / 64)] int64 words (mask_pack's layout) -> ids [H, W] int32: the lowest
+    row whose bit for the pixel's point is set, -1 where none is or the pixel is empty.  No host synchronisation."""
+    H, W, K = _view_bits(keys, bits, N, "view_paint_ids")
+    ids = torch.empty(H, W, dtype=torch.int32, device=keys.device)
+    check(_lib.load().psam_view_paint_ids(keys.data_ptr(), W, H, bits.data_ptr(), K, N, ids.data_ptr(), _stream()), "psam_view_paint_ids")
+    return ids
+
+
+def view_paint_rows(keys: torch.Tensor, bits: torch.Tensor, N: int) -> torch.Tensor:
+    """As view_paint_ids -> rows [K, H, W] uint8: row k's bit of every pixel's point, 0 at an empty pixel."""
+    H, W, K = _view_bits(keys, bits, N, "view_paint_rows")
+    rows = torch.empty(K, H, W, dtype=torch.uint8, device=keys.device)
+    check(_lib.load().psam_view_paint_rows(keys.data_ptr(), W, H, bits.data_ptr(), K, N, rows.data_ptr(), _stream()), "psam_view_paint_rows")
+    return rows
+
+
+def view_lift_bits(xyz: torch.Tensor, camera, keys: torch.Tensor, images: torch.Tensor = None, tau: float = 0.0):
+    """xyz [N, 3] f32, camera, keys [H, W] (view_splat of the same points and camera), images [K, H, W] uint8 or None, tau >= 0 ->
+    (bits [K, ceil(N / 64)] int64 words of mask_pack's layout, area [K] int32): point i has bit k iff it is in view, its depth is at most its centre
+    pixel's winning depth + tau, and images[k] is non-zero at that pixel.  images None: K = 1, every pixel set -- the points visible in the view.
+    No host synchronisation."""
+    import math
+    xyz = _transfer_cloud(xyz, "view_lift_bits: xyz")
+    H, W = _view_keys(keys, "view_lift_bits")
+    P, cam = _view_camera(camera, "view_lift_bits")
+    if (cam[6], cam[5]) != (H, W):
+        raise ValueError(f"view_lift_bits: keys {tuple(keys.shape)} are not the camera's {cam[6]} x {cam[5]} (height x width)")
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or math.isnan(tau) or tau < 0:
+        raise ValueError(f"view_lift_bits: tau must be a number >= 0, got {tau!r}")
+    K = 1
+    if images is not None:
+        if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
+            raise TypeError(f"view_lift_bits: images must be a uint8 tensor, got {getattr(images, 'dtype', type(images).__name__)}")
+        if images.dim() != 3 or images.shape[0] < 1 or tuple(images.shape[1:]) != (H, W):
+            raise ValueError(f"view_lift_bits: images must be [K >= 1, {H}, {W}], got {tuple(images.shape)}")
+        K = images.shape[0]
+        _chk(images, torch.uint8, "images")
+    _chk(xyz, name="xyz"); _chk(keys, torch.int64, "keys")
+    N = xyz.shape[0]
+    bits = torch.empty(K, mask_words(N), dtype=torch.int64, device=xyz.device)
+    area = torch.empty(K, dtype=torch.int32, device=xyz.device)
+    check(_lib.load().psam_view_lift_bits(xyz.data_ptr(), N, *cam, keys.data_ptr(), _p(images), K, float(tau), bits.data_ptr(), area.data_ptr(), _stream()),
+          "psam_view_lift_bits")
+    return bits, area
+
+
 # ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)
 def _region_ws(nbytes: int, dev, what: str):
     if nbytes == 0:

@@ -495,3 +495,86 @@ class PointSAMPredictor:
         radius = float(np.nextafter(np.float32(float(geo.radius[0]) * (1.0 + float(margin))), np.float32(np.inf)))
         self.set_crop(center, radius, voxel_size, max_points, smooth)
         return center, radius
+
+    # -- camera views (point_sam_amd/views.py) -------------------------------------------------------------------
+    def _view_cloud(self, what: str, view=None, cloud: int = 0):
+        """xyz [N, 3] contiguous of the cloud a view shows: the scan after set_scene (also under a crop: a view is of the scan), cloud `cloud` of the batch
+        after set_pointcloud.  With a view: it must have been rendered from a cloud of that many points."""
+        from .views import check_view
+        if view is not None and isinstance(getattr(view, "cloud", None), int):
+            cloud = view.cloud
+        xyz = self._geometry_cloud(what, cloud)[0]
+        if view is not None:
+            check_view(view, xyz.shape[0], what)
+        return xyz.contiguous()
+
+    @torch.no_grad()
+    def render_view(self, camera, splat: int = 1, cloud: int = 0):
+        """The cached cloud as `camera` sees it -> views.View: a z-buffer of point splats, every in-view point drawn into the (2 splat + 1)^2 pixels
+        around its own, the nearest point winning a pixel (ties: the lower index).  After set_scene the scan's points are drawn, with or without an
+        active crop; after set_pointcloud cloud `cloud` of the batch.  One pass over the points, no host synchronisation."""
+        from .views import Camera, View
+        if not isinstance(camera, Camera):
+            raise TypeError(f"render_view: camera must be a views.Camera, got {type(camera).__name__}")
+        xyz = self._view_cloud("render_view", None, cloud)
+        return View(ops.view_splat(xyz, camera, splat), camera, xyz.shape[0], splat, 0 if self.scene is not None else cloud)
+
+    @torch.no_grad()
+    def pick(self, view, pixels, window: int = 2):
+        """The points under pixel clicks: pixels [P, 2] integers (x, y) -> (point_index [P] int32, xyz [P, 3]): per click the point shown by the
+        non-empty pixel nearest to it within `window` pixels on both axes (ties in distance: the nearer point); -1 and NaN coordinates where the window
+        is empty.  No host synchronisation."""
+        from .views import check_pixels
+        xyz = self._view_cloud("pick", view)
+        idx = ops.view_pick(view.keys, check_pixels(pixels, xyz.device, "pick"), window)
+        pts = xyz.index_select(0, idx.clamp_min(0).long())
+        return idx, torch.where((idx < 0)[:, None], torch.full_like(pts, float("nan")), pts)
+
+    @torch.no_grad()
+    def click_pixels(self, view, pixels, labels, window: int = 2):
+        """Pixel clicks as point prompts: -> (prompt_points [1, P, 3], prompt_labels [1, P]) for predict_masks / predict_mask_bits, the coordinates those
+        of the picked points (pick).  A click that hits nothing is a ValueError naming the pixel; finding out costs the call's one host read."""
+        from .views import check_pixels
+        xyz = self._view_cloud("click_pixels", view)
+        pix = check_pixels(pixels, xyz.device, "click_pixels")
+        lab = torch.as_tensor(labels, device=xyz.device).reshape(-1)
+        if lab.numel() != pix.shape[0]:
+            raise ValueError(f"click_pixels: {pix.shape[0]} pixels but {lab.numel()} labels")
+        idx = ops.view_pick(view.keys, pix, window)
+        missed = torch.nonzero(idx < 0)[:, 0].cpu()                                  # the one host read
+        if missed.numel() > 0:
+            x, y = pix[int(missed[0])].tolist()
+            raise ValueError(f"click_pixels: the click at pixel ({x}, {y}) hits no point within {window} pixels")
+        return xyz.index_select(0, idx.long())[None], lab[None]
+
+    @torch.no_grad()
+    def mask_images(self, view, masks, rows: bool = False):
+        """Packed masks as pictures of the view: masks a `Proposals` or bits [K, W] int64 words of the viewed cloud's width (checked as mask_geometry
+        does) -> ids [height, width] int32, per pixel the first (best) mask that holds the point shown there, -1 for none or an empty pixel; with
+        rows=True -> [K, height, width] uint8, one binary image per mask."""
+        if not isinstance(rows, bool):
+            raise ValueError(f"mask_images: rows must be True or False, got {rows!r}")
+        xyz = self._view_cloud("mask_images", view)
+        bits = self._geometry_bits(masks, xyz.shape[0], "mask_images", "the scan" if self.scene is not None else "the cloud")
+        return (ops.view_paint_rows if rows else ops.view_paint_ids)(view.keys, bits, xyz.shape[0])
+
+    @torch.no_grad()
+    def lift_masks(self, view, images, tau: float):
+        """Image masks back to the cloud: images [K, height, width] (or one [height, width]) uint8 / bool, non-zero = inside -> (bits [K, W] int64
+        words of mask_pack's layout, area [K] int32): a point gets bit k iff it is VISIBLE in the view -- in the image, and at most `tau` behind the
+        point that won its pixel -- and images[k] is set at its pixel.  The format mask_geometry, set_crop_to_mask, the NMS and snapshot / transfer
+        take.  (Turning a lifted mask into a prompt mask would need a logit magnitude tuned on a trained checkpoint: not done here.)"""
+        xyz = self._view_cloud("lift_masks", view)
+        if not isinstance(images, torch.Tensor):
+            raise TypeError(f"lift_masks: images must be a tensor, got {type(images).__name__}")
+        if images.dim() == 2:
+            images = images[None]
+        if images.dtype == torch.bool:
+            images = images.to(torch.uint8)
+        return ops.view_lift_bits(xyz, view.camera, view.keys, images.to(xyz.device).contiguous(), tau)
+
+    @torch.no_grad()
+    def visible_bits(self, view, tau: float):
+        """The points visible in the view -> (bits [1, W], area [1]): lift_masks of an all-ones image."""
+        xyz = self._view_cloud("visible_bits", view)
+        return ops.view_lift_bits(xyz, view.camera, view.keys, None, tau)

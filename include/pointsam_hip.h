@@ -380,7 +380,9 @@ int32_t psam_scale_pack_rows_g8_add_dual(const float* X, int64_t ldx, const floa
 
 /* ONE EVA02 (SwiGLU) transformer block of the patch encoder in one call (csrc/blocks.hip) -- timm's block as the reference runs it
  * (pc_sam/model/pc_encoder.py:138-139, no rope): x += proj(SDPA(LN1 x)); x += fc2(LN(SiLU(fc1_g h) * fc1_x h)), h = LN2 x.  "f16x3" arithmetic with
- * every hand-over fused as the Python host does it: eight launches, nothing in between.  Head dim 64, dim % 32 == 0, B * L % 256 == 0.
+ * every hand-over fused as the Python host does it: eight launches, nothing in between.  Head dim 64 (heads == dim / 64), 256 <= dim <= 4096,
+ * dim % 128 == 0 (packed LayerNorm; fused epilogues on whole 128-column tiles), hidden rounded up to 32 a multiple of 64 and >= 128, B * L % 256 == 0;
+ * _prepare refuses any other dim / heads / hidden and psam_eva_block any other B * L with PSAM_EINVAL, before anything is launched.
  * psam_eva_block_prepare (load time; copies the weights to the host once, uses a temporary device buffer, synchronises) packs a block's weights
  * -- given in the reference's / timm's state-dict layout, [out, in] fp32 device pointers -- into `prepared` (psam_eva_block_prepared_bytes) and
  * fills the host-side `plan`; the LayerNorm parameters and the projection bias are read through the plan at run time and must stay alive. */
@@ -409,7 +411,7 @@ int32_t psam_eva_block(const psam_eva_block_plan_t* plan, const void* prepared, 
  * fc2 + residual.  Few token rows (one cloud: M = 512) leave most of the chip idle on whole-tile launches: every plain GEMM of the block takes the
  * library's split-K factor (psam_gemm_f16x3p_splitk) with the partial planes in the caller's workspace; when fc1 needs no split its epilogue hands
  * GELU(.) to fc2 g8-packed (per-row bound from the LayerNorm's L2 norm) and the scale + pack pass disappears.  dim % 32 == 0, hidden % 32 == 0,
- * 256 <= dim <= 4096, B * L >= 256.  `precision`: PSAM_PRECISION_F16X3 (the f32 / bf16x6 arithmetic of the same block is reachable through the
+ * hidden >= 128, 256 <= dim <= 4096, B * L >= 256.  `precision`: PSAM_PRECISION_F16X3 (the f32 / bf16x6 arithmetic of the same block is reachable through the
  * per-operator entries only). */
 #define PSAM_PRECISION_F16X3 2
 typedef struct {
@@ -498,7 +500,9 @@ int32_t psam_twoway_decoder_prepare(const psam_twoway_weights_t* weights, psam_t
 size_t psam_twoway_decoder_ws_bytes(int64_t Z, int32_t T, int32_t G, int32_t dim, int32_t mlp);
 /* tokens [Z*T, dim] (= query_pe), keys [Z*G, dim] in / out (src -> the transformer's second output), pos [Z / rep, G, dim] -> queries [Z*T, dim].
  * counters: the caller's arrival-counter block (PSAM_COUNTER_BYTES, see above) for the fused Linear + LayerNorm launches of the regrouped sequence;
- * NULL = the operator-by-operator sequence (the same operators, other launch boundaries: results equal to fp32 round-off). */
+ * NULL = the operator-by-operator sequence (the same operators, other launch boundaries: results equal to fp32 round-off).
+ * Z % rep == 0, T <= 8192 and G <= 8192 (every attention is psam_attention_small: Lk * 16 <= 128 KiB); anything else is refused with PSAM_EINVAL before
+ * the first launch. */
 int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void* prepared, const float* tokens, float* keys, const float* pos, int32_t rep, int64_t Z,
                             int32_t T, int32_t G, float* queries, void* ws, size_t ws_bytes, int32_t* counters, psam_stream_t stream);
 /* A/B and test hook: 0 = the operator-by-operator launch sequence (what the Python host issues), 1 = the regrouped sequence (fused Linear + LayerNorm

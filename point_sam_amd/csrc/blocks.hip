@@ -159,10 +159,13 @@ PSAM_API int32_t psam_eva_block_prepare(const psam_eva_block_weights_t* wt, psam
 #define WHO "psam_eva_block_prepare"
     PSAM_REQUIRE(wt && plan && prepared, PSAM_EINVAL, WHO ": null pointer");
     const int D = wt->dim, H = wt->hidden, heads = wt->heads;
-    PSAM_REQUIRE(D > 0 && H > 0 && heads > 0 && D % heads == 0 && D / heads == 64 && D % 32 == 0, PSAM_EINVAL,
-                 WHO ": head dim must be 64 and dim % 32 == 0 (the packed-operand attention)");
+    PSAM_REQUIRE(D > 0 && H > 0 && heads > 0 && D % heads == 0 && D / heads == 64, PSAM_EINVAL, WHO ": head dim must be 64 (the packed-operand attention)");
+    // the packed LayerNorm takes 256..4096 columns; the q|k|v GEMM (N = 3 dim, packed output) and fc2 (N = dim, folded LayerNorm) run fused epilogues,
+    // which exist for whole 128-column tiles only
+    PSAM_REQUIRE(D >= 256 && D <= 4096 && D % 128 == 0, PSAM_EINVAL, WHO ": need 256 <= dim <= 4096 and dim % 128 == 0 (packed LayerNorm, fused GEMM epilogues)");
     const int Hp = kpad32(H);
-    PSAM_REQUIRE(Hp % 64 == 0, PSAM_EINVAL, WHO ": hidden rounded up to 32 must be a multiple of 64 (fused SwiGLU epilogue)");
+    PSAM_REQUIRE(Hp % 64 == 0 && Hp >= 128, PSAM_EINVAL,
+                 WHO ": hidden rounded up to 32 must be a multiple of 64 (fused SwiGLU epilogue) and at least 128 (the K of a packed-operand GEMM)");
     PSAM_REQUIRE(prepared_bytes >= psam_eva_block_prepared_bytes(D, H), PSAM_EWORKSPACE, WHO ": prepared buffer too small");
     const float* ptrs[] = {wt->norm1_w, wt->norm1_b, wt->q_w, wt->q_b, wt->k_w, wt->v_w, wt->v_b, wt->proj_w, wt->proj_b, wt->norm2_w, wt->norm2_b,
                            wt->fc1_g_w, wt->fc1_g_b, wt->fc1_x_w, wt->fc1_x_b, wt->mlp_norm_w, wt->mlp_norm_b, wt->fc2_w, wt->fc2_b};
@@ -339,8 +342,8 @@ PSAM_API int32_t psam_eva_gelu_block_prepare(const psam_eva_gelu_block_weights_t
     PSAM_REQUIRE(wt && plan && prepared, PSAM_EINVAL, WHO ": null pointer");
     const int D = wt->dim, H = wt->hidden, heads = wt->heads;
     PSAM_REQUIRE(wt->precision == PSAM_PRECISION_F16X3, PSAM_EINVAL, WHO ": the coarse entry is built for PSAM_PRECISION_F16X3");
-    PSAM_REQUIRE(D >= 256 && D <= 4096 && D % 32 == 0 && H > 0 && H % 32 == 0 && heads > 0 && D % heads == 0, PSAM_EINVAL,
-                 WHO ": need 256 <= dim <= 4096, dim % 32 == 0, hidden % 32 == 0");
+    PSAM_REQUIRE(D >= 256 && D <= 4096 && D % 32 == 0 && H >= 128 && H % 32 == 0 && heads > 0 && D % heads == 0, PSAM_EINVAL,
+                 WHO ": need 256 <= dim <= 4096, dim % 32 == 0, hidden % 32 == 0, hidden >= 128 (the K of a packed-operand GEMM)");
     const int hd = D / heads;
     PSAM_REQUIRE(hd == 64 || (hd > 64 && hd <= 128 && hd % 8 == 0), PSAM_EINVAL, WHO ": head dim must be 64 or a multiple of 8 in (64, 128]");
     PSAM_REQUIRE(prepared_bytes >= psam_eva_gelu_block_prepared_bytes(D, H), PSAM_EWORKSPACE, WHO ": prepared buffer too small");
@@ -808,6 +811,8 @@ PSAM_API int32_t psam_twoway_decoder(const psam_twoway_plan_t* plan, const void*
     const int E = W.dim, IX = W.dim / W.downsample, H = W.heads, mlp = W.mlp;
     const int64_t R = Z * T, I = Z * G;
     PSAM_REQUIRE(rep > 0 && Z > 0 && Z % rep == 0 && T > 0 && G > 0 && R < ((int64_t)1 << 31) && I < ((int64_t)1 << 31), PSAM_EINVAL, "psam_twoway_decoder: bad shape");
+    // every attention is psam_attention_small, whose scores of one query live in LDS (Lk * 16 <= 128 KiB): refused here, before the first launch
+    PSAM_REQUIRE(T <= 8192 && G <= 8192, PSAM_EINVAL, "psam_twoway_decoder: at most 8192 tokens and 8192 patch tokens per prompt set (psam_attention_small)");
     PSAM_REQUIRE(ws_bytes >= psam_twoway_decoder_ws_bytes(Z, T, G, E, mlp), PSAM_EWORKSPACE, "psam_twoway_decoder: workspace too small");
     // Linear `slot` of `layer` (the final attention: layer = depth) with the packed form _prepare made of it (matrices of at least 128 x 128)
     auto lin = [&](int layer, int slot) {

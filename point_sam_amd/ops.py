@@ -703,7 +703,9 @@ class EvaBlock(_EvaStage):
 
     @staticmethod
     def supported(dim: int, heads: int, hidden: int) -> bool:
-        return dim % heads == 0 and dim // heads == 64 and dim % 32 == 0 and 256 <= dim <= 4096 and ((hidden + 31) // 32 * 32) % 64 == 0      # 256..4096: the packed LayerNorm (layernorm_can_pack)
+        # 256..4096: the packed LayerNorm (layernorm_can_pack); % 128: the fused epilogues of the q|k|v GEMM and fc2 (fuse_supported); what psam_eva_block_prepare accepts
+        hp = (hidden + 31) // 32 * 32
+        return heads > 0 and dim % heads == 0 and dim // heads == 64 and 256 <= dim <= 4096 and dim % 128 == 0 and hidden > 0 and hp % 64 == 0 and hp >= 128
 
     def run(self, x, B: int, L: int, ws=None):
         """x [B*L, dim] fp32, updated in place."""
@@ -724,8 +726,10 @@ class EvaGeluBlock(_EvaStage):
 
     @staticmethod
     def supported(dim: int, heads: int, hidden: int) -> bool:
-        hd = dim // heads
-        return dim % heads == 0 and 256 <= dim <= 4096 and dim % 32 == 0 and hidden % 32 == 0 and (hd == 64 or (64 < hd <= 128 and hd % 8 == 0))
+        if heads <= 0 or dim % heads:
+            return False
+        hd = dim // heads      # what psam_eva_gelu_block_prepare accepts
+        return 256 <= dim <= 4096 and dim % 32 == 0 and hidden >= 128 and hidden % 32 == 0 and (hd == 64 or (64 < hd <= 128 and hd % 8 == 0))
 
     def run(self, x, B: int, L: int, ws=None):
         """x [B*L, dim] fp32, updated in place."""

@@ -11,6 +11,7 @@ import torch
 from oracle import pointsam_oracle as O
 from point_sam_amd.config import VIT_GIANT, ModelConfig, get_config
 from point_sam_amd.weights import random_state_dict, state_dict_checksum
+from workspace_check import check_exact_workspace
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
@@ -322,28 +323,6 @@ def test_c_eva_gelu_block_matches_python_sequence(gpu):
     assert lib.psam_eva_gelu_block(ctypes.byref(blk.plan), blk.blob.data_ptr(), x.data_ptr(), 2, 256, small.data_ptr(), small.numel(), None, None) == -3      # PSAM_EWORKSPACE
 
 
-GUARD = 4096
-
-
-def _check_exact_workspace(need, call, reset, outputs, want):
-    """A coarse entry of csrc/blocks.hip on a workspace of exactly its *_ws_bytes.  call(ws, ws_bytes) -> status runs the entry through the C ABI;
-    reset() puts back what it updates in place or writes; outputs() are those tensors, want what the Python wrapper computed with a workspace of its
-    own.  The workspace sits between two guards inside a buffer filled with 0xA5: the call leaves both guards alone and gives the wrapper's bits;
-    with one byte less it answers PSAM_EWORKSPACE and touches nothing."""
-    assert need > 0 and need % 256 == 0
-    buf = torch.full((GUARD + need + GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
-    reset()
-    assert call(buf.data_ptr() + GUARD, need) == 0
-    torch.cuda.synchronize()
-    assert bool((buf[:GUARD] == 0xA5).all()) and bool((buf[GUARD + need:] == 0xA5).all()), "the call wrote outside its workspace"
-    assert len(outputs()) == len(want) and all(torch.equal(a, b) for a, b in zip(outputs(), want))
-    reset()
-    before = [t.clone() for t in outputs()]
-    assert call(buf.data_ptr() + GUARD, need - 1) == -3      # PSAM_EWORKSPACE
-    torch.cuda.synchronize()
-    assert all(torch.equal(a, b) for a, b in zip(outputs(), before))
-
-
 def _record_runs(stage):
     """Every later stage.run(...) also leaves (args, kwargs) in the returned list, tensors cloned before the call."""
     calls, run = [], stage.run
@@ -359,7 +338,7 @@ def _record_runs(stage):
 @pytest.mark.parametrize("kind,B,L", [("swiglu", 2, 128), ("gelu", 2, 256), ("gelu", 9, 256)])
 def test_exact_workspace_of_the_encoder_blocks(gpu, kind, B, L):
     """psam_eva_block (block 0 of ViT-B) and psam_eva_gelu_block (the mini giant block: one cloud, M = 512, split-K planes and counters in use; a batch,
-    M = 2304, the fused GELU hand-over) on a workspace of exactly *_ws_bytes (_check_exact_workspace)."""
+    M = 2304, the fused GELU hand-over) on a workspace of exactly *_ws_bytes (check_exact_workspace)."""
     import ctypes
     from point_sam_amd import ops
     from point_sam_amd.config import ViTConfig
@@ -377,13 +356,13 @@ def test_exact_workspace_of_the_encoder_blocks(gpu, kind, B, L):
         need = lib.psam_eva_gelu_block_ws_bytes(B * L, blk.dim, blk.hidden)
         counters = ops.arrival_counters(x.device)
         call = lambda ws, n: lib.psam_eva_gelu_block(ctypes.byref(blk.plan), blk.blob.data_ptr(), x.data_ptr(), B, L, ws, n, counters.data_ptr(), ops._stream())
-    _check_exact_workspace(need, call, lambda: x.copy_(x0), lambda: [x], [want])
+    check_exact_workspace(need, call, lambda: x.copy_(x0), lambda: [x], [want])
 
 
 @pytest.mark.parametrize("G,K", [(128, 64), (32, 256)])
 def test_exact_workspace_of_the_patch_encoder(gpu, G, K):
     """psam_patch_encoder as the patch embedding calls it, groups of 64 and of 256 (pooled in 64-row parts: the partial maxima reuse two buffers of the
-    workspace), on a workspace of exactly psam_patch_encoder_ws_bytes (_check_exact_workspace)."""
+    workspace), on a workspace of exactly psam_patch_encoder_ws_bytes (check_exact_workspace)."""
     import ctypes
     from point_sam_amd import ops
     lib = ops._lib.load()
@@ -402,11 +381,11 @@ def test_exact_workspace_of_the_patch_encoder(gpu, G, K):
     call = lambda ws, n: lib.psam_patch_encoder(ctypes.byref(enc.plan), enc.blob.data_ptr(), pts.data_ptr(), feats.data_ptr(), centers.data_ptr(), knn_idx.data_ptr(),
                                                 ops._p(kw.get("center_idx")), B, rep, N, G, K, feats.shape[-1], float(kw.get("radius") or 0.0), out.data_ptr(), ws, n,
                                                 ops._stream())
-    _check_exact_workspace(lib.psam_patch_encoder_ws_bytes(groups * K, groups, enc.h0, enc.h1), call, lambda: out.fill_(-7.0), lambda: [out], [want])
+    check_exact_workspace(lib.psam_patch_encoder_ws_bytes(groups * K, groups, enc.h0, enc.h1), call, lambda: out.fill_(-7.0), lambda: [out], [want])
 
 
 def test_exact_workspace_of_the_upscaling(gpu):
-    """psam_upscale_masks as the decoder calls it on a workspace of exactly psam_upscale_masks_ws_bytes (_check_exact_workspace)."""
+    """psam_upscale_masks as the decoder calls it on a workspace of exactly psam_upscale_masks_ws_bytes (check_exact_workspace)."""
     import ctypes
     from point_sam_amd import ops
     lib = ops._lib.load()
@@ -421,12 +400,12 @@ def test_exact_workspace_of_the_upscaling(gpu):
     assert (N, G) == (4096, 64) and torch.isfinite(want).all()
     call = lambda ws, n: lib.psam_upscale_masks(ctypes.byref(up.plan), up.blob.data_ptr(), keys.data_ptr(), idx3.data_ptr(), w3.data_ptr(), hyper.data_ptr(), rep, Z, N, G, C,
                                                 masks.data_ptr(), ws, n, ops._stream())
-    _check_exact_workspace(lib.psam_upscale_masks_ws_bytes(Z, N, G, C, up.dim), call, lambda: masks.fill_(-7.0), lambda: [masks], [want])
+    check_exact_workspace(lib.psam_upscale_masks_ws_bytes(Z, N, G, C, up.dim), call, lambda: masks.fill_(-7.0), lambda: [masks], [want])
 
 
 def test_exact_workspace_of_the_twoway_decoder(gpu):
     """psam_twoway_decoder as the decoder calls it (two clouds, three prompt points each) on a workspace of exactly psam_twoway_decoder_ws_bytes
-    (_check_exact_workspace), in each of its three launch sequences: they use different buffers of the workspace."""
+    (check_exact_workspace), in each of its three launch sequences: they use different buffers of the workspace."""
     import ctypes
     from point_sam_amd import ops
     lib = ops._lib.load()
@@ -451,7 +430,7 @@ def test_exact_workspace_of_the_twoway_decoder(gpu):
             lib.psam_twoway_decoder_force_fast(mode)
             want = tw.run(tokens, keys0.clone(), pos, rep, Z, T, G)
             assert all(torch.isfinite(t).all() for t in want) and not torch.equal(want[1], keys0)
-            _check_exact_workspace(lib.psam_twoway_decoder_ws_bytes(Z, T, G, tw.dim, tw.mlp), call, reset, lambda: [queries, keys], list(want))
+            check_exact_workspace(lib.psam_twoway_decoder_ws_bytes(Z, T, G, tw.dim, tw.mlp), call, reset, lambda: [queries, keys], list(want))
     finally:
         lib.psam_twoway_decoder_force_fast(-1)
 

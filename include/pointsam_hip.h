@@ -801,6 +801,45 @@ int32_t psam_view_lift_bits(const float* xyz, int32_t N, const float* pose, floa
                             float znear, const uint64_t* keys, const uint8_t* img, int32_t K, float tau, uint64_t* bits, int32_t* area,
                             psam_stream_t stream);
 
+/* ---------------------------------------------------------------- RGB-D frames */
+
+/* From pictures to a scan (point_sam_amd/views.py: FrameSet): F depth images with colour and a camera each are unprojected into one compacted scan,
+ * and every frame becomes a view of that scan whose keys point at each pixel's OWN point -- the keys psam_view_pick, the two paints and
+ * psam_view_lift_bits take, dense and without a splat footprint.  All arithmetic is fp32, every operation rounded on its own, division IEEE; there
+ * are no atomics: every output bit is a function of the inputs alone.  No call allocates, creates a stream or an event, or synchronises with the host.
+ *
+ * Inputs.  depth [F, H, W]: fp32 (depth_u16 = 0), or uint16 with a depth_scale (depth_u16 = 1), measured along the camera's +z in the cameras' world
+ *   units.  rgb [F, H, W, 3]: uint8 (rgb_u8 = 1), or fp32 already in the trained convention (rgb_u8 = 0).  cameras [F, 18] fp32 in DEVICE memory, one
+ *   row per frame: the 12 pose words (world -> camera, row-major 3 x 4), then fx, fy, cx, cy, near, far.  The rotation must be orthonormal (the Python
+ *   host checks max|R R^T - I| <= 1e-4 in fp64): the inverse used below is the transpose.  The table is device memory and is not inspected by the entry
+ *   point; the Python host validates it (far > near, far finite) before the call, and a row whose near or far is a NaN keeps no pixel.
+ *   edge: 0 = no edge filter, or a finite number > 0.  1 <= F, sides in 1 .. 8192, F H W <= 2^28.
+ * Depth value   fp32: d = the word.  uint16: d = (float)raw * depth_scale, one rounded multiply.
+ * Range-valid   d finite and d >= near and d <= far: fp32 compares, false for a NaN.  A raw uint16 0 fails d >= near.
+ * Edge filter   a range-valid pixel is dropped iff one of its four neighbours (x +- 1, y +- 1) is inside the image, in the same frame, range-valid, and
+ *               has fabsf(d - d_n) > edge * d: one rounded subtraction, one rounded product with this pixel's own d.  Neighbours outside the image
+ *               or not range-valid do not count.
+ * Kept          a pixel is kept iff it is range-valid and not dropped.  The scan's point order is the kept pixels in ascending (f, y, x);
+ *               index [F, H, W] int32 holds a kept pixel's position in that order, -1 elsewhere; *count (DEVICE memory) = M, the number kept.
+ * Unprojection  a = (((float)x + 0.5f) - cx) / fx,  b = (((float)y + 0.5f) - cy) / fy,  c = (a d, b d, d),  q_i = c_i - P[i][3],
+ *               p_j = ((P[0][j] q_0 + P[1][j] q_1) + P[2][j] q_2): xyz [M, 3], the world point.
+ * Colour        uint8: ((float)v / 255.0f - 0.5f) / 0.5f; fp32: copied.  rgb_out [M, 3].
+ *   xyz, rgb_out need room for F H W points.  ws: the frames workspace-bytes query below gives its size (0 for a shape outside the limits), 16-byte aligned.
+ * Finish.  center: three floats in HOST memory, scale > 0: n_j = (p_j - m_j) / s in place, one subtraction and one division.  poses [F, 12] fp32 in
+ *   DEVICE memory: the cameras' poses in the normalised frame, [R | (R m + t) / s] computed by the host in fp64 and rounded once (near / s goes with
+ *   them; intrinsics are unchanged, the projection is scale-free).  keys [F, H, W] uint64: for a pixel with index i in [0, M) (checked before a point
+ *   is read), z = the third component of the pose applied to n_i, ((P'[2][0] x + P'[2][1] y) + P'[2][2] z) + P'[2][3]; key = (bits(z) << 32) | i if z
+ *   is finite and > 0, all ones otherwise (the point stays in the scan, only the pixel is left empty) and for every pixel without a point.  The depth
+ *   stored is the one psam_view_lift_bits recomputes for the same point: a pixel's own point is visible at tau = 0 by construction.
+ * A null pointer, a shape outside the limits, a flag that is not 0 or 1, depth_scale (16-bit depth only) or scale not finite and positive, edge
+ * negative or not finite, a centre that is not finite, M outside [1, F H W]: -1; a misaligned pointer: -2; a short workspace: -3 -- all before any launch. */
+size_t psam_frames_workspace_bytes(int32_t F, int32_t H, int32_t W);
+int32_t psam_frames_unproject(const void* depth, int32_t depth_u16, float depth_scale, const void* rgb, int32_t rgb_u8, const float* cameras,
+                              int32_t F, int32_t H, int32_t W, float edge, float* xyz, float* rgb_out, int32_t* index, int32_t* count,
+                              void* ws, size_t ws_bytes, psam_stream_t stream);
+int32_t psam_frames_finish(float* xyz, int32_t M, const int32_t* index, const float* poses, int32_t F, int32_t H, int32_t W, const float* center,
+                           float scale, uint64_t* keys, psam_stream_t stream);
+
 /* ---------------------------------------------------------------- connected components of masks */
 
 /* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel

@@ -40,6 +40,8 @@ SOURCES = [
     # camera views: the projection's fp32 operations rounded one at a time; the pose is transfer.hip's (csrc/rigid_pose.h), and so is the reason for
     # leaving SLP vectorisation off.
     ("views.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # RGB-D frames: unprojection, normalisation and the keys' depth rounded one operation at a time; the pose arithmetic is views.hip's.
+    ("frames.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # instance geometry: the extents' fp32 operations rounded one at a time, the moments' fp64 terms exact.  No SLP vectorisation: it packs the three
     # projections into v_pk_mul_f32 / v_pk_add_f32 that broadcast one half of a register pair, the form isa_lint.py refuses; the kernels are gather-bound.
     ("geometry.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

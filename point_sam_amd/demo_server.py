@@ -18,7 +18,9 @@ into the ball around the current /segment mask (predictor.set_crop_to_mask).
 POST /propagate {pointcloud, radius, pose?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
 there (predictor.snapshot / propagate).
 POST /view {camera, splat?} (not in the reference): the loaded cloud as a camera sees it, a z-buffered point-splat image (predictor.render_view) .
-POST /click_pixel {pixel, label, window?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
+POST /click_pixel {pixel, label, window?, frame?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
+POST /frames {depth, rgb, cameras, far, edge?, depth_scale?} (not in the reference): RGB-D frames fused into the loaded cloud (predictor.set_frames);
+/click_pixel with "frame": f then takes a click on photograph f itself.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -86,6 +88,7 @@ class DemoSession:
         self._reset_prompts()
         self.segment_mask = None
         self.view = None                       # the last /view of the loaded cloud (views.View); another cloud drops it
+        self.frames = None                     # /frames: the views.FrameSet the loaded cloud was fused from; another cloud drops it
 
     def _set_cloud(self):
         smooth = {"smooth": True} if self.smooth_edges else {}
@@ -111,6 +114,7 @@ class DemoSession:
             self.crop = None
             self.norm = None
             self.view = None
+            self.frames = None
         return {"response": "success"}
 
     def load_pointcloud(self, path: str) -> dict:
@@ -138,6 +142,7 @@ class DemoSession:
         self.crop = None
         self.norm = norm
         self.view = None
+        self.frames = None
         return {"xyz": xyz.flatten().tolist(), "rgb": rgb.flatten().tolist()}
 
     def static_file(self, rel: str):
@@ -211,13 +216,71 @@ class DemoSession:
             self.segment_mask = ops.mask_unpack(bits, mask.shape[-1])[0]
         return {"seg": self.segment_mask.cpu().numpy().tolist()}
 
+    @staticmethod
+    def _camera(spec):
+        """A camera of a request: {"pose", "fx", "fy", "cx", "cy", "width", "height"} or {"eye", "target", "up", "fov_y_degrees", "width", "height"}, and
+        optionally "near"."""
+        from .views import Camera
+        explicit, aimed = {"pose", "fx", "fy", "cx", "cy", "width", "height"}, {"eye", "target", "up", "fov_y_degrees", "width", "height"}
+        if isinstance(spec, dict) and set(spec) - {"near"} == explicit:
+            return Camera(**spec)
+        if isinstance(spec, dict) and set(spec) - {"near"} == aimed:
+            return Camera.look_at(**spec)
+        raise ValueError(f"camera takes {sorted(explicit)} or {sorted(aimed)}, and optionally near")
+
+    def set_frames(self, data: dict) -> dict:
+        """RGB-D frames as the loaded cloud: {"depth": base64 of F * height * width little-endian words, uint16 if "depth_scale" is given and float32
+        if not, "rgb": base64 of F * height * width * 3 bytes, "cameras": F cameras as /view takes them (pose world -> camera; they carry width and
+        height), "far", "edge" (optional, default 0.05, null = no edge filter), "depth_scale" (optional)}.  The frames are unprojected, fused and
+        normalised by predictor.set_frames (colours as /pointcloud/ has them, rgb / 255) and replace the loaded cloud.  -> {"frames", "width",
+        "height", "num_points", "center", "scale", "xyz", "rgb"}.  /click_pixel with "frame": f then clicks on photograph f."""
+        import base64
+        import binascii
+        with self.lock:
+            need, may = {"depth", "rgb", "cameras", "far"}, {"edge", "depth_scale"}
+            if not isinstance(data, dict) or not need <= set(data) or set(data) - need - may:
+                raise ValueError('/frames takes {"depth", "rgb", "cameras", "far", "edge" (optional), "depth_scale" (optional)}')
+            specs = data["cameras"]
+            if not isinstance(specs, list) or not specs:
+                raise ValueError("cameras must be a non-empty list, one camera per frame")
+            cameras = [self._camera(spec) for spec in specs]
+            F, H, W = len(cameras), cameras[0].height, cameras[0].width
+            if any((c.height, c.width) != (H, W) for c in cameras):
+                raise ValueError("every camera of /frames must have the same width and height")
+            for name in ("far", "depth_scale", "edge"):
+                v = data.get(name)
+                if name in data and not (v is None and name == "edge") and (isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < float("inf")):
+                    raise ValueError(f"{name} must be a finite positive number" + (" or null" if name == "edge" else ""))
+            depth_scale = data.get("depth_scale")
+            try:
+                raw_d, raw_c = (base64.b64decode(data[k], validate=True) if isinstance(data[k], str) else None for k in ("depth", "rgb"))
+            except binascii.Error:
+                raw_d = raw_c = None
+            if raw_d is None or raw_c is None:
+                raise ValueError("depth and rgb must be base64 strings")
+            word = np.dtype("<f4") if depth_scale is None else np.dtype("<u2")
+            if len(raw_d) != F * H * W * word.itemsize or len(raw_c) != F * H * W * 3:
+                raise ValueError(f"{F} frames of {H} x {W} need {F * H * W * word.itemsize} bytes of {word.name} depth and {F * H * W * 3} bytes of rgb, "
+                                 f"got {len(raw_d)} and {len(raw_c)}")
+            depth = np.frombuffer(raw_d, dtype=word).reshape(F, H, W).astype(word.newbyteorder("="))
+            rgb = np.frombuffer(raw_c, dtype=np.uint8).reshape(F, H, W, 3).astype(np.float32) / np.float32(255)
+            smooth = {"smooth": True} if self.smooth_edges else {}
+            with torch.no_grad():
+                fs = self.predictor.set_frames(depth, rgb, cameras, data["far"], edge=data.get("edge", 0.05), depth_scale=depth_scale,
+                                               max_points=self.working_points or F * H * W, **smooth)
+            self.obj_path = "frames"
+            self.pc_xyz, self.pc_rgb = fs.xyz[None], fs.rgb[None]
+            self.crop, self.view, self.frames = None, None, fs
+            self.norm = (np.asarray(fs.center, dtype=np.float64), float(fs.scale))
+            return {"frames": F, "width": W, "height": H, "num_points": fs.num_points, "center": list(fs.center), "scale": fs.scale,
+                    "xyz": fs.xyz.cpu().numpy().flatten().tolist(), "rgb": fs.rgb.cpu().numpy().flatten().tolist()}
+
     def render_view(self, data: dict) -> dict:
         """The loaded cloud as a camera sees it: {"camera": {...}, "splat": s (optional, 0 .. 3, default 1)}; the camera is either {"pose": 3 x 4 or
         4 x 4 rows (cloud -> camera), "fx", "fy", "cx", "cy", "width", "height", "near" (optional)} or {"eye", "target", "up", "fov_y_degrees",
         "width", "height", "near" (optional)}, in the loaded cloud's normalised coordinates.  -> {"width", "height", "rgb": the image's
         height * width * 3 bytes, row-major RGB, base64; an empty pixel is black}.  The view is kept for /click_pixel until another cloud is loaded."""
         import base64
-        from .views import Camera
         with self.lock:
             if self.pc_xyz is None:
                 raise ValueError("/view before a point cloud was set")
@@ -226,13 +289,7 @@ class DemoSession:
             spec, splat = data["camera"], data.get("splat", 1)
             if isinstance(splat, bool) or not isinstance(splat, int) or not 0 <= splat <= 3:
                 raise ValueError("splat must be an integer in 0 .. 3")
-            explicit, aimed = {"pose", "fx", "fy", "cx", "cy", "width", "height"}, {"eye", "target", "up", "fov_y_degrees", "width", "height"}
-            if set(spec) - {"near"} == explicit:
-                camera = Camera(**spec)
-            elif set(spec) - {"near"} == aimed:
-                camera = Camera.look_at(**spec)
-            else:
-                raise ValueError(f"camera takes {sorted(explicit)} or {sorted(aimed)}, and optionally near")
+            camera = self._camera(spec)
             with torch.no_grad():
                 self._set_cloud()
                 view = self.predictor.render_view(camera, splat)
@@ -243,14 +300,22 @@ class DemoSession:
     def click_pixel(self, data: dict) -> dict:
         """A click on the last /view: {"pixel": [x, y], "label": l, "window": w (optional, 0 .. 16, default 2)}.  The point shown nearest to the pixel
         within the window (predictor.click_pixels) becomes the prompt, and the answer is /segment's for that point, bit for bit; a pixel that shows
-        nothing is a 400 that leaves the click state alone."""
+        nothing is a 400 that leaves the click state alone.  With "frame": f (after /frames) the click is on photograph f, not on the last /view."""
         with self.lock:
             if self.pc_xyz is None:
                 raise ValueError("/click_pixel before a point cloud was set")
-            if self.view is None:
+            view = self.view
+            if isinstance(data, dict) and "frame" in data:
+                f = data["frame"]
+                if self.frames is None:
+                    raise ValueError("/click_pixel with a frame before any /frames of this point cloud")
+                if isinstance(f, bool) or not isinstance(f, int) or not 0 <= f < len(self.frames.views):
+                    raise ValueError(f"frame must be an integer in 0 .. {len(self.frames.views) - 1}")
+                view = self.frames.views[f]
+            elif view is None:
                 raise ValueError("/click_pixel before any /view of this point cloud")
-            if not isinstance(data, dict) or not {"pixel", "label"} <= set(data) or set(data) - {"pixel", "label", "window"}:
-                raise ValueError('/click_pixel takes {"pixel": [x, y], "label": l, "window": w (optional)}')
+            if not isinstance(data, dict) or not {"pixel", "label"} <= set(data) or set(data) - {"pixel", "label", "window", "frame"}:
+                raise ValueError('/click_pixel takes {"pixel": [x, y], "label": l, "window": w (optional), "frame": f (optional)}')
             pixel, window = data["pixel"], data.get("window", 2)
             if not isinstance(pixel, list) or len(pixel) != 2 or any(isinstance(v, bool) or not isinstance(v, int) for v in pixel):
                 raise ValueError("pixel must be two integers [x, y]")
@@ -259,7 +324,7 @@ class DemoSession:
             label = int(data["label"])
             with torch.no_grad():
                 self._set_cloud()
-                pts, _ = self.predictor.click_pixels(self.view, [pixel], [label], window)
+                pts, _ = self.predictor.click_pixels(view, [pixel], [label], window)
             return self._segment({"prompt_point": pts[0, 0].cpu().numpy().tolist(), "prompt_label": label})
 
     def propagate(self, data: dict) -> dict:
@@ -489,6 +554,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
                       "/segment_all": lambda: session.segment_all(data), "/propagate": lambda: session.propagate(data),
                       "/view": lambda: session.render_view(data), "/click_pixel": lambda: session.click_pixel(data),
+                      "/frames": lambda: session.set_frames(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/instances": lambda: session.instances(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}

@@ -1725,6 +1725,147 @@ def view_lift_bits(xyz: torch.Tensor, camera, keys: torch.Tensor, images: torch.
     return bits, area
 
 
+# ------------------------------------------------------------------------------------------ RGB-D frames (csrc/frames.hip)
+FRAME_MAX_PIXELS = 1 << 28
+
+
+def _frame_number(value, what: str, allow_none: bool = False):
+    """A finite positive number that stays finite and positive in fp32 -> that fp32 value as a float (None stays None where allowed)."""
+    import numpy as np
+    if value is None and allow_none:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.floating, np.integer)):
+        raise ValueError(f"{what} must be a number, got {value!r}")
+    with np.errstate(over="ignore"):
+        v = np.float32(value)
+    if not (np.isfinite(v) and v > 0):
+        raise ValueError(f"{what} must be finite and positive in fp32, got {value!r}")
+    return float(v)
+
+
+def _frame_cameras(cameras, F: int, H: int, W: int, what: str):
+    """-> [(twelve pose words, fx, fy, cx, cy, near)] per frame, from views.Camera objects (or anything with their attributes) of the frames' size."""
+    if not isinstance(cameras, (list, tuple)) or len(cameras) != F:
+        raise ValueError(f"{what}: cameras must be a list of {F} views.Camera, one per frame, got {type(cameras).__name__}"
+                         + (f" of {len(cameras)}" if isinstance(cameras, (list, tuple)) else ""))
+    rows = []
+    for f, cam in enumerate(cameras):
+        try:
+            words = [float(v) for v in cam.pose_words]
+            row = words + [float(cam.fx), float(cam.fy), float(cam.cx), float(cam.cy), float(cam.near)]
+            size = (int(cam.height), int(cam.width))
+        except (AttributeError, TypeError):
+            raise TypeError(f"{what}: cameras[{f}] must be a views.Camera, got {type(cam).__name__}") from None
+        if len(words) != 12:
+            raise ValueError(f"{what}: the pose of cameras[{f}] must have twelve words, got {len(words)}")
+        if size != (H, W):
+            raise ValueError(f"{what}: cameras[{f}] is {size[0]} x {size[1]} (height x width), the frames are {H} x {W}")
+        rows.append(row)
+    return rows
+
+
+def _frame_shape(t, what: str):
+    if t.dim() != 3 or t.shape[0] < 1 or not (1 <= t.shape[1] <= VIEW_MAX_SIDE and 1 <= t.shape[2] <= VIEW_MAX_SIDE) or t.numel() > FRAME_MAX_PIXELS:
+        raise ValueError(f"{what} must be [F >= 1, height, width] with sides in 1 .. {VIEW_MAX_SIDE} and at most 2^28 pixels, got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def frames_unproject(depth: torch.Tensor, rgb: torch.Tensor, cameras, far, edge=None, depth_scale=None):
+    """depth [F, H, W] f32, or uint16 with a `depth_scale`; rgb [F, H, W, 3] uint8 (0 .. 255), or f32 already in the trained convention; cameras: F
+    views.Camera (pose world -> camera, width x height = W x H); far > every camera's near; edge None or > 0 -> (xyz_world [M, 3] f32, rgb [M, 3] f32,
+    index [F, H, W] int32, M): the pixels with near <= depth <= far that the edge filter leaves (a pixel goes if a valid 4-neighbour differs by more
+    than edge * its own depth), unprojected into the world frame, in ascending (f, y, x); index = a kept pixel's place in that order, -1 elsewhere
+    (include/pointsam_hip.h: RGB-D frames).  Exact and run-to-run identical.  The outputs are allocated for F H W points and narrowed; reading M is
+    the call's one host read.  ValueError if no pixel is kept."""
+    if not isinstance(depth, torch.Tensor) or depth.dtype not in (torch.float32, torch.uint16):
+        raise TypeError(f"frames_unproject: depth must be a float32 or uint16 tensor, got {getattr(depth, 'dtype', type(depth).__name__)}")
+    F, H, W = _frame_shape(depth, "frames_unproject: depth")
+    if not isinstance(rgb, torch.Tensor) or rgb.dtype not in (torch.float32, torch.uint8):
+        raise TypeError(f"frames_unproject: rgb must be a uint8 or float32 tensor, got {getattr(rgb, 'dtype', type(rgb).__name__)}")
+    if tuple(rgb.shape) != (F, H, W, 3):
+        raise ValueError(f"frames_unproject: rgb must be [{F}, {H}, {W}, 3] for this depth, got {tuple(rgb.shape)}")
+    u16 = depth.dtype == torch.uint16
+    if u16 == (depth_scale is None):
+        raise ValueError("frames_unproject: uint16 depth needs a depth_scale, float32 depth takes none" + f", got {depth.dtype} and depth_scale = {depth_scale!r}")
+    scale = _frame_number(depth_scale, "frames_unproject: depth_scale", allow_none=True)
+    zfar = _frame_number(far, "frames_unproject: far")
+    e = _frame_number(edge, "frames_unproject: edge", allow_none=True)
+    rows = _frame_cameras(cameras, F, H, W, "frames_unproject")
+    for f, row in enumerate(rows):
+        if not zfar > row[16]:
+            raise ValueError(f"frames_unproject: far = {zfar} must be larger than the near = {row[16]} of cameras[{f}]")
+    if rgb.device != depth.device:
+        raise ValueError(f"frames_unproject: depth is on {depth.device}, rgb on {rgb.device}")
+    _chk(depth, depth.dtype, "depth"); _chk(rgb, rgb.dtype, "rgb")
+    dev, total = depth.device, F * H * W
+    table = torch.tensor([row + [zfar] for row in rows], dtype=torch.float32).to(dev)          # [F, 18]
+    xyz = torch.empty(total, 3, dtype=torch.float32, device=dev)
+    col = torch.empty(total, 3, dtype=torch.float32, device=dev)
+    index = torch.empty(F, H, W, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _lib.load()
+    ws = torch.empty(L.psam_frames_workspace_bytes(F, H, W) // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    check(L.psam_frames_unproject(depth.data_ptr(), int(u16), 0.0 if scale is None else scale, rgb.data_ptr(), int(rgb.dtype == torch.uint8), table.data_ptr(),
+                                  F, H, W, 0.0 if e is None else e, xyz.data_ptr(), col.data_ptr(), index.data_ptr(), count.data_ptr(), ws.data_ptr(),
+                                  ws.numel() * 8, _stream()), "psam_frames_unproject")
+    M = int(count.item())                                      # the one host read
+    if M == 0:
+        raise ValueError(f"frames_unproject: no pixel of the {F} frames has a depth in [near, {zfar}]" + ("" if e is None else " that the edge filter keeps"))
+    return xyz[:M], col[:M], index, M
+
+
+def frames_finish(xyz_world: torch.Tensor, index: torch.Tensor, cameras, center, scale):
+    """xyz_world [M, 3] f32 and index [F, H, W] int32 of frames_unproject, its cameras, center (three numbers) and scale > 0 -> (xyz [M, 3]: the SAME
+    tensor, normalised in place to (p - center) / scale; keys [F, H, W] int64 words: (bits(depth) << 32) | index per kept pixel, the depth its own
+    point's in the frame's normalised camera, all ones (-1) elsewhere; the normalised cameras: pose [R | (R center + t) / scale] and near / scale,
+    computed in fp64 and rounded once, intrinsics unchanged).  keys[f] with cameras[f] is a view of the scan for view_pick, the paints and
+    view_lift_bits, where a pixel's own point is visible at tau = 0.  No host synchronisation."""
+    import numpy as np
+    from .views import Camera
+    xyz = _transfer_cloud(xyz_world, "frames_finish: xyz_world")
+    if xyz.dim() != xyz_world.dim():
+        raise ValueError(f"frames_finish: xyz_world must be [M, 3] (it is normalised in place), got {tuple(xyz_world.shape)}")
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32:
+        raise TypeError(f"frames_finish: index must be an int32 tensor (frames_unproject), got {getattr(index, 'dtype', type(index).__name__)}")
+    F, H, W = _frame_shape(index, "frames_finish: index")
+    M = xyz.shape[0]
+    if M > F * H * W:
+        raise ValueError(f"frames_finish: {M} points cannot come from {F} x {H} x {W} pixels")
+    rows = _frame_cameras(cameras, F, H, W, "frames_finish")
+    try:
+        m = np.asarray(center.detach().cpu().numpy() if isinstance(center, torch.Tensor) else center, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"frames_finish: center must be three numbers, got {center!r}") from None
+    with np.errstate(over="ignore"):
+        m32 = m.astype(np.float32)
+    if m32.shape != (3,) or not np.isfinite(m32).all():
+        raise ValueError(f"frames_finish: center must be three numbers that are finite in fp32, got {center!r}")
+    if isinstance(scale, torch.Tensor) and scale.numel() == 1:
+        scale = float(scale)
+    s = _frame_number(scale, "frames_finish: scale")
+    # the normalised cameras, all frames at once: [R | (R m + t) / s] and near / s in fp64, rounded to fp32 once
+    md = m32.astype(np.float64)
+    cam64 = np.asarray(rows, dtype=np.float64)                                                  # [F, 17]
+    P = cam64[:, :12].reshape(F, 3, 4).copy()
+    P[:, :, 3] = (((P[:, :, 0] * md[0] + P[:, :, 1] * md[1]) + P[:, :, 2] * md[2]) + P[:, :, 3]) / s
+    with np.errstate(over="ignore"):
+        poses, near = P.reshape(F, 12).astype(np.float32), (cam64[:, 16] / s).astype(np.float32)
+    bad = ~(np.isfinite(poses).all(1) & np.isfinite(near) & (near > 0))
+    if bad.any():
+        f = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"frames_finish: cameras[{f}] has no fp32 form in the normalised frame (pose {poses[f].tolist()}, near {float(near[f])})")
+    normalised = [Camera.from_fp32(poses[f].copy(), row[12], row[13], row[14], row[15], W, H, float(near[f])) for f, row in enumerate(rows)]
+    if index.device != xyz.device:
+        raise ValueError(f"frames_finish: xyz_world is on {xyz.device}, index on {index.device}")
+    _chk(xyz, name="xyz_world"); _chk(index, torch.int32, "index")
+    table = torch.from_numpy(poses).to(xyz.device)                                              # [F, 12]
+    keys = torch.empty(F, H, W, dtype=torch.int64, device=xyz.device)
+    c = (ctypes.c_float * 3)(*[float(v) for v in m32])
+    check(_lib.load().psam_frames_finish(xyz.data_ptr(), M, index.data_ptr(), table.data_ptr(), F, H, W, ctypes.addressof(c), s, keys.data_ptr(), _stream()),
+          "psam_frames_finish")
+    return xyz, keys, normalised
+
+
 # ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)
 def _region_ws(nbytes: int, dev, what: str):
     if nbytes == 0:

@@ -578,3 +578,26 @@ class PointSAMPredictor:
         """The points visible in the view -> (bits [1, W], area [1]): lift_masks of an all-ones image."""
         xyz = self._view_cloud("visible_bits", view)
         return ops.view_lift_bits(xyz, view.camera, view.keys, None, tau)
+
+    # -- RGB-D frames (views.FrameSet) ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def set_frames(self, depth, rgb, cameras, far, edge=0.05, depth_scale=None, center=None, scale=None, voxel_size: float = None,
+                   max_points: int = None, smooth: bool = False):
+        """From pictures to a scan: depth [F, height, width] (float32, or uint16 with `depth_scale`) and rgb [F, height, width, 3] (uint8, or float32
+        in the trained convention) with one views.Camera per frame (pose world -> camera, rotation orthonormal) are unprojected into one scan -- the
+        pixels with near <= depth <= far that the edge filter keeps (edge None: all of them), in ascending (frame, y, x) -- normalised to
+        (p - center) / scale, and handed to set_scene(xyz, rgb, voxel_size, max_points, smooth).  center / scale None: the mean of the kept points and
+        their largest distance from it; both are returned, so that the next batch of frames can be normalised identically (what transfer_masks and
+        propagate require of two scans).  -> views.FrameSet: ``fs.views[f]`` is frame f as a view of the scan whose every kept pixel shows its own
+        point -- pick, click_pixels, mask_images, lift_masks and visible_bits take it as they take a rendered view, on the original photograph;
+        lift_masks then tests occlusion against the frame's measured depth.  Tensors or numpy arrays; two host reads (the count, the normalisation)."""
+        from .views import build_frames, check_frame_cameras
+        _check_smooth(smooth, "set_frames")
+        if (voxel_size is None) == (max_points is None):       # set_scene's rule, asked before any device work
+            raise ValueError("set_frames: give exactly one of voxel_size and max_points")
+        cameras = check_frame_cameras(cameras, "set_frames")
+        dev = getattr(self.model, "device", "cuda")
+        depth, rgb = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a for a in (depth, rgb))      # tensors stay where they are
+        fs = build_frames(depth, rgb, cameras, far, edge, depth_scale, center, scale)
+        self.set_scene(fs.xyz, fs.rgb, voxel_size, max_points, smooth)
+        return fs

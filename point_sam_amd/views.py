@@ -2,6 +2,8 @@
 masks.  A ``Camera`` is a pinhole (pose + intrinsics), a ``View`` is the z-buffer of point splats that ``ops.view_splat`` drew with it; the predictor
 (``render_view`` / ``pick`` / ``click_pixels`` / ``mask_images`` / ``lift_masks`` / ``visible_bits``) goes from pixels to points and back through it.
 The definition -- projection, key, footprint, pick, paint, lift -- is in include/pointsam_hip.h ("camera views"); the kernels are csrc/views.hip.
+The other direction, from pictures to a scan, is a ``FrameSet``: RGB-D frames unprojected into one scan (csrc/frames.hip, "RGB-D frames" in the header),
+every frame a ``View`` of it whose pixels show their own points (``predictor.set_frames``).
 
 Conventions: the camera looks along +z of its own frame, x to the right and y DOWN, so pixel (x, y) = (floor(u), floor(v)) has its origin in the
 image's top-left corner; ``pose`` maps the cloud's frame to the camera's, like the pose of ``ops.transfer_plan``.
@@ -41,6 +43,14 @@ class Camera:
                 raise ValueError(f"Camera: {name} must be an integer in 1 .. {ops.VIEW_MAX_SIDE}, got {side!r}")
         self.width, self.height = int(width), int(height)
         self.near = _f32(near, "near", True)
+
+    @classmethod
+    def from_fp32(cls, pose_words: np.ndarray, fx: float, fy: float, cx: float, cy: float, width: int, height: int, near: float) -> "Camera":
+        """A camera from values that already ARE what the constructor would store (twelve finite fp32 pose words, fp32-representable floats, checked
+        sides): no validation, for code that derives many cameras from validated ones (ops.frames_finish)."""
+        cam = cls.__new__(cls)
+        cam.pose_words, cam.fx, cam.fy, cam.cx, cam.cy, cam.width, cam.height, cam.near = pose_words, fx, fy, cx, cy, width, height, near
+        return cam
 
     @property
     def pose(self) -> np.ndarray:
@@ -110,6 +120,57 @@ class View:
         out = rgb.index_select(0, idx.reshape(-1).clamp_min(0).long()).reshape(idx.shape + (3,))
         bg = torch.as_tensor(background, dtype=rgb.dtype, device=rgb.device).expand(3)
         return torch.where((idx < 0)[..., None], bg, out)
+
+
+ORTHONORMAL_TOLERANCE = 1e-4
+
+
+def check_frame_cameras(cameras, what: str) -> list:
+    """The cameras of RGB-D frames: a non-empty list of Camera whose rotations are orthonormal, max|R R^T - I| <= 1e-4 in fp64 -- unprojection inverts
+    a pose with the transpose.  ValueError names the frame."""
+    if not isinstance(cameras, (list, tuple)) or len(cameras) < 1:
+        raise ValueError(f"{what}: cameras must be a non-empty list of views.Camera, one per frame, got {type(cameras).__name__}")
+    for f, cam in enumerate(cameras):
+        if not isinstance(cam, Camera):
+            raise TypeError(f"{what}: cameras[{f}] must be a views.Camera, got {type(cam).__name__}")
+        R = cam.pose.astype(np.float64)[:, :3]
+        err = float(np.abs(R @ R.T - np.eye(3)).max())
+        if not err <= ORTHONORMAL_TOLERANCE:
+            raise ValueError(f"{what}: the rotation of cameras[{f}] (frame {f}) is not orthonormal: max|R R^T - I| = {err:.3g} > {ORTHONORMAL_TOLERANCE}")
+    return list(cameras)
+
+
+class FrameSet:
+    """RGB-D frames fused into one scan (predictor.set_frames): ``views``, one View per frame with splat = 0 whose keys -- a slice of ``keys``
+    [F, height, width] -- hold every kept pixel's OWN point, with the frame's camera in the normalised frame; ``index`` [F, height, width] int32, a
+    kept pixel's point or -1; ``xyz`` / ``rgb`` [num_points, 3], the scan as set_scene received it; ``center`` (three floats) and ``scale``, the
+    normalisation xyz = (world - center) / scale: pass them to the next set_frames to normalise another batch of frames identically."""
+    __slots__ = ("views", "keys", "index", "xyz", "rgb", "center", "scale", "num_points")
+
+    def __init__(self, keys: torch.Tensor, cameras, index: torch.Tensor, xyz: torch.Tensor, rgb: torch.Tensor, center, scale: float):
+        self.keys, self.index, self.xyz, self.rgb = keys, index, xyz, rgb
+        self.center, self.scale, self.num_points = tuple(float(v) for v in center), float(scale), int(xyz.shape[0])
+        self.views = [View(keys[f], cam, self.num_points, 0) for f, cam in enumerate(cameras)]
+
+
+def build_frames(depth, rgb, cameras, far, edge=0.05, depth_scale=None, center=None, scale=None) -> FrameSet:
+    """Unproject (ops.frames_unproject), normalise and key (ops.frames_finish) -> FrameSet.  center / scale None (both or neither): the rule of
+    evaluation.normalize_points -- the mean, then the largest distance from it -- computed in fp64 on the device and rounded to fp32 once."""
+    cameras = check_frame_cameras(cameras, "set_frames")
+    if (center is None) != (scale is None):
+        raise ValueError("set_frames: pass both center and scale, or neither")
+    if isinstance(center, torch.Tensor):
+        center = center.detach().cpu().numpy()
+    world, col, index, _ = ops.frames_unproject(depth, rgb, cameras, far, edge, depth_scale)
+    if center is None:
+        w64 = world.double()
+        mean = w64.mean(0)
+        stats = torch.cat([mean, ((w64 - mean) ** 2).sum(1).max().sqrt()[None]]).float().cpu().numpy()          # rounded to fp32 once; one host read
+        center, scale = stats[:3], float(stats[3])
+        if not scale > 0:
+            raise ValueError("set_frames: the kept points coincide (scale 0): pass center and scale")
+    xyz, keys, normalised = ops.frames_finish(world, index, cameras, center, scale)
+    return FrameSet(keys, normalised, index, xyz, col, np.asarray(center, dtype=np.float32).reshape(3), float(np.float32(scale)))
 
 
 def check_view(view, num_points: int, what: str) -> View:

@@ -840,6 +840,46 @@ int32_t psam_frames_unproject(const void* depth, int32_t depth_u16, float depth_
 int32_t psam_frames_finish(float* xyz, int32_t M, const int32_t* index, const float* poses, int32_t F, int32_t H, int32_t W, const float* center,
                            float scale, uint64_t* keys, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- label fusion */
+
+/* From the 2-D segmentations of many views to one 3-D labelling of the cloud (point_sam_amd/fusion.py).  V views of one size H x W show one cloud
+ * xyz [N, 3]: keys [V, H, W] uint64 are the keys of psam_frames_finish, or psam_view_splat's of V cameras stacked; labels [V, H, W] int32 hold a
+ * region id per pixel; cameras [V, 17] fp32 in DEVICE memory, one row per view: the 12 pose words (cloud -> camera, row-major 3 x 4), then fx, fy, cx,
+ * cy, near -- the camera of "camera views", its width and height the W and H of the call.  The table is device memory and is not inspected by the
+ * entry points; the Python host refuses a row that is not finite or whose fx, fy or near is not positive.  tau >= 0 (+inf allowed).  All arithmetic
+ * is the projection's, fp32 with every operation rounded on its own; the rest is integers and bits.  There are no atomics: every output is a function
+ * of the inputs alone.  No call allocates, creates a stream or an event, or synchronises with the host.
+ *
+ * Observation of point i in view v.  The point is VISIBLE iff it is in view (the projection of "camera views") with centre pixel p, keys[v][p] is not
+ *   empty and c_z <= depth(keys[v][p]) + tau (one rounded add): the lift rule of psam_view_lift_bits, unchanged.  Its observed label is l =
+ *   labels[v][p].  row_base [V + 1] int32 in DEVICE memory is the exclusive prefix of the views' region counts: count_v = row_base[v + 1] - row_base[v],
+ *   R = row_base[V] (passed by value), region (v, l) is row row_base[v] + l.  l is VALID iff 0 <= l < count_v (and the row lies in [0, R), whatever
+ *   the table holds: nothing is read or written outside the buffers); any other l, INT32_MIN and INT32_MAX included, is a visible but UNLABELLED
+ *   observation.  Without row_base (psam_fuse_vote only: ids that already agree between the views) every l >= 0 is valid.
+ * psam_fuse_region_bits: bits [R + V, ceil(N / 64)] in the layout of psam_mask_pack, area [R + V] (may be NULL) = the rows' popcounts.
+ *   row row_base[v] + l   bit i iff point i is visible in view v with the valid label l: psam_view_lift_bits of the image labels[v] == l
+ *   row R + v             bit i iff point i is visible in view v, labelled or not: psam_view_lift_bits without an image
+ *   Bits at i >= N are zero.  0 <= R <= 2^20.
+ * psam_fuse_vote.  The global label of a labelled observation is g = remap[row_base[v] + l] with remap [R] int32 (DEVICE memory, needs row_base), or
+ *   g = l without a remap; a remap entry below 0 (a region that was empty where the links were made) leaves the observation unlabelled.  The views
+ *   are walked in ascending v with a table of at most 8 distinct global labels in first-seen order, each with a count; an observation whose label is
+ *   not in a full table is dropped.  Outputs, [N] int32 each:
+ *     seen       the visible observations            labelled   those that carry a global label            dropped    those the full table refused
+ *     label      the table entry with the highest count, ties to the LOWER LABEL (not the earlier view); -1 if the table is empty or that count is
+ *                below min_votes (>= 1)
+ *     votes      that count, 0 where label is -1
+ * psam_label_bits: labels [N] int32 -> bits [K, ceil(N / 64)], area [K] (may be NULL): bit i of row k iff labels[i] == k; a value outside [0, K)
+ *   sets nothing.  1 <= K <= 2^20.
+ * A null pointer, N outside [1, 2^28], V outside [1, 4096], a side outside [1, 8192], R or K outside its range, tau negative or NaN, min_votes < 1, a
+ * remap without row_base: -1; a misaligned pointer (keys and bits 8 bytes, every other 4): -2 -- all before any launch. */
+int32_t psam_fuse_region_bits(const float* xyz, int32_t N, const float* cameras, int32_t V, int32_t H, int32_t W, const uint64_t* keys,
+                              const int32_t* labels, const int32_t* row_base, int32_t R, float tau, uint64_t* bits, int32_t* area,
+                              psam_stream_t stream);
+int32_t psam_fuse_vote(const float* xyz, int32_t N, const float* cameras, int32_t V, int32_t H, int32_t W, const uint64_t* keys,
+                       const int32_t* labels, const int32_t* row_base, const int32_t* remap, int32_t R, float tau, int32_t min_votes,
+                       int32_t* label, int32_t* votes, int32_t* seen, int32_t* labelled, int32_t* dropped, psam_stream_t stream);
+int32_t psam_label_bits(const int32_t* labels, int32_t N, int32_t K, uint64_t* bits, int32_t* area, psam_stream_t stream);
+
 /* ---------------------------------------------------------------- connected components of masks */
 
 /* Which points of a packed mask hang together, and the clean-up built on it (point_sam_amd/regions.py).  Cells are those of the voxel

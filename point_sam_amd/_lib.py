@@ -156,6 +156,9 @@ SIGNATURES = {
     "psam_frames_workspace_bytes": (size_t, [i32, i32, i32]),
     "psam_frames_unproject": (i32, [ptr, i32, f32, ptr, i32, ptr, i32, i32, i32, f32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
     "psam_frames_finish": (i32, [ptr, i32, ptr, ptr, i32, i32, i32, ptr, f32, ptr, ptr]),
+    "psam_fuse_region_bits": (i32, [ptr, i32, ptr, i32, i32, i32, ptr, ptr, ptr, i32, f32, ptr, ptr, ptr]),
+    "psam_fuse_vote": (i32, [ptr, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, i32, f32, i32, ptr, ptr, ptr, ptr, ptr, ptr]),
+    "psam_label_bits": (i32, [ptr, i32, i32, ptr, ptr, ptr]),
     "psam_region_neighbors_workspace_bytes": (size_t, [i32]),
     "psam_region_neighbors": (i32, [ptr, ptr, i32, ptr, f32, ptr, ptr, size_t, ptr]),
     "psam_region_labels_workspace_bytes": (size_t, [i32, i32, i32]),

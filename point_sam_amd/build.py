@@ -42,6 +42,8 @@ SOURCES = [
     ("views.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # RGB-D frames: unprojection, normalisation and the keys' depth rounded one operation at a time; the pose arithmetic is views.hip's.
     ("frames.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # label fusion: the projection and the visibility test are views.hip's (csrc/view_camera.h), and so are the flags.
+    ("fusion.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # instance geometry: the extents' fp32 operations rounded one at a time, the moments' fp64 terms exact.  No SLP vectorisation: it packs the three
     # projections into v_pk_mul_f32 / v_pk_add_f32 that broadcast one half of a register pair, the form isa_lint.py refuses; the kernels are gather-bound.
     ("geometry.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

@@ -19,38 +19,14 @@
 #include "common.h"
 #include "rigid_pose.h"
 #include "row_popcount.h"    // the area pass of the lifted masks; u64 (voxel_cell.h)
+#include "view_camera.h"     // ViewCamera, view_project, view_visible: shared with fusion.hip
 
 #include <climits>
 #include <cmath>
 #include <cstdio>
 
 constexpr int VIEW_THREADS = 256;
-constexpr u64 VIEW_EMPTY = ~0ull;
-constexpr int VIEW_MAX_SIDE = 8192, VIEW_MAX_SPLAT = 3, VIEW_MAX_WINDOW = 16;
-constexpr int VIEW_MAX_POINTS = 1 << 28;
-
-struct ViewCamera {
-    RigidPose P;              // cloud frame -> camera frame
-    float fx, fy, cx, cy;
-    float width, height;      // the image's sides as fp32 (<= 8192: exact)
-    float znear;
-    int W, H;
-};
-
-// The centre pixel and the depth of a point, false if it is not in view.
-__device__ __forceinline__ bool view_project(const ViewCamera& C, float x, float y, float z, int& px, int& py, float& depth) {
-#pragma clang fp contract(off)
-    float a, b, c;
-    pose_apply(C.P, x, y, z, a, b, c);
-    const float u = C.fx * (a / c) + C.cx;
-    const float v = C.fy * (b / c) + C.cy;
-    // every compare is false for a NaN; c < +inf with c >= near > 0 is "finite"
-    const bool in = c >= C.znear && c < INFINITY && u >= 0.0f && u < C.width && v >= 0.0f && v < C.height;
-    px = in ? (int)floorf(u) : 0;                                  // the conversion only of a value known to lie in [0, 8192)
-    py = in ? (int)floorf(v) : 0;
-    depth = c;
-    return in;
-}
+constexpr int VIEW_MAX_SPLAT = 3, VIEW_MAX_WINDOW = 16;
 
 // ------------------------------------------------------------------------------------------------ clear
 __global__ __launch_bounds__(VIEW_THREADS) void view_clear_kernel(u64* __restrict__ keys, int64_t pixels) {
@@ -148,9 +124,7 @@ __global__ __launch_bounds__(VIEW_THREADS) void view_lift_kernel(const float* __
         float depth;
         if (view_project(C, xyz[i * 3 + 0], xyz[i * 3 + 1], xyz[i * 3 + 2], px, py, depth)) {
             p = (int64_t)py * C.W + px;
-            const u64 key = keys[p];
-            const float front = __builtin_bit_cast(float, (unsigned)(key >> 32));
-            visible = key != VIEW_EMPTY && depth <= front + tau;    // one rounded add; a NaN front (keys of no splat) is false
+            visible = view_visible(keys[p], depth, tau);
         }
     }
     const int64_t pixels = (int64_t)C.W * C.H;

@@ -21,6 +21,8 @@ POST /view {camera, splat?} (not in the reference): the loaded cloud as a camera
 POST /click_pixel {pixel, label, window?, frame?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
 POST /frames {depth, rgb, cameras, far, edge?, depth_scale?} (not in the reference): RGB-D frames fused into the loaded cloud (predictor.set_frames);
 /click_pixel with "frame": f then takes a click on photograph f itself.
+POST /fuse_labels {labels, tau, overlap?, min_points?, min_votes?, consistent?} (not in the reference): the frames' 2-D segmentations fused into one
+instance labelling of that cloud (predictor.fuse_labels).
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -274,6 +276,40 @@ class DemoSession:
             self.norm = (np.asarray(fs.center, dtype=np.float64), float(fs.scale))
             return {"frames": F, "width": W, "height": H, "num_points": fs.num_points, "center": list(fs.center), "scale": fs.scale,
                     "xyz": fs.xyz.cpu().numpy().flatten().tolist(), "rgb": fs.rgb.cpu().numpy().flatten().tolist()}
+
+    def fuse_labels(self, data: dict) -> dict:
+        """The frames' 2-D segmentations as one labelling of the fused cloud: {"labels": base64 of F * height * width little-endian int32 region ids
+        (below 0: none), "tau", and optionally "overlap", "min_points", "min_votes" (fusion.FusionConfig), "consistent" (the ids already agree between
+        the frames)} -> {"labels": [N ints, -1 = none] as /segment_all has them, "num_instances": k, "sizes": [k point counts]}
+        (predictor.fuse_labels).  Before any /frames of the loaded cloud, or with labels of another shape: a 400."""
+        import base64
+        import binascii
+        from .fusion import FusionConfig
+        with self.lock:
+            if self.frames is None:
+                raise ValueError("/fuse_labels before any /frames of this point cloud")
+            may = {"labels", "tau", "overlap", "min_points", "min_votes", "consistent"}
+            if not isinstance(data, dict) or not {"labels", "tau"} <= set(data) or set(data) - may:
+                raise ValueError('/fuse_labels takes {"labels", "tau", "overlap" (optional), "min_points" (optional), "min_votes" (optional), "consistent" (optional)}')
+            consistent = data.get("consistent", False)
+            if not isinstance(consistent, bool):
+                raise ValueError("consistent must be true or false")
+            cfg = FusionConfig.from_overrides({k: v for k, v in data.items() if k not in ("labels", "consistent")})
+            try:
+                raw = base64.b64decode(data["labels"], validate=True) if isinstance(data["labels"], str) else None
+            except binascii.Error:
+                raw = None
+            if raw is None:
+                raise ValueError("labels must be a base64 string")
+            F, H, W = tuple(self.frames.keys.shape)
+            if len(raw) != F * H * W * 4:
+                raise ValueError(f"{F} frames of {H} x {W} need {F * H * W * 4} bytes of int32 labels, got {len(raw)}")
+            labels = np.frombuffer(raw, dtype="<i4").reshape(F, H, W).astype(np.int32)
+            with torch.no_grad():
+                fused = self.predictor.fuse_labels(self.frames, labels, cfg, consistent=consistent)
+            out = fused.labels.cpu().numpy().astype(int)
+            return {"labels": out.tolist(), "num_instances": int(fused.num_instances),
+                    "sizes": np.bincount(out[out >= 0], minlength=int(fused.num_instances)).tolist()}
 
     def render_view(self, data: dict) -> dict:
         """The loaded cloud as a camera sees it: {"camera": {...}, "splat": s (optional, 0 .. 3, default 1)}; the camera is either {"pose": 3 x 4 or
@@ -554,7 +590,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
             routes = {"/sampled_pointcloud": lambda: session.sampled_pointcloud(data), "/segment": lambda: session.segment(data),
                       "/segment_all": lambda: session.segment_all(data), "/propagate": lambda: session.propagate(data),
                       "/view": lambda: session.render_view(data), "/click_pixel": lambda: session.click_pixel(data),
-                      "/frames": lambda: session.set_frames(data),
+                      "/frames": lambda: session.set_frames(data), "/fuse_labels": lambda: session.fuse_labels(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/instances": lambda: session.instances(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}

@@ -1638,6 +1638,13 @@ def _view_keys(keys, what: str):
     return keys.shape[0], keys.shape[1]
 
 
+def _view_tau(tau, what: str) -> float:
+    import math
+    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or math.isnan(tau) or tau < 0:
+        raise ValueError(f"{what}: tau must be a number >= 0, got {tau!r}")
+    return float(tau)
+
+
 def _view_bits(keys, bits, N: int, what: str):
     H, W = _view_keys(keys, what)
     if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64:
@@ -1700,14 +1707,12 @@ def view_lift_bits(xyz: torch.Tensor, camera, keys: torch.Tensor, images: torch.
     (bits [K, ceil(N / 64)] int64 words of mask_pack's layout, area [K] int32): point i has bit k iff it is in view, its depth is at most its centre
     pixel's winning depth + tau, and images[k] is non-zero at that pixel.  images None: K = 1, every pixel set -- the points visible in the view.
     No host synchronisation."""
-    import math
     xyz = _transfer_cloud(xyz, "view_lift_bits: xyz")
     H, W = _view_keys(keys, "view_lift_bits")
     P, cam = _view_camera(camera, "view_lift_bits")
     if (cam[6], cam[5]) != (H, W):
         raise ValueError(f"view_lift_bits: keys {tuple(keys.shape)} are not the camera's {cam[6]} x {cam[5]} (height x width)")
-    if isinstance(tau, bool) or not isinstance(tau, (int, float)) or math.isnan(tau) or tau < 0:
-        raise ValueError(f"view_lift_bits: tau must be a number >= 0, got {tau!r}")
+    tau = _view_tau(tau, "view_lift_bits")
     K = 1
     if images is not None:
         if not isinstance(images, torch.Tensor) or images.dtype != torch.uint8:
@@ -1864,6 +1869,123 @@ def frames_finish(xyz_world: torch.Tensor, index: torch.Tensor, cameras, center,
     check(_lib.load().psam_frames_finish(xyz.data_ptr(), M, index.data_ptr(), table.data_ptr(), F, H, W, ctypes.addressof(c), s, keys.data_ptr(), _stream()),
           "psam_frames_finish")
     return xyz, keys, normalised
+
+
+# ------------------------------------------------------------------------------------------ label fusion (csrc/fusion.hip)
+FUSE_MAX_VIEWS, FUSE_MAX_ROWS = 4096, 1 << 20
+
+
+def _fuse_views(cameras, keys, labels, what: str):
+    """The views of a fusion call: keys [V, H, W] int64, labels [V, H, W] int32, V cameras of that size -> (V, H, W, the camera rows [V, 17] as a host
+    fp32 array: 12 pose words, fx, fy, cx, cy, near).  Whether the tensors live on the GPU is the caller's last check (_chk)."""
+    import numpy as np
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
+        raise TypeError(f"{what}: keys must be an int64 tensor (frames_finish, or stacked view_splat), got {getattr(keys, 'dtype', type(keys).__name__)}")
+    if keys.dim() != 3 or not (1 <= keys.shape[0] <= FUSE_MAX_VIEWS and 1 <= keys.shape[1] <= VIEW_MAX_SIDE and 1 <= keys.shape[2] <= VIEW_MAX_SIDE):
+        raise ValueError(f"{what}: keys must be [V, height, width] with V in 1 .. {FUSE_MAX_VIEWS} and sides in 1 .. {VIEW_MAX_SIDE}, got {tuple(keys.shape)}")
+    V, H, W = keys.shape
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32:
+        raise TypeError(f"{what}: labels must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+    if tuple(labels.shape) != (V, H, W):
+        raise ValueError(f"{what}: labels must be [{V}, {H}, {W}] like the keys, got {tuple(labels.shape)}")
+    rows = np.asarray(_frame_cameras(cameras, V, H, W, what), dtype=np.float64)
+    with np.errstate(over="ignore"):
+        table = rows.astype(np.float32)
+    bad = ~(np.isfinite(table).all(1) & (table[:, 12] > 0) & (table[:, 13] > 0) & (table[:, 16] > 0))
+    if bad.any():
+        v = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"{what}: cameras[{v}] must be finite in fp32 with fx, fy and near positive, got {rows[v].tolist()}")
+    if labels.device != keys.device:
+        raise ValueError(f"{what}: keys are on {keys.device}, labels on {labels.device}")
+    return V, H, W, table
+
+
+def _fuse_row_base(row_base, V: int, what: str):
+    """row_base: V + 1 integers on the host (a list, an array or a CPU tensor), the exclusive prefix of the views' region counts -> (int32 array, R)."""
+    import numpy as np
+    try:
+        rb = np.asarray(row_base.detach().cpu().numpy() if isinstance(row_base, torch.Tensor) else row_base)
+    except (TypeError, ValueError):
+        rb = None
+    if rb is None or rb.dtype.kind not in "iu" or rb.shape != (V + 1,):
+        raise ValueError(f"{what}: row_base must be {V + 1} integers, the exclusive prefix of the {V} views' region counts, got {row_base!r}")
+    rb = rb.astype(np.int64)
+    if rb[0] != 0 or (np.diff(rb) < 0).any():
+        raise ValueError(f"{what}: row_base must start at 0 and never decrease, got {rb.tolist()}")
+    if rb[-1] > FUSE_MAX_ROWS:
+        raise ValueError(f"{what}: row_base ends at {int(rb[-1])} region rows, more than the {FUSE_MAX_ROWS} a call takes")
+    return rb.astype(np.int32), int(rb[-1])
+
+
+def fuse_region_bits(xyz: torch.Tensor, cameras, keys: torch.Tensor, labels: torch.Tensor, row_base, tau: float):
+    """xyz [N, 3] f32; V cameras with keys [V, H, W] int64 (the FrameSet's, or view_splat's of equal size stacked) and labels [V, H, W] int32; row_base:
+    V + 1 host integers, the exclusive prefix of the views' region counts, R = row_base[V]; tau >= 0 -> (bits [R + V, ceil(N / 64)] int64 words of
+    mask_pack's layout, area [R + V] int32).  Row row_base[v] + l holds the points visible in view v -- view_lift_bits' rule -- whose centre pixel carries
+    the label l in [0, count_v); row R + v the points visible in view v at all (include/pointsam_hip.h: label fusion).  No host synchronisation."""
+    xyz = _transfer_cloud(xyz, "fuse_region_bits: xyz")
+    V, H, W, table = _fuse_views(cameras, keys, labels, "fuse_region_bits")
+    rb, R = _fuse_row_base(row_base, V, "fuse_region_bits")
+    t = _view_tau(tau, "fuse_region_bits")
+    _chk(xyz, name="xyz"); _chk(keys, torch.int64, "keys"); _chk(labels, torch.int32, "labels")
+    dev, N = xyz.device, xyz.shape[0]
+    cam, base = torch.from_numpy(table).to(dev), torch.from_numpy(rb).to(dev)
+    bits = torch.empty(R + V, mask_words(N), dtype=torch.int64, device=dev)
+    area = torch.empty(R + V, dtype=torch.int32, device=dev)
+    check(_lib.load().psam_fuse_region_bits(xyz.data_ptr(), N, cam.data_ptr(), V, H, W, keys.data_ptr(), labels.data_ptr(), base.data_ptr(), R, t,
+                                            bits.data_ptr(), area.data_ptr(), _stream()), "psam_fuse_region_bits")
+    return bits, area
+
+
+def fuse_vote(xyz: torch.Tensor, cameras, keys: torch.Tensor, labels: torch.Tensor, tau: float, row_base=None, remap: torch.Tensor = None,
+              min_votes: int = 1):
+    """The inputs of fuse_region_bits; row_base None: every label >= 0 is a global id; with row_base, a label is valid in [0, count_v) and its global id is
+    remap[row_base[v] + l] (remap [R] int32 on the device, an entry below 0 = no label), or l itself without a remap -> (label, votes, seen, labelled,
+    dropped), [N] int32 each: per point the winner among the at most 8 distinct global labels its visible observations carry in ascending view order
+    (ties: the lower label; -1 below min_votes), the winner's count, and the numbers of visible, labelled and dropped observations.  No host
+    synchronisation."""
+    xyz = _transfer_cloud(xyz, "fuse_vote: xyz")
+    V, H, W, table = _fuse_views(cameras, keys, labels, "fuse_vote")
+    rb, R = (None, 0) if row_base is None else _fuse_row_base(row_base, V, "fuse_vote")
+    t = _view_tau(tau, "fuse_vote")
+    if isinstance(min_votes, bool) or not isinstance(min_votes, int) or not 1 <= min_votes <= FUSE_MAX_VIEWS:
+        raise ValueError(f"fuse_vote: min_votes must be an integer in 1 .. {FUSE_MAX_VIEWS}, got {min_votes!r}")
+    if remap is not None:
+        if rb is None:
+            raise ValueError("fuse_vote: a remap needs the row_base that addresses it")
+        if not isinstance(remap, torch.Tensor) or remap.dtype != torch.int32:
+            raise TypeError(f"fuse_vote: remap must be an int32 tensor, got {getattr(remap, 'dtype', type(remap).__name__)}")
+        if tuple(remap.shape) != (R,):
+            raise ValueError(f"fuse_vote: remap must be [{R}], one entry per region row, got {tuple(remap.shape)}")
+        if remap.device != keys.device:
+            raise ValueError(f"fuse_vote: keys are on {keys.device}, remap on {remap.device}")
+        if R == 0:
+            remap = None                                           # nothing to address
+        else:
+            _chk(remap, torch.int32, "remap")
+    _chk(xyz, name="xyz"); _chk(keys, torch.int64, "keys"); _chk(labels, torch.int32, "labels")
+    dev, N = xyz.device, xyz.shape[0]
+    cam = torch.from_numpy(table).to(dev)
+    base = None if rb is None else torch.from_numpy(rb).to(dev)
+    out = torch.empty(5, N, dtype=torch.int32, device=dev)
+    check(_lib.load().psam_fuse_vote(xyz.data_ptr(), N, cam.data_ptr(), V, H, W, keys.data_ptr(), labels.data_ptr(), _p(base), _p(remap), R, t, min_votes,
+                                     *(out[j].data_ptr() for j in range(5)), _stream()), "psam_fuse_vote")
+    return tuple(out[j] for j in range(5))
+
+
+def label_bits(labels: torch.Tensor, K: int):
+    """labels [N] int32, K in 1 .. 2^20 -> (bits [K, ceil(N / 64)] int64 words of mask_pack's layout, area [K] int32): row k holds the points labelled
+    k; a label outside [0, K) sets nothing.  No host synchronisation."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32:
+        raise TypeError(f"label_bits: labels must be an int32 tensor, got {getattr(labels, 'dtype', type(labels).__name__)}")
+    if labels.dim() != 1 or not 1 <= labels.shape[0] <= 1 << 28:
+        raise ValueError(f"label_bits: labels must be [N] with N in 1 .. 2^28, got {tuple(labels.shape)}")
+    K = _view_int(K, 1, FUSE_MAX_ROWS, "label_bits: K")
+    _chk(labels, torch.int32, "labels")
+    N = labels.shape[0]
+    bits = torch.empty(K, mask_words(N), dtype=torch.int64, device=labels.device)
+    area = torch.empty(K, dtype=torch.int32, device=labels.device)
+    check(_lib.load().psam_label_bits(labels.data_ptr(), N, K, bits.data_ptr(), area.data_ptr(), _stream()), "psam_label_bits")
+    return bits, area
 
 
 # ------------------------------------------------------------------------------------------ connected components of masks (csrc/regions.hip)

@@ -601,3 +601,35 @@ class PointSAMPredictor:
         fs = build_frames(depth, rgb, cameras, far, edge, depth_scale, center, scale)
         self.set_scene(fs.xyz, fs.rgb, voxel_size, max_points, smooth)
         return fs
+
+    # -- multi-view label fusion (point_sam_amd/fusion.py) ---------------------------------------------------------
+    @torch.no_grad()
+    def fuse_labels(self, views, labels, cfg, consistent: bool = False):
+        """The 2-D segmentations of many views as ONE 3-D instance labelling of the cached cloud: views a views.FrameSet (set_frames) or a list of
+        views.View of one size (render_view), labels [V, height, width] int32 (a tensor or a numpy array), a region id per pixel and view; ids below 0
+        are "no label"; cfg a fusion.FusionConfig -> fusion.Fused (labels [N] per point of the cloud the user gave, -1 = none; votes, seen,
+        labelled, dropped; num_instances; bits()).  consistent=False: ids of different views do not correspond -- every (view, id) is a region
+        (count_v = the view's largest id + 1, one host read; more than cfg.max_regions in total is a ValueError), regions of different views are linked
+        by co-visible containment and the instances are the links' connected components (fusion.link_regions).  The region rows and links are made on
+        the working cloud's points after set_scene (the scan itself where it is its own working cloud), so the row matrix stays small; the vote then
+        runs over EVERY point of the scan.  consistent=True: the ids are global already -- the vote only."""
+        from . import fusion
+        from .views import FrameSet, check_view
+        if isinstance(views, FrameSet):
+            vs, keys = views.views, views.keys
+        elif isinstance(views, (list, tuple)) and len(views) >= 1:
+            vs, keys = list(views), None
+        else:
+            raise TypeError(f"fuse_labels: views must be a views.FrameSet or a non-empty list of views.View, got {type(views).__name__}")
+        xyz = self._view_cloud("fuse_labels", vs[0])
+        for v in vs[1:]:
+            check_view(v, xyz.shape[0], "fuse_labels")
+            if tuple(v.keys.shape) != tuple(vs[0].keys.shape) or v.cloud != vs[0].cloud:
+                raise ValueError(f"fuse_labels: the views must have one size and show one cloud, got {tuple(v.keys.shape)} of cloud {v.cloud} beside "
+                                 f"{tuple(vs[0].keys.shape)} of cloud {vs[0].cloud}")
+        if keys is None:
+            keys = torch.stack([v.keys for v in vs])
+        lab = fusion.check_labels(labels, keys.shape, xyz.device, "fuse_labels")
+        sc = self.scene
+        link_xyz = xyz if sc is None or sc.identity else xyz.index_select(0, sc.keep_idx)
+        return fusion.fuse(xyz, link_xyz, [v.camera for v in vs], keys.contiguous(), lab, cfg, consistent)

@@ -758,6 +758,40 @@ int32_t psam_transfer_index_build(const float* src, int32_t N, const float* orig
 int32_t psam_transfer_plan(const float* src, int32_t N, const void* ws, size_t ws_bytes, const float* origin, float inv_h, float r2,
                            const float* qry, int32_t M, const float* pose, float eps, int32_t* idx3, float* w3, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- pose between two clouds */
+
+/* One step of point-to-point ICP on the index above (point_sam_amd/align.py): per query its nearest source within a radius, fused with the sums over
+ * those pairs from which the host solves for the rigid motion.  No per-point intermediate is formed unless `nearest` is asked for; no float atomics.
+ * The call allocates nothing and does not synchronise with the host.
+ *
+ * src, N, index_ws, origin, inv_h: the four the index was built from and its workspace (psam_transfer_index_build).  qry [M, 3] the queries; pose: NULL
+ * (identity), or 12 floats in HOST memory, row-major 3 x 4, query frame -> source frame.  qry_bits: NULL (every query takes part), or ceil(M / 64)
+ * words in the layout of psam_mask_pack: query i takes part when bit i is set; bits past M are IGNORED whatever the caller left there.
+ *     posed coordinate  p: psam_transfer_plan's, bit for bit
+ *     candidates        psam_transfer_plan's: the indexed sources j of the 27 cells around cell(p) with q_j = (dx dx + dy dy) + dz dz <= r2, d = p - src[j],
+ *                       in the same fp32 arithmetic; NaN compares false.  The 27-cell set IS the definition.  r2 is any finite positive value: below
+ *                       the index's own fl32(r * r) it shrinks the search without a rebuild; above it the 27 cells truncate the search
+ *     pair              the candidate lowest in (q, j); a query without a candidate, without a cell, or that takes no part has none
+ *     nearest [M]       (may be NULL) the pair's j, -1 without one
+ * sums [PSAM_ALIGN_SUMS] f64 on the device, over the paired queries, x = the query AS GIVEN (not posed), s = src[pair], both converted to fp64:
+ *     [0] the number of pairs   [1] sum q (the pair's fp32 q, converted)   [2..4] sum x   [5..7] sum s   [8..16] sum x_a s_b, row-major
+ *     [17] sum |x|^2   [18] sum |s|^2   [19] the number of participating queries that have a cell (paired or not)
+ *   Every TERM is exact in fp64 (a converted fp32 value, or the product of two: 48 significant bits; |x|^2 and |s|^2 enter as their three products);
+ *   only the additions round, each an IEEE fp64 addition.  Order of the additions, fixed: lane l of wave w holds query 64 w + l and adds its terms
+ *   starting from 0; the 64 lanes are combined by the xor butterfly 32, 16, 8, 4, 2, 1; a second kernel adds the waves' partials in wave order within
+ *   32 segments of ceil(ceil(M / 64) / 32) consecutive waves, then the segments in order.  The order is a function of M alone -- not of the bits, the
+ *   pose, the data or the schedule: the same inputs give the same twenty words from run to run.  The counts are exact integers.
+ *   Error of the others: |sums - exact| <= (n - 1) u / (1 - (n - 1) u) * sum |term|, u = 2^-53, n the number of terms -- the bound of ANY order.
+ * ws: psam_align_workspace_bytes(M) bytes (0 for M outside (0, 2^28]), 8-byte aligned.
+ * Every refusal comes before any launch and leaves sums untouched: a null pointer (qry_bits, pose and nearest excepted), N or M outside (0, 2^28],
+ * inv_h or r2 not finite and positive, an origin or pose that is not finite: -1; a misaligned pointer (index_ws 16 bytes; sums, ws and qry_bits 8;
+ * src, qry and nearest 4): -2; a short index_ws or ws: -3. */
+#define PSAM_ALIGN_SUMS 20
+size_t psam_align_workspace_bytes(int32_t M);
+int32_t psam_align_step(const float* src, int32_t N, const void* index_ws, size_t index_ws_bytes, const float* origin, float inv_h, float r2,
+                        const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest, double* sums, void* ws,
+                        size_t ws_bytes, psam_stream_t stream);
+
 /* ---------------------------------------------------------------- camera views */
 
 /* A picture of a cloud and the way back from it (point_sam_amd/views.py): a z-buffer of point splats, the point under a pixel, packed masks painted

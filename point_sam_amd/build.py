@@ -37,6 +37,8 @@ SOURCES = [
     # radius 3-NN into another cloud: the cells of scene.hip, the distances and weights of scene_interp.hip.  No SLP vectorisation, as for geometry.hip
     # below: it packs two rows of the pose into a v_pk_mul_f32 that broadcasts one half of a register pair.
     ("transfer.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # one ICP step on transfer.hip's index: the same candidates bit for bit (csrc/transfer_index.h), so the same flags, for the same reasons.
+    ("align.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # camera views: the projection's fp32 operations rounded one at a time; the pose is transfer.hip's (csrc/rigid_pose.h), and so is the reason for
     # leaving SLP vectorisation off.
     ("views.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),

@@ -141,6 +141,13 @@ __device__ __forceinline__ float wave_sum(float v) {      // pairs, quads, 8s, 1
     v += __shfl_xor(v, 16, 64);
     return v + __shfl_xor(v, 32, 64);
 }
+// fp64 wave sum by the xor butterfly 32, 16, 8, 4, 2, 1: each step adds the same two values in both lanes and IEEE addition commutes, so all lanes
+// end up with the same bits, in an order that is a function of the lane numbers alone (geometry.hip, align.hip).  Whole wave must be active.
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
+    return v;
+}
 __device__ __forceinline__ int wave_min_dpp(int v) {
     v = row16_min(v);
     v = min(v, __shfl_xor(v, 16, 64));

@@ -46,11 +46,6 @@ __device__ __forceinline__ unsigned geom_wave_max(unsigned v) {
     for (int d = 32; d >= 1; d >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, d, 64));
     return v;
 }
-__device__ __forceinline__ double geom_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
-    return v;
-}
 
 // The shared bit walk: the wave's range starts at word w0 of a row of W words; f(i) is called for every set bit i < N of the lane's words, in
 // increasing i within a word and words in increasing j.  Bits at positions >= N are dropped before anything is indexed with them.  Returns whether
@@ -133,7 +128,7 @@ __global__ __launch_bounds__(GEOM_THREADS) void moments_partial_kernel(const flo
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
 #pragma unroll
-        for (int c = 0; c < (RGB ? GEOM_SUMS : 9); ++c) s[c] = geom_wave_sum(s[c]);
+        for (int c = 0; c < (RGB ? GEOM_SUMS : 9); ++c) s[c] = wave_sum_f64(s[c]);
 #pragma unroll
         for (int a = 0; a < 3; ++a) { lo[a] = geom_wave_min(lo[a]); hi[a] = geom_wave_max(hi[a]); }
     }

@@ -23,29 +23,7 @@
 #include "interp_select.h"
 #include "rigid_pose.h"      // the pose and its arithmetic, shared with views.hip
 #include "voxel_table.h"
-
-#include <cmath>
-
-constexpr int TRANSFER_THREADS = 256;
-constexpr unsigned TRANSFER_END = ~0u;
-
-struct TransferWs {
-    VoxelWs table;        // keys [C], low [C] = the chain heads
-    unsigned* next;       // [N]
-    size_t bytes;
-};
-
-static inline TransferWs transfer_layout(void* ws, int64_t N) {
-    TransferWs w = {};
-    w.table = voxel_layout(ws, N, false, false);
-    w.next = (unsigned*)((char*)ws + w.table.bytes);
-    w.bytes = w.table.bytes + align16((size_t)N * sizeof(unsigned));
-    return w;
-}
-
-__device__ __forceinline__ bool transfer_cell(float x, float y, float z, float ox, float oy, float oz, float inv_h, u64& cx, u64& cy, u64& cz) {
-    return voxel_axis(x, ox, inv_h, cx) & voxel_axis(y, oy, inv_h, cy) & voxel_axis(z, oz, inv_h, cz);
-}
+#include "transfer_index.h" // the workspace on that table, the cell of a point and the walk over a query's candidates, shared with align.hip
 
 // One thread per source.  next[j] is written by its own source only and read after the kernel boundary.
 __global__ __launch_bounds__(TRANSFER_THREADS) void transfer_insert_kernel(const float* __restrict__ src, int N, float ox, float oy, float oz, float inv_h,
@@ -62,7 +40,7 @@ __global__ __launch_bounds__(TRANSFER_THREADS) void transfer_insert_kernel(const
     next[j] = after;
 }
 
-// One thread per query: 27 look-ups in the finished table, each followed by a walk along the cell's chain.
+// One thread per query: transfer_candidates (27 look-ups in the finished table, each followed by a walk along the cell's chain).
 template <bool POSE>
 __global__ __launch_bounds__(TRANSFER_THREADS) void transfer_plan_kernel(const float* __restrict__ src, int N, const u64* __restrict__ keys,
                                                                        const unsigned* __restrict__ head, const unsigned* __restrict__ next, int capacity,
@@ -78,22 +56,8 @@ __global__ __launch_bounds__(TRANSFER_THREADS) void transfer_plan_kernel(const f
     InterpBest b = interp_none();
     u64 cx, cy, cz;
     if (transfer_cell(px, py, pz, ox, oy, oz, inv_h, cx, cy, cz)) {
-        const int64_t lim = (int64_t)1 << VOXEL_AXIS_BITS;
-        int budget = N;                                            // steps along all 27 chains together
-        for (int o = 0; o < 27; ++o) {
-            const int64_t nx = (int64_t)cx + (o % 3 - 1), ny = (int64_t)cy + (o / 3 % 3 - 1), nz = (int64_t)cz + (o / 9 - 1);
-            if (nx < 0 || nx >= lim || ny < 0 || ny >= lim || nz < 0 || nz >= lim) continue;
-            const int slot = voxel_find(keys, capacity, voxel_key((u64)nx, (u64)ny, (u64)nz));
-            if (slot < 0) continue;
-            unsigned j = head[slot];
-            while (j < (unsigned)N && budget-- > 0) {              // TRANSFER_END is above every N
-                const float* __restrict__ c = src + (int64_t)j * 3;
-                const float dx = px - c[0], dy = py - c[1], dz = pz - c[2];
-                const float q = (dx * dx + dy * dy) + dz * dz;
-                if (q <= r2) interp_insert(b, q, (int)j);
-                j = next[j];
-            }
-        }
+        const TransferIndexView ix = {src, keys, head, next, N, capacity};
+        transfer_candidates(ix, px, py, pz, cx, cy, cz, r2, [&](float q, int j) { interp_insert(b, q, j); });
     }
     interp_finish(b, eps, idx3 + (int64_t)i * 3, w3 + (int64_t)i * 3);
 }
@@ -102,8 +66,6 @@ PSAM_API size_t psam_transfer_index_workspace_bytes(int32_t N) {
     if (N <= 0 || N > VOXEL_MAX_POINTS) return 0;
     return transfer_layout(nullptr, N).bytes;
 }
-
-static inline bool transfer_finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 PSAM_API int32_t psam_transfer_index_build(const float* src, int32_t N, const float* origin, float inv_h, void* ws, size_t ws_bytes, hipStream_t stream) {
     PSAM_REQUIRE(src && origin && ws, PSAM_EINVAL, "psam_transfer_index_build: null pointer");

@@ -1,0 +1,70 @@
+// The cell index of a source cloud, shared by transfer.hip (which builds it and plans the 3-NN transfer with it) and align.hip (the nearest source of
+// an ICP step): the workspace layout, the cell of a point and the walk over a query's candidates are one decision and live here once, so both put
+// the same sources in front of a query bit for bit.  The definition and the index's format: transfer.hip's header.  Translation units that include
+// this are compiled with -ffp-contract=off -fno-slp-vectorize (point_sam_amd/build.py).
+#pragma once
+#include "common.h"
+#include "voxel_table.h"
+
+#include <cmath>
+
+constexpr int TRANSFER_THREADS = 256;
+constexpr unsigned TRANSFER_END = ~0u;
+
+struct TransferWs {
+    VoxelWs table;        // keys [C], low [C] = the chain heads
+    unsigned* next;       // [N]
+    size_t bytes;
+};
+
+static inline TransferWs transfer_layout(void* ws, int64_t N) {
+    TransferWs w = {};
+    w.table = voxel_layout(ws, N, false, false);
+    w.next = (unsigned*)((char*)ws + w.table.bytes);
+    w.bytes = w.table.bytes + align16((size_t)N * sizeof(unsigned));
+    return w;
+}
+
+static inline bool transfer_finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
+
+__device__ __forceinline__ bool transfer_cell(float x, float y, float z, float ox, float oy, float oz, float inv_h, u64& cx, u64& cy, u64& cz) {
+    return voxel_axis(x, ox, inv_h, cx) & voxel_axis(y, oy, inv_h, cy) & voxel_axis(z, oz, inv_h, cz);
+}
+
+// The finished index as a kernel reads it.
+struct TransferIndexView {
+    const float* __restrict__ src;        // [N, 3]
+    const u64* __restrict__ keys;         // [capacity]
+    const unsigned* __restrict__ head;    // [capacity]
+    const unsigned* __restrict__ next;    // [N]
+    int N, capacity;
+};
+
+static inline TransferIndexView transfer_view(const float* src, int64_t N, const void* ws) {
+    const TransferWs w = transfer_layout(const_cast<void*>(ws), N);
+    return {src, (const u64*)w.table.keys, (const unsigned*)w.table.low, (const unsigned*)w.next, (int)N, (int)voxel_capacity(N)};
+}
+
+// The candidates of the point p in cell (cx, cy, cz): 27 look-ups in the finished table, each followed by a walk along the cell's chain; f(q, j) for
+// every indexed source j of those cells with q = (dx dx + dy dy) + dz dz <= r2 (NaN compares false), in chain order -- callers order by (q, j).
+// Bounded: the chains of one query by N steps altogether, and an index outside [0, N) ends a chain.
+template <class F>
+__device__ __forceinline__ void transfer_candidates(const TransferIndexView& ix, float px, float py, float pz, u64 cx, u64 cy, u64 cz, float r2, F&& f) {
+#pragma clang fp contract(off)
+    const int64_t lim = (int64_t)1 << VOXEL_AXIS_BITS;
+    int budget = ix.N;                                             // steps along all 27 chains together
+    for (int o = 0; o < 27; ++o) {
+        const int64_t nx = (int64_t)cx + (o % 3 - 1), ny = (int64_t)cy + (o / 3 % 3 - 1), nz = (int64_t)cz + (o / 9 - 1);
+        if (nx < 0 || nx >= lim || ny < 0 || ny >= lim || nz < 0 || nz >= lim) continue;
+        const int slot = voxel_find(ix.keys, ix.capacity, voxel_key((u64)nx, (u64)ny, (u64)nz));
+        if (slot < 0) continue;
+        unsigned j = ix.head[slot];
+        while (j < (unsigned)ix.N && budget-- > 0) {               // TRANSFER_END is above every N
+            const float* __restrict__ c = ix.src + (int64_t)j * 3;
+            const float dx = px - c[0], dy = py - c[1], dz = pz - c[2];
+            const float q = (dx * dx + dy * dy) + dz * dz;
+            if (q <= r2) f(q, (int)j);
+            j = ix.next[j];
+        }
+    }
+}

@@ -15,7 +15,7 @@ POST /crop {center, radius} . POST /crop/clear (not in the reference): zoom into
 from the ball's own working cloud (predictor.set_crop), still per loaded point, until the crop is cleared or another cloud is loaded.
 POST /instances (not in the reference): /segment_all plus one box per kept mask (predictor.mask_geometry) . POST /crop/selection {margin}: zoom
 into the ball around the current /segment mask (predictor.set_crop_to_mask).
-POST /propagate {pointcloud, radius, pose?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
+POST /propagate {pointcloud, radius, pose?, align?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
 there (predictor.snapshot / propagate).
 POST /view {camera, splat?} (not in the reference): the loaded cloud as a camera sees it, a z-buffered point-splat image (predictor.render_view) .
 POST /click_pixel {pixel, label, window?, frame?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
@@ -364,7 +364,9 @@ class DemoSession:
             return self._segment({"prompt_point": pts[0, 0].cpu().numpy().tolist(), "prompt_label": label})
 
     def propagate(self, data: dict) -> dict:
-        """The next scan of a sequence: {"pointcloud": name, "radius": r, "pose": 3 x 4 or 4 x 4 rows (optional)}.  The kept masks (/next) plus the
+        """The next scan of a sequence: {"pointcloud": name, "radius": r, "pose": 3 x 4 or 4 x 4 rows (optional), "align": {align.AlignConfig fields}
+        (optional: the given pose, or the identity, is refined by ICP before the transfer -- predictor.align -- and the response also carries "pose", the
+        3 x 4 rows used, and "align": {pairs, coverage, rms, iterations, converged})}.  The kept masks (/next) plus the
         current /segment mask become a snapshot of the loaded cloud (a mask's logits are +1 inside, -1 outside: the session keeps masks, not logits);
         the named cloud is loaded as /pointcloud/ does, but normalised with the SAME shift and scale as the cloud it follows (a transfer compares
         coordinates; a point that leaves the unit ball is the model's ValueError), and predictor.propagate re-segments every object there.  radius
@@ -378,8 +380,8 @@ class DemoSession:
             masks = list(self.masks) + ([self.segment_mask.cpu().numpy()] if self.segment_mask is not None else [])
             if not masks:
                 raise ValueError("/propagate before any /segment: there is no mask to carry over")
-            if not isinstance(data, dict) or not {"pointcloud", "radius"} <= set(data) or set(data) - {"pointcloud", "radius", "pose"}:
-                raise ValueError('/propagate takes {"pointcloud": name, "radius": r, "pose": rows (optional)}')
+            if not isinstance(data, dict) or not {"pointcloud", "radius"} <= set(data) or set(data) - {"pointcloud", "radius", "pose", "align"}:
+                raise ValueError('/propagate takes {"pointcloud": name, "radius": r, "pose": rows (optional), "align": {AlignConfig fields} (optional)}')
             name, radius, pose = data["pointcloud"], data["radius"], data.get("pose")
             if not isinstance(name, str) or not name:
                 raise ValueError("pointcloud must be a file name")
@@ -387,6 +389,10 @@ class DemoSession:
                 raise ValueError("radius must be a finite positive number")
             from . import ops
             ops.transfer_pose(pose)                # a bad pose is refused before anything is loaded
+            align_cfg = None
+            if "align" in data:
+                from .align import AlignConfig
+                align_cfg = AlignConfig.from_overrides(data["align"])      # and so is a bad align field
             if any(m.shape != (self.pc_xyz.shape[1],) for m in masks):
                 raise ValueError("/propagate: a kept mask does not belong to the loaded cloud")
             before = (self.pc_xyz, self.pc_rgb, self.obj_path, self.crop, self.norm)
@@ -398,6 +404,10 @@ class DemoSession:
                     snap = self.predictor.snapshot(torch.where(inside, 1.0, -1.0).float())
                     cloud = self._install_pointcloud(*self._read_pointcloud(name, self.norm))
                     self._set_cloud()
+                    found = None
+                    if align_cfg is not None:
+                        found = self.predictor.align(snap, align_cfg, pose)
+                        pose = found.pose.tolist()
                     res = self.predictor.propagate(snap, float(radius), pose)
             except Exception:
                 self.pc_xyz, self.pc_rgb, self.obj_path, self.crop, self.norm = before
@@ -407,8 +417,12 @@ class DemoSession:
             self.masks = [m for m in segs]
             self._reset_prompts()
             self.segment_mask = None
-            return dict(cloud, objects=[{"seg": m.tolist()} for m in segs], lost=res.lost.cpu().numpy().astype(bool).tolist(),
-                        scores=[float(v) if np.isfinite(v) else None for v in scores])
+            out = dict(cloud, objects=[{"seg": m.tolist()} for m in segs], lost=res.lost.cpu().numpy().astype(bool).tolist(),
+                       scores=[float(v) if np.isfinite(v) else None for v in scores])
+            if found is not None:
+                out.update(pose=pose, align=dict(pairs=found.pairs, coverage=found.coverage, rms=found.rms if np.isfinite(found.rms) else None,
+                                                 iterations=found.iterations, converged=found.converged))
+            return out
 
     def set_crop(self, data: dict) -> dict:
         """Zoom: {"center": [x, y, z], "radius": r} in the loaded cloud's coordinates.  The crop is built (and its cloud encoded) now, so an empty

@@ -1605,6 +1605,46 @@ def transfer_plan(index: TransferIndex, xyz: torch.Tensor, pose=None, eps: float
     return idx3, w3
 
 
+# ------------------------------------------------------------------------------------------ pose between two clouds (csrc/align.hip)
+ALIGN_SUMS = 20
+
+
+def align_step(index: TransferIndex, xyz: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None, return_nearest: bool = False):
+    """One ICP step (include/pointsam_hip.h: pose between two clouds): index (transfer_index), xyz [M, 3] f32 (the queries), pose as for transfer_plan
+    -> sums [20] float64 on the device over the pairs (query, nearest source within `radius` of pose(query)): the count, sum q, sum x, sum s,
+    sum x s^T, sum |x|^2, sum |s|^2, and the participating queries that have a cell; x is the query as given, not posed.  radius: None (the index's
+    own) or a smaller one -- a larger one is a ValueError, the 27 cells would silently truncate the search.  bits: None, or [ceil(M / 64)] int64 words
+    in mask_pack's layout: the queries that take part.  return_nearest: also nearest [M] int32, -1 without a pair.  No host synchronisation."""
+    if not isinstance(index, TransferIndex):
+        raise TypeError(f"align_step: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
+    xyz = _transfer_cloud(xyz, "align_step: xyz")
+    words = transfer_pose(pose)
+    r2 = index.r2
+    if radius is not None:
+        r, _, r2 = transfer_radius(radius)
+        if r > index.radius:
+            raise ValueError(f"align_step: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
+    M, N, dev = xyz.shape[0], index.num_source, xyz.device
+    if bits is not None:
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64 or bits.dim() == 2 and bits.shape[0] != 1 or bits.dim() not in (1, 2) or \
+                bits.shape[-1] != mask_words(M):
+            raise ValueError(f"align_step: bits must be one packed row of {mask_words(M)} int64 words for {M} queries, got "
+                             f"{(bits.dtype, tuple(bits.shape)) if isinstance(bits, torch.Tensor) else type(bits).__name__}")
+        bits = bits.reshape(-1)
+        _chk(bits, torch.int64, name="bits")
+    _chk(xyz, name="xyz")
+    L = _lib.load()
+    sums = torch.empty(ALIGN_SUMS, dtype=torch.float64, device=dev)
+    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
+    ws = torch.empty(L.psam_align_workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
+    org = (ctypes.c_float * 3)(*index.origin)
+    P = None if words is None else (ctypes.c_float * 12)(*[float(v) for v in words])
+    check(L.psam_align_step(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org), float(index.inv_h), float(r2),
+                            xyz.data_ptr(), M, None if bits is None else bits.data_ptr(), None if P is None else ctypes.addressof(P),
+                            None if nearest is None else nearest.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_align_step")
+    return (sums, nearest) if return_nearest else sums
+
+
 # ------------------------------------------------------------------------------------------ camera views (csrc/views.hip)
 VIEW_MAX_SIDE, VIEW_MAX_SPLAT, VIEW_MAX_WINDOW = 8192, 3, 16
 

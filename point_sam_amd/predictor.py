@@ -264,6 +264,22 @@ class PointSAMPredictor:
         return bits, area, T.covered(plan).sum()
 
     @torch.no_grad()
+    def align(self, snap, cfg, init=None, mask=None):
+        """The pose from the CURRENT cloud to the snapshot's, estimated by ICP (point_sam_amd/align.py) -> align.Alignment; its `pose` is what
+        transfer_masks / propagate take.  The sources are the snapshot's working cloud, the queries this cloud's working coordinates as encoded;
+        cfg: an align.AlignConfig (its radius is the index's cell size); init: the pose to refine (None: the identity; e.g. odometry); mask: an
+        optional packed row [ceil(Nw / 64)] int64 at working width restricting the queries to one object (a re-scan after something moved).
+        Exactly align.icp(ops.transfer_index(snap.coords, cfg.radius), working coordinates, cfg, init, mask).  One 160-byte host read per step
+        besides the index build's; both scans normalised with the same centre and scale."""
+        from . import align as A
+        from . import transfer as T
+        T.check_snapshot(snap, "align")
+        if not isinstance(cfg, A.AlignConfig):
+            raise TypeError(f"align: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
+        state, _ = self._transfer_cloud("align")
+        return A.icp(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), cfg, init, mask)
+
+    @torch.no_grad()
     def propagate(self, snap, radius: float, pose=None, clicks: int = 1, fill=None):
         """The model re-segments every snapshot object in the CURRENT cloud -> transfer.Propagated.  The carried logits (`prior`: the blend of the
         snapshot's logits at this working cloud's points; where no snapshot point is within `radius`, `fill`, or with fill=None the object's own

@@ -6,7 +6,7 @@ need every object clicked again in every scan.  A `Snapshot` keeps a scan's work
 ops.scene_interp_rows / ops.scene_interp_bits apply it unchanged.  The format is shared on purpose.
 
 Both scans must have been normalised with the SAME centre and scale; `pose` is the rigid motion that remains in those coordinates (new scan -> the
-snapshot's scan).  Nothing here estimates it.
+snapshot's scan).  Where it is not known, or only roughly (odometry), align.py estimates it by ICP on the same index (predictor.align).
 
 No default here -- the radius a caller picks, `clicks = 1`, `fill = None` (the object's own minimum logit) -- has been tuned on a trained checkpoint
 (none exists offline).

@@ -246,6 +246,14 @@ int32_t psam_gemm_f16x3p_ex(const void* A, int64_t lda, const float* scaleA, con
                             const float* bias, const float* residual, int64_t ldr, const float* rowbias, int64_t ldrb, int32_t rowgroup, int32_t M,
                             int32_t N, int32_t K, float alpha, int32_t act, const psam_gemm_fuse_t* fuse, psam_stream_t stream);
 int32_t psam_ln_stats_finalize(const float* stats, int32_t rows, int32_t segs, int32_t cols, float eps, float* mean, float* rstd, psam_stream_t stream);
+/* Linear (128 -> 512) -> LayerNorm -> GELU -> g8-packed rows in one persistent kernel (csrc/patch_rowln.hip): PatchEncoder's per-row half of conv2.0, conv2.1
+ * and its GELU (common.py:493-496) without the [rows, 512] fp32 activation.  x [rows, ldx] / w [512, ldw]: g8-packed operands of 128 columns with their row
+ * scales; rowbias [rows / rowgroup, ldrb]: a bias row per group of rowgroup consecutive rows (the pooled half of conv2.0 with its bias); out [rows, ldo]
+ * receives the packed rows scaled by out_scale[row] = the power of two that puts `bound` (>= max|gamma| sqrt(512) + max|beta|, which bounds every LayerNorm
+ * output and its GELU) into [2^14, 2^15).  h1 == 512, rows % 64 == 0, rows < 2^31, rowgroup % 32 == 0; packed rows 32-byte, the fp32 vectors 16-byte aligned. */
+int32_t psam_linear128_ln_gelu_pack(const void* x, int64_t ldx, const float* x_scale, const void* w, int64_t ldw, const float* w_scale, const float* rowbias,
+                                    int64_t ldrb, int32_t rowgroup, const float* gamma, const float* beta, float eps, float bound, int64_t rows, int32_t h1,
+                                    void* out, int64_t ldo, float* out_scale, psam_stream_t stream);
 /* Row scales and g8 packing of fp32 rows in ONE pass (an activation no LayerNorm produced, e.g. the attention output). */
 int32_t psam_scale_pack_rows_g8(const float* X, int64_t ldx, int32_t rows, int32_t K, void* P, int64_t ldp, float* scale, psam_stream_t stream);
 int32_t psam_linear(const float* x, int64_t ldx, const float* W, int64_t ldw, const float* bias, const float* residual, int64_t ldr, float* y,
@@ -437,7 +445,7 @@ int32_t psam_eva_gelu_block(const psam_eva_gelu_block_plan_t* plan, const void* 
 
 /* PatchEncoder.forward on kNN groups in one call (csrc/blocks.hip): the mini-PointNet of the patch embedding (features = rgb) and of the mask
  * encoder (features = mask logits) -- pc_sam/model/common.py:477-506 after the gather of :99-120 / :126-187 -- "f16x3", fused as the Python host
- * runs it (six launches; both max-pools inside GEMM epilogues -- for group sizes above 64 as 64-row parts + psam_group_max over the parts).
+ * runs it (five launches for hidden dims (128, 512), where psam_linear128_ln_gelu_pack replaces conv2.0's GEMM and the LayerNorm pass, else six; both max-pools inside GEMM epilogues -- for group sizes above 64 as 64-row parts + psam_group_max over the parts).
  * hidden_dims[0] == 128, group size 32 or a multiple of 64, B * rep * G * K % 256 == 0.
  * Weights: the reference's conv1.{0,1,3} / conv2.{0,1,3} tensors ([out, in] fp32 device pointers); the plan keeps pointers to the small ones. */
 typedef struct {

@@ -62,6 +62,7 @@ SIGNATURES = {
     "psam_attention_packed_force_nw": (None, [i32]),
     "psam_attention_packed_last_instance": (i32, []),
     "psam_gemm_f16x3p_fused_row_ln": (i32, [i32]),
+    "psam_linear128_ln_gelu_pack": (i32, [ptr, i64, ptr, ptr, i64, ptr, ptr, i64, i32, ptr, ptr, f32, f32, i64, i32, ptr, i64, ptr, ptr]),
     "psam_gemm_f16x3p_stat_segs": (i32, [i32]),
     "psam_gemm_f16x3p_splitk": (i32, [i32, i32, i32, i32]),
     "psam_nn_group_feats": (i32, [ptr, ptr, ptr, ptr, ptr, i32, i32, i32, i32, i32, i32, ptr, i64, ptr]),

@@ -26,6 +26,7 @@ SOURCES = [
     ("gemm_split.hip", []),
     ("gemm_f16x3p.hip", []),
     ("gemm_f16x3pp.hip", []),
+    ("patch_rowln.hip", []),
     ("attention.hip", []),
     ("rowops.hip", []),
     ("blocks.hip", []),

@@ -544,6 +544,11 @@ PSAM_API int32_t psam_patch_encoder(const psam_patch_encoder_plan_t* plan, const
         f.row_ln_g = plan->c21_w; f.row_ln_b = plan->c21_b; f.row_ln_eps = plan->eps; f.pack_out = 1; f.out_scale = w.rs; f.out_k1 = 0.f; f.out_k2 = plan->ln21_bound;
         rc = psam_gemm_f16x3p_ex(w.x2, a, w.s2, P(plan->o_w20x), a, P(plan->o_s20x), w.x3, b, nullptr, nullptr, 0, w.g1, h1, K, (int32_t)rows, h1, a, 1.f, PSAM_ACT_GELU, &f, stream);
         if (rc) return rc;
+    } else if (h0 == 128 && h1 == 512 && rows % 64 == 0) {
+        // the same three steps in one register-row kernel (patch_rowln.hip): the 128 -> 512 weight stays in registers, x3 receives the packed rows at once
+        rc = psam_linear128_ln_gelu_pack(w.x2, a, w.s2, P(plan->o_w20x), a, P(plan->o_s20x), w.g1, h1, K, plan->c21_w, plan->c21_b, plan->eps, plan->ln21_bound, rows, h1,
+                                         w.x3, b, w.rs, stream);
+        if (rc) return rc;
     } else {
         rc = psam_gemm_f16x3p_ex(w.x2, a, w.s2, P(plan->o_w20x), a, P(plan->o_s20x), w.x3, h1, nullptr, nullptr, 0, w.g1, h1, K, (int32_t)rows, h1, a, 1.f, 0, nullptr, stream);
         if (rc) return rc;

@@ -95,6 +95,8 @@ __device__ __forceinline__ void g8_store_group(unsigned* first, const g8_group& 
     *reinterpret_cast<u32x4*>(first) = g.hi;
     *reinterpret_cast<u32x4*>(first + 4) = g.lo;
 }
+// The regrouping and the store in one step, for a kernel whose lanes hold the runs as above (patch_rowln.hip)
+__device__ __forceinline__ void g8_store_halfwave_group(unsigned* first, const psam_f32x4 x, const psam_f32x4 y, float s) { g8_store_group(first, g8_halfwave_group(x, y, s)); }
 
 // This lane holds columns 2 * lane and 2 * lane + 1 of row `row` of P (ld containers per row; a group of 8 = 4 lanes): one hi and one lo container.
 __device__ __forceinline__ void g8_store_pair(unsigned* P, int64_t row, int ld, int lane, float x0, float x1, float s) {

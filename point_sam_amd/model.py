@@ -271,7 +271,7 @@ class PointCloudSAM:
         fused = (self.precision == "f16x3" and self.fuse_patch and (K in (32, 64) or K % 64 == 0) and ops.fuse_supported(rows, 128) and prefix in self.pe_bound
                  and all((prefix + n) in self.fw for n in (".conv1.3.weight", ".conv2.0.weight#x", ".conv2.3.weight")))
         if fused and self.c_blocks and prefix in getattr(self, "c_patch", {}) and ops.current_gemm_mode() == "f16x3":
-            return self.c_patch[prefix].run(coords, feats, centers, knn_idx, radius=radius, center_idx=center_idx)      # psam_patch_encoder: the same six launches
+            return self.c_patch[prefix].run(coords, feats, centers, knn_idx, radius=radius, center_idx=center_idx)      # psam_patch_encoder: the same launches
         if fused:
             # every hand-over stays in the GEMMs' packed form and both max-pools happen in GEMM epilogues: the [rows, 128] / [rows, 512]
             # activations are written once (packed) or not at all (conv2.3 only leaves its pooled [groups, Cout] rows)
@@ -299,6 +299,16 @@ class PointCloudSAM:
                     bound = self.ln_bound.setdefault(prefix, 1.001 * ops.row_ln_bound(w[prefix + ".conv2.1.weight"], w[prefix + ".conv2.1.bias"]) + 1e-30)
                 ops.linear(h2, self.fw[prefix + ".conv2.0.weight#x"], None, act=ACT_GELU, rowbias=g1, rowgroup=K, x_scale=s2, x_packed=True, out=h3,
                            row_ln=(w[prefix + ".conv2.1.weight"], w[prefix + ".conv2.1.bias"], eps), pack_out=(rs, 0.0, bound))
+                del h2
+            elif ops.linear128_ln_gelu_supported(rows, h0, hd1, K) and (prefix + ".conv2.3.weight") in self.fw and ops.current_gemm_mode() == "f16x3":
+                # the same three steps in one register-row kernel (psam_linear128_ln_gelu_pack): the weight of the 128 -> 512 Linear stays in registers
+                h3 = torch.empty(rows, hd1, dtype=torch.float32, device=coords.device)     # g8-packed container
+                rs, pk = torch.empty(rows, dtype=torch.float32, device=coords.device), True
+                bound = self.ln_bound.get(prefix)
+                if bound is None:
+                    bound = self.ln_bound.setdefault(prefix, 1.001 * ops.row_ln_bound(w[prefix + ".conv2.1.weight"], w[prefix + ".conv2.1.bias"]) + 1e-30)
+                ops.linear128_ln_gelu_pack(h2, s2, self.fw[prefix + ".conv2.0.weight#x"], g1, K, w[prefix + ".conv2.1.weight"], w[prefix + ".conv2.1.bias"], eps, bound,
+                                           h3, rs)
                 del h2
             else:
                 h3 = ops.linear(h2, self.fw[prefix + ".conv2.0.weight#x"], None, rowbias=g1, rowgroup=K, x_scale=s2, x_packed=True)

@@ -443,6 +443,24 @@ def fused_row_ln(N: int) -> bool:
     return bool(_lib.load().psam_gemm_f16x3p_fused_row_ln(int(N)))
 
 
+def linear128_ln_gelu_supported(rows: int, K: int, N: int, rowgroup: int) -> bool:
+    """Shapes of linear128_ln_gelu_pack (csrc/patch_rowln.hip): 128 -> 512 columns on whole 64-row blocks, one bias row per 32-row tile."""
+    return K == 128 and N == 512 and rows > 0 and rows % 64 == 0 and rowgroup > 0 and rowgroup % 32 == 0
+
+
+def linear128_ln_gelu_pack(x, x_scale, fw, rowbias, rowgroup, gamma, beta, eps, bound, out, scale_out):
+    """out = g8(GELU(LayerNorm(x @ fw^T + rowbias[row // rowgroup]) * gamma + beta)), scale_out[row] = the power-of-two scale of `bound`
+    (>= 1.001 * row_ln_bound(gamma, beta)): PatchEncoder's per-row half of conv2.0, conv2.1 and its GELU in one kernel
+    (psam_linear128_ln_gelu_pack).  x [rows, 128] g8-packed with x_scale, fw an F16Weight [512, 128], out [rows, 512] containers."""
+    xp, ldx = _row_view(x, "x")
+    rbp, ldrb = _row_view(rowbias, "rowbias")
+    op, ldo = _row_view(out, "out")
+    check(_lib.load().psam_linear128_ln_gelu_pack(xp, ldx, x_scale.data_ptr(), fw.packed.data_ptr(), fw.packed.stride(0), fw.scale.data_ptr(), rbp, ldrb, int(rowgroup),
+                                                  gamma.data_ptr(), beta.data_ptr(), float(eps), float(bound), x.shape[0], fw.N, op, ldo,
+                                                  scale_out.data_ptr(), _stream()), "psam_linear128_ln_gelu_pack")
+    return out
+
+
 def stat_segs(N: int) -> int:
     return (N // 2 + 31) // 32
 

@@ -992,6 +992,58 @@ size_t psam_instance_extents_workspace_bytes(int32_t K, int32_t N);
 int32_t psam_instance_extents(const float* xyz, const uint64_t* bits, int32_t K, int32_t N, const float* origin, const float* axes, float* lo,
                               float* hi, float* r2max, void* ws, size_t ws_bytes, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- normals and superpoints */
+
+/* Surface normals per occupied voxel, a geometric over-segmentation of the cloud grown from them, and the snapping of packed masks to whole segments
+ * (point_sam_amd/superpoints.py).  The graph is that of the connected components above: inv [N] of psam_voxel_downsample at origin (-1, -1, -1), nbr
+ * [V, 26] of psam_region_neighbors; a point whose inv is outside [0, V) has no cell.  No call allocates or synchronises with the host; the workspace is
+ * the caller's, 16-byte aligned.  A null pointer or a bad shape returns -1, a short workspace -3, a misaligned pointer -2, all before any launch.
+ * 0 < N <= 2^28, 0 < V <= N.
+ *
+ * psam_normals_voxel.  The neighbourhood of voxel v is every point whose voxel is v or one of nbr[v, 0 .. 25]; all points of a voxel share its normal.
+ *   Fixed point: a coordinate p in [-1, 1] has q = floor((double)p * 2^20) + 2^20, an integer in [0, 2^21]; every step is exact.  A point with a
+ *   coordinate that is not finite or outside [-1, 1] takes part in no neighbourhood.
+ *   With the neighbourhood's n points, s = sum q and P = sum q q^T:  S = n P - s s^T, formed EXACTLY in integer arithmetic (128-bit where needed; no
+ *   accepted shape overflows, csrc/normals.hip) and converted to fp64 once, to nearest even.  S does not depend on the order of the points, on any
+ *   translation of q by integers, or on the launch schedule.
+ *   count [V] int32       n
+ *   scatter [V, 6] f64    S: xx, xy, xz, yy, yz, zz; may be NULL
+ *   normal [V, 3] f32     the unit eigenvector of the smallest eigenvalue of S, solved in fp64 (cyclic Jacobi on S scaled by a power of two), rounded
+ *                         to fp32.  Sign, decided on the fp32 values: without a viewpoint the component of largest magnitude is positive, on a tie
+ *                         the lowest axis decides; with viewpoint [3] (HOST memory, finite) the sign gives n . (viewpoint - mean) >= 0 in fp64, mean =
+ *                         (s / n - 2^20) 2^-20 per axis.
+ *   curvature [V] f32     l0 / (l0 + l1 + l2) of the eigenvalues l0 <= l1 <= l2 (l0 not below 0), 0 when the sum is 0
+ *   A voxel with n < min_points (>= 1; an exact integer test) gets normal (0, 0, 0) and curvature 0.
+ *   ws: psam_normals_voxel_workspace_bytes(N, V) = 128 V bytes (sixteen 64-bit integer sums per voxel). */
+size_t psam_normals_voxel_workspace_bytes(int32_t N, int32_t V);
+int32_t psam_normals_voxel(const float* xyz, const int64_t* inv, const int32_t* nbr, int32_t N, int32_t V, int32_t min_points, const float* viewpoint,
+                           int32_t* count, double* scatter, float* normal, float* curvature, void* ws, size_t ws_bytes, psam_stream_t stream);
+/* psam_superpoints: count, normal, curvature as psam_normals_voxel wrote them.  Call voxel v smooth iff count[v] >= min_points and curvature[v] <=
+ *   max_curvature, and let d(v, u) = |(x x' + y y') + z z'| in fp64 from the stored fp32 normals of v and u, every operation rounded on its own.
+ *   Union.   Edge (v, u = nbr[v, o]) joins the two voxels iff both are smooth and d(v, u) >= cos_angle.  The label of a component is its lowest voxel
+ *            rank; the size of a label is the number of POINTS (inv in [0, V)) of its voxels.
+ *   Absorb.  absorb_rounds (0 .. 64) times, every voxel reading the labels and sizes of the round's start: a voxel v whose label has fewer than
+ *            min_size points takes, among its neighbours u whose label has at least min_size, the label of the one with the largest d(v, u) (a
+ *            normal of (0, 0, 0) gives 0); a tie goes to the lower label; without such a neighbour it keeps its label.  Sizes are counted again
+ *            after every round.  min_size = 0 absorbs nothing.
+ *   Compact. The labels still in use become 0 .. S - 1 in increasing order of their value.
+ *   voxel_label [V], point_label [N] = voxel_label[inv[i]] (-1 for a point without a cell), size [V; the first S written, the rest zero], *num = S (DEVICE
+ *   memory), all int32.  ws: psam_superpoints_workspace_bytes(N, V). */
+size_t psam_superpoints_workspace_bytes(int32_t N, int32_t V);
+int32_t psam_superpoints(const int64_t* inv, const int32_t* nbr, const int32_t* count, const float* normal, const float* curvature, int32_t N, int32_t V,
+                         int32_t min_points, float max_curvature, double cos_angle, int32_t min_size, int32_t absorb_rounds, int32_t* voxel_label,
+                         int32_t* point_label, int32_t* size, int32_t* num, void* ws, size_t ws_bytes, psam_stream_t stream);
+/* psam_superpoint_snap: bits [K, ceil(N / 64)] in the layout of the mask proposals (bits past N are ignored), point_label [N], size [S] of
+ *   psam_superpoints, 0 < S <= N given by the caller, 0 <= q16 <= 65535, 0 < K <= 65535.  cnt[k, s] = the set bits of row k whose point has label s
+ *   (a label outside [0, S) counts nowhere).  Bit i of row k of bits_out (must not alias bits; bits past N are zero) is set iff
+ *       0 <= point_label[i] < S  and  (int64)cnt[k, point_label[i]] * 65536 > (int64)q16 * size[point_label[i]]
+ *   q16 = 0: any touch selects the whole superpoint; q16 = 32768: a strict majority, and rows that were disjoint stay disjoint from there on.
+ *   area_out [K] = the popcounts of bits_out, changed [K] uint8 = the row differs from its input below N.
+ *   ws: psam_superpoint_snap_workspace_bytes(K, N, S) = the [K, S] int32 table, rounded up to 16 bytes. */
+size_t psam_superpoint_snap_workspace_bytes(int32_t K, int32_t N, int32_t S);
+int32_t psam_superpoint_snap(const uint64_t* bits, const int32_t* point_label, const int32_t* size, int32_t K, int32_t N, int32_t S, int32_t q16,
+                             uint64_t* bits_out, int32_t* area_out, uint8_t* changed, void* ws, size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

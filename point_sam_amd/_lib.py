@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PSAM_HIP_LIB: A/B tuning hook (another build of the SAME C ABI); there is still no non-HIP fallback
 LIB_PATH = os.environ.get("PSAM_HIP_LIB") or os.path.join(_HERE, "csrc", "libpointsam_hip.so")
 
-i32, i64, f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
+i32, i64, f32, f64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
 ptr, size_t = ctypes.c_void_p, ctypes.c_size_t
 
 # name -> (restype, argtypes); mirrors include/pointsam_hip.h one to one
@@ -172,6 +172,12 @@ SIGNATURES = {
     "psam_instance_moments": (i32, [ptr, ptr, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
     "psam_instance_extents_workspace_bytes": (size_t, [i32, i32]),
     "psam_instance_extents": (i32, [ptr, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_normals_voxel_workspace_bytes": (size_t, [i32, i32]),
+    "psam_normals_voxel": (i32, [ptr, ptr, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_superpoints_workspace_bytes": (size_t, [i32, i32]),
+    "psam_superpoints": (i32, [ptr, ptr, ptr, ptr, ptr, i32, i32, i32, f32, f64, i32, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_superpoint_snap_workspace_bytes": (size_t, [i32, i32, i32]),
+    "psam_superpoint_snap": (i32, [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, size_t, ptr]),
 }
 
 

@@ -50,6 +50,10 @@ SOURCES = [
     # instance geometry: the extents' fp32 operations rounded one at a time, the moments' fp64 terms exact.  No SLP vectorisation: it packs the three
     # projections into v_pk_mul_f32 / v_pk_add_f32 that broadcast one half of a register pair, the form isa_lint.py refuses; the kernels are gather-bound.
     ("geometry.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # normals: the scatter matrix is integer, the fp64 eigen-solve and the sign test rounded one operation at a time; flags as for geometry.hip.
+    ("normals.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # superpoints: the join rule's fp64 dot product is (x x' + y y') + z z' with nothing contracted, so that a host reference decides every edge alike.
+    ("superpoints.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

@@ -18,6 +18,7 @@
 // The root of a finished tree is the lowest rank of its component, whatever order the waves arrived in: it IS the component's id.  Every loop has a
 // bound derived from V (a walk descends at least one rank per step; a failed hook lowers one of its two ends): a logic error ends as a wrong answer.
 #include "common.h"
+#include "region_union.h"    // region_find, region_union, region_shorten, region_flatten
 #include "row_popcount.h"    // block_sum, row_popcount
 #include "voxel_table.h"
 
@@ -99,18 +100,7 @@ PSAM_API int32_t psam_region_neighbors(const float* xyz, const int64_t* keep_idx
 
 // ------------------------------------------------------------------------------------------------ components
 // Per row k: cnt, parent, size (and, with seeds, flag) are [V] slices at k * V of [K, V] arrays.  `active` (may be NULL: every row) skips rows.
-__device__ __forceinline__ int region_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// x's root.  Every step goes to a strictly lower rank; `budget` (shared by all walks of one hook) only ever matters if that invariant were broken.
-__device__ __forceinline__ int region_find(const int* parent, int x, int& budget) {
-    while (budget-- > 0) {
-        const int p = region_load(parent + x);
-        if (p == x) break;
-        x = p;
-    }
-    return x;
-}
-
+// (the walks and the hook: region_union.h)
 __global__ __launch_bounds__(REGION_THREADS) void region_init_kernel(int* __restrict__ cnt, int* __restrict__ parent, int* __restrict__ size,
                                                                    int* __restrict__ flag, int V, u64* __restrict__ best, int* __restrict__ any_seed) {
     const int v = blockIdx.x * REGION_THREADS + threadIdx.x, k = blockIdx.y;
@@ -146,22 +136,9 @@ __global__ __launch_bounds__(REGION_THREADS) void region_hook_kernel(const int* 
     for (int o = 0; o < 13; ++o) {
         const int u = nbr[(int64_t)v * 26 + o];
         if ((unsigned)u >= (unsigned)V || c[u] == 0) continue;
-        // a + b falls with every walk step and every failed hook, and both stay >= 0: 2 V + 2 rounds and 4 V + 16 loads are never reached
-        int a = v, b = u, budget = 4 * V + 16;
-        for (int round = 0; round < 2 * V + 2 && budget > 0; ++round) {
-            a = region_find(par, a, budget);
-            b = region_find(par, b, budget);
-            if (a == b) break;
-            if (a < b) { const int t = a; a = b; b = t; }
-            const int old = atomicCAS(&par[a], a, b);              // hook the higher root under the lower, if it still is a root
-            if (old == a) break;
-            a = old;                                               // somebody hooked it first, under a lower rank: go on from there
-        }
+        region_union(par, v, u, V);
     }
-    // shorten this voxel's own path for the flatten pass: its root is one of its ancestors and never above its parent
-    int budget = V + 1;
-    const int r = region_find(par, v, budget);
-    if (r != v) atomicMin(&par[v], r);
+    region_shorten(par, v, V);
 }
 
 __global__ __launch_bounds__(REGION_THREADS) void region_flatten_kernel(const int* __restrict__ cnt, int* parent, int* __restrict__ size, int V) {
@@ -170,9 +147,7 @@ __global__ __launch_bounds__(REGION_THREADS) void region_flatten_kernel(const in
     const int64_t row = (int64_t)k * V;
     const int c = cnt[row + v];
     if (c == 0) return;
-    int budget = V + 1;
-    const int r = region_find(parent + row, v, budget);           // others store roots meanwhile: still ancestors, still descending
-    __hip_atomic_store(&parent[row + v], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int r = region_flatten(parent + row, v, V);
     if (size) atomicAdd(&size[row + r], c);
 }
 

@@ -62,8 +62,14 @@ class DemoSession:
     ``clean_masks(logits, cfg, points, labels) -> (bits, area, changed)``."""
 
     def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None,
-                 working_points: int = None, clean_min_points: int = None, crop_points: int = None, smooth_edges: bool = False):
+                 working_points: int = None, clean_min_points: int = None, crop_points: int = None, smooth_edges: bool = False,
+                 snap_superpoints: bool = False):
         self.predictor = predictor
+        if not isinstance(snap_superpoints, bool):
+            raise ValueError(f"snap_superpoints must be True or False, got {snap_superpoints!r}")
+        # True: /segment_all and /instances snap every proposal to whole superpoints (ProposalConfig.snap = the default SuperpointConfig, unless the
+        # request gives its own "snap")
+        self.snap_superpoints = snap_superpoints
         if not isinstance(smooth_edges, bool):
             raise ValueError(f"smooth_edges must be True or False, got {smooth_edges!r}")
         # True: the masks of a voxel working cloud or a crop reach the loaded points by a 3-NN blend, not by the voxel representative's value
@@ -474,11 +480,32 @@ class DemoSession:
             raise ValueError(f"{route} before a point cloud was set")
         if not isinstance(data, dict):
             raise ValueError(f"{route} takes a JSON object of ProposalConfig overrides (or nothing)")
+        if self.snap_superpoints and "snap" not in data:
+            data = dict(data, snap={})
         cfg = ProposalConfig.from_overrides(data)
         with torch.no_grad():
             self._set_cloud()
             prop = self.predictor.generate_masks(cfg)[0]
         return prop, {"labels": prop.labels.cpu().numpy().astype(int).tolist(), "num_masks": int(len(prop)), "scores": prop.score.cpu().numpy().astype(float).tolist()}
+
+    def superpoints(self, data: dict) -> dict:
+        """The geometric over-segmentation of the loaded cloud: {"config": {SuperpointConfig fields}} (optional) -> {"labels": [N ints, -1 = a point
+        without a cell], "num_superpoints": S} (predictor.superpoints: small, roughly planar patches grown from the surface normals).  An unknown
+        field or a bad value is a 400.  The click state of /segment is not touched."""
+        from .superpoints import SuperpointConfig
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/superpoints before a point cloud was set")
+            if not isinstance(data, dict) or set(data) - {"config"} or not isinstance(data.get("config", {}), dict):
+                raise ValueError('/superpoints takes {"config": {...}} (or nothing)')
+            try:
+                cfg = SuperpointConfig(**data.get("config", {})).validate()
+            except TypeError as e:
+                raise ValueError(f"bad SuperpointConfig: {e}") from None
+            with torch.no_grad():
+                self._set_cloud()
+                sp = self.predictor.superpoints(cfg)
+            return {"labels": sp.labels.cpu().numpy().astype(int).tolist(), "num_superpoints": int(sp.num)}
 
     def instances(self, data: dict) -> dict:
         """/segment_all plus where every kept mask is: "boxes" = one {center, half, axes (rows), aabb_lo, aabb_hi, count, mean_rgb} per mask, in the
@@ -606,7 +633,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
                       "/view": lambda: session.render_view(data), "/click_pixel": lambda: session.click_pixel(data),
                       "/frames": lambda: session.set_frames(data), "/fuse_labels": lambda: session.fuse_labels(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
-                      "/instances": lambda: session.instances(data), "/crop/selection": lambda: session.crop_selection(data),
+                      "/instances": lambda: session.instances(data), "/superpoints": lambda: session.superpoints(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}
             fn = routes.get(self.path)
             if fn is None:
@@ -642,6 +669,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--smooth-edges", action="store_true",
                     help="with --working-points or under /crop: blend each loaded point's mask value from the three nearest working points (smooth mask edges) "
                          "instead of copying its voxel's")
+    ap.add_argument("--snap-superpoints", action="store_true",
+                    help="/segment_all and /instances: snap every proposal to whole superpoints (planar patches grown from the surface normals)")
     return ap
 
 
@@ -650,7 +679,8 @@ def main():
     from .predictor import PointSAMPredictor
     pred = PointSAMPredictor.from_config(args.config, args.ckpt, precision=args.precision)
     srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points,
-                            clean_min_points=args.clean_min_points, crop_points=args.crop_points, smooth_edges=args.smooth_edges), args.host, args.port)
+                            clean_min_points=args.clean_min_points, crop_points=args.crop_points, smooth_edges=args.smooth_edges,
+                            snap_superpoints=args.snap_superpoints), args.host, args.port)
     print(f"Point-SAM demo back end on http://{args.host}:{args.port}")
     srv.serve_forever()
 

@@ -5,6 +5,7 @@ libpointsam_hip.so launched on ``torch.cuda.current_stream()``.  Inputs must be 
 tensors; there is no CPU path.
 """
 import ctypes
+import math
 import torch
 
 from . import _lib
@@ -2207,3 +2208,111 @@ def mask_extents(xyz: torch.Tensor, bits: torch.Tensor, origin: torch.Tensor, ax
     check(L.psam_instance_extents(xyz.data_ptr(), bits.data_ptr(), K, N, origin.data_ptr(), _p(axes), lo.data_ptr(), hi.data_ptr(), r2max.data_ptr(),
                                   ws.data_ptr(), ws.numel() * 8, _stream()), "psam_instance_extents")
     return lo, hi, r2max
+
+
+# ------------------------------------------------------------------------------------------ normals and superpoints (csrc/normals.hip, csrc/superpoints.hip)
+def _superpoint_ws(nbytes: int, dev, what: str):
+    if nbytes == 0:
+        raise ValueError(f"{what}: the shape is outside what the kernels are built for (K <= 65535 rows per call, N <= 2^28, V <= N, S <= N)")
+    return torch.empty(nbytes // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+
+
+def _superpoint_int(value, lo: int, hi: int, what: str) -> int:
+    if isinstance(value, bool) or not isinstance(value, int) or not lo <= value <= hi:
+        raise ValueError(f"{what} must be an integer in {lo} .. {hi}, got {value!r}")
+    return value
+
+
+def voxel_normals(xyz: torch.Tensor, inv: torch.Tensor, nbr: torch.Tensor, min_points: int = 5, viewpoint=None, scatter: bool = False):
+    """xyz [N, 3] (or [1, N, 3]) f32 in [-1, 1], inv [N] int64, nbr [V, 26] int32 (voxel_downsample / region_neighbors at origin -1) ->
+    (count [V] int32, normal [V, 3] f32, curvature [V] f32, scatter [V, 6] f64 or None) per occupied voxel, over the points of the voxel and of its
+    26 neighbours: their number, the unit eigenvector of the smallest eigenvalue of the exact integer scatter matrix S = n P - s s^T of the
+    fixed-point coordinates floor(p 2^20) + 2^20, and l0 / (l0 + l1 + l2).  A voxel with count < min_points gets (0, 0, 0) and 0.  Sign: the
+    component of largest magnitude is positive (ties: the lowest axis), or with viewpoint (three numbers) n . (viewpoint - mean) >= 0.  scatter: also
+    return S (xx, xy, xz, yy, yz, zz).  Identical bits from run to run and for any order of the points.  No host synchronisation."""
+    if xyz.dim() == 3 and xyz.shape[0] == 1:
+        xyz = xyz[0]
+    _chk(xyz, name="xyz")
+    N, V = _region_graph_chk(inv, nbr, "voxel_normals")
+    if xyz.dim() != 2 or tuple(xyz.shape) != (N, 3):
+        raise ValueError(f"voxel_normals: xyz must be [{N}, 3] like inv, got {tuple(xyz.shape)}")
+    if not (xyz.device == inv.device == nbr.device):
+        raise ValueError(f"voxel_normals: xyz is on {xyz.device}, inv on {inv.device}, nbr on {nbr.device}")
+    min_points = _superpoint_int(min_points, 1, 2 ** 31 - 1, "voxel_normals: min_points")
+    view = None
+    if viewpoint is not None:
+        w = [float(c) for c in (viewpoint.tolist() if isinstance(viewpoint, torch.Tensor) else viewpoint)]
+        if len(w) != 3 or not all(math.isfinite(c) for c in w):
+            raise ValueError(f"voxel_normals: viewpoint must be three finite numbers, got {viewpoint!r}")
+        view = (ctypes.c_float * 3)(*w)
+    L = _lib.load()
+    ws = _superpoint_ws(L.psam_normals_voxel_workspace_bytes(N, V), xyz.device, "voxel_normals")
+    count = torch.empty(V, dtype=torch.int32, device=xyz.device)
+    normal = torch.empty(V, 3, dtype=torch.float32, device=xyz.device)
+    curvature = torch.empty(V, dtype=torch.float32, device=xyz.device)
+    S = torch.empty(V, 6, dtype=torch.float64, device=xyz.device) if scatter else None
+    check(L.psam_normals_voxel(xyz.data_ptr(), inv.data_ptr(), nbr.data_ptr(), N, V, min_points, ctypes.addressof(view) if view is not None else None,
+                               count.data_ptr(), _p(S), normal.data_ptr(), curvature.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()),
+          "psam_normals_voxel")
+    return count, normal, curvature, S
+
+
+def superpoint_labels(inv: torch.Tensor, nbr: torch.Tensor, count: torch.Tensor, normal: torch.Tensor, curvature: torch.Tensor, cos_angle: float,
+                      max_curvature: float, min_points: int = 5, min_size: int = 0, absorb_rounds: int = 2):
+    """inv [N] int64, nbr [V, 26] int32, and voxel_normals' count [V] int32, normal [V, 3] f32, curvature [V] f32 ->
+    (voxel_label [V], point_label [N], size [V]: the first S entries, zeros behind them; num [1] = S), all int32 on the device.  Touching voxels join when
+    both have count >= min_points and curvature <= max_curvature and |n . n'| >= cos_angle (fp64, (x x' + y y') + z z'); then, absorb_rounds times,
+    a voxel of a superpoint below min_size points goes to the neighbouring superpoint of at least min_size with the most parallel normal (ties: the
+    lower label); the labels in use are renumbered 0 .. S - 1 in the order of their lowest voxel rank.  A point without a cell gets -1.  Exact and
+    identical from run to run.  No host synchronisation."""
+    N, V = _region_graph_chk(inv, nbr, "superpoint_labels")
+    _chk(count, torch.int32, "count"); _chk(normal, name="normal"); _chk(curvature, name="curvature")
+    if tuple(count.shape) != (V,) or tuple(normal.shape) != (V, 3) or tuple(curvature.shape) != (V,):
+        raise ValueError(f"superpoint_labels: count, normal, curvature must be [{V}], [{V}, 3], [{V}], got {tuple(count.shape)}, {tuple(normal.shape)}, "
+                         f"{tuple(curvature.shape)}")
+    if not (inv.device == nbr.device == count.device == normal.device == curvature.device):
+        raise ValueError("superpoint_labels: every tensor must be on the same device")
+    min_points = _superpoint_int(min_points, 1, 2 ** 31 - 1, "superpoint_labels: min_points")
+    min_size = _superpoint_int(min_size, 0, 2 ** 31 - 1, "superpoint_labels: min_size")
+    absorb_rounds = _superpoint_int(absorb_rounds, 0, 64, "superpoint_labels: absorb_rounds")
+    cos_angle, max_curvature = float(cos_angle), float(max_curvature)
+    if not -1.0 <= cos_angle <= 1.0 or not 0.0 <= max_curvature < float("inf"):
+        raise ValueError(f"superpoint_labels: need cos_angle in [-1, 1] and a finite max_curvature >= 0, got {cos_angle!r} and {max_curvature!r}")
+    L = _lib.load()
+    ws = _superpoint_ws(L.psam_superpoints_workspace_bytes(N, V), inv.device, "superpoint_labels")
+    voxel_label = torch.empty(V, dtype=torch.int32, device=inv.device)
+    point_label = torch.empty(N, dtype=torch.int32, device=inv.device)
+    size = torch.empty(V, dtype=torch.int32, device=inv.device)
+    num = torch.empty(1, dtype=torch.int32, device=inv.device)
+    check(L.psam_superpoints(inv.data_ptr(), nbr.data_ptr(), count.data_ptr(), normal.data_ptr(), curvature.data_ptr(), N, V, min_points, max_curvature,
+                             cos_angle, min_size, absorb_rounds, voxel_label.data_ptr(), point_label.data_ptr(), size.data_ptr(), num.data_ptr(),
+                             ws.data_ptr(), ws.numel() * 8, _stream()), "psam_superpoints")
+    return voxel_label, point_label, size, num
+
+
+def superpoint_snap_workspace_bytes(K: int, N: int, S: int) -> int:
+    return _lib.load().psam_superpoint_snap_workspace_bytes(K, N, S)
+
+
+def superpoint_snap(bits: torch.Tensor, point_label: torch.Tensor, size: torch.Tensor, q16: int):
+    """bits [K, W] int64 words (mask_pack's layout), point_label [N] int32, size [S] int32 (superpoint_labels', cut to S) ->
+    (bits_out [K, W] int64, area [K] int32, changed [K] uint8): bit i of row k is set iff point i has a label and the row holds more than
+    q16 / 65536 of its superpoint's points, cnt * 65536 > q16 * size in integers.  q16 = 0: any touch; 32768: a strict majority."""
+    _chk(bits, torch.int64, "bits"); _chk(point_label, torch.int32, "point_label"); _chk(size, torch.int32, "size")
+    if point_label.dim() != 1 or size.dim() != 1 or point_label.numel() < 1 or size.numel() < 1:
+        raise ValueError(f"superpoint_snap: point_label must be [N] and size [S], got {tuple(point_label.shape)} and {tuple(size.shape)}")
+    N, S = point_label.numel(), size.numel()
+    if bits.dim() != 2 or bits.shape[0] < 1 or bits.shape[1] != mask_words(N):
+        raise ValueError(f"superpoint_snap: bits {tuple(bits.shape)} for N = {N}")
+    if not (bits.device == point_label.device == size.device):
+        raise ValueError(f"superpoint_snap: bits is on {bits.device}, point_label on {point_label.device}, size on {size.device}")
+    q16 = _superpoint_int(q16, 0, 65535, "superpoint_snap: q16")
+    K = bits.shape[0]
+    L = _lib.load()
+    ws = _superpoint_ws(L.psam_superpoint_snap_workspace_bytes(K, N, S), bits.device, "superpoint_snap")
+    out = torch.empty_like(bits)
+    area = torch.empty(K, dtype=torch.int32, device=bits.device)
+    changed = torch.empty(K, dtype=torch.uint8, device=bits.device)
+    check(L.psam_superpoint_snap(bits.data_ptr(), point_label.data_ptr(), size.data_ptr(), K, N, S, q16, out.data_ptr(), area.data_ptr(),
+                                 changed.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_superpoint_snap")
+    return out, area, changed

@@ -44,6 +44,7 @@ class PointSAMPredictor:
         self._crop_smooth = False       # the same for the active crop (set_crop(smooth=None) takes the scene's setting)
         self._scene_plan = _UNBUILT     # scene.InterpPlan of the cached scene (None: nothing to blend), built by the first predict that needs it
         self._graphs = None             # clean_masks(): (key, [regions.PointGraph per cloud]) of the cached cloud and voxel settings
+        self._superpoints = (None, {})  # superpoints(): (the cloud's key, {(cloud, settings): PointGraph or Superpoints}) -- dropped with the cloud
 
     @classmethod
     def from_config(cls, name: str, ckpt_path: str = None, num_groups: int = None, group_size: int = None, seed: int = 42,
@@ -483,6 +484,55 @@ class PointSAMPredictor:
         xyz, rgb = self._geometry_cloud("mask_geometry", cloud)
         bits = self._geometry_bits(masks, xyz.shape[0], "mask_geometry", "the scan" if self.scene is not None else "the cloud")
         return mask_geometry(xyz.contiguous(), bits, rgb.contiguous(), oriented)
+
+    # -- normals and superpoints (point_sam_amd/superpoints.py) -----------------------------------------------------
+    def _superpoint_cache(self):
+        if self._superpoints[0] != self._key:                         # another cloud since: set_pointcloud / set_scene / set_frames
+            self._superpoints = (self._key, {})
+        return self._superpoints[1]
+
+    def _superpoint_graph(self, what: str, cfg, cloud: int):
+        """(xyz [N, 3], its regions.PointGraph at cfg's voxel settings) for the cloud the user gave, the graph cached with the cloud."""
+        from .regions import build_graph
+        from .superpoints import SuperpointConfig
+        if cfg is not None and not isinstance(cfg, SuperpointConfig):
+            raise TypeError(f"{what}: cfg must be a SuperpointConfig, got {type(cfg).__name__}")
+        cfg = (cfg or SuperpointConfig()).validate()
+        xyz = self._geometry_cloud(what, cloud)[0].contiguous()
+        cache, key = self._superpoint_cache(), ("graph", 0 if self.scene is not None else cloud, cfg.voxel_size, cfg.points_per_voxel)
+        if key not in cache:
+            cache[key] = build_graph(xyz, cfg.voxel_size, cfg.points_per_voxel)
+        return cfg, xyz, cache[key]
+
+    @torch.no_grad()
+    def point_normals(self, viewpoint=None, cfg=None, cloud: int = 0):
+        """(normal [N, 3] f32, curvature [N] f32) per point of the cloud the user gave (the scan after set_scene): the unit normal of the point's
+        voxel neighbourhood, (0, 0, 0) where it holds fewer than ``cfg.min_points`` points, and the surface variation l0 / (l0 + l1 + l2).
+        viewpoint: three numbers in the cloud's coordinates that every normal should face; None: the component of largest magnitude is positive.
+        cfg: a `superpoints.SuperpointConfig` (its voxel settings and min_points count here)."""
+        from .superpoints import estimate_normals
+        cfg, xyz, graph = self._superpoint_graph("point_normals", cfg, cloud)
+        return estimate_normals(graph, xyz, cfg, viewpoint).per_point()
+
+    @torch.no_grad()
+    def superpoints(self, cfg=None, cloud: int = 0):
+        """The `superpoints.Superpoints` of the cloud the user gave (the scan after set_scene, at its full width): small, roughly planar patches
+        grown from the normals.  Cached per configuration until the next set_pointcloud, set_scene or set_frames of another cloud."""
+        from .superpoints import build_superpoints
+        cfg, xyz, graph = self._superpoint_graph("superpoints", cfg, cloud)
+        cache, key = self._superpoint_cache(), ("superpoints", 0 if self.scene is not None else cloud) + cfg.key()
+        if key not in cache:
+            cache[key] = build_superpoints(graph, xyz, cfg)
+        return cache[key]
+
+    @torch.no_grad()
+    def snap_masks(self, masks, cfg=None, min_fraction: float = 0.5, cloud: int = 0):
+        """Masks snapped to whole superpoints: -> (bits [k, W] int64, area [k] int32, changed [k] uint8), every row the union of the superpoints of
+        which it held more than ``min_fraction``.  masks: a `Proposals` or packed bits [k, W] of the width `mask_geometry` takes."""
+        from .superpoints import snap_bits
+        sp = self.superpoints(cfg, cloud)
+        bits = self._geometry_bits(masks, sp.labels.numel(), "snap_masks", "the scan" if self.scene is not None else "the cloud")
+        return snap_bits(sp, bits, min_fraction)
 
     @torch.no_grad()
     def set_crop_to_mask(self, bits_row, margin: float = 0.1, voxel_size: float = None, max_points: int = None, smooth: bool = None):

@@ -33,7 +33,11 @@ class ProposalConfig:
     ``min_region_points`` > 0 (SAM's ``min_mask_region_area``): every candidate that passes the score and stability cuts is cleaned before the area
     filter and the suppression -- complement components (holes) with fewer points are filled, then mask components (islands) with fewer points are
     removed, the largest always kept (point_sam_amd/regions.py).  ``region_voxel_size`` is the cell size of the neighbourhood graph, 0 = chosen so that
-    a voxel holds ``region_points_per_voxel`` points on average: a geometric rule that has NOT been tuned on real data either."""
+    a voxel holds ``region_points_per_voxel`` points on average: a geometric rule that has NOT been tuned on real data either.
+
+    ``snap``: a `superpoints.SuperpointConfig` (or, in from_overrides, a dict of its fields) -- after the clean-up and before the area filter and the
+    suppression every candidate becomes the union of the superpoints of which it holds a strict majority (point_sam_amd/superpoints.py).  None: off,
+    nothing is built."""
     num_prompts: int = 1024        # FPS-sampled prompt points per cloud
     prompt_chunk: int = 64         # prompts per decode() call and cloud
     mask_threshold: float = 0.0
@@ -46,8 +50,14 @@ class ProposalConfig:
     min_region_points: int = 0     # 0 = no clean-up, no graph is built
     region_voxel_size: float = 0.0  # 0 = automatic
     region_points_per_voxel: int = 4
+    snap: Optional["SuperpointConfig"] = None      # None = no snapping, no superpoints are built
 
     def validate(self) -> "ProposalConfig":
+        if self.snap is not None:
+            from .superpoints import SuperpointConfig
+            if not isinstance(self.snap, SuperpointConfig):
+                raise ValueError(f"ProposalConfig.snap must be None or a SuperpointConfig, got {self.snap!r}")
+            self.snap.validate()
         for name in ("num_prompts", "prompt_chunk", "min_points", "min_region_points", "region_points_per_voxel"):
             v = getattr(self, name)
             if isinstance(v, bool) or not isinstance(v, int):
@@ -75,6 +85,12 @@ class ProposalConfig:
         unknown = sorted(set(overrides) - names)
         if unknown:
             raise ValueError(f"unknown ProposalConfig field(s) {unknown}; known: {sorted(names)}")
+        if isinstance(overrides.get("snap"), dict):
+            from .superpoints import SuperpointConfig
+            try:
+                overrides = dict(overrides, snap=SuperpointConfig(**overrides["snap"]))
+            except TypeError as e:
+                raise ValueError(f"ProposalConfig.snap: {e}") from None
         return cls(**overrides).validate()
 
 
@@ -92,7 +108,7 @@ class DeviceProposals:
     valid: torch.Tensor         # [K] uint8
     keep: torch.Tensor          # [K] uint8
     labels: torch.Tensor        # [N] int32
-    changed: Optional[torch.Tensor] = None      # [K] uint8: the clean-up altered the row; None with min_region_points == 0 (bits / area are then raw)
+    changed: Optional[torch.Tensor] = None      # [K] uint8: the clean-up or the snap altered the row; None with min_region_points == 0 and no snap (bits / area are then raw)
 
 
 @dataclass
@@ -109,7 +125,7 @@ class Proposals:
     # [k] int64, multi-crop proposals only: the crop a mask came from, -1 = the whole scene (merge_proposals).  Keyword-only, so the positional
     # constructor still ends with `changed`
     crop_index: Optional[torch.Tensor] = dataclasses.field(default=None, kw_only=True)
-    changed: Optional[torch.Tensor] = None      # [k] uint8: the clean-up altered the mask; None with min_region_points == 0
+    changed: Optional[torch.Tensor] = None      # [k] uint8: the clean-up or the snap altered the mask; None with min_region_points == 0 and no snap
 
     def __len__(self) -> int:
         return self.bits.shape[0]
@@ -208,12 +224,30 @@ def build_region_graphs(state, cfg: ProposalConfig):
 
 
 @torch.no_grad()
-def propose_on_device(model, state, cfg: ProposalConfig, graphs=None) -> List[DeviceProposals]:
+def build_snap_superpoints(state, cfg: ProposalConfig):
+    """One `superpoints.Superpoints` per cloud of the state (None with cfg.snap None).  Synchronises with the host: voxel and superpoint counts."""
+    if cfg.snap is None:
+        return None
+    from .regions import build_graph
+    from .superpoints import build_superpoints
+    out = []
+    for b in range(state.coords.shape[0]):
+        xyz = state.coords[b].contiguous()
+        out.append(build_superpoints(build_graph(xyz, cfg.snap.voxel_size, cfg.snap.points_per_voxel), xyz, cfg.snap))
+    return out
+
+
+@torch.no_grad()
+def propose_on_device(model, state, cfg: ProposalConfig, graphs=None, superpoints=None) -> List[DeviceProposals]:
     """Every kernel of generate_proposals, no host synchronisation: capturable in a HIP graph.  graphs: build_region_graphs(state, cfg), needed
-    (ValueError without) when cfg.min_region_points > 0 -- building them reads voxel counts on the host, so it is not done here."""
+    (ValueError without) when cfg.min_region_points > 0 -- building them reads voxel counts on the host, so it is not done here.  superpoints:
+    build_snap_superpoints(state, cfg), needed likewise when cfg.snap is set."""
     cfg.validate()
     coords = state.coords
     B, N, _ = coords.shape
+    if cfg.snap is not None and (superpoints is None or len(superpoints) != B):
+        raise ValueError(f"snap needs the superpoints of every cloud (build_snap_superpoints): got "
+                         f"{'none' if superpoints is None else len(superpoints)} for {B} cloud(s)")
     if cfg.min_region_points > 0 and (graphs is None or len(graphs) != B):
         raise ValueError(f"min_region_points = {cfg.min_region_points} needs one region graph per cloud (build_region_graphs): got "
                          f"{'none' if graphs is None else len(graphs)} for {B} cloud(s)")
@@ -251,6 +285,10 @@ def propose_on_device(model, state, cfg: ProposalConfig, graphs=None) -> List[De
             select = ops.mask_valid(area, area_hi, area_lo, score, N, 0, 2.0, cfg.pred_iou_thresh, cfg.stability_thresh)
             bits, area, changed = clean_bits(graphs[b], bits, select=select,
                                              cfg=RegionConfig(min_island=cfg.min_region_points, min_hole=cfg.min_region_points))
+        if cfg.snap is not None:
+            from .superpoints import snap_bits
+            bits, area, snapped = snap_bits(superpoints[b], bits)
+            changed = snapped if changed is None else changed | snapped
         valid = ops.mask_valid(area, area_hi, area_lo, score, N, cfg.min_points, cfg.max_area_frac, cfg.pred_iou_thresh, cfg.stability_thresh)
         inter = ops.mask_intersections(bits)
         keep = ops.mask_nms(order, valid, area, inter, cfg.nms_thresh)
@@ -272,7 +310,7 @@ def generate_proposals(model, state, cfg: ProposalConfig = None) -> List[Proposa
     """One `Proposals` per cloud of the encoder state.  Peak memory: one chunk of logits ([B * prompt_chunk, 3, N] f32), K * N / 8 bytes of
     bits and the K x K int32 intersection matrix per cloud (K = 3 * num_prompts) -- never K * N floats."""
     cfg = (cfg or ProposalConfig()).validate()
-    dev = propose_on_device(model, state, cfg, build_region_graphs(state, cfg))
+    dev = propose_on_device(model, state, cfg, build_region_graphs(state, cfg), build_snap_superpoints(state, cfg))
     out = [compact(d) for d in dev]
     model.check_coordinate_range()
     return out

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import normal_cases as NC
 import region_reference as R
 import superpoint_reference as SP
 from point_sam_amd import _lib
@@ -144,6 +145,116 @@ def test_snap_reference_thresholds():
     assert area.tolist() == [0, 3, 0] and changed.tolist() == [1, 1, 0]
     out, _, _ = SP.snap(np.ones((1, 10), dtype=bool), label, size, 65535)      # a full row keeps every labelled point even at the highest threshold
     assert out[0].tolist() == [1, 1, 1, 1, 1, 1, 1, 0, 1, 1]
+
+
+# ------------------------------------------------------------------------------------------------ the cases of tests/normal_cases.py
+def test_committed_triples_have_their_pattern_and_the_search_finds_them():
+    for table, m_bits in ((NC.HIGH, (12, 14)), (NC.LOW, (7, 10))):
+        assert NC.search(m_bits) == {name: triple for name, triple, _ in table}
+        for name, (m, dx, dy), bits in table:
+            x = m * m * dx * dy
+            assert x.bit_length() == bits and (bits > 64) == (table is NC.HIGH) and 2 * m <= 1 << 15
+            assert NC.pattern(x) == NC.pattern(-x) == name
+            # the pattern, spelled out once more on the binary digits: 53 kept, then the half bit, ten more to the end of the top 64, the rest
+            digits = bin(x)[2:]
+            kept, half, mid, rest = digits[:53], digits[53], digits[54:64], digits[64:]
+            if name.startswith("tie"):
+                assert half == "1" and "1" not in mid + rest and kept[-1] == ("1" if name == "tie_odd" else "0")
+                assert float(x) == float((int(kept, 2) + (name == "tie_odd")) << (bits - 53))
+            elif name == "half_sticky":
+                assert half == "1" and "1" not in mid and "1" in rest and float(x) == float((int(kept, 2) + 1) << (bits - 53)), "up"
+            else:
+                assert half == "0" and "0" not in mid and "1" in rest and float(x) == float(int(kept, 2) << (bits - 53)), "down"
+                if name == "below_half_odd":
+                    assert kept[-1] == "1" and rest[0] == "1"
+    assert [n for n, _, _ in NC.HIGH] == ["tie_even", "tie_odd", "below_half", "below_half_odd", "half_sticky"]
+    assert [n for n, _, _ in NC.LOW] == ["tie_even", "tie_odd"]
+
+
+def test_two_cluster_puts_the_product_into_the_scatter_matrix():
+    cases = NC.rounding_cases()
+    assert len(cases) == 2 * (len(NC.HIGH) + len(NC.LOW))
+    for name, (m, d) in cases.items():
+        xyz, inv, nbr = NC.two_cluster(m, d)
+        assert xyz.shape == (2 * m, 3) and xyz.dtype == f32 and len(np.unique(xyz, axis=0)) == 2
+        assert not np.array_equal(xyz[:m], np.tile(xyz[0], (m, 1))), "shuffled"
+        count, s, S = SP.scatter(xyz, inv, nbr)
+        assert count.tolist() == [2 * m] and S == [NC.two_cluster_scatter(m, d)] == [[m * m * d[a] * d[b] for a, b in SP.PAIRS]]
+        assert (S[0][1] < 0) == name.endswith("_neg") and NC.pattern(S[0][1]) == name.split("_", 1)[1].replace("_neg", "")
+
+
+def test_wrong_conversions_are_told_apart_by_the_committed_cases():
+    """Stands in for running a mutated kernel: each wrong int -> fp64 conversion differs from float(exact) on the xy entry of a committed case, for
+    both signs, and in both branches of the conversion where its mistake can show (up to 64 bits only the ties exist, and the two conversions that
+    go through 64 bits are exact there)."""
+    xy = {name: NC.two_cluster_scatter(m, d)[1] for name, (m, d) in NC.rounding_cases().items()}
+    for x in xy.values():                                  # none of them is wrong about a value fp64 holds
+        r = abs(x).bit_length() - 53
+        assert all(f(x >> r << r) == float(x >> r << r) == (x >> r << r) for f in NC.WRONG.values())
+    caught = {n: {name for name, x in xy.items() if f(x) != float(x)} for n, f in NC.WRONG.items()}
+    assert caught["truncating"] >= {"high_tie_odd", "high_tie_odd_neg", "high_half_sticky", "low_tie_odd", "low_tie_odd_neg"}
+    assert caught["half_up"] == {"high_tie_even", "high_tie_even_neg", "low_tie_even", "low_tie_even_neg"}
+    assert caught["twice"] >= {"high_below_half_odd", "high_below_half_odd_neg"} and not any(n.startswith("low") for n in caught["twice"])
+    assert caught["without_sticky"] == {"high_half_sticky", "high_half_sticky_neg"}
+    for x in xy.values():                                  # and a conversion of the magnitude is what the reference does to a negative value
+        assert float(-x) == -float(x)
+
+
+def _exact_scatter(name):
+    xyz, h = NC.cloud_points(name)
+    xyz = np.ascontiguousarray(xyz, dtype=f32)
+    g = R.Graph(xyz, h)
+    return g, SP.scatter(xyz, g.inv, g.nbr)
+
+
+@pytest.mark.parametrize("name", ["wide", "wide18"])
+def test_wide_clouds_need_more_than_64_bits_and_round(name):
+    g, (count, s, S) = _exact_scatter(name)
+    assert len(S) == 8 and count.tolist() == [NC.WIDE[name]] * 8, "every neighbourhood is the whole cloud"
+    largest, above, rounded = NC.scatter_stats(S)
+    assert above > 0 and rounded > 0
+    assert (largest, above, rounded) == NC.WIDE_COUNTS[name]
+    if name == "wide18":
+        assert sorted(abs(x).bit_length() for x in S[0])[0] == 64, "one entry fills the low word exactly: the last value of the branch without a shift"
+
+
+def test_the_older_clouds_never_round():
+    """Every scatter entry of the clouds test_count_and_scatter_equal_the_exact_integers runs is an integer fp64 holds: that test sees no rounding
+    at all, which is why the rounding cases above exist.  Should this change, that test's equality still holds -- this only keeps the record."""
+    for name in ("box", "sphere", "uniform6000", "grid", "edge", "duplicates", "heavy", "small63", "small65", "small4"):
+        _, (count, s, S) = _exact_scatter(name)
+        largest, above, rounded = NC.scatter_stats(S)
+        assert largest <= 53 and above == 0 and rounded == 0, name
+
+
+@pytest.mark.parametrize("name", sorted(NC.degenerate_fixed()))
+def test_degenerate_neighbourhoods_have_the_stated_spectrum(name):
+    """eigvalsh of float(S).  "Zero" and "equal" mean to 1e-14 l2: LAPACK's eigenvalues carry an error of a small multiple of 2^-53 |M|."""
+    q, spectrum = NC.degenerate_fixed()[name]
+    xyz, inv, nbr = NC.degenerate(name)
+    count, s, S = SP.scatter(xyz, inv, nbr)
+    assert count.tolist() == [len(q)] and len(q) >= 5
+    pts = [tuple(int(c) for c in p) for p in q]            # S once more, from the integers the case was built of
+    assert S[0] == [len(pts) * sum(p[a] * p[b] for p in pts) - sum(p[a] for p in pts) * sum(p[b] for p in pts) for a, b in SP.PAIRS]
+    assert all(float(x) == x for x in S[0]), "small cases: the eigen solve's input is exact"
+    lam = SP.eigen(count, S)[2][0]
+    top, tol = lam[2], 1e-14 * lam[2]
+    for i, tok in enumerate(spectrum):
+        if tok == "0":
+            assert abs(lam[i]) <= tol
+        elif tok == "e":
+            assert tol < lam[i] <= 1e-9 * top
+        else:
+            assert lam[i] > 0.1 * top
+        for j in range(i):
+            if spectrum[j][0] != tok[0]:
+                assert lam[i] - lam[j] > 0.1 * top
+            elif tok[0] not in "0e":
+                assert tol < lam[i] - lam[j] <= 0.01 * lam[i] if "~" in tok + spectrum[j] else abs(lam[i] - lam[j]) <= tol
+    if name == "coincident":
+        assert S[0] == [0] * 6
+    if name == "cubic":
+        assert S[0][1] == S[0][2] == S[0][4] == 0 and S[0][0] == S[0][3] == S[0][5] > 0
 
 
 # ------------------------------------------------------------------------------------------------ configuration and chunking

@@ -800,6 +800,29 @@ int32_t psam_align_step(const float* src, int32_t N, const void* index_ws, size_
                         const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest, double* sums, void* ws,
                         size_t ws_bytes, psam_stream_t stream);
 
+/* The score of a global pose search (point_sam_amd/align.py: search): under each of P poses, the number of queries that land on the indexed cloud.
+ * One launch for all P poses; the call allocates nothing, needs no workspace and does not synchronise with the host.
+ *
+ * src, N, index_ws, origin, inv_h, r2, qry [M, 3]: psam_align_step's.  poses [P, 12] f32 in DEVICE memory, each row-major 3 x 4, query frame ->
+ * source frame.  counts [P] int32 on the device:
+ *     counts[p]         the number of queries i with AT LEAST ONE candidate under pose p
+ *     posed coordinate  p_a = ((P[a][0] x + P[a][1] y) + P[a][2] z) + P[a][3]: psam_transfer_plan's, bit for bit
+ *     candidates        psam_align_step's: the indexed sources j of the 27 cells around cell(p) with q_j = (dx dx + dy dy) + dz dz <= r2, d = p - src[j],
+ *                       in the same fp32 arithmetic; NaN compares false.  The 27-cell set IS the definition, no cell is pruned by a geometric bound.
+ *                       r2 at or below the index's own fl32(r * r); above it the 27 cells truncate the search
+ *     no hit            a query without a cell -- one that is not finite, or whose posed coordinate is not finite or outside [0, 2^21) cells on an axis
+ *   Hence counts[p] == sums[0] of psam_align_step with pose p, the same r2 and no qry_bits, for every p.  Existence needs no order among the
+ *   candidates: the walk visits psam_align_step's cells and chains in the same order under the same step bound and stops at the first hit.  The
+ *   counts are integers added with integer atomics onto words the call itself clears on the stream: exact, and independent of schedule and order.
+ * The poses are in device memory, so this entry CANNOT validate them: the caller does, before the upload (ops.align_score: every entry finite).  A
+ * pose that is not finite yields coordinates that are not finite and a count of 0.
+ * Limits: 0 < N, M <= 2^28, 0 < P <= 2^20.  Every refusal comes before any launch and leaves counts untouched: a null pointer, N, M or P outside its
+ * range, inv_h or r2 not finite and positive, an origin that is not finite: -1; a misaligned pointer (index_ws 16 bytes; src, qry, poses and counts
+ * 4): -2; a short index_ws: -3. */
+#define PSAM_ALIGN_SCORE_POSES 4      /* poses per workgroup: a chunk of the grid (query tiles x pose chunks) */
+int32_t psam_pose_score(const float* src, int32_t N, const void* index_ws, size_t index_ws_bytes, const float* origin, float inv_h, float r2,
+                         const float* qry, int32_t M, const float* poses, int32_t P, int32_t* counts, psam_stream_t stream);
+
 /* ---------------------------------------------------------------- camera views */
 
 /* A picture of a cloud and the way back from it (point_sam_amd/views.py): a z-buffer of point splats, the point under a pixel, packed masks painted

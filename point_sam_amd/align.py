@@ -8,8 +8,15 @@ The sums are over the queries AS GIVEN, so each step solves for the whole pose: 
 
 ICP is a local method: it refines an initial pose (the identity, or odometry) whose error is small against the search radius and the scene's
 structure; it does not search globally.  `Alignment.coverage` and `rms` say how far to trust the answer.
+
+`search` is the global part, for callers without even a rough pose (a room re-scanned from another doorway, an object put down elsewhere): a grid of
+candidate poses (`rotation_grid` x anchors x a translation lattice, `candidate_poses`) is scored on a sample of the queries by ONE launch
+(ops.align_score: per pose the number of sampled queries that land within a radius of a source -- an exact integer), the `keep` best are refined by
+`icp`, and the refinement with the most pairs wins.  The count alone does not decide: a false optimum of a partial overlap can cover as many
+sampled queries as the truth, and only the refinement tells them apart.
 """
 import dataclasses
+import math
 
 import numpy as np
 
@@ -73,7 +80,7 @@ class AlignConfig:
 class Alignment:
     """icp's answer.  pose: 3 x 4 fp64, query frame -> source frame: what transfer_masks / propagate take.  pairs, rms: of the last step whose solve
     succeeded -- its pairs were found under the pose BEFORE that solve, rms is their root mean square distance AFTER it; coverage = pairs / the
-    participating queries that have a cell.  history: (pairs, rms, radius) per step taken."""
+    participating queries that have a cell.  history: (pairs, rms, radius) per step taken.  search: None from icp; from `search` its SearchRecord."""
     pose: np.ndarray
     pairs: int
     coverage: float
@@ -82,6 +89,7 @@ class Alignment:
     converged: bool
     reason: str
     history: list
+    search: object = None
 
 
 def solve_rigid(sums):
@@ -160,3 +168,235 @@ def icp(index, xyz, cfg: AlignConfig, init=None, bits=None, step=None) -> Alignm
             out.converged, out.reason = True, "fixed point" if fixed else "tolerance"
             return out
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the global search
+MAX_POSES = ops.ALIGN_SCORE_MAX_POSES
+GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class SearchConfig:
+    """The grid `search` scores.  rotations: "yaw" (yaw_steps >= 1 turns by 2 pi k / yaw_steps about `up`, three numbers, not all zero), "so3" (`axes`
+    >= 1 directions on the Fibonacci sphere, each with `rolls` >= 1 rolls about it: rotation_grid), or an explicit [R, 3, 3] array of rotation
+    matrices.  anchors: None (the source centroid) or [A, 3] positions in the source frame where the query centroid may land -- e.g. the instance
+    centroids of mask_geometry when an object is looked for.  offsets: g >= 0, the (2 g + 1)^3 translations offset_step * (i, j, k), -g <= i, j, k <=
+    g, tried around each centre match (a partial overlap moves the centroid).  sample >= 1: the most queries scored.  radius: the scoring radius,
+    None: the AlignConfig's; it may not exceed the index's.  keep >= 1: how many of the best-scoring candidates icp refines.
+    rotations x anchors x offsets may not exceed 2^20 poses.  NONE of the defaults has been tuned on real data."""
+    rotations: object = "yaw"
+    yaw_steps: int = 72
+    up: tuple = (0.0, 0.0, 1.0)
+    axes: int = 96
+    rolls: int = 24
+    offsets: int = 0
+    offset_step: float = 0.1
+    anchors: object = None
+    sample: int = 1024
+    radius: float = None
+    keep: int = 8
+
+    def __post_init__(self):
+        def number(v):
+            return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+        def integer(v, lo, hi):
+            return not isinstance(v, bool) and isinstance(v, int) and lo <= v <= hi
+
+        def array(v, tail, what):
+            try:
+                a = np.array(v, dtype=np.float64)
+            except (TypeError, ValueError):
+                a = None
+            if a is None or a.ndim != len(tail) + 1 or a.shape[1:] != tail or not 1 <= len(a) <= MAX_POSES or not np.isfinite(a).all():
+                raise ValueError(f"SearchConfig: {what} must be a finite [n, {', '.join(map(str, tail))}] array with 1 <= n <= 2^20, got {v!r}")
+            a.setflags(write=False)
+            return a
+        if isinstance(self.rotations, str):
+            if self.rotations not in ("yaw", "so3"):
+                raise ValueError(f'SearchConfig: rotations must be "yaw", "so3" or an [R, 3, 3] array, got {self.rotations!r}')
+        else:
+            Rs = array(self.rotations, (3, 3), "rotations")
+            if np.abs(Rs @ Rs.transpose(0, 2, 1) - np.eye(3)).max() > 1e-6 or np.abs(np.linalg.det(Rs) - 1.0).max() > 1e-6:
+                raise ValueError("SearchConfig: every matrix of rotations must be orthonormal with determinant +1 (to 1e-6)")
+            object.__setattr__(self, "rotations", Rs)
+        for name, hi in (("yaw_steps", MAX_POSES), ("axes", MAX_POSES), ("rolls", MAX_POSES), ("sample", 1 << 28), ("keep", 1024)):
+            if not integer(getattr(self, name), 1, hi):
+                raise ValueError(f"SearchConfig: {name} must be an integer in 1 .. {hi}, got {getattr(self, name)!r}")
+        if not integer(self.offsets, 0, 16):
+            raise ValueError(f"SearchConfig: offsets must be an integer in 0 .. 16, got {self.offsets!r}")
+        if not number(self.offset_step) or not self.offset_step > 0:
+            raise ValueError(f"SearchConfig: offset_step must be a finite positive number, got {self.offset_step!r}")
+        up = self.up
+        if not isinstance(up, (tuple, list)) or len(up) != 3 or not all(number(v) for v in up) or not any(v != 0 for v in up):
+            raise ValueError(f"SearchConfig: up must be three finite numbers, not all zero, got {up!r}")
+        object.__setattr__(self, "up", tuple(float(v) for v in up))
+        if self.anchors is not None:
+            object.__setattr__(self, "anchors", array(self.anchors, (3,), "anchors"))
+        if self.radius is not None:
+            if not number(self.radius):
+                raise ValueError(f"SearchConfig: radius must be None or a finite positive number, got {self.radius!r}")
+            ops.transfer_radius(self.radius)
+        if self.num_rotations * (1 if self.anchors is None else len(self.anchors)) * (2 * self.offsets + 1) ** 3 > MAX_POSES:
+            raise ValueError(f"SearchConfig: {self.num_rotations} rotations x {1 if self.anchors is None else len(self.anchors)} anchors x "
+                             f"{(2 * self.offsets + 1) ** 3} offsets exceed 2^20 poses")
+
+    @classmethod
+    def from_overrides(cls, data: dict) -> "SearchConfig":
+        """A config from a dict of fields (a request's body; rotations, up and anchors as nested lists): an unknown field is a ValueError, like a bad
+        value."""
+        names = {f.name for f in dataclasses.fields(cls)}
+        if not isinstance(data, dict) or set(data) - names:
+            raise ValueError(f"SearchConfig takes optionally {sorted(names)}, got {sorted(data) if isinstance(data, dict) else data!r}")
+        return cls(**data)
+
+    @property
+    def num_rotations(self) -> int:
+        if isinstance(self.rotations, str):
+            return self.yaw_steps if self.rotations == "yaw" else self.axes * self.rolls
+        return len(self.rotations)
+
+
+@dataclasses.dataclass
+class SearchRecord:
+    """What `search` did.  poses: the candidates scored; sample: the queries they were scored on; candidates: per refined candidate, in the order
+    refined (best count first), dict(pose_index, count, pairs, rms, converged); chosen: the position in `candidates` of the one returned."""
+    poses: int
+    sample: int
+    candidates: list
+    chosen: int
+
+
+def _axis_rotation(axis, angle: float) -> np.ndarray:
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    K = np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return np.eye(3) + math.sin(angle) * K + (1.0 - math.cos(angle)) * (K @ K)
+
+
+def rotation_to(d) -> np.ndarray:
+    """The shortest-arc rotation [3, 3] fp64 that takes +z to the direction d (normalised here): about z x d by the angle between them; for d = -z,
+    where every axis in the xy plane is as short, the half turn about x."""
+    d = np.asarray(d, dtype=np.float64).reshape(3)
+    d = d / np.linalg.norm(d)
+    s2 = d[0] * d[0] + d[1] * d[1]                                                # sin^2 of the angle, |z x d|^2
+    if d[2] < 0 and s2 < 1e-200:
+        return np.diag([1.0, -1.0, -1.0])
+    K = np.array([[0.0, 0.0, d[0]], [0.0, 0.0, d[1]], [-d[0], -d[1], 0.0]])       # the cross-product matrix of v = z x d = (-d_y, d_x, 0)
+    # I + K + K^2 (1 - cos) / sin^2; (1 - cos) / sin^2 = 1 / (1 + cos), each form used where it does not cancel
+    return np.eye(3) + K + (K @ K) * (1.0 / (1.0 + d[2]) if d[2] >= 0 else (1.0 - d[2]) / s2)
+
+
+def rotation_grid(cfg: SearchConfig) -> np.ndarray:
+    """-> [R, 3, 3] fp64.  "yaw": entry k turns by 2 pi k / yaw_steps about `up` (entry 0 is the identity).  "so3": direction k of the Fibonacci
+    sphere is d_k = (s cos(k g), s sin(k g), z_k) with z_k = 1 - (2 k + 1) / axes, s = sqrt(1 - z_k^2), g the golden angle pi (3 - sqrt 5); entry
+    k * rolls + j = rotation_to(d_k) composed with the roll by 2 pi j / rolls about +z (the roll first).  An explicit array: itself."""
+    if not isinstance(cfg, SearchConfig):
+        raise TypeError(f"rotation_grid: cfg must be a SearchConfig, got {type(cfg).__name__}")
+    if not isinstance(cfg.rotations, str):
+        return np.array(cfg.rotations)
+    if cfg.rotations == "yaw":
+        return np.stack([_axis_rotation(cfg.up, 2.0 * math.pi * k / cfg.yaw_steps) for k in range(cfg.yaw_steps)])
+    rolls = [_axis_rotation((0.0, 0.0, 1.0), 2.0 * math.pi * j / cfg.rolls) for j in range(cfg.rolls)]
+    out = np.empty((cfg.axes, cfg.rolls, 3, 3))
+    for k in range(cfg.axes):
+        z = 1.0 - (2 * k + 1) / cfg.axes
+        s = math.sqrt(max(0.0, 1.0 - z * z))
+        tilt = rotation_to((s * math.cos(k * GOLDEN_ANGLE), s * math.sin(k * GOLDEN_ANGLE), z))
+        for j in range(cfg.rolls):
+            out[k, j] = tilt @ rolls[j]
+    return out.reshape(-1, 3, 3)
+
+
+def candidate_poses(cfg: SearchConfig, source_centroid, query_centroid) -> np.ndarray:
+    """-> [P, 3, 4] fp64, query frame -> source frame: for each rotation R of rotation_grid, each anchor c (cfg.anchors, or the source centroid) and
+    each offset o of the lattice, [R | c - R q + o] with q the query centroid -- the pose that turns the queries by R about their centroid and puts
+    it at c + o.  Index = (rotation * anchors + anchor) * offsets + offset; offset = ((k + g) (2 g + 1) + (j + g)) (2 g + 1) + (i + g) for
+    o = offset_step * (i, j, k): x runs fastest."""
+    Rs = rotation_grid(cfg)
+    q = np.asarray(query_centroid, dtype=np.float64).reshape(3)
+    anchors = np.asarray(source_centroid, dtype=np.float64).reshape(1, 3) if cfg.anchors is None else cfg.anchors
+    if not (np.isfinite(q).all() and np.isfinite(anchors).all()):
+        raise ValueError("candidate_poses: the centroids must be finite")
+    g = cfg.offsets
+    steps = np.arange(-g, g + 1, dtype=np.float64) * float(cfg.offset_step)
+    oz, oy, ox = np.meshgrid(steps, steps, steps, indexing="ij")
+    offs = np.stack([ox.reshape(-1), oy.reshape(-1), oz.reshape(-1)], 1)                 # x fastest
+    t = (anchors[None, :, None, :] - (Rs @ q)[:, None, None, :]) + offs[None, None, :, :]  # [R, A, O, 3]
+    out = np.empty(t.shape[:3] + (3, 4))
+    out[..., :3] = Rs[:, None, None]
+    out[..., 3] = t
+    return out.reshape(-1, 3, 4)
+
+
+def _host(a) -> np.ndarray:
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def sample_positions(n: int, sample: int) -> np.ndarray:
+    """Which of n participating queries (in index order) are scored: all of them for n <= sample, else the ones at positions (k n) // sample."""
+    return np.arange(n, dtype=np.int64) if n <= sample else (np.arange(sample, dtype=np.int64) * n) // sample
+
+
+def search(index, xyz, cfg: SearchConfig, icp_cfg: AlignConfig, bits=None, score=None, step=None) -> Alignment:
+    """A pose without a starting pose.  index: ops.transfer_index of the sources at icp_cfg.radius (anything with `src_xyz` when `score` and `step`
+    are stand-ins); xyz [M, 3] the queries; bits: an optional packed row, the queries that take part -> Alignment, its `search` a SearchRecord.
+      1. the queries scored: sample_positions among the participating ones, in index order -- deterministic (with bits, one host read of the row)
+      2. the centroids of the sources and of those queries, in fp64; candidate_poses
+      3. ONE ops.align_score over all candidates at cfg.radius (None: icp_cfg.radius), and one host read of the P counts
+      4. the candidates ordered by (-count, index); the first cfg.keep each refined by icp(index, xyz, icp_cfg, init=pose, bits=bits, step=step)
+      5. the refinement with the most pairs; ties go to the lower rms, then to the earlier candidate.  Where none has a pair, the first one's
+         Alignment (converged=False, its reason says why).
+    score / step: stand-ins for ops.align_score / ops.align_step with their signatures (a reference, a test)."""
+    if not isinstance(cfg, SearchConfig):
+        raise TypeError(f"search: cfg must be a SearchConfig, got {type(cfg).__name__}")
+    if not isinstance(icp_cfg, AlignConfig):
+        raise TypeError(f"search: icp_cfg must be an AlignConfig, got {type(icp_cfg).__name__}")
+    radius = icp_cfg.radius if cfg.radius is None else cfg.radius
+    if radius > icp_cfg.radius:
+        raise ValueError(f"search: the scoring radius {radius} exceeds the AlignConfig's {icp_cfg.radius}, the cell size of the index")
+    score = ops.align_score if score is None else score
+    rows = xyz[0] if len(xyz.shape) == 3 and xyz.shape[0] == 1 else xyz
+    M = rows.shape[0]
+    if bits is None:
+        part = None
+        n = M
+    else:
+        words = _host(bits).reshape(-1).view(np.uint64)
+        part = np.nonzero(((words[:, None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).reshape(-1)[:M])[0]
+        n = len(part)
+    if n == 0:
+        raise ValueError("search: no query takes part")
+    pick = sample_positions(n, cfg.sample)
+    if part is not None:
+        pick = part[pick]
+    if hasattr(rows, "detach"):
+        import torch
+        picked = rows if part is None and n <= cfg.sample else rows.index_select(0, torch.from_numpy(pick).to(rows.device))
+        picked = picked.contiguous()
+        qc = _host(picked.double().mean(0))
+    else:
+        picked = np.ascontiguousarray(np.asarray(rows)[pick])
+        qc = picked.astype(np.float64).mean(0)
+    src = index.src_xyz
+    sc = _host(src.double().mean(0)) if hasattr(src, "detach") else np.asarray(src, dtype=np.float64).mean(0)
+    if not (np.isfinite(qc).all() and np.isfinite(sc).all()):
+        raise ValueError("search: the sources and the scored queries must be finite")
+    poses = candidate_poses(cfg, sc, qc)
+    counts = _host(score(index, picked, poses, radius)).astype(np.int64).reshape(-1)      # the one host read of the scoring
+    if counts.shape != (len(poses),):
+        raise ValueError(f"search: score must return one count per pose, got {counts.shape} for {len(poses)} poses")
+    order = np.lexsort((np.arange(len(poses)), -counts))[:cfg.keep]
+    runs, record = [], SearchRecord(len(poses), len(pick), [], 0)
+    for p in order.tolist():
+        out = icp(index, xyz, icp_cfg, init=poses[p], bits=bits, step=step)
+        runs.append(out)
+        record.candidates.append(dict(pose_index=p, count=int(counts[p]), pairs=out.pairs, rms=out.rms, converged=out.converged))
+    best = 0
+    for k in range(1, len(runs)):
+        a, b = runs[k], runs[best]
+        if a.pairs > b.pairs or (a.pairs == b.pairs and a.pairs > 0 and a.rms < b.rms):
+            best = k
+    record.chosen = best
+    runs[best].search = record
+    return runs[best]

@@ -1,6 +1,6 @@
-// The cell index of a source cloud, shared by transfer.hip (which builds it and plans the 3-NN transfer with it) and align.hip (the nearest source of
-// an ICP step): the workspace layout, the cell of a point and the walk over a query's candidates are one decision and live here once, so both put
-// the same sources in front of a query bit for bit.  The definition and the index's format: transfer.hip's header.  Translation units that include
+// The cell index of a source cloud, shared by transfer.hip (which builds it and plans the 3-NN transfer with it), align.hip (the nearest source of
+// an ICP step) and align_score.hip (whether a posed query has a source in reach at all): the workspace layout, the cell of a point and the walk over
+// a query's candidates are one decision and live here once, so all three put the same sources in front of a query bit for bit.  The definition and the index's format: transfer.hip's header.  Translation units that include
 // this are compiled with -ffp-contract=off -fno-slp-vectorize (point_sam_amd/build.py).
 #pragma once
 #include "common.h"
@@ -67,4 +67,28 @@ __device__ __forceinline__ void transfer_candidates(const TransferIndexView& ix,
             j = ix.next[j];
         }
     }
+}
+
+// Whether the point p in cell (cx, cy, cz) has a candidate at all (align_score.hip): transfer_candidates' walk -- the same 27 cells in the same order,
+// the same q, the same bound on the chain steps -- left at the first source with q <= r2.  True exactly where transfer_candidates would call f at
+// least once: the steps the walk skips come after that call and cannot take it back.
+__device__ __forceinline__ bool transfer_any_candidate(const TransferIndexView& ix, float px, float py, float pz, u64 cx, u64 cy, u64 cz, float r2) {
+#pragma clang fp contract(off)
+    const int64_t lim = (int64_t)1 << VOXEL_AXIS_BITS;
+    int budget = ix.N;                                             // steps along all 27 chains together
+    for (int o = 0; o < 27; ++o) {
+        const int64_t nx = (int64_t)cx + (o % 3 - 1), ny = (int64_t)cy + (o / 3 % 3 - 1), nz = (int64_t)cz + (o / 9 - 1);
+        if (nx < 0 || nx >= lim || ny < 0 || ny >= lim || nz < 0 || nz >= lim) continue;
+        const int slot = voxel_find(ix.keys, ix.capacity, voxel_key((u64)nx, (u64)ny, (u64)nz));
+        if (slot < 0) continue;
+        unsigned j = ix.head[slot];
+        while (j < (unsigned)ix.N && budget-- > 0) {               // TRANSFER_END is above every N
+            const float* __restrict__ c = ix.src + (int64_t)j * 3;
+            const float dx = px - c[0], dy = py - c[1], dz = pz - c[2];
+            const float q = (dx * dx + dy * dy) + dz * dz;
+            if (q <= r2) return true;
+            j = ix.next[j];
+        }
+    }
+    return false;
 }

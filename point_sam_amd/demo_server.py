@@ -15,7 +15,7 @@ POST /crop {center, radius} . POST /crop/clear (not in the reference): zoom into
 from the ball's own working cloud (predictor.set_crop), still per loaded point, until the crop is cleared or another cloud is loaded.
 POST /instances (not in the reference): /segment_all plus one box per kept mask (predictor.mask_geometry) . POST /crop/selection {margin}: zoom
 into the ball around the current /segment mask (predictor.set_crop_to_mask).
-POST /propagate {pointcloud, radius, pose?, align?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
+POST /propagate {pointcloud, radius, pose?, align?, search?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
 there (predictor.snapshot / propagate).
 POST /view {camera, splat?} (not in the reference): the loaded cloud as a camera sees it, a z-buffered point-splat image (predictor.render_view) .
 POST /click_pixel {pixel, label, window?, frame?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
@@ -372,7 +372,9 @@ class DemoSession:
     def propagate(self, data: dict) -> dict:
         """The next scan of a sequence: {"pointcloud": name, "radius": r, "pose": 3 x 4 or 4 x 4 rows (optional), "align": {align.AlignConfig fields}
         (optional: the given pose, or the identity, is refined by ICP before the transfer -- predictor.align -- and the response also carries "pose", the
-        3 x 4 rows used, and "align": {pairs, coverage, rms, iterations, converged})}.  The kept masks (/next) plus the
+        3 x 4 rows used, and "align": {pairs, coverage, rms, iterations, converged}), "search": {align.SearchConfig fields} (optional, only together
+        with "align" and without "pose": no starting pose is known, a grid of candidate poses is scored and the best are refined -- align.search -- and
+        the response's "align" also carries "search": {poses, sample, chosen, candidates: [{pose_index, count, pairs, rms, converged}]})}.  The kept masks (/next) plus the
         current /segment mask become a snapshot of the loaded cloud (a mask's logits are +1 inside, -1 outside: the session keeps masks, not logits);
         the named cloud is loaded as /pointcloud/ does, but normalised with the SAME shift and scale as the cloud it follows (a transfer compares
         coordinates; a point that leaves the unit ball is the model's ValueError), and predictor.propagate re-segments every object there.  radius
@@ -386,6 +388,12 @@ class DemoSession:
             masks = list(self.masks) + ([self.segment_mask.cpu().numpy()] if self.segment_mask is not None else [])
             if not masks:
                 raise ValueError("/propagate before any /segment: there is no mask to carry over")
+            search_fields = None
+            if isinstance(data, dict) and "search" in data:
+                if "align" not in data or "pose" in data:
+                    raise ValueError('/propagate: "search" is valid only together with "align" and without "pose"')
+                search_fields = data["search"]
+                data = {k: v for k, v in data.items() if k != "search"}
             if not isinstance(data, dict) or not {"pointcloud", "radius"} <= set(data) or set(data) - {"pointcloud", "radius", "pose", "align"}:
                 raise ValueError('/propagate takes {"pointcloud": name, "radius": r, "pose": rows (optional), "align": {AlignConfig fields} (optional)}')
             name, radius, pose = data["pointcloud"], data["radius"], data.get("pose")
@@ -399,6 +407,10 @@ class DemoSession:
             if "align" in data:
                 from .align import AlignConfig
                 align_cfg = AlignConfig.from_overrides(data["align"])      # and so is a bad align field
+            search_cfg = None
+            if search_fields is not None:
+                from .align import SearchConfig
+                search_cfg = SearchConfig.from_overrides(search_fields)    # or a bad search field
             if any(m.shape != (self.pc_xyz.shape[1],) for m in masks):
                 raise ValueError("/propagate: a kept mask does not belong to the loaded cloud")
             before = (self.pc_xyz, self.pc_rgb, self.obj_path, self.crop, self.norm)
@@ -412,7 +424,7 @@ class DemoSession:
                     self._set_cloud()
                     found = None
                     if align_cfg is not None:
-                        found = self.predictor.align(snap, align_cfg, pose)
+                        found = self.predictor.align(snap, align_cfg, pose) if search_cfg is None else self.predictor.align(snap, align_cfg, search=search_cfg)
                         pose = found.pose.tolist()
                     res = self.predictor.propagate(snap, float(radius), pose)
             except Exception:
@@ -428,6 +440,10 @@ class DemoSession:
             if found is not None:
                 out.update(pose=pose, align=dict(pairs=found.pairs, coverage=found.coverage, rms=found.rms if np.isfinite(found.rms) else None,
                                                  iterations=found.iterations, converged=found.converged))
+                if search_cfg is not None:
+                    rec = found.search
+                    out["align"]["search"] = dict(poses=rec.poses, sample=rec.sample, chosen=rec.chosen, candidates=[
+                        dict(c, rms=c["rms"] if np.isfinite(c["rms"]) else None) for c in rec.candidates])
             return out
 
     def set_crop(self, data: dict) -> dict:

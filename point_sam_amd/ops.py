@@ -1664,6 +1664,66 @@ def align_step(index: TransferIndex, xyz: torch.Tensor, pose=None, radius=None, 
     return (sums, nearest) if return_nearest else sums
 
 
+ALIGN_SCORE_POSES = 4            # PSAM_ALIGN_SCORE_POSES: the poses one workgroup of psam_pose_score takes a tile of queries through
+ALIGN_SCORE_MAX_POSES = 1 << 20
+
+
+def transfer_poses(poses):
+    """[P, 3, 4] or [P, 4, 4] array-like of host numbers -> [P, 12] fp32 words: every row as transfer_pose gives it, and transfer_pose's ValueError for
+    the first row it refuses (a value that is not finite in fp32, a 4 x 4 whose last row is not (0, 0, 0, 1))."""
+    import numpy as np
+    if isinstance(poses, torch.Tensor):
+        poses = poses.detach().cpu().numpy()
+    try:
+        A = np.asarray(poses, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError("align_score: poses must be a [P, 3, 4] or [P, 4, 4] array of numbers") from None
+    if A.ndim != 3 or A.shape[1:] not in ((3, 4), (4, 4)) or not 1 <= A.shape[0] <= ALIGN_SCORE_MAX_POSES:
+        raise ValueError(f"align_score: poses must be [P, 3, 4] or [P, 4, 4] with 1 <= P <= 2^20, got shape {A.shape}")
+    with np.errstate(over="ignore"):
+        words = A[:, :3].astype(np.float32).reshape(len(A), 12)
+    bad = ~np.isfinite(words).all(1)
+    if A.shape[1] == 4:
+        bad |= (A[:, 3] != np.array([0.0, 0.0, 0.0, 1.0])).any(1)
+    if bad.any():
+        transfer_pose(A[int(np.argmax(bad))])                 # the first bad row, in transfer_pose's own words
+        raise ValueError(f"align_score: pose {int(np.argmax(bad))} is not a rigid pose")
+    return np.ascontiguousarray(words)
+
+
+def align_score(index: TransferIndex, xyz: torch.Tensor, poses, radius=None):
+    """The score of a pose search (include/pointsam_hip.h: pose between two clouds): index (transfer_index), xyz [M, 3] f32 (the queries), poses
+    -> counts [P] int32 on the device: under pose p, the queries with at least one indexed source within `radius` of pose_p(query) -- exactly
+    int(align_step(index, xyz, pose_p, radius)[0]) for every p, from ONE launch.  poses: [P, 3, 4] or [P, 4, 4] host numbers (an array-like or a
+    tensor), every row checked as transfer_pose checks a pose (ValueError for a value that is not finite or a bad last row); or a [P, 12] float32
+    tensor ON THE DEVICE, the rows' twelve words, which is taken AS VALIDATED -- the kernel cannot refuse a pose, one that is not finite scores 0.
+    radius: None (the index's own) or a smaller one, a larger one is a ValueError as for align_step.  1 <= P <= 2^20.  No host synchronisation."""
+    if not isinstance(index, TransferIndex):
+        raise TypeError(f"align_score: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
+    xyz = _transfer_cloud(xyz, "align_score: xyz")
+    r2 = index.r2
+    if radius is not None:
+        r, _, r2 = transfer_radius(radius)
+        if r > index.radius:
+            raise ValueError(f"align_score: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
+    M, N, dev = xyz.shape[0], index.num_source, xyz.device
+    if isinstance(poses, torch.Tensor) and poses.is_cuda and poses.dim() == 2:
+        if poses.shape[1] != 12 or not 1 <= poses.shape[0] <= ALIGN_SCORE_MAX_POSES:
+            raise ValueError(f"align_score: device poses must be [P, 12] with 1 <= P <= 2^20, got {tuple(poses.shape)}")
+        words = _chk(poses, name="poses")
+        _chk(xyz, name="xyz")
+    else:
+        host = transfer_poses(poses)
+        _chk(xyz, name="xyz")
+        words = torch.from_numpy(host).to(dev)
+    P = words.shape[0]
+    counts = torch.empty(P, dtype=torch.int32, device=dev)
+    org = (ctypes.c_float * 3)(*index.origin)
+    check(_lib.load().psam_pose_score(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org), float(index.inv_h),
+                                       float(r2), xyz.data_ptr(), M, words.data_ptr(), P, counts.data_ptr(), _stream()), "psam_pose_score")
+    return counts
+
+
 # ------------------------------------------------------------------------------------------ camera views (csrc/views.hip)
 VIEW_MAX_SIDE, VIEW_MAX_SPLAT, VIEW_MAX_WINDOW = 8192, 3, 16
 

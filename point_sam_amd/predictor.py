@@ -265,19 +265,31 @@ class PointSAMPredictor:
         return bits, area, T.covered(plan).sum()
 
     @torch.no_grad()
-    def align(self, snap, cfg, init=None, mask=None):
+    def align(self, snap, cfg, init=None, mask=None, search=None):
         """The pose from the CURRENT cloud to the snapshot's, estimated by ICP (point_sam_amd/align.py) -> align.Alignment; its `pose` is what
         transfer_masks / propagate take.  The sources are the snapshot's working cloud, the queries this cloud's working coordinates as encoded;
         cfg: an align.AlignConfig (its radius is the index's cell size); init: the pose to refine (None: the identity; e.g. odometry); mask: an
         optional packed row [ceil(Nw / 64)] int64 at working width restricting the queries to one object (a re-scan after something moved).
         Exactly align.icp(ops.transfer_index(snap.coords, cfg.radius), working coordinates, cfg, init, mask).  One 160-byte host read per step
-        besides the index build's; both scans normalised with the same centre and scale."""
+        besides the index build's; both scans normalised with the same centre and scale.
+        search: None, or an align.SearchConfig for a caller without even a rough pose: a grid of candidate poses is scored in one launch and the best
+        few are refined by the same ICP -- exactly align.search(the same index, working coordinates, search, cfg, mask); the Alignment's `search`
+        says what was tried.  Its scoring radius may not exceed cfg.radius, and it takes no `init` (ValueError): the search IS the start."""
         from . import align as A
         from . import transfer as T
         T.check_snapshot(snap, "align")
         if not isinstance(cfg, A.AlignConfig):
             raise TypeError(f"align: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
+        if search is not None:
+            if not isinstance(search, A.SearchConfig):
+                raise TypeError(f"align: search must be an align.SearchConfig or None, got {type(search).__name__}")
+            if init is not None:
+                raise ValueError("align: init and search exclude each other: a search starts from its own candidates")
+            if search.radius is not None and search.radius > cfg.radius:
+                raise ValueError(f"align: search.radius {search.radius} exceeds cfg.radius {cfg.radius}, the cell size of the index")
         state, _ = self._transfer_cloud("align")
+        if search is not None:
+            return A.search(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), search, cfg, mask)
         return A.icp(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), cfg, init, mask)
 
     @torch.no_grad()

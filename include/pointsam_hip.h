@@ -800,6 +800,34 @@ int32_t psam_align_step(const float* src, int32_t N, const void* index_ws, size_
                         const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest, double* sums, void* ws,
                         size_t ws_bytes, psam_stream_t stream);
 
+/* One step of point-to-PLANE ICP on the same index (point_sam_amd/align.py: solve_plane): psam_align_step's pair per query, and the sums of the 6 x 6
+ * normal equations of the linearised point-to-plane residual.  The call allocates nothing and does not synchronise with the host; no atomics.
+ *
+ * Every argument of psam_align_step means what it means there.  src_normals [N, 3] f32 (non-null, 4-byte aligned): one normal per source, taken as
+ * given -- not normalised, either sign; psam_normals_voxel's output fits.
+ *     pair, nearest     psam_align_step's, bit for bit: the same posed coordinate p, cells, candidates and order (q, j)
+ *     used pair         one whose normal n has nn = (n_x n_x + n_y n_y) + n_z n_z, in fp32, finite and > 0: the (0, 0, 0) of a voxel below min_points
+ *                       drops out, and so does a normal with a NaN or an infinity -- it enters no sum
+ *     terms             p (the POSED coordinate's fp32 words; the query itself without a pose), s = src[pair] and n converted to fp64, then in fp64,
+ *                       every operation rounded on its own: d = p - s; r = (d_x n_x + d_y n_y) + d_z n_z; c = p x n, c_x = p_y n_z - p_z n_y and
+ *                       cyclic; J = (c_x, c_y, c_z, n_x, n_y, n_z)
+ * sums [PSAM_PLANE_SUMS] f64 on the device:
+ *     [0] the number of used pairs   [1] sum q over them (the pair's fp32 q, converted)   [2] sum r r   [3..8] sum J_a r
+ *     [9..29] sum J_a J_b for a <= b, the upper triangle row-major: 00, 01, .., 05, 11, .., 55
+ *     [30] the number of paired queries whose pair was not used   [31] the number of participating queries that have a cell (paired or not)
+ *   Order of the additions, fixed, and psam_align_step's: lane l of wave w holds the one term of query 64 w + l; the 64 lanes are combined by the xor
+ *   butterfly 32, 16, 8, 4, 2, 1; a second kernel adds the waves' partials in wave order within 32 segments of ceil(ceil(M / 64) / 32) consecutive
+ *   waves, then the segments in order.  A function of M alone: the same inputs give the same thirty-two words from run to run.  The counts are exact.
+ *   Error of the others: |sums - sum of the terms| <= (n - 1) u / (1 - (n - 1) u) * sum |term|, u = 2^-53, n the number of terms.
+ * ws: psam_plane_workspace_bytes(M) bytes (0 for M outside (0, 2^28]), 8-byte aligned.
+ * Refusals: psam_align_step's codes in its order, before any launch, sums untouched; src_normals counts among the pointers that may not be null (-1)
+ * and must be 4-byte aligned (-2). */
+#define PSAM_PLANE_SUMS 32
+size_t psam_plane_workspace_bytes(int32_t M);
+int32_t psam_plane_step(const float* src, const float* src_normals, int32_t N, const void* index_ws, size_t index_ws_bytes, const float* origin,
+                        float inv_h, float r2, const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest, double* sums,
+                        void* ws, size_t ws_bytes, psam_stream_t stream);
+
 /* The score of a global pose search (point_sam_amd/align.py: search): under each of P poses, the number of queries that land on the indexed cloud.
  * One launch for all P poses; the call allocates nothing, needs no workspace and does not synchronise with the host.
  *

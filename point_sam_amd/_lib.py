@@ -151,6 +151,8 @@ SIGNATURES = {
     "psam_transfer_plan": (i32, [ptr, i32, ptr, size_t, ptr, f32, f32, ptr, i32, ptr, f32, ptr, ptr, ptr]),
     "psam_align_workspace_bytes": (size_t, [i32]),
     "psam_align_step": (i32, [ptr, i32, ptr, size_t, ptr, f32, f32, ptr, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_plane_workspace_bytes": (size_t, [i32]),
+    "psam_plane_step": (i32, [ptr, ptr, i32, ptr, size_t, ptr, f32, f32, ptr, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
     "psam_pose_score": (i32, [ptr, i32, ptr, size_t, ptr, f32, f32, ptr, i32, ptr, i32, ptr, ptr]),
     "psam_view_splat": (i32, [ptr, i32, ptr, f32, f32, f32, f32, i32, i32, f32, i32, ptr, ptr]),
     "psam_view_pick": (i32, [ptr, i32, i32, ptr, i32, i32, ptr, ptr]),

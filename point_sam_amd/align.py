@@ -9,6 +9,12 @@ The sums are over the queries AS GIVEN, so each step solves for the whole pose: 
 ICP is a local method: it refines an initial pose (the identity, or odometry) whose error is small against the search radius and the scene's
 structure; it does not search globally.  `Alignment.coverage` and `rms` say how far to trust the answer.
 
+Rooms are floors, walls and table tops, the surfaces ALONG which point-to-point ICP crawls: a query slides over a plane at no cost to the true
+motion but is held by its nearest sample.  With a normal per source (`icp(..., normals=...)`: predictor.snapshot(normals=True) keeps the voxel
+normals of normals.hip) every step minimises the distance to the pair's tangent PLANE instead: one ops.align_plane_step (32 fp64 words: the 6 x 6
+normal equations of the linearised residual), one 256-byte host read and `solve_plane`.  That step is a small motion composed onto the pose, so
+the run ends by tolerance on the update (`PlaneConfig`), typically in a handful of steps.
+
 `search` is the global part, for callers without even a rough pose (a room re-scanned from another doorway, an object put down elsewhere): a grid of
 candidate poses (`rotation_grid` x anchors x a translation lattice, `candidate_poses`) is scored on a sample of the queries by ONE launch
 (ops.align_score: per pose the number of sampled queries that land within a radius of a source -- an exact integer), the `keep` best are refined by
@@ -116,6 +122,75 @@ def solve_rigid(sums):
     return np.concatenate([R, t[:, None]], 1), float(np.sqrt(max(residual, 0.0) / n))
 
 
+@dataclasses.dataclass(frozen=True)
+class PlaneConfig:
+    """Point-to-plane ICP (icp / search with `normals`).  tol_rotation (radians) / tol_translation, both > 0: a step at the final radius whose update
+    (omega, v) has |omega| <= tol_rotation and |v| <= tol_translation ends the run as converged.  A point-to-plane step is composed onto the fp64
+    pose while the kernel linearises at its fp32 rounding, so the pose does not settle on a bit-exact fixed point the way point-to-point does: it
+    jitters at the level of an fp32 ulp of a pose word near 1 (6e-8; about 2e-8 was seen on the fixture of the tests), and the tolerances must sit
+    above that; they sit at 1e-6, well below the last update that still moved the pose there (4.6e-5).  condition in (0, 1): the solve is refused as
+    degenerate when the smallest eigenvalue of the 6 x 6 system is <= condition x the largest (a single plane leaves three motions free).
+    NONE of the defaults has been tuned on real data."""
+    tol_rotation: float = 1e-6
+    tol_translation: float = 1e-6
+    condition: float = 1e-10
+
+    def __post_init__(self):
+        for name in ("tol_rotation", "tol_translation", "condition"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < float("inf"):
+                raise ValueError(f"PlaneConfig: {name} must be a finite positive number, got {v!r}")
+        if not self.condition < 1:
+            raise ValueError(f"PlaneConfig: condition must lie in (0, 1), got {self.condition!r}")
+
+    @classmethod
+    def from_overrides(cls, data: dict) -> "PlaneConfig":
+        """A config from a dict of fields (a request's body): an unknown field is a ValueError, like a bad value."""
+        names = {f.name for f in dataclasses.fields(cls)}
+        if not isinstance(data, dict) or set(data) - names:
+            raise ValueError(f"PlaneConfig takes optionally {sorted(names)}, got {sorted(data) if isinstance(data, dict) else data!r}")
+        return cls(**data)
+
+
+def _rodrigues(w) -> np.ndarray:
+    th = float(np.linalg.norm(w))
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    if th < 1e-12:                                         # sin(th) / th and (1 - cos th) / th^2 at their limits: the next terms are th^2 / 6 and / 24
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (math.sin(th) / th) * K + ((1.0 - math.cos(th)) / (th * th)) * (K @ K)
+
+
+def solve_plane(sums, pose, condition: float = PlaneConfig.condition):
+    """The 32 sums of ops.align_plane_step, taken under `pose` (3 x 4 fp64) -> (new pose 3 x 4 fp64, rms, |omega|, |v|).  A = the symmetric 6 x 6 of
+    [9..29], g = [3..8]; z = (omega, v) solves A z = -g (by the eigen-decomposition of A: np.linalg.eigh), the minimiser of sum (r + J . z)^2, the
+    point-to-plane residual linearised in a small rotation omega and translation v of the POSED queries.  The update is composed onto the fp64 pose:
+    R' = the rotation nearest (SVD) to Rodrigues(omega) R, t' = Rodrigues(omega) t + v.  rms = sqrt(max([2] + z . g, 0) / [0]): the linearised
+    residual after the step.  ValueError("degenerate: ...") for fewer than 6 used pairs or a smallest eigenvalue <= condition x the largest."""
+    m = np.asarray(sums, dtype=np.float64).reshape(-1)
+    if m.shape != (ops.PLANE_SUMS,) or not np.isfinite(m).all():
+        raise ValueError(f"solve_plane: sums must be {ops.PLANE_SUMS} finite numbers (ops.align_plane_step)")
+    P = np.asarray(pose, dtype=np.float64)
+    if P.shape != (3, 4) or not np.isfinite(P).all():
+        raise ValueError("solve_plane: pose must be a finite 3 x 4 array")
+    n = m[0]
+    if n < 6:
+        raise ValueError("degenerate: fewer than 6 used pairs")
+    A = np.zeros((6, 6))
+    A[np.triu_indices(6)] = m[9:30]
+    A = A + np.triu(A, 1).T
+    g = m[3:9]
+    lam, V = np.linalg.eigh(A)
+    if not lam[0] > condition * lam[-1]:
+        raise ValueError("degenerate: the used pairs' planes leave a motion free")
+    z = -(V @ ((V.T @ g) / lam))
+    W = _rodrigues(z[:3])
+    U, _, Vt = np.linalg.svd(W @ P[:, :3])
+    R = U @ np.diag([1.0, 1.0, 1.0 if np.linalg.det(U @ Vt) > 0 else -1.0]) @ Vt
+    t = W @ P[:, 3] + z[3:]
+    rms = float(np.sqrt(max(m[2] + z @ g, 0.0) / n))
+    return np.concatenate([R, t[:, None]], 1), rms, float(np.linalg.norm(z[:3])), float(np.linalg.norm(z[3:]))
+
+
 def _initial(init) -> np.ndarray:
     if init is None:
         return np.concatenate([np.eye(3), np.zeros((3, 1))], 1)
@@ -129,15 +204,28 @@ def _rotation_angle(A, B) -> float:
     return float(np.arccos(min(1.0, max(-1.0, c))))
 
 
-def icp(index, xyz, cfg: AlignConfig, init=None, bits=None, step=None) -> Alignment:
+def icp(index, xyz, cfg: AlignConfig, init=None, bits=None, step=None, normals=None, plane=None) -> Alignment:
     """index: ops.transfer_index of the sources at cfg.radius; xyz [M, 3] the queries; init: the pose to start from (None: the identity); bits: an
     optional packed row, the queries that take part -> Alignment.  Each step is one ops.align_step under the current pose, one 160-byte host read
     and one solve_rigid.  Stops converged when the twelve fp32 words of the new pose equal the previous step's at the final radius (the next step
     would be bit-identical: a fixed point), or when both tolerances are positive and met there; stops unconverged, with the last good pose, when a
     step has fewer than cfg.min_pairs pairs or a degenerate solve, or when the iterations run out.  `step`: a stand-in for ops.align_step with its
-    signature (a reference, a test)."""
+    signature (a reference, a test).
+    normals [N, 3] f32, one per source: point-to-plane.  Each step is one ops.align_plane_step, one 256-byte host read and one solve_plane; cfg's
+    radius schedule, iterations and min_pairs (against word [0], the USED pairs) hold, its tolerances do not: the run is converged when, at the
+    final radius, the update is within plane.tol_rotation and plane.tol_translation ("tolerance"), or the fp32 words repeat ("fixed point").
+    coverage = used pairs / participating queries that have a cell; `step` then stands in for ops.align_plane_step (index, xyz, normals, pose,
+    radius, bits).  plane: a PlaneConfig (None: the defaults); without normals it is a ValueError."""
     if not isinstance(cfg, AlignConfig):
         raise TypeError(f"icp: cfg must be an AlignConfig, got {type(cfg).__name__}")
+    if normals is None:
+        if plane is not None:
+            raise ValueError("icp: plane configures point-to-plane ICP and needs normals")
+    else:
+        plane = PlaneConfig() if plane is None else plane
+        if not isinstance(plane, PlaneConfig):
+            raise TypeError(f"icp: plane must be a PlaneConfig or None, got {type(plane).__name__}")
+        return _icp_plane(index, xyz, cfg, init, bits, ops.align_plane_step if step is None else step, normals, plane)
     step = ops.align_step if step is None else step
     pose = _initial(init)
     last = cfg.step_radius(10 ** 9)
@@ -166,6 +254,38 @@ def icp(index, xyz, cfg: AlignConfig, init=None, bits=None, step=None) -> Alignm
         out.pose, out.pairs, out.rms, out.coverage = pose, pairs, rms, pairs / max(sums[19], 1.0)
         if radius == last and (fixed or small):
             out.converged, out.reason = True, "fixed point" if fixed else "tolerance"
+            return out
+    return out
+
+
+def _icp_plane(index, xyz, cfg, init, bits, step, normals, plane) -> Alignment:
+    """icp's loop with the point-to-plane step and solve."""
+    pose = _initial(init)
+    last = cfg.step_radius(10 ** 9)
+    out = Alignment(pose, 0, 0.0, float("nan"), 0, False, "iterations", [])
+    for k in range(cfg.iterations):
+        radius = cfg.step_radius(k)
+        sums = step(index, xyz, normals, pose, radius, bits)
+        sums = np.asarray(sums.cpu().numpy() if hasattr(sums, "cpu") else sums, dtype=np.float64)      # the one host read of the step
+        out.iterations = k + 1
+        pairs = int(sums[0])
+        if pairs < cfg.min_pairs:
+            out.history.append((pairs, float("nan"), radius))
+            out.reason = f"pairs: {pairs} < min_pairs {cfg.min_pairs}"
+            return out
+        try:
+            new, rms, rot, tr = solve_plane(sums, pose, plane.condition)
+        except ValueError as e:
+            out.history.append((pairs, float("nan"), radius))
+            out.reason = str(e)
+            return out
+        out.history.append((pairs, rms, radius))
+        fixed = np.array_equal(new.astype(np.float32), pose.astype(np.float32))
+        small = rot <= plane.tol_rotation and tr <= plane.tol_translation
+        pose = new
+        out.pose, out.pairs, out.rms, out.coverage = pose, pairs, rms, pairs / max(sums[31], 1.0)
+        if radius == last and (fixed or small):
+            out.converged, out.reason = True, "tolerance" if small else "fixed point"
             return out
     return out
 
@@ -338,7 +458,7 @@ def sample_positions(n: int, sample: int) -> np.ndarray:
     return np.arange(n, dtype=np.int64) if n <= sample else (np.arange(sample, dtype=np.int64) * n) // sample
 
 
-def search(index, xyz, cfg: SearchConfig, icp_cfg: AlignConfig, bits=None, score=None, step=None) -> Alignment:
+def search(index, xyz, cfg: SearchConfig, icp_cfg: AlignConfig, bits=None, score=None, step=None, normals=None, plane=None) -> Alignment:
     """A pose without a starting pose.  index: ops.transfer_index of the sources at icp_cfg.radius (anything with `src_xyz` when `score` and `step`
     are stand-ins); xyz [M, 3] the queries; bits: an optional packed row, the queries that take part -> Alignment, its `search` a SearchRecord.
       1. the queries scored: sample_positions among the participating ones, in index order -- deterministic (with bits, one host read of the row)
@@ -347,11 +467,14 @@ def search(index, xyz, cfg: SearchConfig, icp_cfg: AlignConfig, bits=None, score
       4. the candidates ordered by (-count, index); the first cfg.keep each refined by icp(index, xyz, icp_cfg, init=pose, bits=bits, step=step)
       5. the refinement with the most pairs; ties go to the lower rms, then to the earlier candidate.  Where none has a pair, the first one's
          Alignment (converged=False, its reason says why).
-    score / step: stand-ins for ops.align_score / ops.align_step with their signatures (a reference, a test)."""
+    score / step: stand-ins for ops.align_score / ops.align_step with their signatures (a reference, a test).
+    normals / plane: passed to every refinement (icp: point-to-plane); the scoring is the same."""
     if not isinstance(cfg, SearchConfig):
         raise TypeError(f"search: cfg must be a SearchConfig, got {type(cfg).__name__}")
     if not isinstance(icp_cfg, AlignConfig):
         raise TypeError(f"search: icp_cfg must be an AlignConfig, got {type(icp_cfg).__name__}")
+    if normals is None and plane is not None:
+        raise ValueError("search: plane configures point-to-plane ICP and needs normals")
     radius = icp_cfg.radius if cfg.radius is None else cfg.radius
     if radius > icp_cfg.radius:
         raise ValueError(f"search: the scoring radius {radius} exceeds the AlignConfig's {icp_cfg.radius}, the cell size of the index")
@@ -389,7 +512,7 @@ def search(index, xyz, cfg: SearchConfig, icp_cfg: AlignConfig, bits=None, score
     order = np.lexsort((np.arange(len(poses)), -counts))[:cfg.keep]
     runs, record = [], SearchRecord(len(poses), len(pick), [], 0)
     for p in order.tolist():
-        out = icp(index, xyz, icp_cfg, init=poses[p], bits=bits, step=step)
+        out = icp(index, xyz, icp_cfg, init=poses[p], bits=bits, step=step, normals=normals, plane=plane)
         runs.append(out)
         record.candidates.append(dict(pose_index=p, count=int(counts[p]), pairs=out.pairs, rms=out.rms, converged=out.converged))
     best = 0

@@ -40,6 +40,8 @@ SOURCES = [
     ("transfer.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # one ICP step on transfer.hip's index: the same candidates bit for bit (csrc/transfer_index.h), so the same flags, for the same reasons.
     ("align.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # one point-to-plane ICP step: align.hip's pair bit for bit (the same shared headers), so align.hip's flags.
+    ("align_plane.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # the score of a pose search: align.hip's posed coordinate, cell and candidates for P poses at once, so align.hip's flags.
     ("align_score.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # camera views: the projection's fp32 operations rounded one at a time; the pose is transfer.hip's (csrc/rigid_pose.h), and so is the reason for

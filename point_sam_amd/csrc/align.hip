@@ -13,8 +13,8 @@
 // product of two: 48 significant bits; |x|^2 is added as its three exact products, x first), only the additions round.  Nothing is accumulated
 // across waves in flight, so there are no atomics, and:
 //
-//   the order of every fp64 addition is a function of M and the constants below alone -- per lane: query 64 w + lane of wave w, its terms in the
-//   order written, starting from 0; per wave: the xor butterfly 32, 16, 8, 4, 2, 1 (wave_sum_f64: all lanes agree); per call: the second kernel
+//   the order of every fp64 addition is a function of M and the constants (below, align_combine.h) alone -- per lane: query 64 w + lane of wave w, its
+//   terms in the order written, starting from 0; per wave: the xor butterfly 32, 16, 8, 4, 2, 1 (wave_sum_f64: all lanes agree); per call: the second kernel
 //   adds the waves' partials of a segment of ALIGN_SEGMENT(M) consecutive waves in wave order, then the segments in segment order -- neither the
 //   bits, the pose, the data nor the schedule enters it.  The same inputs give the same twenty words from run to run.
 //
@@ -23,14 +23,10 @@
 #include "common.h"
 #include "rigid_pose.h"
 #include "transfer_index.h"
+#include "align_combine.h"      // the second kernel, shared with align_plane.hip
 
 constexpr int ALIGN_THREADS = 256;
 constexpr int ALIGN_SUMS = PSAM_ALIGN_SUMS;
-constexpr int ALIGN_SEGMENTS = 32;                                 // the second kernel: ALIGN_SEGMENTS x 32 threads, column c of segment s at thread 32 s + c
-constexpr int ALIGN_COLUMNS = 32;
-static_assert(ALIGN_SUMS <= ALIGN_COLUMNS, "one thread per column");
-
-static inline int64_t align_waves(int64_t M) { return psam_cdiv(M, WAVE); }
 
 // One thread per query; the wave's partial sums go to part[wave, 20].
 template <bool POSE>
@@ -91,25 +87,6 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_pair_kernel(TransferIndex
     }
 }
 
-// One workgroup.  Thread 32 s + c adds column c of the waves [s per, (s + 1) per) in wave order; then thread c adds the segments in segment order.
-__global__ __launch_bounds__(ALIGN_SEGMENTS * ALIGN_COLUMNS) void align_combine_kernel(const double* __restrict__ part, int waves, int per,
-                                                                                       double* __restrict__ sums) {
-    __shared__ double seg[ALIGN_SEGMENTS][ALIGN_COLUMNS];
-    const int c = threadIdx.x % ALIGN_COLUMNS, s = threadIdx.x / ALIGN_COLUMNS;
-    double acc = 0.0;
-    if (c < ALIGN_SUMS) {
-        const int hi = min((s + 1) * per, waves);
-        for (int w = s * per; w < hi; ++w) acc = acc + part[(int64_t)w * ALIGN_SUMS + c];
-    }
-    seg[s][c] = acc;
-    __syncthreads();
-    if (s == 0 && c < ALIGN_SUMS) {
-        double total = 0.0;
-        for (int t = 0; t < ALIGN_SEGMENTS; ++t) total = total + seg[t][c];
-        sums[c] = total;
-    }
-}
-
 PSAM_API size_t psam_align_workspace_bytes(int32_t M) {
     if (M <= 0 || M > VOXEL_MAX_POINTS) return 0;
     return (size_t)align_waves(M) * ALIGN_SUMS * sizeof(double);
@@ -145,7 +122,7 @@ PSAM_API int32_t psam_align_step(const float* src, int32_t N, const void* index_
     const int32_t st = psam_launch_status("psam_align_step: launch failed");
     if (st != PSAM_OK) return st;
     const int waves = (int)align_waves(M);
-    hipLaunchKernelGGL(align_combine_kernel, dim3(1), dim3(ALIGN_SEGMENTS * ALIGN_COLUMNS), 0, stream, (const double*)part, waves,
+    hipLaunchKernelGGL(align_combine_kernel<ALIGN_SUMS>, dim3(1), dim3(ALIGN_SEGMENTS * ALIGN_COLUMNS), 0, stream, (const double*)part, waves,
                        (int)psam_cdiv(waves, ALIGN_SEGMENTS), sums);
     return psam_launch_status("psam_align_step: combine launch failed");
 }

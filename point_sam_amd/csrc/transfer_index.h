@@ -1,6 +1,6 @@
-// The cell index of a source cloud, shared by transfer.hip (which builds it and plans the 3-NN transfer with it), align.hip (the nearest source of
-// an ICP step) and align_score.hip (whether a posed query has a source in reach at all): the workspace layout, the cell of a point and the walk over
-// a query's candidates are one decision and live here once, so all three put the same sources in front of a query bit for bit.  The definition and the index's format: transfer.hip's header.  Translation units that include
+// The cell index of a source cloud, shared by transfer.hip (which builds it and plans the 3-NN transfer with it), align.hip and align_plane.hip (the
+// nearest source of an ICP step) and align_score.hip (whether a posed query has a source in reach at all): the workspace layout, the cell of a point
+// and the walk over a query's candidates are one decision and live here once, so all of them put the same sources in front of a query bit for bit.  The definition and the index's format: transfer.hip's header.  Translation units that include
 // this are compiled with -ffp-contract=off -fno-slp-vectorize (point_sam_amd/build.py).
 #pragma once
 #include "common.h"

@@ -15,7 +15,7 @@ POST /crop {center, radius} . POST /crop/clear (not in the reference): zoom into
 from the ball's own working cloud (predictor.set_crop), still per loaded point, until the crop is cleared or another cloud is loaded.
 POST /instances (not in the reference): /segment_all plus one box per kept mask (predictor.mask_geometry) . POST /crop/selection {margin}: zoom
 into the ball around the current /segment mask (predictor.set_crop_to_mask).
-POST /propagate {pointcloud, radius, pose?, align?, search?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
+POST /propagate {pointcloud, radius, pose?, align?, search?, plane?} (not in the reference): the next scan of a sequence -- the kept masks are carried over and re-segmented
 there (predictor.snapshot / propagate).
 POST /view {camera, splat?} (not in the reference): the loaded cloud as a camera sees it, a z-buffered point-splat image (predictor.render_view) .
 POST /click_pixel {pixel, label, window?, frame?}: a click on that image, answered exactly as /segment answers a click on the point shown there.
@@ -374,7 +374,9 @@ class DemoSession:
         (optional: the given pose, or the identity, is refined by ICP before the transfer -- predictor.align -- and the response also carries "pose", the
         3 x 4 rows used, and "align": {pairs, coverage, rms, iterations, converged}), "search": {align.SearchConfig fields} (optional, only together
         with "align" and without "pose": no starting pose is known, a grid of candidate poses is scored and the best are refined -- align.search -- and
-        the response's "align" also carries "search": {poses, sample, chosen, candidates: [{pose_index, count, pairs, rms, converged}]})}.  The kept masks (/next) plus the
+        the response's "align" also carries "search": {poses, sample, chosen, candidates: [{pose_index, count, pairs, rms, converged}]}), "plane":
+        {align.PlaneConfig fields} (optional, only together with "align": the snapshot is taken with its voxel normals and every ICP step is
+        point-to-plane -- far fewer steps between scans of floors and walls; the response has the same fields)}.  The kept masks (/next) plus the
         current /segment mask become a snapshot of the loaded cloud (a mask's logits are +1 inside, -1 outside: the session keeps masks, not logits);
         the named cloud is loaded as /pointcloud/ does, but normalised with the SAME shift and scale as the cloud it follows (a transfer compares
         coordinates; a point that leaves the unit ball is the model's ValueError), and predictor.propagate re-segments every object there.  radius
@@ -394,8 +396,15 @@ class DemoSession:
                     raise ValueError('/propagate: "search" is valid only together with "align" and without "pose"')
                 search_fields = data["search"]
                 data = {k: v for k, v in data.items() if k != "search"}
+            has_plane = isinstance(data, dict) and "plane" in data
+            if has_plane:
+                if "align" not in data:
+                    raise ValueError('/propagate: "plane" is valid only together with "align"')
+                plane_fields = data["plane"]
+                data = {k: v for k, v in data.items() if k != "plane"}
             if not isinstance(data, dict) or not {"pointcloud", "radius"} <= set(data) or set(data) - {"pointcloud", "radius", "pose", "align"}:
-                raise ValueError('/propagate takes {"pointcloud": name, "radius": r, "pose": rows (optional), "align": {AlignConfig fields} (optional)}')
+                raise ValueError('/propagate takes {"pointcloud": name, "radius": r, "pose": rows (optional), "align": {AlignConfig fields} (optional), '
+                                 '"search": {SearchConfig fields} and "plane": {PlaneConfig fields} (optional, beside "align")}')
             name, radius, pose = data["pointcloud"], data["radius"], data.get("pose")
             if not isinstance(name, str) or not name:
                 raise ValueError("pointcloud must be a file name")
@@ -411,6 +420,10 @@ class DemoSession:
             if search_fields is not None:
                 from .align import SearchConfig
                 search_cfg = SearchConfig.from_overrides(search_fields)    # or a bad search field
+            plane_cfg = None
+            if has_plane:
+                from .align import PlaneConfig
+                plane_cfg = PlaneConfig.from_overrides(plane_fields)       # or a bad plane field
             if any(m.shape != (self.pc_xyz.shape[1],) for m in masks):
                 raise ValueError("/propagate: a kept mask does not belong to the loaded cloud")
             before = (self.pc_xyz, self.pc_rgb, self.obj_path, self.crop, self.norm)
@@ -419,12 +432,15 @@ class DemoSession:
                     self.crop = None
                     self._set_cloud()
                     inside = torch.from_numpy(np.stack(masks).astype(bool)).to(self.device)
-                    snap = self.predictor.snapshot(torch.where(inside, 1.0, -1.0).float())
+                    logits = torch.where(inside, 1.0, -1.0).float()
+                    snap = self.predictor.snapshot(logits) if plane_cfg is None else self.predictor.snapshot(logits, normals=True)
                     cloud = self._install_pointcloud(*self._read_pointcloud(name, self.norm))
                     self._set_cloud()
                     found = None
                     if align_cfg is not None:
-                        found = self.predictor.align(snap, align_cfg, pose) if search_cfg is None else self.predictor.align(snap, align_cfg, search=search_cfg)
+                        more = {} if plane_cfg is None else {"plane": plane_cfg}
+                        found = (self.predictor.align(snap, align_cfg, pose, **more) if search_cfg is None else
+                                 self.predictor.align(snap, align_cfg, search=search_cfg, **more))
                         pose = found.pose.tolist()
                     res = self.predictor.propagate(snap, float(radius), pose)
             except Exception:

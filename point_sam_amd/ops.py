@@ -1626,6 +1626,7 @@ def transfer_plan(index: TransferIndex, xyz: torch.Tensor, pose=None, eps: float
 
 # ------------------------------------------------------------------------------------------ pose between two clouds (csrc/align.hip)
 ALIGN_SUMS = 20
+PLANE_SUMS = 32      # PSAM_PLANE_SUMS (csrc/align_plane.hip)
 
 
 def align_step(index: TransferIndex, xyz: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None, return_nearest: bool = False):
@@ -1634,23 +1635,8 @@ def align_step(index: TransferIndex, xyz: torch.Tensor, pose=None, radius=None, 
     sum x s^T, sum |x|^2, sum |s|^2, and the participating queries that have a cell; x is the query as given, not posed.  radius: None (the index's
     own) or a smaller one -- a larger one is a ValueError, the 27 cells would silently truncate the search.  bits: None, or [ceil(M / 64)] int64 words
     in mask_pack's layout: the queries that take part.  return_nearest: also nearest [M] int32, -1 without a pair.  No host synchronisation."""
-    if not isinstance(index, TransferIndex):
-        raise TypeError(f"align_step: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
-    xyz = _transfer_cloud(xyz, "align_step: xyz")
-    words = transfer_pose(pose)
-    r2 = index.r2
-    if radius is not None:
-        r, _, r2 = transfer_radius(radius)
-        if r > index.radius:
-            raise ValueError(f"align_step: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
+    xyz, words, r2, bits = _align_arguments("align_step", index, xyz, pose, radius, bits)
     M, N, dev = xyz.shape[0], index.num_source, xyz.device
-    if bits is not None:
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64 or bits.dim() == 2 and bits.shape[0] != 1 or bits.dim() not in (1, 2) or \
-                bits.shape[-1] != mask_words(M):
-            raise ValueError(f"align_step: bits must be one packed row of {mask_words(M)} int64 words for {M} queries, got "
-                             f"{(bits.dtype, tuple(bits.shape)) if isinstance(bits, torch.Tensor) else type(bits).__name__}")
-        bits = bits.reshape(-1)
-        _chk(bits, torch.int64, name="bits")
     _chk(xyz, name="xyz")
     L = _lib.load()
     sums = torch.empty(ALIGN_SUMS, dtype=torch.float64, device=dev)
@@ -1661,6 +1647,62 @@ def align_step(index: TransferIndex, xyz: torch.Tensor, pose=None, radius=None, 
     check(L.psam_align_step(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org), float(index.inv_h), float(r2),
                             xyz.data_ptr(), M, None if bits is None else bits.data_ptr(), None if P is None else ctypes.addressof(P),
                             None if nearest is None else nearest.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_align_step")
+    return (sums, nearest) if return_nearest else sums
+
+
+def _align_arguments(what: str, index, xyz, pose, radius, bits):
+    """The checks align_step and align_plane_step share, in one order, before any device work -> (xyz [M, 3], the pose's fp32 words or None, r2, bits
+    as one checked row or None)."""
+    if not isinstance(index, TransferIndex):
+        raise TypeError(f"{what}: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
+    xyz = _transfer_cloud(xyz, f"{what}: xyz")
+    words = transfer_pose(pose)
+    r2 = index.r2
+    if radius is not None:
+        r, _, r2 = transfer_radius(radius)
+        if r > index.radius:
+            raise ValueError(f"{what}: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
+    M = xyz.shape[0]
+    if bits is not None:
+        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64 or bits.dim() == 2 and bits.shape[0] != 1 or bits.dim() not in (1, 2) or \
+                bits.shape[-1] != mask_words(M):
+            raise ValueError(f"{what}: bits must be one packed row of {mask_words(M)} int64 words for {M} queries, got "
+                             f"{(bits.dtype, tuple(bits.shape)) if isinstance(bits, torch.Tensor) else type(bits).__name__}")
+        bits = bits.reshape(-1)
+        _chk(bits, torch.int64, name="bits")
+    return xyz, words, r2, bits
+
+
+def align_plane_step(index: TransferIndex, xyz: torch.Tensor, normals: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None,
+                     return_nearest: bool = False):
+    """One point-to-plane ICP step (include/pointsam_hip.h: pose between two clouds): align_step's arguments and pairs, plus normals [N, 3] f32 on the
+    index's device, one per indexed source (voxel_normals' fit; taken as given, either sign) -> sums [32] float64 on the device over the USED pairs
+    -- those whose normal has a finite, positive squared length: [0] their number, [1] sum q, [2] sum r r, [3..8] sum J r, [9..29] the upper triangle
+    of sum J J^T row-major, [30] the paired queries whose pair was not used, [31] the participating queries that have a cell; r = (p - s) . n and
+    J = (p x n, n) with p the POSED query.  align.solve_plane turns them into the next pose.  return_nearest: also nearest [M] int32, align_step's.
+    No host synchronisation."""
+    xyz, words, r2, bits = _align_arguments("align_plane_step", index, xyz, pose, radius, bits)
+    if not isinstance(normals, torch.Tensor):
+        raise TypeError(f"align_plane_step: normals must be a tensor, got {type(normals).__name__}")
+    if normals.dim() != 2 or tuple(normals.shape) != (index.num_source, 3):
+        raise ValueError(f"align_plane_step: normals must be [{index.num_source}, 3], one per indexed source, got {tuple(normals.shape)}")
+    if normals.dtype != torch.float32:
+        raise TypeError(f"align_plane_step: normals: expected {torch.float32}, got {normals.dtype}")
+    if normals.device != index.src_xyz.device:
+        raise ValueError(f"align_plane_step: normals are on {normals.device}, the index on {index.src_xyz.device}")
+    M, N, dev = xyz.shape[0], index.num_source, xyz.device
+    _chk(xyz, name="xyz")
+    _chk(normals, name="normals")
+    L = _lib.load()
+    sums = torch.empty(PLANE_SUMS, dtype=torch.float64, device=dev)
+    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
+    ws = torch.empty(L.psam_plane_workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
+    org = (ctypes.c_float * 3)(*index.origin)
+    P = None if words is None else (ctypes.c_float * 12)(*[float(v) for v in words])
+    check(L.psam_plane_step(index.src_xyz.data_ptr(), normals.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org),
+                            float(index.inv_h), float(r2), xyz.data_ptr(), M, None if bits is None else bits.data_ptr(),
+                            None if P is None else ctypes.addressof(P), None if nearest is None else nearest.data_ptr(), sums.data_ptr(), ws.data_ptr(),
+                            ws.numel() * 8, _stream()), "psam_plane_step")
     return (sums, nearest) if return_nearest else sums
 
 

@@ -233,10 +233,12 @@ class PointSAMPredictor:
         return self._state, self.scene
 
     @torch.no_grad()
-    def snapshot(self, logits: torch.Tensor):
+    def snapshot(self, logits: torch.Tensor, normals=False):
         """What the next scan needs of this one: -> transfer.Snapshot of the working cloud's coordinates as encoded and the K objects' logits at working
         width.  logits [K, n] f32, n the scan's or the working cloud's width; of a scan-width row the representatives' own words are kept (exact, as
-        for a prompt_mask).  RuntimeError before any cloud is set and under an active crop."""
+        for a prompt_mask).  normals: True, or a superpoints.SuperpointConfig (its voxel settings and min_points), also keeps the voxel normal of
+        every working point -- point_normals(cfg=...)[0] at the representatives (scene.keep_idx), or the cloud's own rows without a scene -- which
+        align(plane=...) needs; no host read beyond point_normals'.  RuntimeError before any cloud is set and under an active crop."""
         from . import transfer as T
         from .scene import reduce_prompt_mask
         state, sc = self._transfer_cloud("snapshot")
@@ -244,7 +246,11 @@ class PointSAMPredictor:
         logits = T.check_snapshot_logits(logits, (Nw,) if sc is None else (Nw, sc.num_points), "snapshot")
         if sc is not None:
             logits = reduce_prompt_mask(sc, logits)
-        return T.Snapshot(state.coords[0].contiguous(), logits.to(self.model.device).contiguous(), logits.shape[0])
+        kept = None
+        if normals is not False and normals is not None:
+            kept = self.point_normals(cfg=None if normals is True else normals)[0]      # a TypeError for anything but a SuperpointConfig
+            kept = (kept if sc is None else kept.index_select(0, sc.keep_idx)).contiguous()
+        return T.Snapshot(state.coords[0].contiguous(), logits.to(self.model.device).contiguous(), logits.shape[0], kept)
 
     def _scan_xyz(self, state, sc):
         return state.coords[0].contiguous() if sc is None else self._keepalive[0]
@@ -265,7 +271,7 @@ class PointSAMPredictor:
         return bits, area, T.covered(plan).sum()
 
     @torch.no_grad()
-    def align(self, snap, cfg, init=None, mask=None, search=None):
+    def align(self, snap, cfg, init=None, mask=None, search=None, plane=None):
         """The pose from the CURRENT cloud to the snapshot's, estimated by ICP (point_sam_amd/align.py) -> align.Alignment; its `pose` is what
         transfer_masks / propagate take.  The sources are the snapshot's working cloud, the queries this cloud's working coordinates as encoded;
         cfg: an align.AlignConfig (its radius is the index's cell size); init: the pose to refine (None: the identity; e.g. odometry); mask: an
@@ -274,12 +280,23 @@ class PointSAMPredictor:
         besides the index build's; both scans normalised with the same centre and scale.
         search: None, or an align.SearchConfig for a caller without even a rough pose: a grid of candidate poses is scored in one launch and the best
         few are refined by the same ICP -- exactly align.search(the same index, working coordinates, search, cfg, mask); the Alignment's `search`
-        says what was tried.  Its scoring radius may not exceed cfg.radius, and it takes no `init` (ValueError): the search IS the start."""
+        says what was tried.  Its scoring radius may not exceed cfg.radius, and it takes no `init` (ValueError): the search IS the start.
+        plane: None, an align.PlaneConfig, or True for its defaults: point-to-plane ICP on the snapshot's normals (snapshot(..., normals=True); a
+        ValueError without them) -- exactly align.icp / align.search on the same index with normals=snap.normals, plane=the config: far fewer steps
+        where the scans are floors and walls, one 256-byte host read per step."""
         from . import align as A
         from . import transfer as T
         T.check_snapshot(snap, "align")
         if not isinstance(cfg, A.AlignConfig):
             raise TypeError(f"align: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
+        normals = None
+        if plane is not None:
+            plane = A.PlaneConfig() if plane is True else plane
+            if not isinstance(plane, A.PlaneConfig):
+                raise TypeError(f"align: plane must be an align.PlaneConfig, True or None, got {type(plane).__name__}")
+            if snap.normals is None:
+                raise ValueError("align: plane needs the snapshot's normals: take it with snapshot(..., normals=True)")
+            normals = snap.normals
         if search is not None:
             if not isinstance(search, A.SearchConfig):
                 raise TypeError(f"align: search must be an align.SearchConfig or None, got {type(search).__name__}")
@@ -289,8 +306,8 @@ class PointSAMPredictor:
                 raise ValueError(f"align: search.radius {search.radius} exceeds cfg.radius {cfg.radius}, the cell size of the index")
         state, _ = self._transfer_cloud("align")
         if search is not None:
-            return A.search(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), search, cfg, mask)
-        return A.icp(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), cfg, init, mask)
+            return A.search(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), search, cfg, mask, normals=normals, plane=plane)
+        return A.icp(ops.transfer_index(snap.coords, cfg.radius), state.coords[0].contiguous(), cfg, init, mask, normals=normals, plane=plane)
 
     @torch.no_grad()
     def propagate(self, snap, radius: float, pose=None, clicks: int = 1, fill=None):

@@ -28,10 +28,12 @@ class TransferPlan:
 @dataclass
 class Snapshot:
     """What predictor.snapshot keeps of a scan: `coords` [Nw, 3] the working cloud as encoded, `logits` [K, Nw] the objects' logits at working width (the
-    representatives' own words), `num_masks` = K."""
+    representatives' own words), `num_masks` = K; `normals` [Nw, 3] f32, the voxel normal at every working point, or None: kept on request
+    (predictor.snapshot(normals=True)) for point-to-plane alignment (predictor.align(plane=...))."""
     coords: torch.Tensor
     logits: torch.Tensor
     num_masks: int
+    normals: torch.Tensor = None
 
 
 @dataclass
@@ -52,6 +54,10 @@ def check_snapshot(snap, what: str) -> Snapshot:
     c, l = snap.coords, snap.logits
     if c.dim() != 2 or c.shape[1] != 3 or l.dim() != 2 or l.shape[1] != c.shape[0] or l.shape[0] != snap.num_masks or snap.num_masks < 1:
         raise ValueError(f"{what}: a snapshot holds coords [Nw, 3] and logits [K, Nw] with K >= 1, got {tuple(c.shape)}, {tuple(l.shape)}, K = {snap.num_masks}")
+    n = snap.normals
+    if n is not None and (not isinstance(n, torch.Tensor) or tuple(n.shape) != (c.shape[0], 3) or n.dtype != torch.float32):
+        raise ValueError(f"{what}: a snapshot's normals are None or [Nw, 3] float32 with Nw = {c.shape[0]}, got "
+                         f"{(tuple(n.shape), n.dtype) if isinstance(n, torch.Tensor) else type(n).__name__}")
     return snap
 
 

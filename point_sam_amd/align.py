@@ -29,8 +29,30 @@ import numpy as np
 from . import ops
 
 
+def _number(v) -> bool:
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+def _integer(v, lo, hi) -> bool:
+    return not isinstance(v, bool) and isinstance(v, int) and lo <= v <= hi
+
+
+class _Overrides:
+    """from_overrides of the three configs; REQUIRED: the fields without a default."""
+    REQUIRED = ()
+
+    @classmethod
+    def from_overrides(cls, data: dict):
+        """A config from a dict of fields (a request's body; arrays as nested lists): an unknown field is a ValueError, like a bad value."""
+        names = {f.name for f in dataclasses.fields(cls)}
+        if not isinstance(data, dict) or set(data) - names or set(cls.REQUIRED) - set(data):
+            raise ValueError(f"{cls.__name__} takes {''.join(r + ' and ' for r in cls.REQUIRED)}optionally {sorted(names - set(cls.REQUIRED))}, "
+                             f"got {sorted(data) if isinstance(data, dict) else data!r}")
+        return cls(**data)
+
+
 @dataclasses.dataclass(frozen=True)
-class AlignConfig:
+class AlignConfig(_Overrides):
     """radius: the search radius of step 0, and the cell size of the index (normalised coordinates); final_radius (None: radius): where the shrinking
     stops; shrink in (0, 1]: the radius of step k is max(final_radius, radius * shrink**k); iterations >= 1: the most steps; min_pairs >= 3: fewer
     pairs end the run; tol_rotation (radians) / tol_translation: when BOTH are positive, a step that changes the pose by less than both, at the final
@@ -43,38 +65,26 @@ class AlignConfig:
     min_pairs: int = 16
     tol_rotation: float = 0.0
     tol_translation: float = 0.0
+    REQUIRED = ("radius",)
 
     def __post_init__(self):
-        def number(v):
-            return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
-
-        def integer(v, lo, hi):
-            return not isinstance(v, bool) and isinstance(v, int) and lo <= v <= hi
-        if not number(self.radius):
+        if not _number(self.radius):
             raise ValueError(f"AlignConfig: radius must be a finite positive number, got {self.radius!r}")
         ops.transfer_radius(self.radius)
         if self.final_radius is not None:
-            if not number(self.final_radius) or not 0 < self.final_radius <= self.radius:
+            if not _number(self.final_radius) or not 0 < self.final_radius <= self.radius:
                 raise ValueError(f"AlignConfig: final_radius must be None or lie in (0, radius], got {self.final_radius!r}")
             ops.transfer_radius(self.final_radius)
-        if not number(self.shrink) or not 0 < self.shrink <= 1:
+        if not _number(self.shrink) or not 0 < self.shrink <= 1:
             raise ValueError(f"AlignConfig: shrink must lie in (0, 1], got {self.shrink!r}")
-        if not integer(self.iterations, 1, 10000):
+        if not _integer(self.iterations, 1, 10000):
             raise ValueError(f"AlignConfig: iterations must be an integer in 1 .. 10000, got {self.iterations!r}")
-        if not integer(self.min_pairs, 3, 1 << 28):
+        if not _integer(self.min_pairs, 3, 1 << 28):
             raise ValueError(f"AlignConfig: min_pairs must be an integer in 3 .. 2^28, got {self.min_pairs!r}")
         for name in ("tol_rotation", "tol_translation"):
             v = getattr(self, name)
-            if not number(v) or v < 0:
+            if not _number(v) or v < 0:
                 raise ValueError(f"AlignConfig: {name} must be a finite number >= 0, got {v!r}")
-
-    @classmethod
-    def from_overrides(cls, data: dict) -> "AlignConfig":
-        """A config from a dict of fields (a request's body): an unknown field is a ValueError, like a bad value."""
-        names = {f.name for f in dataclasses.fields(cls)}
-        if not isinstance(data, dict) or set(data) - names or "radius" not in data:
-            raise ValueError(f"AlignConfig takes radius and optionally {sorted(names - {'radius'})}, got {sorted(data) if isinstance(data, dict) else data!r}")
-        return cls(**data)
 
     def step_radius(self, k: int) -> float:
         """The search radius of step k."""
@@ -123,7 +133,7 @@ def solve_rigid(sums):
 
 
 @dataclasses.dataclass(frozen=True)
-class PlaneConfig:
+class PlaneConfig(_Overrides):
     """Point-to-plane ICP (icp / search with `normals`).  tol_rotation (radians) / tol_translation, both > 0: a step at the final radius whose update
     (omega, v) has |omega| <= tol_rotation and |v| <= tol_translation ends the run as converged.  A point-to-plane step is composed onto the fp64
     pose while the kernel linearises at its fp32 rounding, so the pose does not settle on a bit-exact fixed point the way point-to-point does: it
@@ -138,18 +148,10 @@ class PlaneConfig:
     def __post_init__(self):
         for name in ("tol_rotation", "tol_translation", "condition"):
             v = getattr(self, name)
-            if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 < v < float("inf"):
+            if not _number(v) or not v > 0:
                 raise ValueError(f"PlaneConfig: {name} must be a finite positive number, got {v!r}")
         if not self.condition < 1:
             raise ValueError(f"PlaneConfig: condition must lie in (0, 1), got {self.condition!r}")
-
-    @classmethod
-    def from_overrides(cls, data: dict) -> "PlaneConfig":
-        """A config from a dict of fields (a request's body): an unknown field is a ValueError, like a bad value."""
-        names = {f.name for f in dataclasses.fields(cls)}
-        if not isinstance(data, dict) or set(data) - names:
-            raise ValueError(f"PlaneConfig takes optionally {sorted(names)}, got {sorted(data) if isinstance(data, dict) else data!r}")
-        return cls(**data)
 
 
 def _rodrigues(w) -> np.ndarray:
@@ -215,77 +217,63 @@ def icp(index, xyz, cfg: AlignConfig, init=None, bits=None, step=None, normals=N
     radius schedule, iterations and min_pairs (against word [0], the USED pairs) hold, its tolerances do not: the run is converged when, at the
     final radius, the update is within plane.tol_rotation and plane.tol_translation ("tolerance"), or the fp32 words repeat ("fixed point").
     coverage = used pairs / participating queries that have a cell; `step` then stands in for ops.align_plane_step (index, xyz, normals, pose,
-    radius, bits).  plane: a PlaneConfig (None: the defaults); without normals it is a ValueError."""
+    radius, bits).  plane: a PlaneConfig (None: the defaults); without normals it is a ValueError.
+    Both kinds run ONE loop; they differ in the step, in the solve (-> new pose, rms, whether the update is small), in the word that counts the
+    queries with a cell (19 / 31), and in the reason given when the words repeat AND the update is small: point-to-point says "fixed point",
+    point-to-plane "tolerance"."""
     if not isinstance(cfg, AlignConfig):
         raise TypeError(f"icp: cfg must be an AlignConfig, got {type(cfg).__name__}")
     if normals is None:
         if plane is not None:
             raise ValueError("icp: plane configures point-to-plane ICP and needs normals")
+        step = ops.align_step if step is None else step
+        cell_word, both = ops.ALIGN_SUMS - 1, "fixed point"
+
+        def take(pose, radius):
+            return step(index, xyz, pose, radius, bits)
+
+        def solve(sums, pose):
+            new, rms = solve_rigid(sums)
+            return new, rms, (cfg.tol_rotation > 0 and cfg.tol_translation > 0 and _rotation_angle(pose, new) <= cfg.tol_rotation and
+                              float(np.linalg.norm(new[:, 3] - pose[:, 3])) <= cfg.tol_translation)
     else:
         plane = PlaneConfig() if plane is None else plane
         if not isinstance(plane, PlaneConfig):
             raise TypeError(f"icp: plane must be a PlaneConfig or None, got {type(plane).__name__}")
-        return _icp_plane(index, xyz, cfg, init, bits, ops.align_plane_step if step is None else step, normals, plane)
-    step = ops.align_step if step is None else step
-    pose = _initial(init)
-    last = cfg.step_radius(10 ** 9)
-    out = Alignment(pose, 0, 0.0, float("nan"), 0, False, "iterations", [])
-    for k in range(cfg.iterations):
-        radius = cfg.step_radius(k)
-        sums = step(index, xyz, pose, radius, bits)
-        sums = np.asarray(sums.cpu().numpy() if hasattr(sums, "cpu") else sums, dtype=np.float64)      # the one host read of the step
-        out.iterations = k + 1
-        pairs = int(sums[0])
-        if pairs < cfg.min_pairs:
-            out.history.append((pairs, float("nan"), radius))
-            out.reason = f"pairs: {pairs} < min_pairs {cfg.min_pairs}"
-            return out
-        try:
-            new, rms = solve_rigid(sums)
-        except ValueError as e:
-            out.history.append((pairs, float("nan"), radius))
-            out.reason = str(e)
-            return out
-        out.history.append((pairs, rms, radius))
-        fixed = np.array_equal(new.astype(np.float32), pose.astype(np.float32))
-        small = (cfg.tol_rotation > 0 and cfg.tol_translation > 0 and _rotation_angle(pose, new) <= cfg.tol_rotation and
-                 float(np.linalg.norm(new[:, 3] - pose[:, 3])) <= cfg.tol_translation)
-        pose = new
-        out.pose, out.pairs, out.rms, out.coverage = pose, pairs, rms, pairs / max(sums[19], 1.0)
-        if radius == last and (fixed or small):
-            out.converged, out.reason = True, "fixed point" if fixed else "tolerance"
-            return out
-    return out
+        step = ops.align_plane_step if step is None else step
+        cell_word, both = ops.PLANE_SUMS - 1, "tolerance"
 
+        def take(pose, radius):
+            return step(index, xyz, normals, pose, radius, bits)
 
-def _icp_plane(index, xyz, cfg, init, bits, step, normals, plane) -> Alignment:
-    """icp's loop with the point-to-plane step and solve."""
-    pose = _initial(init)
-    last = cfg.step_radius(10 ** 9)
-    out = Alignment(pose, 0, 0.0, float("nan"), 0, False, "iterations", [])
-    for k in range(cfg.iterations):
-        radius = cfg.step_radius(k)
-        sums = step(index, xyz, normals, pose, radius, bits)
-        sums = np.asarray(sums.cpu().numpy() if hasattr(sums, "cpu") else sums, dtype=np.float64)      # the one host read of the step
-        out.iterations = k + 1
-        pairs = int(sums[0])
-        if pairs < cfg.min_pairs:
-            out.history.append((pairs, float("nan"), radius))
-            out.reason = f"pairs: {pairs} < min_pairs {cfg.min_pairs}"
-            return out
-        try:
+        def solve(sums, pose):
             new, rms, rot, tr = solve_plane(sums, pose, plane.condition)
+            return new, rms, rot <= plane.tol_rotation and tr <= plane.tol_translation
+    pose = _initial(init)
+    last = cfg.step_radius(10 ** 9)
+    out = Alignment(pose, 0, 0.0, float("nan"), 0, False, "iterations", [])
+    for k in range(cfg.iterations):
+        radius = cfg.step_radius(k)
+        sums = take(pose, radius)
+        sums = np.asarray(sums.cpu().numpy() if hasattr(sums, "cpu") else sums, dtype=np.float64)      # the one host read of the step
+        out.iterations = k + 1
+        pairs = int(sums[0])
+        if pairs < cfg.min_pairs:
+            out.history.append((pairs, float("nan"), radius))
+            out.reason = f"pairs: {pairs} < min_pairs {cfg.min_pairs}"
+            return out
+        try:
+            new, rms, small = solve(sums, pose)
         except ValueError as e:
             out.history.append((pairs, float("nan"), radius))
             out.reason = str(e)
             return out
         out.history.append((pairs, rms, radius))
         fixed = np.array_equal(new.astype(np.float32), pose.astype(np.float32))
-        small = rot <= plane.tol_rotation and tr <= plane.tol_translation
         pose = new
-        out.pose, out.pairs, out.rms, out.coverage = pose, pairs, rms, pairs / max(sums[31], 1.0)
+        out.pose, out.pairs, out.rms, out.coverage = pose, pairs, rms, pairs / max(sums[cell_word], 1.0)
         if radius == last and (fixed or small):
-            out.converged, out.reason = True, "tolerance" if small else "fixed point"
+            out.converged, out.reason = True, both if fixed and small else "fixed point" if fixed else "tolerance"
             return out
     return out
 
@@ -296,7 +284,7 @@ GOLDEN_ANGLE = math.pi * (3.0 - math.sqrt(5.0))
 
 
 @dataclasses.dataclass(frozen=True, eq=False)
-class SearchConfig:
+class SearchConfig(_Overrides):
     """The grid `search` scores.  rotations: "yaw" (yaw_steps >= 1 turns by 2 pi k / yaw_steps about `up`, three numbers, not all zero), "so3" (`axes`
     >= 1 directions on the Fibonacci sphere, each with `rolls` >= 1 rolls about it: rotation_grid), or an explicit [R, 3, 3] array of rotation
     matrices.  anchors: None (the source centroid) or [A, 3] positions in the source frame where the query centroid may land -- e.g. the instance
@@ -317,12 +305,6 @@ class SearchConfig:
     keep: int = 8
 
     def __post_init__(self):
-        def number(v):
-            return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
-
-        def integer(v, lo, hi):
-            return not isinstance(v, bool) and isinstance(v, int) and lo <= v <= hi
-
         def array(v, tail, what):
             try:
                 a = np.array(v, dtype=np.float64)
@@ -341,34 +323,25 @@ class SearchConfig:
                 raise ValueError("SearchConfig: every matrix of rotations must be orthonormal with determinant +1 (to 1e-6)")
             object.__setattr__(self, "rotations", Rs)
         for name, hi in (("yaw_steps", MAX_POSES), ("axes", MAX_POSES), ("rolls", MAX_POSES), ("sample", 1 << 28), ("keep", 1024)):
-            if not integer(getattr(self, name), 1, hi):
+            if not _integer(getattr(self, name), 1, hi):
                 raise ValueError(f"SearchConfig: {name} must be an integer in 1 .. {hi}, got {getattr(self, name)!r}")
-        if not integer(self.offsets, 0, 16):
+        if not _integer(self.offsets, 0, 16):
             raise ValueError(f"SearchConfig: offsets must be an integer in 0 .. 16, got {self.offsets!r}")
-        if not number(self.offset_step) or not self.offset_step > 0:
+        if not _number(self.offset_step) or not self.offset_step > 0:
             raise ValueError(f"SearchConfig: offset_step must be a finite positive number, got {self.offset_step!r}")
         up = self.up
-        if not isinstance(up, (tuple, list)) or len(up) != 3 or not all(number(v) for v in up) or not any(v != 0 for v in up):
+        if not isinstance(up, (tuple, list)) or len(up) != 3 or not all(_number(v) for v in up) or not any(v != 0 for v in up):
             raise ValueError(f"SearchConfig: up must be three finite numbers, not all zero, got {up!r}")
         object.__setattr__(self, "up", tuple(float(v) for v in up))
         if self.anchors is not None:
             object.__setattr__(self, "anchors", array(self.anchors, (3,), "anchors"))
         if self.radius is not None:
-            if not number(self.radius):
+            if not _number(self.radius):
                 raise ValueError(f"SearchConfig: radius must be None or a finite positive number, got {self.radius!r}")
             ops.transfer_radius(self.radius)
         if self.num_rotations * (1 if self.anchors is None else len(self.anchors)) * (2 * self.offsets + 1) ** 3 > MAX_POSES:
             raise ValueError(f"SearchConfig: {self.num_rotations} rotations x {1 if self.anchors is None else len(self.anchors)} anchors x "
                              f"{(2 * self.offsets + 1) ** 3} offsets exceed 2^20 poses")
-
-    @classmethod
-    def from_overrides(cls, data: dict) -> "SearchConfig":
-        """A config from a dict of fields (a request's body; rotations, up and anchors as nested lists): an unknown field is a ValueError, like a bad
-        value."""
-        names = {f.name for f in dataclasses.fields(cls)}
-        if not isinstance(data, dict) or set(data) - names:
-            raise ValueError(f"SearchConfig takes optionally {sorted(names)}, got {sorted(data) if isinstance(data, dict) else data!r}")
-        return cls(**data)
 
     @property
     def num_rotations(self) -> int:

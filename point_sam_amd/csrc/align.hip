@@ -13,19 +13,20 @@
 // product of two: 48 significant bits; |x|^2 is added as its three exact products, x first), only the additions round.  Nothing is accumulated
 // across waves in flight, so there are no atomics, and:
 //
-//   the order of every fp64 addition is a function of M and the constants (below, align_combine.h) alone -- per lane: query 64 w + lane of wave w, its
+//   the order of every fp64 addition is a function of M and the constants of align_combine.h alone -- per lane: query 64 w + lane of wave w, its
 //   terms in the order written, starting from 0; per wave: the xor butterfly 32, 16, 8, 4, 2, 1 (wave_sum_f64: all lanes agree); per call: the second kernel
 //   adds the waves' partials of a segment of ALIGN_SEGMENT(M) consecutive waves in wave order, then the segments in segment order -- neither the
 //   bits, the pose, the data nor the schedule enters it.  The same inputs give the same twenty words from run to run.
 //
 // A wave without a participating query that has a cell stores twenty exact zeros and skips the butterfly.
 // Every fp32 operation is rounded on its own (-ffp-contract=off).  Caller-owned workspace; no allocation, no host synchronisation.
+// The wave's row (the all-zero row, the butterfly, lane 0's store), the second kernel and the host entry are align_combine.h's, shared with
+// align_plane.hip.  The pair of a query is written out in both kernels: moved into a shared helper it ran slower (align_combine.h).
 #include "common.h"
 #include "rigid_pose.h"
 #include "transfer_index.h"
-#include "align_combine.h"      // the second kernel, shared with align_plane.hip
+#include "align_combine.h"
 
-constexpr int ALIGN_THREADS = 256;
 constexpr int ALIGN_SUMS = PSAM_ALIGN_SUMS;
 
 // One thread per query; the wave's partial sums go to part[wave, 20].
@@ -56,10 +57,7 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_pair_kernel(TransferIndex
     if (nearest && i < M) nearest[i] = bj;
     double* __restrict__ out = part + (int64_t)(i >> 6) * ALIGN_SUMS;
     const int lane = threadIdx.x & 63;
-    if (__ballot(cell) == 0) {                                     // wave-uniform: nothing to add
-        if (lane < ALIGN_SUMS) out[lane] = 0.0;
-        return;
-    }
+    if (align_zero_row<ALIGN_SUMS>(cell, out, lane)) return;
     double s[ALIGN_SUMS];
 #pragma unroll
     for (int c = 0; c < ALIGN_SUMS; ++c) s[c] = 0.0;
@@ -79,50 +77,16 @@ __global__ __launch_bounds__(ALIGN_THREADS) void align_pair_kernel(TransferIndex
         }
     }
     s[19] = cell ? 1.0 : 0.0;
-#pragma unroll
-    for (int c = 0; c < ALIGN_SUMS; ++c) s[c] = wave_sum_f64(s[c]);
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < ALIGN_SUMS; ++c) out[c] = s[c];
-    }
+    align_store_row<ALIGN_SUMS>(s, out, lane);
 }
 
-PSAM_API size_t psam_align_workspace_bytes(int32_t M) {
-    if (M <= 0 || M > VOXEL_MAX_POINTS) return 0;
-    return (size_t)align_waves(M) * ALIGN_SUMS * sizeof(double);
-}
+PSAM_API size_t psam_align_workspace_bytes(int32_t M) { return align_workspace_bytes<ALIGN_SUMS>(M); }
 
 PSAM_API int32_t psam_align_step(const float* src, int32_t N, const void* index_ws, size_t index_ws_bytes, const float* origin, float inv_h, float r2,
                                  const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest, double* sums, void* ws,
                                  size_t ws_bytes, hipStream_t stream) {
-    PSAM_REQUIRE(src && index_ws && origin && qry && sums && ws, PSAM_EINVAL, "psam_align_step: null pointer");
-    PSAM_REQUIRE(N > 0 && N <= VOXEL_MAX_POINTS, PSAM_EINVAL, "psam_align_step: need 0 < N <= 2^28");
-    PSAM_REQUIRE(M > 0 && M <= VOXEL_MAX_POINTS, PSAM_EINVAL, "psam_align_step: need 0 < M <= 2^28");
-    PSAM_REQUIRE(std::isfinite(inv_h) && inv_h > 0.0f, PSAM_EINVAL, "psam_align_step: inv_h must be finite and positive");
-    PSAM_REQUIRE(std::isfinite(r2) && r2 > 0.0f, PSAM_EINVAL, "psam_align_step: r2 must be finite and positive");
-    PSAM_REQUIRE(transfer_finite3(origin), PSAM_EINVAL, "psam_align_step: origin must be finite");
-    RigidPose P = {};
-    PSAM_REQUIRE(!pose || pose_load(pose, P), PSAM_EINVAL, "psam_align_step: pose must be finite");
-    PSAM_REQUIRE((((uintptr_t)sums | (uintptr_t)ws | (uintptr_t)qry_bits) & 7) == 0 && ((uintptr_t)index_ws & 15) == 0 &&
-                     (((uintptr_t)src | (uintptr_t)qry | (uintptr_t)nearest) & 3) == 0,
-                 PSAM_EALIGN, "psam_align_step: index_ws must be 16-byte aligned, sums, ws and qry_bits 8-byte aligned, src, qry and nearest 4-byte aligned");
-    PSAM_REQUIRE(index_ws_bytes >= transfer_layout(nullptr, N).bytes, PSAM_EWORKSPACE,
-                 "psam_align_step: index workspace too small (psam_transfer_index_workspace_bytes)");
-    PSAM_REQUIRE(ws_bytes >= psam_align_workspace_bytes(M), PSAM_EWORKSPACE, "psam_align_step: workspace too small (psam_align_workspace_bytes)");
-    const TransferIndexView ix = transfer_view(src, N, index_ws);
-    const dim3 grid((unsigned)psam_cdiv(M, ALIGN_THREADS)), block(ALIGN_THREADS);
-    double* part = (double*)ws;
-    if (pose) {
-        hipLaunchKernelGGL(align_pair_kernel<true>, grid, block, 0, stream, ix, origin[0], origin[1], origin[2], inv_h, r2, qry, (int)M,
-                           (const u64*)qry_bits, P, (int*)nearest, part);
-    } else {
-        hipLaunchKernelGGL(align_pair_kernel<false>, grid, block, 0, stream, ix, origin[0], origin[1], origin[2], inv_h, r2, qry, (int)M,
-                           (const u64*)qry_bits, P, (int*)nearest, part);
-    }
-    const int32_t st = psam_launch_status("psam_align_step: launch failed");
-    if (st != PSAM_OK) return st;
-    const int waves = (int)align_waves(M);
-    hipLaunchKernelGGL(align_combine_kernel<ALIGN_SUMS>, dim3(1), dim3(ALIGN_SEGMENTS * ALIGN_COLUMNS), 0, stream, (const double*)part, waves,
-                       (int)psam_cdiv(waves, ALIGN_SEGMENTS), sums);
-    return psam_launch_status("psam_align_step: combine launch failed");
+    static const char* const aligned = "index_ws must be 16-byte aligned, sums, ws and qry_bits 8-byte aligned, src, qry and nearest 4-byte aligned";
+    static const TransferEntry entry = {"psam_align_step", "index workspace", aligned, aligned};
+    return align_step_entry<ALIGN_SUMS>(entry, "workspace too small (psam_align_workspace_bytes)", align_pair_kernel<true>, align_pair_kernel<false>, src, N,
+                                        index_ws, index_ws_bytes, origin, inv_h, r2, qry, M, qry_bits, pose, nearest, sums, ws, ws_bytes, stream);
 }

@@ -24,6 +24,8 @@
 //
 // A wave without a participating query that has a cell stores thirty-two exact zeros and skips the butterfly.
 // Every fp32 operation is rounded on its own (-ffp-contract=off).  Caller-owned workspace; no allocation, no host synchronisation.
+// The wave's row (the all-zero row, the butterfly, lane 0's store), the second kernel and the host entry are align_combine.h's, shared with
+// align.hip.  The pair of a query is written out in both kernels: moved into a shared helper it ran slower (align_combine.h).
 #include "common.h"
 #include "rigid_pose.h"
 #include "transfer_index.h"
@@ -31,18 +33,17 @@
 
 #include <cmath>
 
-constexpr int PLANE_THREADS = 256;
 constexpr int PLANE_SUMS = PSAM_PLANE_SUMS;
 static_assert(PLANE_SUMS == 2 + 1 + 6 + 21 + 2, "count, q, r r, J r, the upper triangle of J J^T, unused, with a cell");
 
 // One thread per query; the wave's partial sums go to part[wave, 32].
 template <bool POSE>
-__global__ __launch_bounds__(PLANE_THREADS) void plane_pair_kernel(TransferIndexView ix, const float* __restrict__ nrm, float ox, float oy, float oz,
+__global__ __launch_bounds__(ALIGN_THREADS) void plane_pair_kernel(TransferIndexView ix, const float* __restrict__ nrm, float ox, float oy, float oz,
                                                                   float inv_h, float r2, const float* __restrict__ qry, int M,
                                                                   const u64* __restrict__ bits, RigidPose P, int* __restrict__ nearest,
                                                                   double* __restrict__ part) {
 #pragma clang fp contract(off)
-    const int i = blockIdx.x * PLANE_THREADS + threadIdx.x;
+    const int i = blockIdx.x * ALIGN_THREADS + threadIdx.x;
     if ((i & ~(WAVE - 1)) >= M) return;                            // wave-uniform: the block's waves past the last query
     bool takes_part = i < M;
     if (takes_part && bits) takes_part = (bits[i >> 6] >> (i & 63)) & 1ull;
@@ -64,10 +65,7 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_pair_kernel(TransferIndex
     if (nearest && i < M) nearest[i] = bj;
     double* __restrict__ out = part + (int64_t)(i >> 6) * PLANE_SUMS;
     const int lane = threadIdx.x & 63;
-    if (__ballot(cell) == 0) {                                     // wave-uniform: nothing to add
-        if (lane < PLANE_SUMS) out[lane] = 0.0;
-        return;
-    }
+    if (align_zero_row<PLANE_SUMS>(cell, out, lane)) return;
     double s[PLANE_SUMS];
 #pragma unroll
     for (int c = 0; c < PLANE_SUMS; ++c) s[c] = 0.0;
@@ -95,51 +93,17 @@ __global__ __launch_bounds__(PLANE_THREADS) void plane_pair_kernel(TransferIndex
         }
     }
     s[31] = cell ? 1.0 : 0.0;
-#pragma unroll
-    for (int c = 0; c < PLANE_SUMS; ++c) s[c] = wave_sum_f64(s[c]);
-    if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < PLANE_SUMS; ++c) out[c] = s[c];
-    }
+    align_store_row<PLANE_SUMS>(s, out, lane);
 }
 
-PSAM_API size_t psam_plane_workspace_bytes(int32_t M) {
-    if (M <= 0 || M > VOXEL_MAX_POINTS) return 0;
-    return (size_t)align_waves(M) * PLANE_SUMS * sizeof(double);
-}
+PSAM_API size_t psam_plane_workspace_bytes(int32_t M) { return align_workspace_bytes<PLANE_SUMS>(M); }
 
 PSAM_API int32_t psam_plane_step(const float* src, const float* src_normals, int32_t N, const void* index_ws, size_t index_ws_bytes, const float* origin,
                                  float inv_h, float r2, const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest,
                                  double* sums, void* ws, size_t ws_bytes, hipStream_t stream) {
-    PSAM_REQUIRE(src && src_normals && index_ws && origin && qry && sums && ws, PSAM_EINVAL, "psam_plane_step: null pointer");
-    PSAM_REQUIRE(N > 0 && N <= VOXEL_MAX_POINTS, PSAM_EINVAL, "psam_plane_step: need 0 < N <= 2^28");
-    PSAM_REQUIRE(M > 0 && M <= VOXEL_MAX_POINTS, PSAM_EINVAL, "psam_plane_step: need 0 < M <= 2^28");
-    PSAM_REQUIRE(std::isfinite(inv_h) && inv_h > 0.0f, PSAM_EINVAL, "psam_plane_step: inv_h must be finite and positive");
-    PSAM_REQUIRE(std::isfinite(r2) && r2 > 0.0f, PSAM_EINVAL, "psam_plane_step: r2 must be finite and positive");
-    PSAM_REQUIRE(transfer_finite3(origin), PSAM_EINVAL, "psam_plane_step: origin must be finite");
-    RigidPose P = {};
-    PSAM_REQUIRE(!pose || pose_load(pose, P), PSAM_EINVAL, "psam_plane_step: pose must be finite");
-    PSAM_REQUIRE((((uintptr_t)sums | (uintptr_t)ws | (uintptr_t)qry_bits) & 7) == 0 && ((uintptr_t)index_ws & 15) == 0 &&
-                     (((uintptr_t)src | (uintptr_t)src_normals | (uintptr_t)qry | (uintptr_t)nearest) & 3) == 0,
-                 PSAM_EALIGN,
-                 "psam_plane_step: index_ws must be 16-byte aligned, sums, ws and qry_bits 8-byte aligned, src, src_normals, qry and nearest 4-byte aligned");
-    PSAM_REQUIRE(index_ws_bytes >= transfer_layout(nullptr, N).bytes, PSAM_EWORKSPACE,
-                 "psam_plane_step: index workspace too small (psam_transfer_index_workspace_bytes)");
-    PSAM_REQUIRE(ws_bytes >= psam_plane_workspace_bytes(M), PSAM_EWORKSPACE, "psam_plane_step: workspace too small (psam_plane_workspace_bytes)");
-    const TransferIndexView ix = transfer_view(src, N, index_ws);
-    const dim3 grid((unsigned)psam_cdiv(M, PLANE_THREADS)), block(PLANE_THREADS);
-    double* part = (double*)ws;
-    if (pose) {
-        hipLaunchKernelGGL(plane_pair_kernel<true>, grid, block, 0, stream, ix, src_normals, origin[0], origin[1], origin[2], inv_h, r2, qry, (int)M,
-                           (const u64*)qry_bits, P, (int*)nearest, part);
-    } else {
-        hipLaunchKernelGGL(plane_pair_kernel<false>, grid, block, 0, stream, ix, src_normals, origin[0], origin[1], origin[2], inv_h, r2, qry, (int)M,
-                           (const u64*)qry_bits, P, (int*)nearest, part);
-    }
-    const int32_t st = psam_launch_status("psam_plane_step: launch failed");
-    if (st != PSAM_OK) return st;
-    const int waves = (int)align_waves(M);
-    hipLaunchKernelGGL(align_combine_kernel<PLANE_SUMS>, dim3(1), dim3(ALIGN_SEGMENTS * ALIGN_COLUMNS), 0, stream, (const double*)part, waves,
-                       (int)psam_cdiv(waves, ALIGN_SEGMENTS), sums);
-    return psam_launch_status("psam_plane_step: combine launch failed");
+    static const char* const aligned =
+        "index_ws must be 16-byte aligned, sums, ws and qry_bits 8-byte aligned, src, src_normals, qry and nearest 4-byte aligned";
+    static const TransferEntry entry = {"psam_plane_step", "index workspace", aligned, aligned};
+    return align_step_entry<PLANE_SUMS>(entry, "workspace too small (psam_plane_workspace_bytes)", plane_pair_kernel<true>, plane_pair_kernel<false>, src, N,
+                                        index_ws, index_ws_bytes, origin, inv_h, r2, qry, M, qry_bits, pose, nearest, sums, ws, ws_bytes, stream, src_normals);
 }

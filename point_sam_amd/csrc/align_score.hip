@@ -59,17 +59,12 @@ __global__ __launch_bounds__(SCORE_THREADS) void align_score_kernel(TransferInde
 
 PSAM_API int32_t psam_pose_score(const float* src, int32_t N, const void* index_ws, size_t index_ws_bytes, const float* origin, float inv_h, float r2,
                                   const float* qry, int32_t M, const float* poses, int32_t P, int32_t* counts, hipStream_t stream) {
-    PSAM_REQUIRE(src && index_ws && origin && qry && poses && counts, PSAM_EINVAL, "psam_pose_score: null pointer");
-    PSAM_REQUIRE(N > 0 && N <= VOXEL_MAX_POINTS, PSAM_EINVAL, "psam_pose_score: need 0 < N <= 2^28");
-    PSAM_REQUIRE(M > 0 && M <= VOXEL_MAX_POINTS, PSAM_EINVAL, "psam_pose_score: need 0 < M <= 2^28");
+    static const char* const aligned = "index_ws must be 16-byte aligned, src, qry, poses and counts 4-byte aligned";
+    static const TransferEntry entry = {"psam_pose_score", "index workspace", aligned, aligned};
+    const int32_t st = transfer_check_query(entry, src, N, index_ws, index_ws_bytes, origin, inv_h, r2, qry, M, poses && counts,
+                                            (((uintptr_t)poses | (uintptr_t)counts) & 3) == 0);
+    if (st != PSAM_OK) return st;
     PSAM_REQUIRE(P > 0 && P <= SCORE_MAX_POSES, PSAM_EINVAL, "psam_pose_score: need 0 < P <= 2^20");
-    PSAM_REQUIRE(std::isfinite(inv_h) && inv_h > 0.0f, PSAM_EINVAL, "psam_pose_score: inv_h must be finite and positive");
-    PSAM_REQUIRE(std::isfinite(r2) && r2 > 0.0f, PSAM_EINVAL, "psam_pose_score: r2 must be finite and positive");
-    PSAM_REQUIRE(transfer_finite3(origin), PSAM_EINVAL, "psam_pose_score: origin must be finite");
-    PSAM_REQUIRE(((uintptr_t)index_ws & 15) == 0 && (((uintptr_t)src | (uintptr_t)qry | (uintptr_t)poses | (uintptr_t)counts) & 3) == 0, PSAM_EALIGN,
-                 "psam_pose_score: index_ws must be 16-byte aligned, src, qry, poses and counts 4-byte aligned");
-    PSAM_REQUIRE(index_ws_bytes >= transfer_layout(nullptr, N).bytes, PSAM_EWORKSPACE,
-                 "psam_pose_score: index workspace too small (psam_transfer_index_workspace_bytes)");
     if (hipMemsetAsync(counts, 0, (size_t)P * sizeof(int32_t), stream) != hipSuccess) {
         (void)hipGetLastError();
         psam_set_error("psam_pose_score: clearing counts failed");

@@ -1553,13 +1553,50 @@ def transfer_pose(pose):
         raise ValueError(f"transfer: pose must be a 3 x 4 or 4 x 4 array of numbers, got {pose!r}") from None
     if P.shape not in ((3, 4), (4, 4)):
         raise ValueError(f"transfer: pose must be 3 x 4 or 4 x 4, got shape {P.shape}")
-    if P.shape == (4, 4) and not np.array_equal(P[3], [0.0, 0.0, 0.0, 1.0]):
+    words, bad_row, bad_value = _pose_words(P)
+    if bad_row:
         raise ValueError(f"transfer: the last row of a 4 x 4 pose must be (0, 0, 0, 1), got {P[3].tolist()}")
-    with np.errstate(over="ignore"):
-        words = P[:3].astype(np.float32).reshape(12)
-    if not np.isfinite(words).all():
+    if bad_value:
         raise ValueError("transfer: pose must be finite in fp32")
     return words
+
+
+def _pose_words(A):
+    """[..., 3 or 4, 4] fp64 -> (the fp32 words [..., 12] of the upper 3 x 4; where a fourth row is not (0, 0, 0, 1); where a word is not finite)."""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        words = A[..., :3, :].astype(np.float32).reshape(A.shape[:-2] + (12,))
+    bad_row = (A[..., 3, :] != np.array([0.0, 0.0, 0.0, 1.0])).any(-1) if A.shape[-2] == 4 else np.zeros(A.shape[:-2], dtype=bool)
+    return words, bad_row, ~np.isfinite(words).all(-1)
+
+
+def _pose_arg(words):
+    """transfer_pose's words (twelve contiguous fp32) -> (their ctypes copy, kept alive by the caller for the call; its address), or (None, None)
+    without a pose.  One buffer copy: converting the words one by one cost more than the rest of a step's argument handling."""
+    if words is None:
+        return None, None
+    P = (ctypes.c_float * 12).from_buffer_copy(words)
+    return P, ctypes.addressof(P)
+
+
+def _transfer_query(what: str, index, xyz, radius=None):
+    """The checks every user of an index shares, in one order, before any device work: the index, the query cloud, an optional smaller radius
+    -> (xyz [M, 3], r2)."""
+    if not isinstance(index, TransferIndex):
+        raise TypeError(f"{what}: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
+    xyz = _transfer_cloud(xyz, f"{what}: xyz")
+    r2 = index.r2
+    if radius is not None:
+        r, _, r2 = transfer_radius(radius)
+        if r > index.radius:
+            raise ValueError(f"{what}: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
+    return xyz, r2
+
+
+def _transfer_args(index, r2):
+    """-> (the origin's ctypes array, kept alive by the caller for the call; the seven leading arguments of the C entries that search an index)."""
+    org = (ctypes.c_float * 3)(*index.origin)
+    return org, (index.src_xyz.data_ptr(), index.num_source, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org), float(index.inv_h), float(r2))
 
 
 def _transfer_cloud(xyz, what: str):
@@ -1606,21 +1643,17 @@ def transfer_plan(index: TransferIndex, xyz: torch.Tensor, pose=None, eps: float
     int32, w3 [M, 3] f32) in scene_interp_plan's format: per query the up to three sources nearest to pose(xyz), by (squared distance, index), among
     those within the radius in its own and the 26 surrounding cells; a query without one gets idx3 = -1, w3 = 0.  scene_interp_rows /
     scene_interp_bits apply the plan.  No host synchronisation."""
-    if not isinstance(index, TransferIndex):
-        raise TypeError(f"transfer_plan: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
-    xyz = _transfer_cloud(xyz, "transfer_plan: xyz")
+    xyz, r2 = _transfer_query("transfer_plan", index, xyz)
     words = transfer_pose(pose)
     if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0 < eps < float("inf"):
         raise ValueError(f"transfer_plan: eps must be finite and positive, got {eps!r}")
     _chk(xyz, name="xyz")
-    M, N, dev = xyz.shape[0], index.num_source, xyz.device
+    M, dev = xyz.shape[0], xyz.device
     idx3 = torch.empty(M, 3, dtype=torch.int32, device=dev)
     w3 = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    org = (ctypes.c_float * 3)(*index.origin)
-    P = None if words is None else (ctypes.c_float * 12)(*[float(v) for v in words])
-    check(_lib.load().psam_transfer_plan(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org),
-                                         float(index.inv_h), float(index.r2), xyz.data_ptr(), M, None if P is None else ctypes.addressof(P), float(eps),
-                                         idx3.data_ptr(), w3.data_ptr(), _stream()), "psam_transfer_plan")
+    org, lead = _transfer_args(index, r2)
+    P, pose_ptr = _pose_arg(words)
+    check(_lib.load().psam_transfer_plan(*lead, xyz.data_ptr(), M, pose_ptr, float(eps), idx3.data_ptr(), w3.data_ptr(), _stream()), "psam_transfer_plan")
     return idx3, w3
 
 
@@ -1636,32 +1669,16 @@ def align_step(index: TransferIndex, xyz: torch.Tensor, pose=None, radius=None, 
     own) or a smaller one -- a larger one is a ValueError, the 27 cells would silently truncate the search.  bits: None, or [ceil(M / 64)] int64 words
     in mask_pack's layout: the queries that take part.  return_nearest: also nearest [M] int32, -1 without a pair.  No host synchronisation."""
     xyz, words, r2, bits = _align_arguments("align_step", index, xyz, pose, radius, bits)
-    M, N, dev = xyz.shape[0], index.num_source, xyz.device
     _chk(xyz, name="xyz")
     L = _lib.load()
-    sums = torch.empty(ALIGN_SUMS, dtype=torch.float64, device=dev)
-    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
-    ws = torch.empty(L.psam_align_workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
-    org = (ctypes.c_float * 3)(*index.origin)
-    P = None if words is None else (ctypes.c_float * 12)(*[float(v) for v in words])
-    check(L.psam_align_step(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org), float(index.inv_h), float(r2),
-                            xyz.data_ptr(), M, None if bits is None else bits.data_ptr(), None if P is None else ctypes.addressof(P),
-                            None if nearest is None else nearest.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_align_step")
-    return (sums, nearest) if return_nearest else sums
+    return _align_call(L.psam_align_step, L.psam_align_workspace_bytes, "psam_align_step", ALIGN_SUMS, index, xyz, words, r2, bits, return_nearest)
 
 
 def _align_arguments(what: str, index, xyz, pose, radius, bits):
-    """The checks align_step and align_plane_step share, in one order, before any device work -> (xyz [M, 3], the pose's fp32 words or None, r2, bits
-    as one checked row or None)."""
-    if not isinstance(index, TransferIndex):
-        raise TypeError(f"{what}: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
-    xyz = _transfer_cloud(xyz, f"{what}: xyz")
+    """The checks align_step and align_plane_step share, in one order, before any device work: _transfer_query's, the pose and the bits
+    -> (xyz [M, 3], the pose's fp32 words or None, r2, bits as one checked row or None)."""
+    xyz, r2 = _transfer_query(what, index, xyz, radius)
     words = transfer_pose(pose)
-    r2 = index.r2
-    if radius is not None:
-        r, _, r2 = transfer_radius(radius)
-        if r > index.radius:
-            raise ValueError(f"{what}: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
     M = xyz.shape[0]
     if bits is not None:
         if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64 or bits.dim() == 2 and bits.shape[0] != 1 or bits.dim() not in (1, 2) or \
@@ -1671,6 +1688,20 @@ def _align_arguments(what: str, index, xyz, pose, radius, bits):
         bits = bits.reshape(-1)
         _chk(bits, torch.int64, name="bits")
     return xyz, words, r2, bits
+
+
+def _align_call(step, workspace_bytes, name: str, num_sums: int, index, xyz, words, r2, bits, return_nearest: bool, *extra):
+    """What the two steps launch alike: the outputs, the workspace and the C entry `step` (`name` for its errors); extra: the device pointers that
+    entry takes after src."""
+    M, dev = xyz.shape[0], xyz.device
+    sums = torch.empty(num_sums, dtype=torch.float64, device=dev)
+    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
+    ws = torch.empty(workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
+    org, (src, *lead) = _transfer_args(index, r2)
+    P, pose_ptr = _pose_arg(words)
+    check(step(src, *extra, *lead, xyz.data_ptr(), M, None if bits is None else bits.data_ptr(), pose_ptr, None if nearest is None else nearest.data_ptr(),
+               sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), name)
+    return (sums, nearest) if return_nearest else sums
 
 
 def align_plane_step(index: TransferIndex, xyz: torch.Tensor, normals: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None,
@@ -1690,20 +1721,11 @@ def align_plane_step(index: TransferIndex, xyz: torch.Tensor, normals: torch.Ten
         raise TypeError(f"align_plane_step: normals: expected {torch.float32}, got {normals.dtype}")
     if normals.device != index.src_xyz.device:
         raise ValueError(f"align_plane_step: normals are on {normals.device}, the index on {index.src_xyz.device}")
-    M, N, dev = xyz.shape[0], index.num_source, xyz.device
     _chk(xyz, name="xyz")
     _chk(normals, name="normals")
     L = _lib.load()
-    sums = torch.empty(PLANE_SUMS, dtype=torch.float64, device=dev)
-    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
-    ws = torch.empty(L.psam_plane_workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
-    org = (ctypes.c_float * 3)(*index.origin)
-    P = None if words is None else (ctypes.c_float * 12)(*[float(v) for v in words])
-    check(L.psam_plane_step(index.src_xyz.data_ptr(), normals.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org),
-                            float(index.inv_h), float(r2), xyz.data_ptr(), M, None if bits is None else bits.data_ptr(),
-                            None if P is None else ctypes.addressof(P), None if nearest is None else nearest.data_ptr(), sums.data_ptr(), ws.data_ptr(),
-                            ws.numel() * 8, _stream()), "psam_plane_step")
-    return (sums, nearest) if return_nearest else sums
+    return _align_call(L.psam_plane_step, L.psam_plane_workspace_bytes, "psam_plane_step", PLANE_SUMS, index, xyz, words, r2, bits, return_nearest,
+                       normals.data_ptr())
 
 
 ALIGN_SCORE_POSES = 4            # PSAM_ALIGN_SCORE_POSES: the poses one workgroup of psam_pose_score takes a tile of queries through
@@ -1722,11 +1744,8 @@ def transfer_poses(poses):
         raise ValueError("align_score: poses must be a [P, 3, 4] or [P, 4, 4] array of numbers") from None
     if A.ndim != 3 or A.shape[1:] not in ((3, 4), (4, 4)) or not 1 <= A.shape[0] <= ALIGN_SCORE_MAX_POSES:
         raise ValueError(f"align_score: poses must be [P, 3, 4] or [P, 4, 4] with 1 <= P <= 2^20, got shape {A.shape}")
-    with np.errstate(over="ignore"):
-        words = A[:, :3].astype(np.float32).reshape(len(A), 12)
-    bad = ~np.isfinite(words).all(1)
-    if A.shape[1] == 4:
-        bad |= (A[:, 3] != np.array([0.0, 0.0, 0.0, 1.0])).any(1)
+    words, bad_row, bad_value = _pose_words(A)
+    bad = bad_row | bad_value
     if bad.any():
         transfer_pose(A[int(np.argmax(bad))])                 # the first bad row, in transfer_pose's own words
         raise ValueError(f"align_score: pose {int(np.argmax(bad))} is not a rigid pose")
@@ -1740,15 +1759,8 @@ def align_score(index: TransferIndex, xyz: torch.Tensor, poses, radius=None):
     tensor), every row checked as transfer_pose checks a pose (ValueError for a value that is not finite or a bad last row); or a [P, 12] float32
     tensor ON THE DEVICE, the rows' twelve words, which is taken AS VALIDATED -- the kernel cannot refuse a pose, one that is not finite scores 0.
     radius: None (the index's own) or a smaller one, a larger one is a ValueError as for align_step.  1 <= P <= 2^20.  No host synchronisation."""
-    if not isinstance(index, TransferIndex):
-        raise TypeError(f"align_score: index must be a TransferIndex (ops.transfer_index), got {type(index).__name__}")
-    xyz = _transfer_cloud(xyz, "align_score: xyz")
-    r2 = index.r2
-    if radius is not None:
-        r, _, r2 = transfer_radius(radius)
-        if r > index.radius:
-            raise ValueError(f"align_score: radius {float(r)} exceeds the index's {float(index.radius)}: the search covers the 27 cells around a query only")
-    M, N, dev = xyz.shape[0], index.num_source, xyz.device
+    xyz, r2 = _transfer_query("align_score", index, xyz, radius)
+    M, dev = xyz.shape[0], xyz.device
     if isinstance(poses, torch.Tensor) and poses.is_cuda and poses.dim() == 2:
         if poses.shape[1] != 12 or not 1 <= poses.shape[0] <= ALIGN_SCORE_MAX_POSES:
             raise ValueError(f"align_score: device poses must be [P, 12] with 1 <= P <= 2^20, got {tuple(poses.shape)}")
@@ -1760,9 +1772,8 @@ def align_score(index: TransferIndex, xyz: torch.Tensor, poses, radius=None):
         words = torch.from_numpy(host).to(dev)
     P = words.shape[0]
     counts = torch.empty(P, dtype=torch.int32, device=dev)
-    org = (ctypes.c_float * 3)(*index.origin)
-    check(_lib.load().psam_pose_score(index.src_xyz.data_ptr(), N, index.ws.data_ptr(), index.ws.numel() * 8, ctypes.addressof(org), float(index.inv_h),
-                                       float(r2), xyz.data_ptr(), M, words.data_ptr(), P, counts.data_ptr(), _stream()), "psam_pose_score")
+    org, lead = _transfer_args(index, r2)
+    check(_lib.load().psam_pose_score(*lead, xyz.data_ptr(), M, words.data_ptr(), P, counts.data_ptr(), _stream()), "psam_pose_score")
     return counts
 
 

@@ -241,9 +241,10 @@ def test_align_entry_points_reject_bad_arguments_on_the_host():
     bad_org = (ctypes.c_float * 3)(-1.0, float("nan"), -1.0)
     bad_pose = (ctypes.c_float * 12)(*([0.0] * 11 + [float("inf")]))
 
-    def refused(status, code, word):
+    def refused(status, code, text):      # the whole text, as the entry worded it before its checks moved into the shared headers
         assert status == code, (status, lib.psam_last_error_string())
-        assert word in lib.psam_last_error_string(), lib.psam_last_error_string()
+        assert lib.psam_last_error_string() == b"psam_align_step: " + text, lib.psam_last_error_string()
+    aligned = b"index_ws must be 16-byte aligned, sums, ws and qry_bits 8-byte aligned, src, qry and nearest 4-byte aligned"
 
     size = lib.psam_align_workspace_bytes
     assert size(1) == size(64) == 160 and size(65) == 320 and size(6007) == 94 * 160 and size(1 << 28) == (1 << 22) * 160
@@ -253,22 +254,22 @@ def test_align_entry_points_reject_bad_arguments_on_the_host():
                 nearest=None, sums=p, ws=p, ws_bytes=big)
     call = lambda **kw: lib.psam_align_step(*{**good, **kw}.values(), None)
     for name in ("src", "index_ws", "origin", "qry", "sums", "ws"):
-        refused(call(**{name: None}), -1, b"null")
-    for name, word in (("N", b"0 < N"), ("M", b"0 < M")):
+        refused(call(**{name: None}), -1, b"null pointer")
+    for name, word in (("N", b"need 0 < N <= 2^28"), ("M", b"need 0 < M <= 2^28")):
         for bad in (0, -5, (1 << 28) + 1):
             refused(call(**{name: bad}), -1, word)
     for name in ("inv_h", "r2"):
         for bad in (0.0, -1.0, float("inf"), float("nan")):
-            refused(call(**{name: bad}), -1, name.encode())
-    refused(call(origin=ctypes.addressof(bad_org)), -1, b"origin")
-    refused(call(pose=ctypes.addressof(bad_pose)), -1, b"pose")
-    refused(call(index_ws=p + 8), -2, b"aligned")
+            refused(call(**{name: bad}), -1, name.encode() + b" must be finite and positive")
+    refused(call(origin=ctypes.addressof(bad_org)), -1, b"origin must be finite")
+    refused(call(pose=ctypes.addressof(bad_pose)), -1, b"pose must be finite")
+    refused(call(index_ws=p + 8), -2, aligned)
     for name in ("sums", "ws", "qry_bits"):
-        refused(call(**{name: p + 4}), -2, b"aligned")
+        refused(call(**{name: p + 4}), -2, aligned)
     for name in ("src", "qry", "nearest"):
-        refused(call(**{name: p + 2}), -2, b"aligned")
-    refused(call(index_ws_bytes=lib.psam_transfer_index_workspace_bytes(N) - 1), -3, b"workspace too small")
-    refused(call(ws_bytes=size(M) - 1), -3, b"workspace too small")
+        refused(call(**{name: p + 2}), -2, aligned)
+    refused(call(index_ws_bytes=lib.psam_transfer_index_workspace_bytes(N) - 1), -3, b"index workspace too small (psam_transfer_index_workspace_bytes)")
+    refused(call(ws_bytes=size(M) - 1), -3, b"workspace too small (psam_align_workspace_bytes)")
 
 
 # ------------------------------------------------------------------------------------------------ ops

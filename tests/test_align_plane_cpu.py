@@ -285,6 +285,67 @@ def test_icp_host_loop_stops_on_few_used_pairs_and_a_single_plane():
     assert not out.converged and "degenerate" in out.reason and out.iterations == 1 and np.array_equal(out.pose, IDENTITY)
 
 
+def _host_loop_cases():
+    """(name, a run of align.icp on a stand-in step) for every way the host loop ends, point to point and point to plane, on the fixtures of
+    align_reference.py and align_plane_reference.py."""
+    a, n, b = P.plane_case()
+    cfg = X.AlignConfig(A.ICP_RADIUS, A.ICP_FINAL, A.ICP_SHRINK, A.ICP_ITERATIONS)
+
+    def point(r_index):
+        return lambda index, xyz, pose, radius, bits: A.step(a, r_index, xyz, np.asarray(pose, dtype=np.float64).astype(f32), radius)[1]
+    done = X.icp("index", b, cfg, step=point(A.ICP_RADIUS))
+    yield "point", done
+    yield "point, out of iterations", X.icp("index", b, dataclasses.replace(cfg, iterations=3), step=point(A.ICP_RADIUS))
+    # started at the fixed point with tolerances set: the words repeat AND the update is small
+    yield "point, fixed and small", X.icp("index", b, X.AlignConfig(A.ICP_FINAL, tol_rotation=1e-4, tol_translation=1e-4), init=done.pose,
+                                          step=point(A.ICP_FINAL))
+    # one step short of the fixed point, generous tolerances: small alone
+    yield "point, small", X.icp("index", b, X.AlignConfig(A.ICP_FINAL, tol_rotation=1e-2, tol_translation=1e-2), init=A.TRUE_POSE, step=point(A.ICP_FINAL))
+    yield "point, few pairs", X.icp("index", (b + f32(5.0)).astype(f32), X.AlignConfig(A.ICP_RADIUS), step=point(A.ICP_RADIUS))
+    line = np.outer(np.linspace(-0.5, 0.5, 40), [1.0, 0.5, 0.25]).astype(f32)
+    yield "point, collinear", X.icp("index", line, X.AlignConfig(0.1), step=lambda index, xyz, pose, radius, bits: A.step(line, 0.1, xyz, None, radius)[1])
+
+    log = []
+    plane = _reference_step(a, A.ICP_RADIUS, n, log)
+    done = X.icp("index", b, cfg, step=plane, normals=n)
+    yield "plane", done
+    yield "plane, out of iterations", X.icp("index", b, dataclasses.replace(cfg, iterations=3), step=plane, normals=n)
+    yield "plane, tight", X.icp("index", b, dataclasses.replace(cfg, iterations=8), step=plane, normals=n, plane=X.PlaneConfig(1e-12, 1e-12))
+    # sums whose gradient [3..8] is zero: the update is exactly zero, so the words repeat AND the update is small
+    still = log[len(done.history) - 1].copy()
+    still[3:9] = 0.0
+    yield "plane, fixed and small", X.icp("index", b, X.AlignConfig(A.ICP_FINAL), init=IDENTITY, step=lambda *args: still, normals=n)
+    few = np.zeros_like(n)
+    near = A.step(a, A.ICP_RADIUS, b, IDENTITY.astype(f32))[0]
+    keep = np.unique(near[near >= 0])[:3]
+    few[keep] = n[keep]
+    yield "plane, few used pairs", X.icp("index", b, X.AlignConfig(A.ICP_RADIUS), step=_reference_step(a, A.ICP_RADIUS, few), normals=few)
+    floor = np.where((n[:, 2:3] == 1), n, 0).astype(f32)
+    yield "plane, one plane", X.icp("index", b, X.AlignConfig(A.ICP_RADIUS), step=_reference_step(a, A.ICP_RADIUS, floor), normals=floor)
+
+
+def _alignment_record(out):
+    """An Alignment as JSON holds it: every float in float.hex, so that nothing is lost and a NaN has a spelling."""
+    h = lambda v: float(v).hex()
+    return dict(pose=[h(v) for v in np.asarray(out.pose).reshape(-1)], pairs=out.pairs, coverage=h(out.coverage), rms=h(out.rms), iterations=out.iterations,
+                converged=out.converged, reason=out.reason, history=[[p, h(rms), h(radius)] for p, rms, radius in out.history], search=out.search)
+
+
+def test_icp_runs_one_loop_with_the_results_of_the_two_it_replaced():
+    """align.icp ran two copies of its loop, one per kind of step, until they became one.  tests/golden/align_icp_loops.json holds what the two copies
+    returned for _host_loop_cases() -- every field of the Alignment, history, reason and iterations included, every float as float.hex -- recorded
+    with the last commit that had both.  The one loop must return the same, field for field.  In particular the reason when the fp32 words repeat AND
+    the update is small stays "fixed point" for point to point and "tolerance" for point to plane."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "align_icp_loops.json")))
+    got = {name: _alignment_record(out) for name, out in _host_loop_cases()}
+    assert sorted(got) == sorted(want)
+    for name in want:
+        assert got[name] == want[name], name
+    assert got["point, fixed and small"]["reason"] == "fixed point" and got["plane, fixed and small"]["reason"] == "tolerance"
+    assert {r["reason"].split(":")[0] for r in want.values()} == {"fixed point", "tolerance", "iterations", "pairs", "degenerate"}
+
+
 def test_plane_without_normals_and_other_bad_arguments_are_refused():
     b = np.zeros((10, 3), dtype=f32)
     cfg = X.AlignConfig(0.1)
@@ -335,7 +396,8 @@ def test_plane_entry_points_are_declared_bound_and_exported():
     assert "atomic" not in src.replace("no atomics", "") and "order of every fp64 addition is a function of M" in src
     # one copy of the posed coordinate, the cell, the candidate walk and the second kernel: both steps take them from the shared headers
     for name, header in (("bool transfer_cell(", "transfer_index.h"), ("void transfer_candidates(", "transfer_index.h"), ("void pose_apply(", "rigid_pose.h"),
-                         ("void align_combine_kernel(", "align_combine.h"), ("int64_t align_waves(", "align_combine.h")):
+                         ("void align_combine_kernel(", "align_combine.h"), ("int64_t align_waves(", "align_combine.h"), ("bool align_zero_row(", "align_combine.h"),
+                         ("void align_store_row(", "align_combine.h"), ("int32_t align_step_entry(", "align_combine.h")):
         assert name in open(os.path.join(csrc, header)).read(), name
         for f in ("align.hip", "align_plane.hip"):
             text = open(os.path.join(csrc, f)).read()
@@ -350,9 +412,11 @@ def test_plane_entry_points_reject_bad_arguments_on_the_host():
     bad_org = (ctypes.c_float * 3)(-1.0, float("nan"), -1.0)
     bad_pose = (ctypes.c_float * 12)(*([0.0] * 11 + [float("inf")]))
 
-    def refused(status, code, word):
+    def refused(status, code, text):      # the whole text, as the entry worded it before its checks moved into the shared headers
         assert status == code, (status, lib.psam_last_error_string())
-        assert word in lib.psam_last_error_string() and b"psam_plane_step" in lib.psam_last_error_string(), lib.psam_last_error_string()
+        assert lib.psam_last_error_string() == b"psam_plane_step: " + text, lib.psam_last_error_string()
+    aligned = b"index_ws must be 16-byte aligned, sums, ws and qry_bits 8-byte aligned, src, src_normals, qry and nearest 4-byte aligned"
+    small = b"workspace too small (psam_plane_workspace_bytes)"
 
     size = lib.psam_plane_workspace_bytes
     assert size(1) == size(64) == 256 and size(65) == 512 and size(6007) == 94 * 256 and size(1 << 28) == (1 << 22) * 256
@@ -362,27 +426,27 @@ def test_plane_entry_points_reject_bad_arguments_on_the_host():
                 pose=None, nearest=None, sums=p, ws=p, ws_bytes=big)
     call = lambda **kw: lib.psam_plane_step(*{**good, **kw}.values(), None)
     for name in ("src", "src_normals", "index_ws", "origin", "qry", "sums", "ws"):
-        refused(call(**{name: None}), -1, b"null")
-    for name, word in (("N", b"0 < N"), ("M", b"0 < M")):
+        refused(call(**{name: None}), -1, b"null pointer")
+    for name, word in (("N", b"need 0 < N <= 2^28"), ("M", b"need 0 < M <= 2^28")):
         for bad in (0, -5, (1 << 28) + 1):
             refused(call(**{name: bad}), -1, word)
     for name in ("inv_h", "r2"):
         for bad in (0.0, -1.0, float("inf"), float("nan")):
-            refused(call(**{name: bad}), -1, name.encode())
-    refused(call(origin=ctypes.addressof(bad_org)), -1, b"origin")
-    refused(call(pose=ctypes.addressof(bad_pose)), -1, b"pose")
-    refused(call(index_ws=p + 8), -2, b"aligned")
+            refused(call(**{name: bad}), -1, name.encode() + b" must be finite and positive")
+    refused(call(origin=ctypes.addressof(bad_org)), -1, b"origin must be finite")
+    refused(call(pose=ctypes.addressof(bad_pose)), -1, b"pose must be finite")
+    refused(call(index_ws=p + 8), -2, aligned)
     for name in ("sums", "ws", "qry_bits"):
-        refused(call(**{name: p + 4}), -2, b"aligned")
+        refused(call(**{name: p + 4}), -2, aligned)
     for name in ("src", "src_normals", "qry", "nearest"):
-        refused(call(**{name: p + 2}), -2, b"aligned")
-    refused(call(index_ws_bytes=lib.psam_transfer_index_workspace_bytes(N) - 1), -3, b"workspace too small")
-    refused(call(ws_bytes=size(M) - 1), -3, b"workspace too small")
-    refused(call(ws_bytes=lib.psam_align_workspace_bytes(M)), -3, b"workspace too small")      # the point-to-point size does not do
+        refused(call(**{name: p + 2}), -2, aligned)
+    refused(call(index_ws_bytes=lib.psam_transfer_index_workspace_bytes(N) - 1), -3, b"index workspace too small (psam_transfer_index_workspace_bytes)")
+    refused(call(ws_bytes=size(M) - 1), -3, small)
+    refused(call(ws_bytes=lib.psam_align_workspace_bytes(M)), -3, small)      # the point-to-point size does not do
     # the order of psam_align_step: a null pointer before a range, a range before an alignment, an alignment before a size
-    refused(call(src_normals=None, N=0), -1, b"null")
-    refused(call(N=0, qry=p + 2), -1, b"0 < N")
-    refused(call(src_normals=p + 2, ws_bytes=0), -2, b"aligned")
+    refused(call(src_normals=None, N=0), -1, b"null pointer")
+    refused(call(N=0, qry=p + 2), -1, b"need 0 < N <= 2^28")
+    refused(call(src_normals=p + 2, ws_bytes=0), -2, aligned)
 
 
 # ------------------------------------------------------------------------------------------------ ops

@@ -337,25 +337,26 @@ def test_score_entry_rejects_bad_arguments_on_the_host():
     org = (ctypes.c_float * 3)(-1.0, -1.0, -1.0)
     bad_org = (ctypes.c_float * 3)(-1.0, float("nan"), -1.0)
 
-    def refused(status, code, word):
+    def refused(status, code, text):      # the whole text, as the entry worded it before its checks moved into the shared header
         assert status == code, (status, lib.psam_last_error_string())
-        assert word in lib.psam_last_error_string(), lib.psam_last_error_string()
+        assert lib.psam_last_error_string() == b"psam_pose_score: " + text, lib.psam_last_error_string()
+    aligned = b"index_ws must be 16-byte aligned, src, qry, poses and counts 4-byte aligned"
     N, M, P, big = 1000, 100, 7, 1 << 20
     good = dict(src=p, N=N, index_ws=p, index_ws_bytes=big, origin=ctypes.addressof(org), inv_h=4.0, r2=0.0625, qry=p, M=M, poses=p, P=P, counts=p)
     call = lambda **kw: lib.psam_pose_score(*{**good, **kw}.values(), None)
     for name in ("src", "index_ws", "origin", "qry", "poses", "counts"):
-        refused(call(**{name: None}), -1, b"null")
-    for name, word, top in (("N", b"0 < N", 1 << 28), ("M", b"0 < M", 1 << 28), ("P", b"0 < P", 1 << 20)):
+        refused(call(**{name: None}), -1, b"null pointer")
+    for name, word, top in (("N", b"need 0 < N <= 2^28", 1 << 28), ("M", b"need 0 < M <= 2^28", 1 << 28), ("P", b"need 0 < P <= 2^20", 1 << 20)):
         for bad in (0, -5, top + 1):
             refused(call(**{name: bad}), -1, word)
     for name in ("inv_h", "r2"):
         for bad in (0.0, -1.0, float("inf"), float("nan")):
-            refused(call(**{name: bad}), -1, name.encode())
-    refused(call(origin=ctypes.addressof(bad_org)), -1, b"origin")
-    refused(call(index_ws=p + 8), -2, b"aligned")
+            refused(call(**{name: bad}), -1, name.encode() + b" must be finite and positive")
+    refused(call(origin=ctypes.addressof(bad_org)), -1, b"origin must be finite")
+    refused(call(index_ws=p + 8), -2, aligned)
     for name in ("src", "qry", "poses", "counts"):
-        refused(call(**{name: p + 2}), -2, b"aligned")
-    refused(call(index_ws_bytes=lib.psam_transfer_index_workspace_bytes(N) - 1), -3, b"workspace too small")
+        refused(call(**{name: p + 2}), -2, aligned)
+    refused(call(index_ws_bytes=lib.psam_transfer_index_workspace_bytes(N) - 1), -3, b"index workspace too small (psam_transfer_index_workspace_bytes)")
 
 
 def test_align_score_refuses_bad_arguments_before_the_library_is_touched(monkeypatch):

@@ -96,9 +96,12 @@ def test_transfer_entry_points_reject_bad_arguments_on_the_host():
     o, bo = ctypes.addressof(org), ctypes.addressof(bad_org)
     pose = (ctypes.c_float * 12)(*([0.0] * 11 + [float("inf")]))
 
-    def refused(status, code, word):
+    entry = [b"psam_transfer_index_build: "]
+
+    def refused(status, code, text):      # the whole text, as the entry worded it before its checks moved into the shared header
         assert status == code, (status, lib.psam_last_error_string())
-        assert word in lib.psam_last_error_string(), lib.psam_last_error_string()
+        assert lib.psam_last_error_string() == entry[0] + text, lib.psam_last_error_string()
+    small = b"workspace too small (psam_transfer_index_workspace_bytes)"
 
     size = lib.psam_transfer_index_workspace_bytes
     assert size(131072) == (1 << 18) * 12 + 131072 * 4                               # 2^18 slots of a key and a head, one link per source
@@ -106,35 +109,36 @@ def test_transfer_entry_points_reject_bad_arguments_on_the_host():
     assert size(0) == 0 and size(-1) == 0 and size((1 << 28) + 1) == 0
     N, big = 1000, 1 << 20
     build = lambda *a: lib.psam_transfer_index_build(*a, None)
-    refused(build(None, N, o, 4.0, p, big), -1, b"null")
-    refused(build(p, N, None, 4.0, p, big), -1, b"null")
-    refused(build(p, N, o, 4.0, None, big), -1, b"null")
-    refused(build(p, 0, o, 4.0, p, big), -1, b"0 < N")
-    refused(build(p, (1 << 28) + 1, o, 4.0, p, big), -1, b"0 < N")
+    refused(build(None, N, o, 4.0, p, big), -1, b"null pointer")
+    refused(build(p, N, None, 4.0, p, big), -1, b"null pointer")
+    refused(build(p, N, o, 4.0, None, big), -1, b"null pointer")
+    refused(build(p, 0, o, 4.0, p, big), -1, b"need 0 < N <= 2^28")
+    refused(build(p, (1 << 28) + 1, o, 4.0, p, big), -1, b"need 0 < N <= 2^28")
     for bad in (0.0, -1.0, float("inf"), float("nan")):
-        refused(build(p, N, o, bad, p, big), -1, b"inv_h")
-    refused(build(p, N, bo, 4.0, p, big), -1, b"origin")
-    refused(build(p, N, o, 4.0, p, size(N) - 1), -3, b"workspace too small")
-    refused(build(p, N, o, 4.0, p + 8, big), -2, b"aligned")
-    refused(build(p + 2, N, o, 4.0, p, big), -2, b"aligned")
+        refused(build(p, N, o, bad, p, big), -1, b"inv_h must be finite and positive")
+    refused(build(p, N, bo, 4.0, p, big), -1, b"origin must be finite")
+    refused(build(p, N, o, 4.0, p, size(N) - 1), -3, small)
+    refused(build(p, N, o, 4.0, p + 8, big), -2, b"workspace must be 16-byte aligned, src 4-byte aligned")
+    refused(build(p + 2, N, o, 4.0, p, big), -2, b"workspace must be 16-byte aligned, src 4-byte aligned")
 
     plan = lambda *a: lib.psam_transfer_plan(*a, None)
+    entry[0] = b"psam_transfer_plan: "
     good = dict(src=p, N=N, ws=p, ws_bytes=big, origin=o, inv_h=4.0, r2=0.0625, qry=p, M=10, pose=None, eps=1e-8, idx3=p, w3=p)
     call = lambda **kw: plan(*{**good, **kw}.values())
     for name in ("src", "ws", "origin", "qry", "idx3", "w3"):
-        refused(call(**{name: None}), -1, b"null")
-    for name, word in (("N", b"0 < N"), ("M", b"0 < M")):
+        refused(call(**{name: None}), -1, b"null pointer")
+    for name, word in (("N", b"need 0 < N <= 2^28"), ("M", b"need 0 < M <= 2^28")):
         for bad in (0, -5, (1 << 28) + 1):
             refused(call(**{name: bad}), -1, word)
     for name in ("inv_h", "r2", "eps"):
         for bad in (0.0, -1.0, float("inf"), float("nan")):
-            refused(call(**{name: bad}), -1, name.encode())
-    refused(call(origin=bo), -1, b"origin")
-    refused(call(pose=ctypes.addressof(pose)), -1, b"pose")
-    refused(call(ws_bytes=size(N) - 1), -3, b"workspace too small")
-    refused(call(ws=p + 8), -2, b"aligned")
+            refused(call(**{name: bad}), -1, name.encode() + b" must be finite and positive")
+    refused(call(origin=bo), -1, b"origin must be finite")
+    refused(call(pose=ctypes.addressof(pose)), -1, b"pose must be finite")
+    refused(call(ws_bytes=size(N) - 1), -3, small)
+    refused(call(ws=p + 8), -2, b"workspace must be 16-byte aligned")
     for name in ("src", "qry", "idx3", "w3"):
-        refused(call(**{name: p + 2}), -2, b"aligned")
+        refused(call(**{name: p + 2}), -2, b"src, qry, idx3 and w3 must be 4-byte aligned")
 
 
 # ------------------------------------------------------------------------------------------------ the Python host

@@ -1095,6 +1095,52 @@ size_t psam_superpoint_snap_workspace_bytes(int32_t K, int32_t N, int32_t S);
 int32_t psam_superpoint_snap(const uint64_t* bits, const int32_t* point_label, const int32_t* size, int32_t K, int32_t N, int32_t S, int32_t q16,
                              uint64_t* bits_out, int32_t* area_out, uint8_t* changed, void* ws, size_t ws_bytes, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- scan map */
+
+/* A scan map accumulates posed scans into one persistent, labelled voxel map in the normalised frame (point_sam_amd/scanmap.py).  A map voxel is the
+ * voxel of psam_voxel_downsample at origin (-1, -1, -1) and the map's inv_h, bit for bit.  The library allocates nothing and keeps no state: the map
+ * lives in a block of the caller's, psam_map_bytes bytes of DEVICE memory, 16-byte aligned, and every entry takes the block with the two capacities
+ * it was cleared with (0 < max_voxels, max_pairs <= 2^28).  A null pointer or a bad shape returns -1, a short block or workspace -3, a misaligned
+ * pointer -2, all before any launch.  No call synchronises with the host.
+ *
+ * The block begins with PSAM_MAP_HEADER_INTS int32 words, which the caller may read back:
+ *   0 max_voxels   1 max_pairs   2 inv_h (the bits of the float)   3 flags   4 V, the number of voxels   5 the number of adds so far
+ *   6 the number of distinct (id, label) pairs   7 .. 9 of the last add: its new voxels, accepted points, rejected points
+ *   10, 11 the accepted points of all adds, one uint64                12 .. 15 zero
+ * flags != 0: the map is dead until it is cleared (1: an add would have passed max_voxels, 2: its pairs passed max_pairs, 4: its accepted points
+ * would have passed 2^31 - 1 in total, the bound under which every count fits an int32 and every sum a 64-bit word).  Both capacity conditions are
+ * functions of the inputs alone.  A dead map is never written outside its block, and its adds change nothing further.
+ *
+ * psam_map_clear.  Empties the map and sets inv_h (finite, positive; the voxel size is 1 / inv_h).
+ * psam_map_add.  xyz, rgb [M, 3] fp32, labels [M] int32 or NULL, pose: 12 floats in HOST memory (row-major 3 x 4, scan frame -> map frame, finite) or
+ *   NULL for the identity, which applies no arithmetic.  0 < M <= 2^28.  Point i:
+ *     p = ((P[a][0] x + P[a][1] y) + P[a][2] z) + P[a][3] per axis, every fp32 operation rounded on its own;
+ *     cell_a = floorf((p_a - (-1)) * inv_h), which must lie in [0, 2^21);  fixed point q = floor((double)v * 2^20) + 2^20 for v in [-1, 1].
+ *   The point is accepted iff all three cells exist, -1 <= p_a <= 1 and -1 <= rgb <= 1 on every axis (a NaN compares false).  ids [M] int32: the
+ *   voxel of an accepted point, -1 for a rejected one.  Voxel ids are dense and permanent: a voxel new in this add gets V_before + r, r its rank
+ *   among the new voxels ordered by the lowest accepted point index in them.  Per voxel the map keeps count, sum q [3], sum of the colours' q [3]
+ *   (exact integers), first_seen and last_seen (the number of the add, from 1), and per (voxel, label >= 0) the number of points: a negative label
+ *   is an unlabelled observation.  ws: psam_map_add_workspace_bytes(M) bytes, 16-byte aligned.
+ * psam_map_locate.  ids [M] of xyz under the pose: the same position test and cell, -1 where the map has no such voxel.  Changes nothing.
+ * psam_map_labels.  label, votes [V] int32: per voxel the label with the most points, a tie going to the LOWER label; -1 and 0 where the best count
+ *   is below min_votes (>= 1).  0 < V <= max_voxels; entries past the map's own V get -1 and 0.
+ * psam_map_cloud.  xyz, rgb [V, 3] fp32 = fl32(fl64(fl64(sum) / fl64(count)) * 2^-20 - 1), every fp64 operation rounded on its own; zeros past V.
+ * psam_map_fields.  count, first_seen, last_seen [V] int32, keys [V] int64 (cell_x | cell_y << 21 | cell_z << 42) and sums [V, 6] int64 (sum q of the
+ *   position, then of the colour), each may be NULL (not all); past V: 0, 0, 0, -1, 0. */
+#define PSAM_MAP_HEADER_INTS 16
+size_t psam_map_bytes(int32_t max_voxels, int32_t max_pairs);
+int32_t psam_map_clear(void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, float inv_h, psam_stream_t stream);
+size_t psam_map_add_workspace_bytes(int32_t M);
+int32_t psam_map_add(void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, const float* xyz, const float* rgb, const int32_t* labels,
+                     int32_t M, const float* pose, int32_t* ids, void* ws, size_t ws_bytes, psam_stream_t stream);
+int32_t psam_map_locate(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, const float* xyz, int32_t M, const float* pose,
+                        int32_t* ids, psam_stream_t stream);
+int32_t psam_map_labels(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, int32_t min_votes, int32_t* label,
+                        int32_t* votes, psam_stream_t stream);
+int32_t psam_map_cloud(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, float* xyz, float* rgb, psam_stream_t stream);
+int32_t psam_map_fields(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, int32_t* count, int32_t* first_seen,
+                        int32_t* last_seen, int64_t* keys, int64_t* sums, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

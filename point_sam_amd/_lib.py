@@ -181,6 +181,14 @@ SIGNATURES = {
     "psam_superpoints": (i32, [ptr, ptr, ptr, ptr, ptr, i32, i32, i32, f32, f64, i32, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
     "psam_superpoint_snap_workspace_bytes": (size_t, [i32, i32, i32]),
     "psam_superpoint_snap": (i32, [ptr, ptr, ptr, i32, i32, i32, i32, ptr, ptr, ptr, ptr, size_t, ptr]),
+    "psam_map_bytes": (size_t, [i32, i32]),
+    "psam_map_clear": (i32, [ptr, size_t, i32, i32, f32, ptr]),
+    "psam_map_add_workspace_bytes": (size_t, [i32]),
+    "psam_map_add": (i32, [ptr, size_t, i32, i32, ptr, ptr, ptr, i32, ptr, ptr, ptr, size_t, ptr]),
+    "psam_map_locate": (i32, [ptr, size_t, i32, i32, ptr, i32, ptr, ptr, ptr]),
+    "psam_map_labels": (i32, [ptr, size_t, i32, i32, i32, i32, ptr, ptr, ptr]),
+    "psam_map_cloud": (i32, [ptr, size_t, i32, i32, i32, ptr, ptr, ptr]),
+    "psam_map_fields": (i32, [ptr, size_t, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]),
 }
 
 

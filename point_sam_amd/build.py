@@ -58,6 +58,8 @@ SOURCES = [
     ("normals.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # superpoints: the join rule's fp64 dot product is (x x' + y y') + z z' with nothing contracted, so that a host reference decides every edge alike.
     ("superpoints.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # scan maps: scene.hip's cells of the pose of csrc/rigid_pose.h, and an fp64 mean rounded one operation at a time; flags as for transfer.hip.
+    ("scanmap.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

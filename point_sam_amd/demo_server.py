@@ -23,6 +23,8 @@ POST /frames {depth, rgb, cameras, far, edge?, depth_scale?} (not in the referen
 /click_pixel with "frame": f then takes a click on photograph f itself.
 POST /fuse_labels {labels, tau, overlap?, min_points?, min_votes?, consistent?} (not in the reference): the frames' 2-D segmentations fused into one
 instance labelling of that cloud (predictor.fuse_labels).
+POST /map/add {pose?, labels?} . POST /map {min_votes?} . POST /map/clear (not in the reference): the loaded cloud, under its pose, is added to the
+session's scan map (predictor.map_add, point_sam_amd/scanmap.py); /map returns the map's voxels as a cloud with one voted label each.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -63,8 +65,13 @@ class DemoSession:
 
     def __init__(self, predictor, models_dir: str = ".", pointcloud: str = None, output_dir: str = "results", device="cuda", static_dir: str = None,
                  working_points: int = None, clean_min_points: int = None, crop_points: int = None, smooth_edges: bool = False,
-                 snap_superpoints: bool = False):
+                 snap_superpoints: bool = False, map_voxel_size: float = 2.0 ** -6, map_max_voxels: int = 1 << 20):
         self.predictor = predictor
+        from . import ops
+        ops.map_inv_h(map_voxel_size)
+        ops.map_capacities(map_max_voxels)
+        # /map/add: the voxel size and the capacity of the session's scan map (scanmap.ScanMap), created by the first add
+        self.map_voxel_size, self.map_max_voxels, self.scan_map = float(map_voxel_size), map_max_voxels, None
         if not isinstance(snap_superpoints, bool):
             raise ValueError(f"snap_superpoints must be True or False, got {snap_superpoints!r}")
         # True: /segment_all and /instances snap every proposal to whole superpoints (ProposalConfig.snap = the default SuperpointConfig, unless the
@@ -558,6 +565,77 @@ class DemoSession:
                                   "aabb_hi": num(geo.aabb_hi[k]), "count": int(geo.count[k]), "mean_rgb": None if geo.mean_rgb is None else num(geo.mean_rgb[k])})
             return dict(out, boxes=boxes)
 
+    # ---- the scan map (point_sam_amd/scanmap.py) -----------------------------------------------------------------
+    def _map_error(self, call):
+        """Runs `call`; a map past its capacities is the client's 400, not a crash of the handler."""
+        from .scanmap import MapOverflow
+        try:
+            return call()
+        except MapOverflow as e:
+            raise ValueError(str(e)) from None
+
+    def map_add(self, data: dict) -> dict:
+        """Adds the loaded cloud to the session's scan map (created by the first add: predictor.new_map(map_voxel_size, map_max_voxels)): {"pose": 3 x
+        4 or 4 x 4 rows from the loaded cloud's coordinates to the map's (optional), "labels": [N ints, negative = none] (optional; without it point n
+        gets the index of the first kept /next mask or current /segment mask that holds it, -1 outside all)} -> {"new_voxels", "accepted",
+        "rejected", "num_voxels", "num_adds"}.  A bad value or a full map is a 400."""
+        with self.lock:
+            if self.pc_xyz is None:
+                raise ValueError("/map/add before a point cloud was set")
+            if not isinstance(data, dict) or set(data) - {"pose", "labels"}:
+                raise ValueError('/map/add takes {"pose": rows (optional), "labels": [ints] (optional)}')
+            from . import ops
+            pose = data.get("pose")
+            ops.transfer_pose(pose)
+            N = self.pc_xyz.shape[1]
+            if "labels" in data:
+                lab = data["labels"]
+                if not isinstance(lab, list) or len(lab) != N or any(isinstance(v, bool) or not isinstance(v, int) or not -2 ** 31 <= v < 2 ** 31 for v in lab):
+                    raise ValueError(f"labels must be a list of {N} 32-bit integers, one per point of the loaded cloud")
+                labels = np.asarray(lab, dtype=np.int32)
+            else:
+                masks = list(self.masks) + ([self.segment_mask.cpu().numpy()] if self.segment_mask is not None else [])
+                if any(m.shape != (N,) for m in masks):
+                    raise ValueError("/map/add: a kept mask does not belong to the loaded cloud")
+                labels = np.full(N, -1, dtype=np.int32)
+                for k in reversed(range(len(masks))):
+                    labels[np.asarray(masks[k], dtype=bool)] = k
+            with torch.no_grad():
+                crop, self.crop = self.crop, None          # the whole loaded cloud is the scan, whatever crop is active
+                try:
+                    self._set_cloud()
+                    if self.scan_map is None:
+                        self.scan_map = self.predictor.new_map(self.map_voxel_size, self.map_max_voxels)
+                    res = self._map_error(lambda: self.predictor.map_add(self.scan_map, torch.from_numpy(labels).to(self.device), pose))
+                finally:
+                    self.crop = crop
+            return {"new_voxels": int(res.new_voxels), "accepted": int(res.accepted), "rejected": int(res.rejected),
+                    "num_voxels": int(self.scan_map.num_voxels), "num_adds": int(self.scan_map.num_adds)}
+
+    def map_get(self, data: dict) -> dict:
+        """The map as a cloud: {"min_votes": n (optional, default 1)} -> {"xyz", "rgb" (flattened, as /pointcloud/), "labels": [V ints, -1 = none],
+        "votes": [V ints]}.  Before any /map/add: a 400."""
+        with self.lock:
+            if not isinstance(data, dict) or set(data) - {"min_votes"}:
+                raise ValueError('/map takes {"min_votes": n} (or nothing)')
+            min_votes = data.get("min_votes", 1)
+            if isinstance(min_votes, bool) or not isinstance(min_votes, int) or not 1 <= min_votes < 2 ** 31:
+                raise ValueError("min_votes must be an integer >= 1")
+            if self.scan_map is None or self.scan_map.num_voxels == 0:
+                raise ValueError("/map before any /map/add: the map is empty")
+            with torch.no_grad():
+                xyz, rgb = self._map_error(self.scan_map.cloud)
+                label, votes = self._map_error(lambda: self.scan_map.labels(min_votes))
+            return {"xyz": xyz.cpu().numpy().astype(np.float64).flatten().tolist(), "rgb": rgb.cpu().numpy().astype(np.float64).flatten().tolist(),
+                    "labels": label.cpu().numpy().astype(int).tolist(), "votes": votes.cpu().numpy().astype(int).tolist()}
+
+    def map_clear(self) -> dict:
+        """Empties the session's scan map (a map that hit a capacity lives again)."""
+        with self.lock:
+            if self.scan_map is not None:
+                self.scan_map.clear()
+            return {"status": "cleared"}
+
     def crop_selection(self, data: dict) -> dict:
         """Zoom into the object just segmented: {"margin": m} (optional, default 0.1) -> the ball around the current /segment mask, its centre the
         mask's centroid and its radius the distance to the farthest point of the mask times 1 + m (predictor.set_crop_to_mask); from then on as
@@ -666,6 +744,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
                       "/frames": lambda: session.set_frames(data), "/fuse_labels": lambda: session.fuse_labels(data),
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/instances": lambda: session.instances(data), "/superpoints": lambda: session.superpoints(data), "/crop/selection": lambda: session.crop_selection(data),
+                      "/map/add": lambda: session.map_add(data), "/map": lambda: session.map_get(data), "/map/clear": session.map_clear,
                       "/clear": session.clear, "/next": session.next, "/save": session.save}
             fn = routes.get(self.path)
             if fn is None:
@@ -703,6 +782,8 @@ def build_parser() -> argparse.ArgumentParser:
                          "instead of copying its voxel's")
     ap.add_argument("--snap-superpoints", action="store_true",
                     help="/segment_all and /instances: snap every proposal to whole superpoints (planar patches grown from the surface normals)")
+    ap.add_argument("--map-voxel-size", type=float, default=2.0 ** -6, help="POST /map/add: the voxel size of the session's scan map (normalised units)")
+    ap.add_argument("--map-max-voxels", type=int, default=1 << 20, help="POST /map/add: the scan map's capacity in voxels; an add past it is a 400")
     return ap
 
 
@@ -712,7 +793,8 @@ def main():
     pred = PointSAMPredictor.from_config(args.config, args.ckpt, precision=args.precision)
     srv = serve(DemoSession(pred, args.models_dir, args.pointcloud, static_dir=args.static_dir, working_points=args.working_points,
                             clean_min_points=args.clean_min_points, crop_points=args.crop_points, smooth_edges=args.smooth_edges,
-                            snap_superpoints=args.snap_superpoints), args.host, args.port)
+                            snap_superpoints=args.snap_superpoints, map_voxel_size=args.map_voxel_size, map_max_voxels=args.map_max_voxels),
+                args.host, args.port)
     print(f"Point-SAM demo back end on http://{args.host}:{args.port}")
     srv.serve_forever()
 

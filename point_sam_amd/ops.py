@@ -2429,3 +2429,148 @@ def superpoint_snap(bits: torch.Tensor, point_label: torch.Tensor, size: torch.T
     check(L.psam_superpoint_snap(bits.data_ptr(), point_label.data_ptr(), size.data_ptr(), K, N, S, q16, out.data_ptr(), area.data_ptr(),
                                  changed.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_superpoint_snap")
     return out, area, changed
+
+
+# ------------------------------------------------------------------------------------------ scan maps (csrc/scanmap.hip)
+MAP_MAX = 1 << 28                # points per add, and both capacities
+MAP_HEADER_INTS = 16             # PSAM_MAP_HEADER_INTS
+MAP_FLAG_VOXELS, MAP_FLAG_PAIRS, MAP_FLAG_COUNTS = 1, 2, 4
+# the header's words (include/pointsam_hip.h: scan map)
+MAP_H_FLAGS, MAP_H_V, MAP_H_ADDS, MAP_H_PAIRS, MAP_H_NEW, MAP_H_ACCEPTED, MAP_H_REJECTED = 3, 4, 5, 6, 7, 8, 9
+
+
+def map_inv_h(voxel_size):
+    """-> fl32(1 / fl32(voxel_size)), as voxel_downsample forms it.  ValueError unless the size and its inverse are finite positive fp32 numbers."""
+    import numpy as np
+    if isinstance(voxel_size, bool) or not isinstance(voxel_size, (int, float, np.floating, np.integer)):
+        raise ValueError(f"map: voxel_size must be a number, got {voxel_size!r}")
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        h = np.float32(voxel_size)
+        inv_h = np.float32(1) / h
+    if not (np.isfinite(h) and h > 0 and np.isfinite(inv_h) and inv_h > 0):
+        raise ValueError(f"map: voxel_size must be finite and positive with a finite positive fp32 inverse, got {voxel_size!r}")
+    return inv_h
+
+
+def map_capacities(max_voxels, max_pairs=None):
+    """-> (max_voxels, max_pairs), both integers in 1 .. 2^28; max_pairs None = 2 * max_voxels (at most 2^28)."""
+    max_voxels = _superpoint_int(max_voxels, 1, MAP_MAX, "map: max_voxels")
+    max_pairs = min(2 * max_voxels, MAP_MAX) if max_pairs is None else _superpoint_int(max_pairs, 1, MAP_MAX, "map: max_pairs")
+    return max_voxels, max_pairs
+
+
+def map_bytes(max_voxels: int, max_pairs: int) -> int:
+    """The bytes of a map block (psam_map_bytes)."""
+    max_voxels, max_pairs = map_capacities(max_voxels, max_pairs)
+    return _lib.load().psam_map_bytes(max_voxels, max_pairs)
+
+
+def _map_block(what: str, block, max_voxels, max_pairs):
+    """The checks every map entry shares -> the block's seven leading arguments (pointer, bytes, capacities)."""
+    max_voxels, max_pairs = map_capacities(max_voxels, max_pairs)
+    if not isinstance(block, torch.Tensor):
+        raise TypeError(f"{what}: block must be a tensor, got {type(block).__name__}")
+    if block.dtype != torch.int64 or block.dim() != 1:
+        raise TypeError(f"{what}: block must be a one-dimensional int64 tensor, got {tuple(block.shape)} {block.dtype}")
+    need = _lib.load().psam_map_bytes(max_voxels, max_pairs)
+    if block.numel() * 8 < need:
+        raise ValueError(f"{what}: the block holds {block.numel() * 8} bytes, a map of {max_voxels} voxels and {max_pairs} pairs needs {need}")
+    _chk(block, torch.int64, "block")
+    return block.data_ptr(), block.numel() * 8, max_voxels, max_pairs
+
+
+def _map_points(what: str, t, name: str, like=None):
+    t = _transfer_cloud(t, f"{what}: {name}")
+    if like is not None and tuple(t.shape) != tuple(like.shape):
+        raise ValueError(f"{what}: {name} must be {tuple(like.shape)} like xyz, got {tuple(t.shape)}")
+    return t
+
+
+def _map_count(what: str, V, max_voxels) -> int:
+    return _superpoint_int(V, 1, max_voxels if isinstance(max_voxels, int) and not isinstance(max_voxels, bool) else MAP_MAX, f"{what}: V")
+
+
+def map_clear(block: torch.Tensor, max_voxels: int, max_pairs: int, voxel_size) -> None:
+    """Empties the map in `block` (int64 words, map_bytes) and sets its voxel size.  No host synchronisation."""
+    inv_h = map_inv_h(voxel_size)
+    lead = _map_block("map_clear", block, max_voxels, max_pairs)
+    check(_lib.load().psam_map_clear(*lead, float(inv_h), _stream()), "psam_map_clear")
+
+
+def map_header(block: torch.Tensor):
+    """The block's header as a list of MAP_HEADER_INTS integers: one host read."""
+    if not isinstance(block, torch.Tensor) or block.dtype != torch.int64 or block.dim() != 1 or block.numel() * 2 < MAP_HEADER_INTS:
+        raise TypeError("map_header: block must be a one-dimensional int64 tensor of a map's size")
+    return block[:MAP_HEADER_INTS // 2].view(torch.int32).tolist()
+
+
+def map_add(block: torch.Tensor, max_voxels: int, max_pairs: int, xyz: torch.Tensor, rgb: torch.Tensor, labels: torch.Tensor = None, pose=None):
+    """xyz, rgb [M, 3] f32, labels [M] int32 or None, pose (transfer_pose's forms, scan frame -> map frame, None = identity) -> (ids [M] int32, header):
+    one add (include/pointsam_hip.h: scan map).  header = map_header after the add, the call's one host read; the caller looks at its flags."""
+    xyz = _map_points("map_add", xyz, "xyz")
+    rgb = _map_points("map_add", rgb, "rgb", xyz)
+    M = xyz.shape[0]
+    if labels is not None:
+        if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int32:
+            raise TypeError(f"map_add: labels must be an int32 tensor or None, got {getattr(labels, 'dtype', type(labels).__name__)}")
+        if tuple(labels.shape) != (M,):
+            raise ValueError(f"map_add: labels must be [{M}] like xyz, got {tuple(labels.shape)}")
+    words = transfer_pose(pose)
+    lead = _map_block("map_add", block, max_voxels, max_pairs)
+    _chk(xyz, name="xyz"); _chk(rgb, name="rgb")
+    if labels is not None:
+        _chk(labels, torch.int32, "labels")
+    if not (xyz.device == rgb.device == block.device and (labels is None or labels.device == xyz.device)):
+        raise ValueError(f"map_add: xyz is on {xyz.device}, rgb on {rgb.device}, the block on {block.device}")
+    L = _lib.load()
+    ws = torch.empty(L.psam_map_add_workspace_bytes(M) // 8 + 2, dtype=torch.int64, device=xyz.device)      # torch allocations are at least 16-byte aligned
+    ids = torch.empty(M, dtype=torch.int32, device=xyz.device)
+    P, pose_ptr = _pose_arg(words)
+    check(L.psam_map_add(*lead, xyz.data_ptr(), rgb.data_ptr(), _p(labels), M, pose_ptr, ids.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()),
+          "psam_map_add")
+    return ids, map_header(block)
+
+
+def map_locate(block: torch.Tensor, max_voxels: int, max_pairs: int, xyz: torch.Tensor, pose=None) -> torch.Tensor:
+    """xyz [M, 3] f32 under pose -> ids [M] int32: the map's voxel at each point, -1 where there is none or the point is not accepted.  No host
+    synchronisation; changes nothing."""
+    xyz = _map_points("map_locate", xyz, "xyz")
+    words = transfer_pose(pose)
+    lead = _map_block("map_locate", block, max_voxels, max_pairs)
+    _chk(xyz, name="xyz")
+    ids = torch.empty(xyz.shape[0], dtype=torch.int32, device=xyz.device)
+    P, pose_ptr = _pose_arg(words)
+    check(_lib.load().psam_map_locate(*lead, xyz.data_ptr(), xyz.shape[0], pose_ptr, ids.data_ptr(), _stream()), "psam_map_locate")
+    return ids
+
+
+def map_labels(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, min_votes: int = 1):
+    """-> (label [V] int32, votes [V] int32): per voxel the label with the most points, ties to the lower label; -1 and 0 below min_votes."""
+    V = _map_count("map_labels", V, max_voxels)
+    min_votes = _superpoint_int(min_votes, 1, 2 ** 31 - 1, "map_labels: min_votes")
+    lead = _map_block("map_labels", block, max_voxels, max_pairs)
+    out = torch.empty(2, V, dtype=torch.int32, device=block.device)
+    check(_lib.load().psam_map_labels(*lead, V, min_votes, out[0].data_ptr(), out[1].data_ptr(), _stream()), "psam_map_labels")
+    return out[0], out[1]
+
+
+def map_cloud(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int):
+    """-> (xyz [V, 3] f32, rgb [V, 3] f32): per voxel the mean position and colour, fl32(fl64(sum) / fl64(count) * 2^-20 - 1)."""
+    V = _map_count("map_cloud", V, max_voxels)
+    lead = _map_block("map_cloud", block, max_voxels, max_pairs)
+    out = torch.empty(2, V, 3, dtype=torch.float32, device=block.device)
+    check(_lib.load().psam_map_cloud(*lead, V, out[0].data_ptr(), out[1].data_ptr(), _stream()), "psam_map_cloud")
+    return out[0], out[1]
+
+
+def map_fields(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int):
+    """-> (count [V] int32, first_seen [V] int32, last_seen [V] int32, keys [V] int64, sums [V, 6] int64): the map's integers per voxel; sums = the
+    fixed-point sums of the position, then of the colour."""
+    V = _map_count("map_fields", V, max_voxels)
+    lead = _map_block("map_fields", block, max_voxels, max_pairs)
+    out = torch.empty(3, V, dtype=torch.int32, device=block.device)
+    keys = torch.empty(V, dtype=torch.int64, device=block.device)
+    sums = torch.empty(V, 6, dtype=torch.int64, device=block.device)
+    check(_lib.load().psam_map_fields(*lead, V, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), keys.data_ptr(), sums.data_ptr(), _stream()),
+          "psam_map_fields")
+    return out[0], out[1], out[2], keys, sums

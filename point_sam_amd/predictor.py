@@ -356,6 +356,44 @@ class PointSAMPredictor:
             points[keep], labels[keep] = pc, pl
         return T.Propagated(out, scores, lost, prior_area, float(counts[K]) / Nw, points, labels)
 
+    # -- the map the scans accumulate into (point_sam_amd/scanmap.py) ------------------------------------------
+    def _map_scan(self, m, what: str):
+        """(xyz, rgb) [M, 3] of the CURRENT scan: after set_scene its full-resolution points and colours, otherwise the cloud as encoded."""
+        from .scanmap import ScanMap
+        if not isinstance(m, ScanMap):
+            raise TypeError(f"{what}: m must be a scanmap.ScanMap, got {type(m).__name__}")
+        state, sc = self._transfer_cloud(what)
+        if sc is not None:
+            return self._keepalive[0], self._keepalive[1]
+        return state.coords[0].contiguous(), state.features[0].contiguous()
+
+    def new_map(self, voxel_size, max_voxels: int, max_pairs: int = None):
+        """An empty scanmap.ScanMap on the model's device."""
+        from .scanmap import ScanMap
+        return ScanMap(voxel_size, max_voxels, max_pairs, device=self.model.device)
+
+    @torch.no_grad()
+    def map_add(self, m, labels: torch.Tensor = None, pose=None):
+        """Adds the CURRENT scan to the scanmap.ScanMap `m` -> scanmap.AddResult.  labels [M] int32 at the scan's width (e.g.
+        scanmap.labels_from_logits of propagate()'s logits) or None; pose: 3 x 4 or 4 x 4 from this scan's coordinates to the map's (align()'s `pose`
+        where the map was begun with the snapshot's scan), None = the identity.  RuntimeError before any cloud is set and under an active crop;
+        scanmap.MapOverflow past the map's capacities.  One host read, the map's header."""
+        xyz, rgb = self._map_scan(m, "map_add")
+        return m.add(xyz, rgb, labels, pose)
+
+    @torch.no_grad()
+    def map_lookup(self, m, pose=None, min_votes: int = 1) -> torch.Tensor:
+        """Per point of the CURRENT scan the map's voted label at its voxel -> [M] int32, -1 where the map has no voxel there or the voxel no label
+        with min_votes votes; all -1 for an empty map.  No host read."""
+        xyz, _ = self._map_scan(m, "map_lookup")
+        if isinstance(min_votes, bool) or not isinstance(min_votes, int) or not 1 <= min_votes <= 2 ** 31 - 1:
+            raise ValueError(f"map_lookup: min_votes must be an integer in 1 .. 2^31 - 1, got {min_votes!r}")
+        ids = m.locate(xyz, pose)
+        if m.num_voxels == 0:                                      # an empty map has no voxel anywhere: locate's -1 for every point
+            return ids
+        label = m.labels(min_votes)[0]
+        return torch.where(ids >= 0, label.index_select(0, ids.clamp(min=0).long()), torch.full_like(ids, -1))
+
     @torch.no_grad()
     def generate_masks(self, cfg=None, crops=None):
         """Automatic mask proposals for the cached cloud(s), no prompts needed (point_sam_amd/proposals.py): a list with one `Proposals` per

@@ -1,0 +1,168 @@
+"""Scan maps: posed scans accumulate into one persistent, labelled voxel map (csrc/scanmap.hip, predictor.map_add / map_lookup).
+
+A walk through a room gives fifty scans, each with the masks propagate() or fuse_labels() gave it; a `ScanMap` holds them together.  It lives in the
+common normalised frame ([-1, 1]^3, the same centre and scale for every scan), and its voxels are those of set_scene(voxel_size=h): every add puts each
+accepted point of a scan, under the scan's pose, into its voxel, and the voxel keeps exact integer sums of positions and colours and one count per
+instance label seen there.  Out of it come
+
+    cloud()     one denoised cloud: the mean position and mean colour per voxel;
+    labels()    one instance label per voxel, voted over everything ever seen there (ties to the lower label);
+    ids         voxel ids that never change: a voxel keeps the id its first add gave it, so packed masks over the map (bits()) stay valid as it grows.
+
+Every sum is an integer, so every output is the same bits from run to run and for any order of the points inside an add (ids follow the order).  The
+definition is in include/pointsam_hip.h ("scan map"); tests/scanmap_reference.py states it again in numpy.
+
+Overflow is an error, never a silent drop: an add that would take the map past max_voxels, or its distinct (voxel, label) pairs past max_pairs,
+raises MapOverflow, and so does every later call until clear().
+
+Not built: removing or decaying voxels, free-space carving, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, loop closure.  No default here has been
+tuned on real scans or a trained checkpoint.  Beyond the voxel and pair capacities a map takes at most 2^31 - 1 accepted points in all (the bound that
+keeps counts and votes in int32 and every sum in one 64-bit word); that refusal is not exercised by any test.
+"""
+from dataclasses import dataclass
+
+import torch
+
+from . import ops
+
+
+class MapOverflow(RuntimeError):
+    """An add went past the map's max_voxels or max_pairs (or 2^31 - 1 accepted points in all): the map is dead until clear()."""
+
+
+@dataclass
+class AddResult:
+    ids: torch.Tensor         # [M] int32: the voxel of every accepted point, -1 for a rejected one
+    new_voxels: int
+    accepted: int
+    rejected: int
+
+
+def labels_from_logits(logits: torch.Tensor, ids=None, threshold: float = 0.0) -> torch.Tensor:
+    """logits [K, M] float32, ids [K] integers (None: 0 .. K - 1), threshold -> [M] int32: per point ids[argmax over k] where the column's maximum is
+    > threshold, else -1.  A NaN or -inf never wins: rows of propagate()'s lost objects take no point.  Plain torch."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1:
+        raise ValueError(f"labels_from_logits: logits must be a [K, M] tensor with K, M >= 1, got "
+                         f"{tuple(logits.shape) if isinstance(logits, torch.Tensor) else type(logits).__name__}")
+    if logits.dtype != torch.float32:
+        raise TypeError(f"labels_from_logits: logits of float32, got {logits.dtype}")
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float)) or threshold != threshold:
+        raise ValueError(f"labels_from_logits: threshold must be a number, got {threshold!r}")
+    K = logits.shape[0]
+    if ids is not None:
+        ids = torch.as_tensor(ids)
+        if ids.dtype not in (torch.int32, torch.int64) or tuple(ids.shape) != (K,):
+            raise ValueError(f"labels_from_logits: ids must be [{K}] integers, got {tuple(ids.shape)} {ids.dtype}")
+        if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) > 2 ** 31 - 1):
+            raise ValueError("labels_from_logits: ids must lie in 0 .. 2^31 - 1")
+        ids = ids.to(device=logits.device, dtype=torch.int32)
+    clean = torch.where(torch.isnan(logits), torch.full_like(logits, float("-inf")), logits)
+    best, arg = clean.max(dim=0)
+    label = arg.to(torch.int32) if ids is None else ids.index_select(0, arg)
+    return torch.where(best > threshold, label, torch.full_like(label, -1)).contiguous()
+
+
+def _overflow_message(flags: int, max_voxels: int, max_pairs: int) -> str:
+    why = []
+    if flags & ops.MAP_FLAG_VOXELS:
+        why.append(f"more than max_voxels = {max_voxels} voxels")
+    if flags & ops.MAP_FLAG_PAIRS:
+        why.append(f"more than max_pairs = {max_pairs} (voxel, label) pairs")
+    if flags & ops.MAP_FLAG_COUNTS:
+        why.append("more than 2^31 - 1 accepted points in all")
+    return "ScanMap: " + " and ".join(why or [f"flags {flags}"]) + ": the map is dead until clear()"
+
+
+class ScanMap:
+    """ScanMap(voxel_size, max_voxels, max_pairs=None (2 * max_voxels), device="cuda").  The arguments are checked before any device work; the block
+    (ops.map_bytes) is allocated once and cleared."""
+
+    def __init__(self, voxel_size, max_voxels: int, max_pairs: int = None, device="cuda"):
+        ops.map_inv_h(voxel_size)
+        self.max_voxels, self.max_pairs = ops.map_capacities(max_voxels, max_pairs)
+        self.voxel_size = float(voxel_size)
+        self._block = torch.empty(ops.map_bytes(self.max_voxels, self.max_pairs) // 8 + 2, dtype=torch.int64, device=device)
+        self._V = self._adds = self._flags = 0
+        self.clear()
+
+    # -- state ---------------------------------------------------------------------------------------------
+    @property
+    def num_voxels(self) -> int:
+        return self._V
+
+    @property
+    def num_adds(self) -> int:
+        return self._adds
+
+    @property
+    def device(self):
+        return self._block.device
+
+    def clear(self) -> None:
+        """Empties the map; a dead map lives again."""
+        ops.map_clear(self._block, self.max_voxels, self.max_pairs, self.voxel_size)
+        self._V = self._adds = self._flags = 0
+
+    def _alive(self, what: str):
+        if self._flags:
+            raise MapOverflow(f"{what}: " + _overflow_message(self._flags, self.max_voxels, self.max_pairs))
+        return self._block, self.max_voxels, self.max_pairs
+
+    def _filled(self, what: str):
+        lead = self._alive(what)
+        if self._V == 0:
+            raise ValueError(f"{what}: the map is empty")
+        return lead + (self._V,)
+
+    # -- growing -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def add(self, xyz: torch.Tensor, rgb: torch.Tensor, labels: torch.Tensor = None, pose=None) -> AddResult:
+        """One scan: xyz, rgb [M, 3] f32, labels [M] int32 or None (a negative label is an unlabelled observation), pose 3 x 4 or 4 x 4 from the
+        scan's frame to the map's, or None.  One host read, of the map's header.  MapOverflow past a capacity."""
+        lead = self._alive("add")
+        ids, header = ops.map_add(*lead, xyz, rgb, labels, pose)
+        self._flags = header[ops.MAP_H_FLAGS]
+        if self._flags:
+            raise MapOverflow("add: " + _overflow_message(self._flags, self.max_voxels, self.max_pairs))
+        self._V, self._adds = header[ops.MAP_H_V], header[ops.MAP_H_ADDS]
+        return AddResult(ids, header[ops.MAP_H_NEW], header[ops.MAP_H_ACCEPTED], header[ops.MAP_H_REJECTED])
+
+    # -- reading -------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def locate(self, xyz: torch.Tensor, pose=None) -> torch.Tensor:
+        """ids [M] int32 of xyz under the pose: -1 where the map has no such voxel or the position is not accepted.  No host read."""
+        return ops.map_locate(*self._alive("locate"), xyz, pose)
+
+    @torch.no_grad()
+    def labels(self, min_votes: int = 1):
+        """(label [V] int32, votes [V] int32); -1 and 0 where the best count is below min_votes."""
+        return ops.map_labels(*self._filled("labels"), min_votes)
+
+    @torch.no_grad()
+    def cloud(self):
+        """(xyz [V, 3] f32, rgb [V, 3] f32): the voxels' mean positions and colours -- a scan like any other."""
+        return ops.map_cloud(*self._filled("cloud"))
+
+    def _fields(self, what: str):
+        return ops.map_fields(*self._filled(what))
+
+    def counts(self) -> torch.Tensor:
+        return self._fields("counts")[0]
+
+    def first_seen(self) -> torch.Tensor:
+        return self._fields("first_seen")[1]
+
+    def last_seen(self) -> torch.Tensor:
+        return self._fields("last_seen")[2]
+
+    def keys(self) -> torch.Tensor:
+        return self._fields("keys")[3]
+
+    def sums(self):
+        """(sum_q [V, 3] int64, sum_c [V, 3] int64): the exact fixed-point sums behind cloud(), q = floor(v * 2^20) + 2^20 per observation."""
+        s = self._fields("sums")[4]
+        return s[:, :3], s[:, 3:]
+
+    def bits(self, K: int):
+        """ops.label_bits of labels(): (bits [K, ceil(V / 64)] int64, area [K] int32), row k the voxels voted k."""
+        return ops.label_bits(self.labels()[0].contiguous(), K)

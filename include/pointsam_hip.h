@@ -1141,6 +1141,56 @@ int32_t psam_map_cloud(const void* map, size_t map_bytes, int32_t max_voxels, in
 int32_t psam_map_fields(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, int32_t* count, int32_t* first_seen,
                         int32_t* last_seen, int64_t* keys, int64_t* sums, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- scan map carving */
+
+/* Free-space carving of a scan map (ScanMap.carve): the cells between the sensor and what it measured were seen through, and a map voxel that rays
+ * keep passing through is a ghost -- a person who walked by, a chair that was moved.  A carve never writes the map block and never adds a voxel: its
+ * state lives in a second block of the caller's, psam_carve_bytes(max_voxels) = 64 + 16 max_voxels bytes of DEVICE memory, 16-byte aligned, cleared
+ * by psam_carve_clear and used with one map of the same max_voxels.  Return codes as for the map entries; no call synchronises with the host.
+ *
+ * Cells and rays.  One carve takes a scan xyz [M, 3], its pose (as psam_map_add), a sensor origin (3 floats in HOST memory, the scan's frame, finite),
+ * margin (0 <= margin < 2^21) and stamp (1 <= stamp <= 2^31 - 1).  A point's cell is psam_map_add's: the same pose arithmetic, the same acceptance
+ * test (all three cells exist and -1 <= p_a <= 1; colour plays no part).  The origin goes through the same arithmetic on the device; if it has no
+ * cell, no ray is cast (header word 3 = 0; hits are still marked).  Rays run from cell centre to cell centre, so two points in one cell give one
+ * ray: the rays of a carve are its distinct accepted endpoint cells other than the origin's cell.  Against the true ray from the sensor to the point
+ * this shifts a ray by at most half a voxel.
+ *
+ * The cells of a ray.  The ray from cell o to cell e crosses the cells c != o, e whose OPEN box meets the segment between the centres of o and e; a
+ * segment that only touches an edge or a corner of a cell does not cross it.  The integer walk that enumerates exactly this set, in order: with
+ * n_a = |e_a - o_a|, s_a = sign(e_a - o_a), k = (0, 0, 0), cur = o, repeat
+ *   1. among the axes with k_a < n_a find the least (2 k_a + 1) / (2 n_a), compared as (2 k_a + 1) n_b < (2 k_b + 1) n_a (products below 2^43: exact);
+ *   2. step every axis tied at the minimum: k_a += 1, cur_a += s_a;
+ *   3. stop when cur == e; otherwise cur is a crossed cell.
+ * The walk of (o, e) is the reverse of the walk of (e, o).  Right after the k-th crossing of the longest axis a (1 <= k <= n_a) every other axis has
+ * k_b = min(n_b, ((2 k - 1) n_b + n_a) div (2 n_a)): a walk can start in the middle of a ray.
+ *
+ * What a carve changes.  Per map voxel id the block keeps four int32 words: hits, misses, last_hit, last_missed.
+ *   hit     a map voxel that is an endpoint cell of this carve (the origin's cell included, where a point lies in it):
+ *           if last_hit < stamp then hits += 1 and last_hit = stamp;
+ *   missed  then, a map voxel that some ray crosses at Chebyshev distance > margin from that ray's end cell and that was not hit in this carve
+ *           (last_hit != stamp): if last_missed < stamp then misses += 1 and last_missed = stamp.
+ * So a voxel counts at most once per carve, and a hit beats a miss inside one carve (rays graze the near surface on their way to the far one).  hits
+ * counts carves, not points.  The same carve again with the same stamp changes no voxel's words.  Set semantics over integers: the result is a
+ * function of the inputs alone.  A dead map (flags != 0) is neither marked nor walked.
+ *
+ * The block begins with PSAM_CARVE_HEADER_INTS int32 words, which the caller may read back:
+ *   0 max_voxels   1 carves so far (calls that raised the stamp)   2 the highest stamp   3 the last carve's origin has a cell
+ *   4 .. 8 of the last call: rays, accepted points, rejected points, voxels whose hits it raised, voxels whose misses it raised   9 zero
+ *   10, 11 one uint64: the crossed cells beyond the margin, summed over the rays of the last call (a function of the inputs)   12 .. 15 zero
+ *
+ * psam_carve_clear.  Zeroes every voxel's words and the header, sets word 0.
+ * psam_carve_scan.  One carve; ws: psam_carve_workspace_bytes(M) bytes, 16-byte aligned; 0 < M <= 2^28.  Four launches.
+ * psam_carve_fields.  hits, misses, last_hit, last_missed [V] int32, each may be NULL (not all); 0 < V <= max_voxels; voxels the map added after the
+ *   last carve read 0. */
+#define PSAM_CARVE_HEADER_INTS 16
+size_t psam_carve_bytes(int32_t max_voxels);
+int32_t psam_carve_clear(void* carve, size_t carve_bytes, int32_t max_voxels, psam_stream_t stream);
+size_t psam_carve_workspace_bytes(int32_t M);
+int32_t psam_carve_scan(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, void* carve, size_t carve_bytes, const float* xyz,
+                        int32_t M, const float* pose, const float* origin, int32_t margin, int32_t stamp, void* ws, size_t ws_bytes, psam_stream_t stream);
+int32_t psam_carve_fields(const void* carve, size_t carve_bytes, int32_t max_voxels, int32_t V, int32_t* hits, int32_t* misses, int32_t* last_hit,
+                          int32_t* last_missed, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,11 @@ SIGNATURES = {
     "psam_map_labels": (i32, [ptr, size_t, i32, i32, i32, i32, ptr, ptr, ptr]),
     "psam_map_cloud": (i32, [ptr, size_t, i32, i32, i32, ptr, ptr, ptr]),
     "psam_map_fields": (i32, [ptr, size_t, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]),
+    "psam_carve_bytes": (size_t, [i32]),
+    "psam_carve_clear": (i32, [ptr, size_t, i32, ptr]),
+    "psam_carve_workspace_bytes": (size_t, [i32]),
+    "psam_carve_scan": (i32, [ptr, size_t, i32, i32, ptr, size_t, ptr, i32, ptr, ptr, i32, i32, ptr, size_t, ptr]),
+    "psam_carve_fields": (i32, [ptr, size_t, i32, i32, ptr, ptr, ptr, ptr, ptr]),
 }
 
 

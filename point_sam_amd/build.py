@@ -60,6 +60,8 @@ SOURCES = [
     ("superpoints.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # scan maps: scene.hip's cells of the pose of csrc/rigid_pose.h, and an fp64 mean rounded one operation at a time; flags as for transfer.hip.
     ("scanmap.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # scan map carving: scanmap.hip's point, pose and cell bit for bit (csrc/map_block.h), so scanmap.hip's flags; the walk itself is integer.
+    ("carve.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

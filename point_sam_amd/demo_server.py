@@ -578,15 +578,26 @@ class DemoSession:
         """Adds the loaded cloud to the session's scan map (created by the first add: predictor.new_map(map_voxel_size, map_max_voxels)): {"pose": 3 x
         4 or 4 x 4 rows from the loaded cloud's coordinates to the map's (optional), "labels": [N ints, negative = none] (optional; without it point n
         gets the index of the first kept /next mask or current /segment mask that holds it, -1 outside all)} -> {"new_voxels", "accepted",
-        "rejected", "num_voxels", "num_adds"}.  A bad value or a full map is a 400."""
+        "rejected", "num_voxels", "num_adds"}.  With "origin": [x, y, z] (the sensor's position in the loaded cloud's coordinates) the scan is then carved
+        (predictor.map_carve, "margin": cells, optional, default 1) and the answer gains {"rays", "hit_voxels", "missed_voxels", "crossed",
+        "num_carves"}.  A bad value or a full map is a 400."""
         with self.lock:
             if self.pc_xyz is None:
                 raise ValueError("/map/add before a point cloud was set")
-            if not isinstance(data, dict) or set(data) - {"pose", "labels"}:
-                raise ValueError('/map/add takes {"pose": rows (optional), "labels": [ints] (optional)}')
+            if not isinstance(data, dict) or set(data) - {"pose", "labels", "origin", "margin"}:
+                raise ValueError('/map/add takes {"pose": rows (optional), "labels": [ints] (optional), "origin": [x, y, z] (optional), "margin": n (optional)}')
             from . import ops
             pose = data.get("pose")
             ops.transfer_pose(pose)
+            origin, margin = data.get("origin"), data.get("margin", 1)
+            if "margin" in data and origin is None:
+                raise ValueError('"margin" belongs to a carve: give "origin" too')
+            if origin is not None:
+                if not isinstance(origin, list) or len(origin) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, float)) for v in origin):
+                    raise ValueError('"origin" must be three numbers')
+                if isinstance(margin, bool) or not isinstance(margin, int) or not 0 <= margin <= ops.CARVE_MAX_MARGIN:
+                    raise ValueError('"margin" must be an integer in 0 .. 2^21 - 1')
+                ops.carve_origin(origin, pose, self.map_voxel_size)
             N = self.pc_xyz.shape[1]
             if "labels" in data:
                 lab = data["labels"]
@@ -607,17 +618,26 @@ class DemoSession:
                     if self.scan_map is None:
                         self.scan_map = self.predictor.new_map(self.map_voxel_size, self.map_max_voxels)
                     res = self._map_error(lambda: self.predictor.map_add(self.scan_map, torch.from_numpy(labels).to(self.device), pose))
+                    cut = None if origin is None else self._map_error(lambda: self.predictor.map_carve(self.scan_map, origin, pose, margin))
                 finally:
                     self.crop = crop
-            return {"new_voxels": int(res.new_voxels), "accepted": int(res.accepted), "rejected": int(res.rejected),
-                    "num_voxels": int(self.scan_map.num_voxels), "num_adds": int(self.scan_map.num_adds)}
+            out = {"new_voxels": int(res.new_voxels), "accepted": int(res.accepted), "rejected": int(res.rejected),
+                   "num_voxels": int(self.scan_map.num_voxels), "num_adds": int(self.scan_map.num_adds)}
+            if cut is not None:
+                out.update(rays=int(cut.rays), hit_voxels=int(cut.hit_voxels), missed_voxels=int(cut.missed_voxels), crossed=int(cut.crossed),
+                           num_carves=int(self.scan_map.num_carves))
+            return out
 
     def map_get(self, data: dict) -> dict:
         """The map as a cloud: {"min_votes": n (optional, default 1)} -> {"xyz", "rgb" (flattened, as /pointcloud/), "labels": [V ints, -1 = none],
-        "votes": [V ints]}.  Before any /map/add: a 400."""
+        "votes": [V ints]}.  With "min_misses": n (>= 0) also "occupied": [V booleans], ScanMap.occupied(n) -- false where carving voted the voxel
+        free.  Before any /map/add: a 400."""
         with self.lock:
-            if not isinstance(data, dict) or set(data) - {"min_votes"}:
-                raise ValueError('/map takes {"min_votes": n} (or nothing)')
+            if not isinstance(data, dict) or set(data) - {"min_votes", "min_misses"}:
+                raise ValueError('/map takes {"min_votes": n, "min_misses": n} (or nothing)')
+            min_misses = data.get("min_misses")
+            if min_misses is not None and (isinstance(min_misses, bool) or not isinstance(min_misses, int) or not 0 <= min_misses < 2 ** 31):
+                raise ValueError("min_misses must be an integer >= 0")
             min_votes = data.get("min_votes", 1)
             if isinstance(min_votes, bool) or not isinstance(min_votes, int) or not 1 <= min_votes < 2 ** 31:
                 raise ValueError("min_votes must be an integer >= 1")
@@ -626,8 +646,12 @@ class DemoSession:
             with torch.no_grad():
                 xyz, rgb = self._map_error(self.scan_map.cloud)
                 label, votes = self._map_error(lambda: self.scan_map.labels(min_votes))
-            return {"xyz": xyz.cpu().numpy().astype(np.float64).flatten().tolist(), "rgb": rgb.cpu().numpy().astype(np.float64).flatten().tolist(),
-                    "labels": label.cpu().numpy().astype(int).tolist(), "votes": votes.cpu().numpy().astype(int).tolist()}
+                occupied = None if min_misses is None else self._map_error(lambda: self.scan_map.occupied(min_misses))
+            out = {"xyz": xyz.cpu().numpy().astype(np.float64).flatten().tolist(), "rgb": rgb.cpu().numpy().astype(np.float64).flatten().tolist(),
+                   "labels": label.cpu().numpy().astype(int).tolist(), "votes": votes.cpu().numpy().astype(int).tolist()}
+            if occupied is not None:
+                out["occupied"] = occupied.cpu().numpy().astype(bool).tolist()
+            return out
 
     def map_clear(self) -> dict:
         """Empties the session's scan map (a map that hit a capacity lives again)."""

@@ -2574,3 +2574,111 @@ def map_fields(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int):
     check(_lib.load().psam_map_fields(*lead, V, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), keys.data_ptr(), sums.data_ptr(), _stream()),
           "psam_map_fields")
     return out[0], out[1], out[2], keys, sums
+
+
+# ------------------------------------------------------------------------------------------ scan map carving (csrc/carve.hip)
+CARVE_HEADER_INTS = 16           # PSAM_CARVE_HEADER_INTS
+CARVE_MAX_MARGIN = (1 << 21) - 1
+# the header's words (include/pointsam_hip.h: scan map carving); 10, 11 hold CROSSED as one uint64
+CARVE_H_CARVES, CARVE_H_STAMP, CARVE_H_ORIGIN, CARVE_H_RAYS, CARVE_H_ACCEPTED, CARVE_H_REJECTED, CARVE_H_HIT, CARVE_H_MISSED, CARVE_H_CROSSED = \
+    1, 2, 3, 4, 5, 6, 7, 8, 10
+
+
+def carve_origin(origin, pose=None, voxel_size=None):
+    """Three numbers (the sensor's position in the scan's frame) -> their fp32 words [3].  With a voxel size: the origin goes through the pose and the
+    cell arithmetic of a map point in numpy fp32, exactly as the device does it, and a ValueError says where it has no cell (off [-1, 1]^3)."""
+    import numpy as np
+    if isinstance(origin, torch.Tensor):
+        origin = origin.detach().cpu().numpy()
+    try:
+        o = np.asarray(origin, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"carve: origin must be three numbers, got {origin!r}") from None
+    if o.shape != (3,) or o.dtype.kind != "f":
+        raise ValueError(f"carve: origin must be three numbers, got {origin!r}")
+    with np.errstate(over="ignore"):
+        o = o.astype(np.float32)
+    if not np.isfinite(o).all():
+        raise ValueError(f"carve: origin must be finite in fp32, got {origin!r}")
+    if voxel_size is not None:
+        inv_h = map_inv_h(voxel_size)
+        words = transfer_pose(pose)
+        p = o
+        with np.errstate(all="ignore"):
+            if words is not None:
+                w = np.asarray(words, dtype=np.float32).reshape(3, 4)
+                p = np.array([((w[a, 0] * o[0] + w[a, 1] * o[1]) + w[a, 2] * o[2]) + w[a, 3] for a in range(3)], dtype=np.float32)
+            c = np.floor((p - np.float32(-1)) * inv_h)
+            ok = (c >= 0) & (c < np.float32(1 << 21)) & (p >= np.float32(-1)) & (p <= np.float32(1))
+        if not ok.all():
+            raise ValueError(f"carve: the origin lands at {p.tolist()} in the map's frame, outside [-1, 1]^3: it has no cell, so no ray can be cast")
+    return o
+
+
+def carve_bytes(max_voxels: int) -> int:
+    """The bytes of a carve block (psam_carve_bytes): 64 + 16 max_voxels."""
+    return _lib.load().psam_carve_bytes(_superpoint_int(max_voxels, 1, MAP_MAX, "carve: max_voxels"))
+
+
+def _carve_block(what: str, carve, max_voxels, on_device: bool = True):
+    """The checks every carve entry shares -> the block's three leading arguments (pointer, bytes, max_voxels).  on_device False: the shape alone,
+    for a caller that has other shapes to ask about before the first device check."""
+    max_voxels = _superpoint_int(max_voxels, 1, MAP_MAX, f"{what}: max_voxels")
+    if not isinstance(carve, torch.Tensor):
+        raise TypeError(f"{what}: carve must be a tensor, got {type(carve).__name__}")
+    if carve.dtype != torch.int64 or carve.dim() != 1:
+        raise TypeError(f"{what}: carve must be a one-dimensional int64 tensor, got {tuple(carve.shape)} {carve.dtype}")
+    need = _lib.load().psam_carve_bytes(max_voxels)
+    if carve.numel() * 8 < need:
+        raise ValueError(f"{what}: the carve block holds {carve.numel() * 8} bytes, a map of {max_voxels} voxels needs {need}")
+    if on_device:
+        _chk(carve, torch.int64, "carve")
+    return carve.data_ptr(), carve.numel() * 8, max_voxels
+
+
+def carve_clear(carve: torch.Tensor, max_voxels: int) -> None:
+    """Empties the carve block (int64 words, carve_bytes).  No host synchronisation."""
+    check(_lib.load().psam_carve_clear(*_carve_block("carve_clear", carve, max_voxels), _stream()), "psam_carve_clear")
+
+
+def carve_header(carve: torch.Tensor):
+    """The carve block's header as a list of CARVE_HEADER_INTS integers, words 10 and 11 joined into CARVE_H_CROSSED: one 64-byte host read."""
+    if not isinstance(carve, torch.Tensor) or carve.dtype != torch.int64 or carve.dim() != 1 or carve.numel() * 2 < CARVE_HEADER_INTS:
+        raise TypeError("carve_header: carve must be a one-dimensional int64 tensor of a carve block's size")
+    h = carve[:CARVE_HEADER_INTS // 2].view(torch.int32).tolist()
+    h[CARVE_H_CROSSED] = (h[CARVE_H_CROSSED] & 0xffffffff) | ((h[CARVE_H_CROSSED + 1] & 0xffffffff) << 32)
+    return h
+
+
+def carve_scan(block: torch.Tensor, max_voxels: int, max_pairs: int, carve: torch.Tensor, xyz: torch.Tensor, origin, pose=None, margin: int = 1,
+               stamp: int = 1):
+    """One carve of the map in `block` into the carve block `carve` (include/pointsam_hip.h: scan map carving): xyz [M, 3] f32, origin three numbers in
+    the scan's frame, pose as map_add's, 0 <= margin < 2^21, 1 <= stamp <= 2^31 - 1 -> carve_header after it, the call's one host read."""
+    xyz = _map_points("carve_scan", xyz, "xyz")
+    o = carve_origin(origin)
+    margin = _superpoint_int(margin, 0, CARVE_MAX_MARGIN, "carve_scan: margin")
+    stamp = _superpoint_int(stamp, 1, 2 ** 31 - 1, "carve_scan: stamp")
+    words = transfer_pose(pose)
+    _carve_block("carve_scan", carve, max_voxels, on_device=False)
+    lead = _map_block("carve_scan", block, max_voxels, max_pairs)
+    tail = _carve_block("carve_scan", carve, lead[2])
+    _chk(xyz, name="xyz")
+    if not (xyz.device == block.device == carve.device):
+        raise ValueError(f"carve_scan: xyz is on {xyz.device}, the block on {block.device}, the carve block on {carve.device}")
+    L = _lib.load()
+    M = xyz.shape[0]
+    ws = torch.empty(L.psam_carve_workspace_bytes(M) // 8 + 2, dtype=torch.int64, device=xyz.device)
+    P, pose_ptr = _pose_arg(words)
+    O = (ctypes.c_float * 3)(*o.tolist())
+    check(L.psam_carve_scan(*lead, tail[0], tail[1], xyz.data_ptr(), M, pose_ptr, ctypes.addressof(O), margin, stamp, ws.data_ptr(), ws.numel() * 8,
+                            _stream()), "psam_carve_scan")
+    return carve_header(carve)
+
+
+def carve_fields(carve: torch.Tensor, max_voxels: int, V: int):
+    """-> (hits, misses, last_hit, last_missed), each [V] int32: the carve block's integers per map voxel id."""
+    V = _map_count("carve_fields", V, max_voxels)
+    lead = _carve_block("carve_fields", carve, max_voxels)
+    out = torch.empty(4, V, dtype=torch.int32, device=carve.device)
+    check(_lib.load().psam_carve_fields(*lead, V, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), _stream()), "psam_carve_fields")
+    return out[0], out[1], out[2], out[3]

@@ -382,6 +382,40 @@ class PointSAMPredictor:
         return m.add(xyz, rgb, labels, pose)
 
     @torch.no_grad()
+    def map_carve(self, m, origin, pose=None, margin: int = 1):
+        """Carves the free space the CURRENT scan saw through out of `m` (ScanMap.carve) -> scanmap.CarveResult.  origin: the sensor's position in
+        this scan's coordinates (three numbers); pose as map_add's.  Call it after map_add of the same scan, from the map's first scan on: hits
+        count carves.  One 64-byte host read."""
+        xyz, _ = self._map_scan(m, "map_carve")
+        return m.carve(xyz, origin, pose, margin)
+
+    @torch.no_grad()
+    def map_carve_frames(self, m, fs, pose=None, margin: int = 1) -> list:
+        """One carve per frame of a views.FrameSet (set_frames) over that frame's own points -> a list of scanmap.CarveResult, None for a frame
+        that kept no pixel.  A frame's points are contiguous in fs.xyz and fs.index[f] names them; its origin is the camera's centre in the
+        normalised frame, -R^T t of fs.views[f].camera in fp64, rounded to fp32 once.  One host read for the frames' ranges, then one per carve."""
+        from .scanmap import ScanMap
+        from .views import FrameSet
+        if not isinstance(m, ScanMap):
+            raise TypeError(f"map_carve_frames: m must be a scanmap.ScanMap, got {type(m).__name__}")
+        if not isinstance(fs, FrameSet):
+            raise TypeError(f"map_carve_frames: fs must be a views.FrameSet (set_frames), got {type(fs).__name__}")
+        F = fs.index.shape[0]
+        idx = fs.index.reshape(F, -1)
+        lo = torch.where(idx >= 0, idx, torch.full_like(idx, fs.num_points)).amin(1)
+        span = torch.stack([lo, idx.amax(1)]).cpu().tolist()                       # the one host read of the ranges
+        out = []
+        for f in range(F):
+            first, last = span[0][f], span[1][f]
+            if last < 0:
+                out.append(None)
+                continue
+            P = fs.views[f].camera.pose.astype(np.float64)
+            centre = (-P[:, :3].T @ P[:, 3]).astype(np.float32)
+            out.append(m.carve(fs.xyz[first:last + 1], centre, pose, margin))
+        return out
+
+    @torch.no_grad()
     def map_lookup(self, m, pose=None, min_votes: int = 1) -> torch.Tensor:
         """Per point of the CURRENT scan the map's voted label at its voxel -> [M] int32, -1 where the map has no voxel there or the voxel no label
         with min_votes votes; all -1 for an empty map.  No host read."""

@@ -15,7 +15,13 @@ definition is in include/pointsam_hip.h ("scan map"); tests/scanmap_reference.py
 Overflow is an error, never a silent drop: an add that would take the map past max_voxels, or its distinct (voxel, label) pairs past max_pairs,
 raises MapOverflow, and so does every later call until clear().
 
-Not built: removing or decaying voxels, free-space carving, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, loop closure.  No default here has been
+Free space (csrc/carve.hip): carve() walks the ray from the sensor's cell to the cell of every point of a scan and counts, per voxel and per carve,
+whether the voxel held a point (a hit) or was seen through (a miss); occupied() reads the two counts.  What walked through the room once -- a person,
+a chair since moved, depth noise at an edge -- is then voted free, and cloud()[occupied()] shows no ghosts.  The walk is exact integer arithmetic
+between cell centres (at most half a voxel off the true ray); the counts live in a second block, and the map's own block is never written by a carve.
+
+Not built: removing or decaying voxels (occupied() is a read-out; a freed voxel keeps its id, sums and votes), rays from an origin outside
+[-1, 1]^3, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, loop closure.  No default here has been
 tuned on real scans or a trained checkpoint.  Beyond the voxel and pair capacities a map takes at most 2^31 - 1 accepted points in all (the bound that
 keeps counts and votes in int32 and every sum in one 64-bit word); that refusal is not exercised by any test.
 """
@@ -36,6 +42,22 @@ class AddResult:
     new_voxels: int
     accepted: int
     rejected: int
+
+
+@dataclass
+class CarveResult:
+    rays: int                 # distinct endpoint cells other than the origin's
+    accepted: int
+    rejected: int
+    hit_voxels: int           # voxels whose hits this carve raised
+    missed_voxels: int        # voxels whose misses this carve raised
+    crossed: int              # cells crossed beyond the margin, summed over the rays: a function of the inputs
+
+
+def occupied_from_counts(hits: torch.Tensor, misses: torch.Tensor, min_misses: int = 2, num: int = 1, den: int = 1) -> torch.Tensor:
+    """not free, free iff misses >= min_misses and misses * den > hits * num, in int64.  Plain torch."""
+    h, m = hits.to(torch.int64), misses.to(torch.int64)
+    return ~((m >= min_misses) & (m * den > h * num))
 
 
 def labels_from_logits(logits: torch.Tensor, ids=None, threshold: float = 0.0) -> torch.Tensor:
@@ -83,6 +105,7 @@ class ScanMap:
         self.voxel_size = float(voxel_size)
         self._block = torch.empty(ops.map_bytes(self.max_voxels, self.max_pairs) // 8 + 2, dtype=torch.int64, device=device)
         self._V = self._adds = self._flags = 0
+        self._carve, self._carves = None, 0                        # the carve block: allocated by the first carve()
         self.clear()
 
     # -- state ---------------------------------------------------------------------------------------------
@@ -99,9 +122,12 @@ class ScanMap:
         return self._block.device
 
     def clear(self) -> None:
-        """Empties the map; a dead map lives again."""
+        """Empties the map and its carve block; a dead map lives again."""
         ops.map_clear(self._block, self.max_voxels, self.max_pairs, self.voxel_size)
         self._V = self._adds = self._flags = 0
+        if self._carve is not None:
+            ops.carve_clear(self._carve, self.max_voxels)
+        self._carves = 0
 
     def _alive(self, what: str):
         if self._flags:
@@ -162,6 +188,61 @@ class ScanMap:
         """(sum_q [V, 3] int64, sum_c [V, 3] int64): the exact fixed-point sums behind cloud(), q = floor(v * 2^20) + 2^20 per observation."""
         s = self._fields("sums")[4]
         return s[:, :3], s[:, 3:]
+
+    # -- carving (csrc/carve.hip) ---------------------------------------------------------------------------
+    @property
+    def num_carves(self) -> int:
+        return self._carves
+
+    @torch.no_grad()
+    def carve(self, xyz: torch.Tensor, origin, pose=None, margin: int = 1) -> CarveResult:
+        """Clears the free space a scan saw through: xyz [M, 3] f32 and pose as add()'s, origin = the sensor's position in the scan's frame (three
+        numbers).  Every map voxel that holds a point of the scan is hit; every map voxel that a ray from the origin's cell to a point's cell
+        crosses, more than `margin` cells (Chebyshev) before the ray's end and not itself hit by this scan, is missed.  Each counts once per carve:
+        hits() counts CARVES, not points, so carve a map from its first scan on -- a voxel added without a carve has hits = 0.  Rays run from cell
+        centre to cell centre, at most half a voxel off the true ray.  The map itself is never written.  ValueError before any launch for an origin
+        that lands outside [-1, 1]^3; MapOverflow for a dead map.  One 64-byte host read, the carve block's header; the block (ops.carve_bytes) is
+        allocated by the first carve."""
+        lead = self._alive("carve")
+        ops.carve_origin(origin, pose, self.voxel_size)
+        if self._carve is None:
+            self._carve = torch.empty(ops.carve_bytes(self.max_voxels) // 8, dtype=torch.int64, device=self.device)
+            ops.carve_clear(self._carve, self.max_voxels)
+        h = ops.carve_scan(*lead, self._carve, xyz, origin, pose, margin, self._carves + 1)
+        self._carves = h[ops.CARVE_H_CARVES]
+        return CarveResult(h[ops.CARVE_H_RAYS], h[ops.CARVE_H_ACCEPTED], h[ops.CARVE_H_REJECTED], h[ops.CARVE_H_HIT], h[ops.CARVE_H_MISSED],
+                           h[ops.CARVE_H_CROSSED])
+
+    def _carve_fields(self, what: str):
+        block, max_voxels, _, V = self._filled(what)
+        if self._carve is None:                                    # never carved: nothing was ever seen through
+            return tuple(torch.zeros(4, V, dtype=torch.int32, device=self.device))
+        return ops.carve_fields(self._carve, max_voxels, V)
+
+    def hits(self) -> torch.Tensor:
+        """[V] int32: the carves in which the voxel held a point."""
+        return self._carve_fields("hits")[0]
+
+    def misses(self) -> torch.Tensor:
+        """[V] int32: the carves in which a ray passed through the voxel and no point of that scan lay in it."""
+        return self._carve_fields("misses")[1]
+
+    def last_hit(self) -> torch.Tensor:
+        """[V] int32: the number of the last carve that hit the voxel (from 1), 0 for none."""
+        return self._carve_fields("last_hit")[2]
+
+    def last_missed(self) -> torch.Tensor:
+        return self._carve_fields("last_missed")[3]
+
+    @torch.no_grad()
+    def occupied(self, min_misses: int = 2, num: int = 1, den: int = 1) -> torch.Tensor:
+        """[V] bool.  A voxel is FREE iff misses >= min_misses and misses * den > hits * num (int64): seen through at least min_misses times, and
+        more than num / den times as often as it was hit.  Before any carve everything is occupied.  hits counts carves, not points (carve())."""
+        for name, v, lo in (("min_misses", min_misses, 0), ("num", num, 0), ("den", den, 1)):
+            if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= 2 ** 31 - 1:
+                raise ValueError(f"occupied: {name} must be an integer in {lo} .. 2^31 - 1, got {v!r}")
+        hits, misses = self._carve_fields("occupied")[:2]
+        return occupied_from_counts(hits, misses, min_misses, num, den)
 
     def bits(self, K: int):
         """ops.label_bits of labels(): (bits [K, ceil(V / 64)] int64, area [K] int32), row k the voxels voted k."""

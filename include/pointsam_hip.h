@@ -1191,6 +1191,39 @@ int32_t psam_carve_scan(const void* map, size_t map_bytes, int32_t max_voxels, i
 int32_t psam_carve_fields(const void* carve, size_t carve_bytes, int32_t max_voxels, int32_t V, int32_t* hits, int32_t* misses, int32_t* last_hit,
                           int32_t* last_missed, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- scan map tracking */
+
+/* One step of point-to-point ICP of a scan against a scan map (ScanMap.track_step, ScanMap.track): per query the nearest map voxel -- its mean
+ * position -- within a radius, found by probing the map's own voxel table, fused with psam_align_step's twenty sums over those pairs.  No cloud is read
+ * out of the map and no index is built.  The map block is only read.  The call allocates nothing, uses no atomics and does not synchronise with the host.
+ *
+ * map, map_bytes, max_voxels, max_pairs: the block as every psam_map_* entry takes it.  V: voxel ids below V are candidates (0 < V <= max_voxels;
+ * normally the map's own V; ids the map has not given out are never found).  skip: NULL, or ceil(V / 64) words over voxel ids in the layout of
+ * psam_mask_pack: a voxel whose bit is set is no candidate.  min_count >= 1: a voxel observed fewer times is no candidate.  reach in 1 .. 4.
+ * qry [M, 3], qry_bits, pose (12 floats in HOST memory, scan frame -> map frame, or NULL: the query as given): psam_align_step's.
+ *     takes part        query i, if qry_bits is NULL or its bit i is set; bits past M are ignored
+ *     posed coordinate  p = ((P[a][0] x + P[a][1] y) + P[a][2] z) + P[a][3] per axis, every fp32 operation rounded on its own (psam_map_add's)
+ *     cell              the query has a cell iff psam_map_add would accept p (colour apart): cell_a = floorf((p_a - (-1)) * inv_h) in [0, 2^21) and
+ *                       -1 <= p_a <= 1 on every axis, inv_h the map header's.  Exactly the points psam_map_locate accepts
+ *     candidates        the map voxels v whose cell is one of the (2 reach + 1)^3 cells around cell(p) (a cell with a coordinate below 0 or at or
+ *                       above 2^21 is skipped), with v < V, count(v) >= min_count, the bit of v in skip clear, and
+ *                       q = (dx dx + dy dy) + dz dz <= r2 in fp32, each operation rounded on its own, NaN false; d = p - s, s the voxel's mean position
+ *                       with the bits psam_map_cloud gives it.  The cube of cells IS the definition: no cell is dropped by a geometric bound
+ *     pair              the candidate lowest in (q, v).  Neither the probe order nor the schedule enters any output
+ *     nearest [M]       (may be NULL) the pair's voxel id, -1 without one
+ * sums [PSAM_ALIGN_SUMS] f64 on the device: psam_align_step's twenty words with s the voxel's mean, x the query AS GIVEN (not posed): every term exact
+ *   in fp64, the additions in psam_align_step's fixed order (a function of M alone), [19] the number of participating queries that have a cell.
+ *   The same inputs give the same twenty words from run to run.
+ * ws: psam_track_workspace_bytes(M) = psam_align_workspace_bytes(M) bytes (0 for M outside (0, 2^28]), 8-byte aligned.
+ * Every refusal comes before any launch and leaves sums and nearest untouched: a null map, qry, sums or ws, M outside (0, 2^28], V outside
+ * (0, max_voxels], bad capacities, reach outside 1 .. 4, min_count < 1, r2 not finite and positive, a pose that is not finite: -1; a misaligned
+ * pointer (map 16 bytes; sums, ws, skip and qry_bits 8; qry and nearest 4): -2; a short map block or ws: -3. */
+#define PSAM_TRACK_MAX_REACH 4
+size_t psam_track_workspace_bytes(int32_t M);
+int32_t psam_track_step(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, const uint64_t* skip, int32_t min_count,
+                        int32_t reach, float r2, const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest,
+                        double* sums, void* ws, size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

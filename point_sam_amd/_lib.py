@@ -194,6 +194,8 @@ SIGNATURES = {
     "psam_carve_workspace_bytes": (size_t, [i32]),
     "psam_carve_scan": (i32, [ptr, size_t, i32, i32, ptr, size_t, ptr, i32, ptr, ptr, i32, i32, ptr, size_t, ptr]),
     "psam_carve_fields": (i32, [ptr, size_t, i32, i32, ptr, ptr, ptr, ptr, ptr]),
+    "psam_track_workspace_bytes": (size_t, [i32]),
+    "psam_track_step": (i32, [ptr, size_t, i32, i32, i32, ptr, i32, i32, f32, ptr, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
 }
 
 

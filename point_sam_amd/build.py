@@ -62,6 +62,8 @@ SOURCES = [
     ("scanmap.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # scan map carving: scanmap.hip's point, pose and cell bit for bit (csrc/map_block.h), so scanmap.hip's flags; the walk itself is integer.
     ("carve.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # scan map tracking: scanmap.hip's point, cell and voxel mean (csrc/map_block.h) and align.hip's distance and sums, so the flags of both.
+    ("track.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

@@ -1,5 +1,5 @@
-// The scan map's block and a point's way into it, shared by scanmap.hip (the map's own entries) and carve.hip (free-space carving): the block's
-// layout, the header's words, the pose arithmetic and the acceptance test of a point are one decision and live here once.  The block is described
+// The scan map's block and a point's way into it, shared by scanmap.hip (the map's own entries), carve.hip (free-space carving) and track.hip (ICP steps
+// on the map's voxels): the block's layout, the header's words, the pose arithmetic, the acceptance test of a point and a voxel's mean are one decision and live here once.  The block is described
 // at the top of scanmap.hip.  Translation units that include this are compiled with -ffp-contract=off and -fno-slp-vectorize (point_sam_amd/build.py).
 #pragma once
 #include "common.h"
@@ -75,3 +75,13 @@ __device__ __forceinline__ bool map_point(const float* __restrict__ xyz, int64_t
 }
 
 __device__ __forceinline__ float map_inv_h(const int* __restrict__ header) { return __builtin_bit_cast(float, header[MAP_H_INV_H]); }
+
+// ------------------------------------------------------------------------------------------------ a voxel's mean
+// fl32(fl64(fl64(sum) / fl64(count)) * 2^-20 - 1): the quotient rounds once, the scaling is exact, the difference rounds once, then fp64 -> fp32
+__device__ __forceinline__ float map_mean(u64 sum, u64 count) {
+#pragma clang fp contract(off)
+    const double m = (double)sum / (double)count;
+    const double s = m * 0x1p-20;
+    const double d = s - 1.0;
+    return (float)d;
+}

@@ -241,15 +241,6 @@ __global__ __launch_bounds__(MAP_THREADS) void map_labels_kernel(const int* __re
     votes[v] = ok ? n : 0;
 }
 
-// fl32(fl64(fl64(sum) / fl64(count)) * 2^-20 - 1): the quotient rounds once, the scaling is exact, the difference rounds once, then fp64 -> fp32
-__device__ __forceinline__ float map_mean(u64 sum, u64 count) {
-#pragma clang fp contract(off)
-    const double m = (double)sum / (double)count;
-    const double s = m * 0x1p-20;
-    const double d = s - 1.0;
-    return (float)d;
-}
-
 __global__ __launch_bounds__(MAP_THREADS) void map_cloud_kernel(const int* __restrict__ header, const u64* __restrict__ rows, int V, float* __restrict__ xyz,
                                                                 float* __restrict__ rgb) {
     const int v = blockIdx.x * MAP_THREADS + threadIdx.x;

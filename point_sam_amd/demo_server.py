@@ -24,7 +24,8 @@ POST /frames {depth, rgb, cameras, far, edge?, depth_scale?} (not in the referen
 POST /fuse_labels {labels, tau, overlap?, min_points?, min_votes?, consistent?} (not in the reference): the frames' 2-D segmentations fused into one
 instance labelling of that cloud (predictor.fuse_labels).
 POST /map/add {pose?, labels?} . POST /map {min_votes?} . POST /map/clear (not in the reference): the loaded cloud, under its pose, is added to the
-session's scan map (predictor.map_add, point_sam_amd/scanmap.py); /map returns the map's voxels as a cloud with one voted label each.
+session's scan map (predictor.map_add, point_sam_amd/scanmap.py), with "track": {AlignConfig fields} after its pose was refined against the map
+(predictor.map_align); /map returns the map's voxels as a cloud with one voted label each.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -580,15 +581,23 @@ class DemoSession:
         gets the index of the first kept /next mask or current /segment mask that holds it, -1 outside all)} -> {"new_voxels", "accepted",
         "rejected", "num_voxels", "num_adds"}.  With "origin": [x, y, z] (the sensor's position in the loaded cloud's coordinates) the scan is then carved
         (predictor.map_carve, "margin": cells, optional, default 1) and the answer gains {"rays", "hit_voxels", "missed_voxels", "crossed",
-        "num_carves"}.  A bad value or a full map is a 400."""
+        "num_carves"}.  With "track": {align.AlignConfig fields} the pose is first refined against the map itself (predictor.map_align, the request's
+        pose as its start; skipped while the map is empty), the scan is added and carved under the refined pose, and the answer gains {"pose": the 3 x 4
+        rows used, "pairs", "coverage", "rms", "converged", "reason"}.  A bad value or a full map is a 400."""
         with self.lock:
             if self.pc_xyz is None:
                 raise ValueError("/map/add before a point cloud was set")
-            if not isinstance(data, dict) or set(data) - {"pose", "labels", "origin", "margin"}:
-                raise ValueError('/map/add takes {"pose": rows (optional), "labels": [ints] (optional), "origin": [x, y, z] (optional), "margin": n (optional)}')
+            if not isinstance(data, dict) or set(data) - {"pose", "labels", "origin", "margin", "track"}:
+                raise ValueError('/map/add takes {"pose": rows (optional), "labels": [ints] (optional), "origin": [x, y, z] (optional), "margin": n (optional), '
+                                 '"track": {AlignConfig fields} (optional)}')
             from . import ops
             pose = data.get("pose")
             ops.transfer_pose(pose)
+            track_cfg = None
+            if "track" in data:
+                from .align import AlignConfig
+                track_cfg = AlignConfig.from_overrides(data["track"])      # a bad track field is a 400 before anything is touched
+                ops.track_reach(track_cfg.radius, self.map_voxel_size)
             origin, margin = data.get("origin"), data.get("margin", 1)
             if "margin" in data and origin is None:
                 raise ValueError('"margin" belongs to a carve: give "origin" too')
@@ -617,6 +626,12 @@ class DemoSession:
                     self._set_cloud()
                     if self.scan_map is None:
                         self.scan_map = self.predictor.new_map(self.map_voxel_size, self.map_max_voxels)
+                    found = None
+                    if track_cfg is not None and self.scan_map.num_voxels > 0:      # an empty map has nothing to track against: the pose as given
+                        found = self._map_error(lambda: self.predictor.map_align(self.scan_map, track_cfg, pose))
+                        pose = found.pose.tolist()
+                        if origin is not None:
+                            ops.carve_origin(origin, pose, self.map_voxel_size)
                     res = self._map_error(lambda: self.predictor.map_add(self.scan_map, torch.from_numpy(labels).to(self.device), pose))
                     cut = None if origin is None else self._map_error(lambda: self.predictor.map_carve(self.scan_map, origin, pose, margin))
                 finally:
@@ -626,6 +641,13 @@ class DemoSession:
             if cut is not None:
                 out.update(rays=int(cut.rays), hit_voxels=int(cut.hit_voxels), missed_voxels=int(cut.missed_voxels), crossed=int(cut.crossed),
                            num_carves=int(self.scan_map.num_carves))
+            if track_cfg is not None:
+                if found is None:
+                    out.update(pose=np.eye(4)[:3].tolist() if pose is None else np.asarray(pose, dtype=np.float64)[:3].tolist(), pairs=0, coverage=0.0,
+                               rms=None, converged=False, reason="the map was empty: nothing to track against")
+                else:
+                    out.update(pose=pose, pairs=int(found.pairs), coverage=float(found.coverage), rms=found.rms if np.isfinite(found.rms) else None,
+                               converged=bool(found.converged), reason=found.reason)
             return out
 
     def map_get(self, data: dict) -> dict:

@@ -1679,15 +1679,20 @@ def _align_arguments(what: str, index, xyz, pose, radius, bits):
     -> (xyz [M, 3], the pose's fp32 words or None, r2, bits as one checked row or None)."""
     xyz, r2 = _transfer_query(what, index, xyz, radius)
     words = transfer_pose(pose)
-    M = xyz.shape[0]
-    if bits is not None:
-        if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64 or bits.dim() == 2 and bits.shape[0] != 1 or bits.dim() not in (1, 2) or \
-                bits.shape[-1] != mask_words(M):
-            raise ValueError(f"{what}: bits must be one packed row of {mask_words(M)} int64 words for {M} queries, got "
-                             f"{(bits.dtype, tuple(bits.shape)) if isinstance(bits, torch.Tensor) else type(bits).__name__}")
-        bits = bits.reshape(-1)
-        _chk(bits, torch.int64, name="bits")
-    return xyz, words, r2, bits
+    return xyz, words, r2, _packed_row(what, "bits", bits, xyz.shape[0], "queries")
+
+
+def _packed_row(what: str, name: str, bits, n: int, of: str):
+    """None, or one packed row over n items (mask_pack's layout) -> the row as [ceil(n / 64)] int64 words, checked."""
+    if bits is None:
+        return None
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int64 or bits.dim() == 2 and bits.shape[0] != 1 or bits.dim() not in (1, 2) or \
+            bits.shape[-1] != mask_words(n):
+        raise ValueError(f"{what}: {name} must be one packed row of {mask_words(n)} int64 words for {n} {of}, got "
+                         f"{(bits.dtype, tuple(bits.shape)) if isinstance(bits, torch.Tensor) else type(bits).__name__}")
+    bits = bits.reshape(-1)
+    _chk(bits, torch.int64, name=name)
+    return bits
 
 
 def _align_call(step, workspace_bytes, name: str, num_sums: int, index, xyz, words, r2, bits, return_nearest: bool, *extra):
@@ -2682,3 +2687,51 @@ def carve_fields(carve: torch.Tensor, max_voxels: int, V: int):
     out = torch.empty(4, V, dtype=torch.int32, device=carve.device)
     check(_lib.load().psam_carve_fields(*lead, V, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), _stream()), "psam_carve_fields")
     return out[0], out[1], out[2], out[3]
+
+
+# ------------------------------------------------------------------------------------------ scan map tracking (csrc/track.hip)
+TRACK_MAX_REACH = 4              # PSAM_TRACK_MAX_REACH
+
+
+def track_reach(radius, voxel_size) -> int:
+    """The cells a search of `radius` looks out from a query's own cell on a map of `voxel_size`: max(1, ceil(fl32(radius) * fl32(1 / fl32(voxel_size)))),
+    the product and the ceiling in fp64 on those fp32 values.  ValueError above TRACK_MAX_REACH: a step visits (2 reach + 1)^3 cells per query."""
+    import math
+    r, _, _ = transfer_radius(radius)
+    reach = max(1, math.ceil(float(r) * float(map_inv_h(voxel_size))))
+    if reach > TRACK_MAX_REACH:
+        raise ValueError(f"track: radius {float(r)} is {reach} voxels of size {float(voxel_size)}: the search reaches at most {TRACK_MAX_REACH} cells "
+                         f"from a query's own ({(2 * TRACK_MAX_REACH + 1) ** 3} cells per query)")
+    return reach
+
+
+def track_step(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, xyz: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None,
+               skip: torch.Tensor = None, min_count: int = 1, return_nearest: bool = False, *, voxel_size):
+    """One ICP step of a scan against a scan map (include/pointsam_hip.h: scan map tracking): the map's block, capacities and V, xyz [M, 3] f32 (the
+    queries), pose as map_add's (scan frame -> map frame) -> sums [20] float64 on the device, align_step's words over the pairs (query, nearest map
+    voxel within `radius` of pose(query)): the voxel's mean position, cloud()'s bits, found in the map's own table -- no cloud, no index.  radius:
+    None = the voxel size; at most TRACK_MAX_REACH voxels (track_reach).  bits: align_step's.  skip: None, or [ceil(V / 64)] int64 words over voxel
+    ids: a voxel whose bit is set is never paired.  min_count: a voxel observed fewer times is never paired.  return_nearest: also nearest [M] int32,
+    the voxel id, -1 without a pair.  voxel_size: the size the map was cleared with (the header is not read back).  No host synchronisation."""
+    xyz = _map_points("track_step", xyz, "xyz")
+    words = transfer_pose(pose)
+    _, _, r2 = transfer_radius(voxel_size if radius is None else radius)
+    reach = track_reach(voxel_size if radius is None else radius, voxel_size)
+    M = xyz.shape[0]
+    bits = _packed_row("track_step", "bits", bits, M, "queries")
+    V = _map_count("track_step", V, max_voxels)
+    skip = _packed_row("track_step", "skip", skip, V, "voxels")
+    min_count = _superpoint_int(min_count, 1, 2 ** 31 - 1, "track_step: min_count")
+    lead = _map_block("track_step", block, max_voxels, max_pairs)
+    _chk(xyz, name="xyz")
+    if not (xyz.device == block.device and (bits is None or bits.device == xyz.device) and (skip is None or skip.device == xyz.device)):
+        raise ValueError(f"track_step: xyz is on {xyz.device}, the block on {block.device}; bits and skip must be there too")
+    dev = xyz.device
+    L = _lib.load()
+    sums = torch.empty(ALIGN_SUMS, dtype=torch.float64, device=dev)
+    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
+    ws = torch.empty(L.psam_track_workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
+    P, pose_ptr = _pose_arg(words)
+    check(L.psam_track_step(*lead, V, _p(skip), min_count, reach, float(r2), xyz.data_ptr(), M, _p(bits), pose_ptr, _p(nearest), sums.data_ptr(),
+                            ws.data_ptr(), ws.numel() * 8, _stream()), "psam_track_step")
+    return (sums, nearest) if return_nearest else sums

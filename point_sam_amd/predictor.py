@@ -429,6 +429,28 @@ class PointSAMPredictor:
         return torch.where(ids >= 0, label.index_select(0, ids.clamp(min=0).long()), torch.full_like(ids, -1))
 
     @torch.no_grad()
+    def map_align(self, m, cfg, init=None, mask=None, occupied=None, min_count: int = 1):
+        """The pose of the CURRENT scan against the scanmap.ScanMap `m` itself, by ICP on the map's own voxels (ScanMap.track) -> align.Alignment; its
+        `pose` is what map_add and map_carve take.  The coordinates are the ones map_add would add (after set_scene the full-resolution points).
+        Exactly m.track(those, cfg, init, mask, occupied, min_count): cfg an align.AlignConfig with a radius of at most 4 voxels, init the pose to
+        refine (odometry, the previous scan's pose, align()'s frame-to-frame estimate), mask an optional packed row [ceil(M / 64)] int64 at the
+        scan's width, occupied None / True / a [V] bool tensor.  Frame to model: the error of one scan's pose does not enter the next one's."""
+        xyz, _ = self._map_scan(m, "map_align")
+        return m.track(xyz, cfg, init, mask, occupied, min_count)
+
+    @torch.no_grad()
+    def map_nearest(self, m, pose=None, radius=None, min_votes: int = 1) -> torch.Tensor:
+        """map_lookup through the NEAREST voxel within `radius` (None: the voxel size) instead of the point's own: per point of the CURRENT scan the
+        voted label of the map voxel whose mean lies nearest to the posed point -> [M] int32, -1 where no voxel is in reach or that voxel has no label
+        with min_votes votes.  One ScanMap.track_step(return_nearest=True); ValueError for an empty map.  No host read."""
+        xyz, _ = self._map_scan(m, "map_nearest")
+        if isinstance(min_votes, bool) or not isinstance(min_votes, int) or not 1 <= min_votes <= 2 ** 31 - 1:
+            raise ValueError(f"map_nearest: min_votes must be an integer in 1 .. 2^31 - 1, got {min_votes!r}")
+        _, ids = m.track_step(xyz, pose, radius, return_nearest=True)
+        label = m.labels(min_votes)[0]
+        return torch.where(ids >= 0, label.index_select(0, ids.clamp(min=0).long()), torch.full_like(ids, -1))
+
+    @torch.no_grad()
     def generate_masks(self, cfg=None, crops=None):
         """Automatic mask proposals for the cached cloud(s), no prompts needed (point_sam_amd/proposals.py): a list with one `Proposals` per
         cloud -- kept masks best first, bit-packed, and one instance label per point.  cfg: a `ProposalConfig` (None = its defaults).

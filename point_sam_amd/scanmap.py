@@ -20,8 +20,15 @@ whether the voxel held a point (a hit) or was seen through (a miss); occupied() 
 a chair since moved, depth noise at an edge -- is then voted free, and cloud()[occupied()] shows no ghosts.  The walk is exact integer arithmetic
 between cell centres (at most half a voxel off the true ray); the counts live in a second block, and the map's own block is never written by a carve.
 
+Tracking (csrc/track.hip): the poses of a walk are otherwise frame to frame, and their errors add up.  track() registers a scan against the MAP, the one
+object that has seen the whole walk: align.icp's loop, where a step (track_step) pairs every point of the scan with the nearest map voxel -- its
+mean position, cloud()'s bits -- by probing the map's own voxel table.  No cloud is read out and no index is built; the step sums ops.align_step's
+twenty words, so the solve and the loop are align.py's unchanged.
+
 Not built: removing or decaying voxels (occupied() is a read-out; a freed voxel keeps its id, sums and votes), rays from an origin outside
-[-1, 1]^3, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, loop closure.  No default here has been
+[-1, 1]^3, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, pose-graph optimisation (track() places a scan against the map, it does not go back and
+move the scans already added), point-to-plane against the map (the map stores no normals), a global search against the map (track() refines an
+initial pose), a search that reaches more than 4 voxels from a query's own.  No default here has been
 tuned on real scans or a trained checkpoint.  Beyond the voxel and pair capacities a map takes at most 2^31 - 1 accepted points in all (the bound that
 keeps counts and votes in int32 and every sum in one 64-bit word); that refusal is not exercised by any test.
 """
@@ -247,3 +254,41 @@ class ScanMap:
     def bits(self, K: int):
         """ops.label_bits of labels(): (bits [K, ceil(V / 64)] int64, area [K] int32), row k the voxels voted k."""
         return ops.label_bits(self.labels()[0].contiguous(), K)
+
+    # -- tracking (csrc/track.hip) ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def track_step(self, xyz: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None, skip: torch.Tensor = None, min_count: int = 1,
+                   return_nearest: bool = False):
+        """One ICP step of a scan against the map (ops.track_step): xyz [M, 3] f32, pose from the scan's frame to the map's -> sums [20] float64 on
+        the device, ops.align_step's words over the pairs (point, nearest voxel mean within `radius` of the posed point; None: the voxel size), and
+        with return_nearest the voxel id per point, -1 without a pair.  bits: a packed row over the points that take part; skip: a packed row over
+        voxel ids that are never paired; min_count: the fewest observations of a voxel that is.  MapOverflow for a dead map, ValueError for an empty
+        one.  No host read."""
+        block, max_voxels, max_pairs, V = self._filled("track_step")
+        return ops.track_step(block, max_voxels, max_pairs, V, xyz, pose, radius, bits, skip, min_count, return_nearest, voxel_size=self.voxel_size)
+
+    @torch.no_grad()
+    def track(self, xyz: torch.Tensor, cfg, init=None, bits: torch.Tensor = None, occupied=None, min_count: int = 1):
+        """The pose of a scan against the map, by ICP -> align.Alignment; its `pose` maps the scan's frame to the map's: what add() and carve() take.
+        Exactly align.icp(self, xyz, cfg, init, bits, step=...) with track_step as the step: cfg an align.AlignConfig whose radius is at most 4 voxels
+        (ops.track_reach; ValueError before any launch), init the pose to refine (odometry, or the last scan's pose).  occupied: None, True
+        (self.occupied()) or a [V] bool tensor: only those voxels are paired (a scan is not pulled towards ghosts); the mask is packed once.  One
+        160-byte host read per step."""
+        from . import align as A
+        if not isinstance(cfg, A.AlignConfig):
+            raise TypeError(f"track: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
+        ops.track_reach(cfg.radius, self.voxel_size)
+        if occupied is not None and occupied is not True and not isinstance(occupied, torch.Tensor):
+            raise TypeError(f"track: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
+        V = self._filled("track")[3]
+        skip = None
+        if occupied is not None:
+            if occupied is True:
+                occupied = self.occupied()
+            if occupied.dtype != torch.bool or tuple(occupied.shape) != (V,) or occupied.device != self.device:
+                raise ValueError(f"track: occupied must be [{V}] bool on {self.device}, got {tuple(occupied.shape)} {occupied.dtype} on {occupied.device}")
+            skip = ops.mask_pack((~occupied).to(torch.float32)[None].contiguous(), 0.5, 0.0)[0][0]
+
+        def step(m, points, pose, radius, row):
+            return m.track_step(points, pose, radius, row, skip, min_count)
+        return A.icp(self, xyz, cfg, init, bits, step=step)

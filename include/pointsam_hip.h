@@ -1224,6 +1224,55 @@ int32_t psam_track_step(const void* map, size_t map_bytes, int32_t max_voxels, i
                         int32_t reach, float r2, const float* qry, int32_t M, const uint64_t* qry_bits, const float* pose, int32_t* nearest,
                         double* sums, void* ws, size_t ws_bytes, psam_stream_t stream);
 
+/* One step of point-to-PLANE ICP of a scan against a scan map (ScanMap.track_plane_step, ScanMap.track with normals): psam_track_step's pair per
+ * query, fused with psam_plane_step's thirty-two sums over the used pairs.  The map block is only read; no atomics, no allocation, no host
+ * synchronisation.
+ *
+ * Every argument of psam_track_step means what it means there.  normals [V, 3] f32 (non-null, 4-byte aligned): one normal per voxel id, taken as
+ * given -- not normalised, either sign; psam_scanmap_normals' output fits.
+ *     pair, nearest     psam_track_step's, bit for bit: the same posed coordinate p, cell, cube, skip, min_count, r2 and order (q, v)
+ *     used pair         psam_plane_step's: nn = (n_x n_x + n_y n_y) + n_z n_z in fp32 finite and > 0
+ *     terms             psam_plane_step's with p the POSED coordinate's fp32 words (the query itself without a pose), s the pair's fp32 mean
+ *                       (psam_map_cloud's bits) and n = normals[pair], all converted to fp64: d = p - s; r = (d_x n_x + d_y n_y) + d_z n_z;
+ *                       c = p x n; J = (c, n)
+ * sums [PSAM_PLANE_SUMS] f64 on the device: psam_plane_step's words in psam_plane_step's fixed order of addition (a function of M alone); [30] the
+ *   paired queries whose pair is not used, [31] the participating queries that have a cell.  The same inputs give the same words from run to run.
+ * ws: psam_scanmap_plane_workspace_bytes(M) = psam_plane_workspace_bytes(M) bytes (0 for M outside (0, 2^28]), 8-byte aligned.
+ * Refusals: psam_track_step's codes in its order, before any launch, sums and nearest untouched; normals counts among the pointers that may not be
+ * null (-1) and must be 4-byte aligned (-2). */
+size_t psam_scanmap_plane_workspace_bytes(int32_t M);
+int32_t psam_scanmap_plane_step(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, const float* normals,
+                              const uint64_t* skip, int32_t min_count, int32_t reach, float r2, const float* qry, int32_t M, const uint64_t* qry_bits,
+                              const float* pose, int32_t* nearest, double* sums, void* ws, size_t ws_bytes, psam_stream_t stream);
+
+/* ---------------------------------------------------------------- scan map normals */
+
+/* One surface normal and curvature per voxel of a scan map (ScanMap.normals), from the map's own block: the eigenvector of the smallest eigenvalue of
+ * the scatter matrix of the MEANS of the voxels around it.  The map block is only read; there is no workspace, no atomics, no allocation and no host
+ * synchronisation.
+ *
+ * map, map_bytes, max_voxels, max_pairs, V, skip, min_count: psam_track_step's.
+ *     allowed voxel     u is allowed iff u < V, count(u) >= min_count and its bit in skip is clear (skip may be NULL)
+ *     neighbourhood     of voxel id v < V: the allowed voxels in the (2 reach + 1)^3 cells around v's own cell (key_of_id[v]); a cell with a coordinate
+ *                       below 0 or at or above 2^21 is skipped.  reach is 1 or 2: 27 or 125 cells.  If v itself is not allowed its neighbourhood is
+ *                       empty: count 0, normal (0, 0, 0), curvature 0, scatter 0
+ *     point of a voxel  its mean with the bits psam_map_cloud gives it (the s psam_track_step pairs with), in fixed point:
+ *                       q_a = floor((double)s_a * 2^20) + 2^20, an integer in [0, 2^21]
+ *     scatter           n the number of voxels of the neighbourhood, s = sum q, P = sum q q^T, S = n P - s s^T, all integers, exact: n <= 125 and
+ *                       q <= 2^21 give P_ab < 2^49, n P_ab < 2^56, s_a s_b < 2^56, so S fits a signed 64-bit word.  S goes to fp64 once, rounded to
+ *                       nearest even.  Neither the order of the cube nor the schedule enters any output
+ *     normal            n < min_voxels (min_voxels >= 1): (0, 0, 0) and curvature 0, exactly.  Otherwise psam_normals_voxel's solve on S: scaled by a
+ *                       power of two, cyclic Jacobi in fp64, the eigenvector of the smallest eigenvalue (ties: the lowest axis) normalised and
+ *                       rounded to fp32, curvature l0 / (l0 + l1 + l2), and the sign without a viewpoint: the component of largest magnitude
+ *                       (ties: the lowest axis) is positive, decided on the stored fp32 values
+ * count [V] i32, normal [V, 3] f32, curvature [V] f32; scatter [V, 6] f64 (may be NULL): xx, xy, xz, yy, yz, zz of S.
+ * Every refusal comes before any launch and leaves the outputs untouched: a null map, count, normal or curvature, V outside (0, max_voxels], bad
+ * capacities, reach outside 1 .. 2, min_voxels < 1, min_count < 1: -1; a misaligned pointer (map 16 bytes; skip and scatter 8; count, normal and
+ * curvature 4): -2; a short map block: -3. */
+#define PSAM_SCANMAP_NORMALS_MAX_REACH 2
+int32_t psam_scanmap_normals(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, const uint64_t* skip, int32_t min_count,
+                         int32_t reach, int32_t min_voxels, int32_t* count, double* scatter, float* normal, float* curvature, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,8 +62,11 @@ SOURCES = [
     ("scanmap.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # scan map carving: scanmap.hip's point, pose and cell bit for bit (csrc/map_block.h), so scanmap.hip's flags; the walk itself is integer.
     ("carve.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
-    # scan map tracking: scanmap.hip's point, cell and voxel mean (csrc/map_block.h) and align.hip's distance and sums, so the flags of both.
+    # scan map tracking, point to point and point to plane: scanmap.hip's point, cell and voxel mean (csrc/map_block.h) and the distance and sums of
+    # align.hip / align_plane.hip, so the flags of all three.
     ("track.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # scan map normals: scanmap.hip's voxel mean and fixed point (csrc/map_block.h) and normals.hip's eigen-solve (csrc/normal_eigen.h), so the flags of both.
+    ("map_normals.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

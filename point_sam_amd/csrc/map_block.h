@@ -1,5 +1,5 @@
-// The scan map's block and a point's way into it, shared by scanmap.hip (the map's own entries), carve.hip (free-space carving) and track.hip (ICP steps
-// on the map's voxels): the block's layout, the header's words, the pose arithmetic, the acceptance test of a point and a voxel's mean are one decision and live here once.  The block is described
+// The scan map's block and a point's way into it, shared by scanmap.hip (the map's own entries), carve.hip (free-space carving), track.hip (ICP steps
+// on the map's voxels) and map_normals.hip (a normal per voxel): the block's layout, the header's words, the pose arithmetic, the acceptance test of a point and a voxel's mean are one decision and live here once.  The block is described
 // at the top of scanmap.hip.  Translation units that include this are compiled with -ffp-contract=off and -fno-slp-vectorize (point_sam_amd/build.py).
 #pragma once
 #include "common.h"
@@ -84,4 +84,18 @@ __device__ __forceinline__ float map_mean(u64 sum, u64 count) {
     const double s = m * 0x1p-20;
     const double d = s - 1.0;
     return (float)d;
+}
+
+// ------------------------------------------------------------------------------------------------ a cell's slot, probed in stages
+// voxel_find (voxel_table.h) from its second probe on: `cur` is what the first probe read at `pos`
+__device__ __forceinline__ int map_find_rest(const u64* __restrict__ keys, int capacity, u64 key, unsigned pos, u64 cur) {
+    const unsigned mask = (unsigned)capacity - 1u;
+    for (int probe = 1; probe <= capacity; ++probe) {
+        if (cur == VOXEL_EMPTY) break;
+        if (cur == key) return (int)pos;
+        if (probe == capacity) break;
+        pos = (pos + 1u) & mask;
+        cur = keys[pos];
+    }
+    return -1;
 }

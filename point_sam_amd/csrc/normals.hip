@@ -15,21 +15,14 @@
 //   P_ab = high * 2^32 + low <= 2^70, n P_ab <= 2^98 and s_a s_b <= 2^98: both, and their difference, fit a signed 128-bit integer.
 // A sum over 27 rows of the table is a sum over the neighbourhood's points, so the same bounds hold for it.  N above 2^28 is refused before launch.
 //
-// int128 -> fp64 is done here, not left to the compiler's run-time routine: the value's top 64 bits with a sticky bit for the rest, one correctly
+// int128 -> fp64 is done by hand (normal_eigen.h), not left to the compiler's run-time routine: the value's top 64 bits with a sticky bit for the rest, one correctly
 // rounded u64 -> fp64 conversion (the sticky bit sits ten places below the rounding position), and an exact scaling.  Round to nearest even, like
 // float(int) of the reference.
-#include "common.h"
-
-#include <cmath>
-
-typedef unsigned long long u64;
-typedef __int128 i128;
-typedef unsigned __int128 u128;
+#include "normal_eigen.h"     // the int128 -> fp64 conversion and the eigen-solve, shared with map_normals.hip
 
 constexpr int NORMAL_THREADS = 256;
 constexpr int NORMAL_MAX_POINTS = 1 << 28;
 constexpr int NORMAL_ROW = 16;                     // u64 words per voxel of the table: count, 3 sums, 6 low limbs, 6 high limbs
-constexpr int NORMAL_SWEEPS = 24;                  // cyclic Jacobi converges quadratically: a 3 x 3 matrix is diagonal to the last bit after five or six
 
 static inline unsigned normal_blocks(int64_t n) { return (unsigned)psam_cdiv(n, NORMAL_THREADS); }
 
@@ -65,50 +58,7 @@ __global__ __launch_bounds__(NORMAL_THREADS) void normal_moments_kernel(const fl
     }
 }
 
-// ------------------------------------------------------------------------------------------------ eigen
-__device__ __forceinline__ double normal_to_double(i128 v) {
-    const bool neg = v < 0;
-    const u128 m = neg ? (u128)0 - (u128)v : (u128)v;
-    const u64 hi = (u64)(m >> 64), lo = (u64)m;
-    double d;
-    if (hi == 0) {
-        d = (double)lo;                                            // one rounding: hi32 * 2^32 (exact) + lo32 (exact)
-    } else {
-        const int shift = 64 - __builtin_clzll(hi);               // 1 .. 64: the value has 64 + shift bits
-        u64 top = (u64)(m >> shift);
-        const u128 rest = m & (((u128)1 << shift) - 1);
-        if (rest != 0) top |= 1ull;                                // sticky
-        d = ldexp((double)top, shift);
-    }
-    return neg ? -d : d;
-}
-
-// One Jacobi rotation of the symmetric matrix a (full storage) in the plane (P, Q), R the third axis; the columns of e follow.
-template <int P, int Q, int R>
-__device__ __forceinline__ void normal_rotate(double (&a)[3][3], double (&e)[3][3]) {
-    const double apq = a[P][Q];
-    if (apq == 0.0) return;
-    if (fabs(apq) <= 0x1p-70 * (fabs(a[P][P]) + fabs(a[Q][Q]))) {      // below the last bit of both diagonal entries: it is zero
-        a[P][Q] = a[Q][P] = 0.0;
-        return;
-    }
-    const double theta = (a[Q][Q] - a[P][P]) / (2.0 * apq);
-    const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-    const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-    a[P][P] = a[P][P] - t * apq;
-    a[Q][Q] = a[Q][Q] + t * apq;
-    a[P][Q] = a[Q][P] = 0.0;
-    const double arp = a[R][P], arq = a[R][Q];
-    a[R][P] = a[P][R] = c * arp - s * arq;
-    a[R][Q] = a[Q][R] = s * arp + c * arq;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const double erp = e[r][P], erq = e[r][Q];
-        e[r][P] = c * erp - s * erq;
-        e[r][Q] = s * erp + c * erq;
-    }
-}
-
+// ------------------------------------------------------------------------------------------------ eigen (the solve: normal_eigen.h)
 __global__ __launch_bounds__(NORMAL_THREADS) void normal_eigen_kernel(const u64* __restrict__ table, const int* __restrict__ nbr, int V, int min_points,
                                                                     int has_view, float wx, float wy, float wz, int* __restrict__ count,
                                                                     double* __restrict__ scatter, float* __restrict__ normal,
@@ -140,30 +90,7 @@ __global__ __launch_bounds__(NORMAL_THREADS) void normal_eigen_kernel(const u64*
     }
     float out[3] = {0.0f, 0.0f, 0.0f}, curv = 0.0f;
     if ((int64_t)n >= (int64_t)min_points && n > 0) {
-        // scaled by a power of two (exact) so that the largest entry is near 1: eigenvectors and the curvature do not change
-        double big = 0.0;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) big = fmax(big, fabs(S[c]));
-        int ex = 0;
-        if (big > 0.0) frexp(big, &ex);
-        double a[3][3], e[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
-#pragma unroll
-        for (int c = 0; c < 6; ++c) a[ia[c]][ib[c]] = a[ib[c]][ia[c]] = ldexp(S[c], -ex);
-        for (int sweep = 0; sweep < NORMAL_SWEEPS; ++sweep) {
-            if (a[0][1] == 0.0 && a[0][2] == 0.0 && a[1][2] == 0.0) break;
-            normal_rotate<0, 1, 2>(a, e);
-            normal_rotate<0, 2, 1>(a, e);
-            normal_rotate<1, 2, 0>(a, e);
-        }
-        // the smallest eigenvalue; on a tie the lowest axis
-        double l0 = a[0][0], nx = e[0][0], ny = e[1][0], nz = e[2][0];
-        if (a[1][1] < l0) { l0 = a[1][1]; nx = e[0][1]; ny = e[1][1]; nz = e[2][1]; }
-        if (a[2][2] < l0) { l0 = a[2][2]; nx = e[0][2]; ny = e[1][2]; nz = e[2][2]; }
-        const double len = sqrt(nx * nx + ny * ny + nz * nz);
-        out[0] = (float)(nx / len); out[1] = (float)(ny / len); out[2] = (float)(nz / len);
-        const double sum = (a[0][0] + a[1][1]) + a[2][2];
-        l0 = l0 < 0.0 ? 0.0 : l0;                                  // S is positive semi-definite: below zero is rounding
-        curv = sum > 0.0 ? (float)(l0 / sum) : 0.0f;
+        normal_solve(S, out, curv);
         // the sign, decided on the stored fp32 values
         bool flip;
         if (has_view) {
@@ -174,9 +101,7 @@ __global__ __launch_bounds__(NORMAL_THREADS) void normal_eigen_kernel(const u64*
                              (double)out[2] * ((double)wz - mz);
             flip = d < 0.0;
         } else {
-            const float ax = fabsf(out[0]), ay = fabsf(out[1]), az = fabsf(out[2]);
-            const float lead = (ax >= ay && ax >= az) ? out[0] : (ay >= az ? out[1] : out[2]);
-            flip = lead < 0.0f;
+            flip = normal_flip_default(out);
         }
         if (flip) { out[0] = -out[0]; out[1] = -out[1]; out[2] = -out[2]; }
     }

@@ -2735,3 +2735,69 @@ def track_step(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, xyz
     check(L.psam_track_step(*lead, V, _p(skip), min_count, reach, float(r2), xyz.data_ptr(), M, _p(bits), pose_ptr, _p(nearest), sums.data_ptr(),
                             ws.data_ptr(), ws.numel() * 8, _stream()), "psam_track_step")
     return (sums, nearest) if return_nearest else sums
+
+
+def track_plane_step(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, xyz: torch.Tensor, normals: torch.Tensor, pose=None, radius=None,
+                     bits: torch.Tensor = None, skip: torch.Tensor = None, min_count: int = 1, return_nearest: bool = False, *, voxel_size):
+    """One point-to-plane ICP step of a scan against a scan map (include/pointsam_hip.h: scan map tracking): track_step's arguments and pair, bit for
+    bit, and normals [V, 3] f32, one per voxel id, taken as given (map_normals' output fits) -> sums [32] float64 on the device, align_plane_step's
+    words over the used pairs: p the posed point, s the voxel's mean, n its normal.  Word [30] counts the pairs whose normal is zero or not finite,
+    word [31] the participating queries that have a cell.  return_nearest: also nearest [M] int32.  No host synchronisation."""
+    xyz = _map_points("track_plane_step", xyz, "xyz")
+    words = transfer_pose(pose)
+    _, _, r2 = transfer_radius(voxel_size if radius is None else radius)
+    reach = track_reach(voxel_size if radius is None else radius, voxel_size)
+    M = xyz.shape[0]
+    bits = _packed_row("track_plane_step", "bits", bits, M, "queries")
+    V = _map_count("track_plane_step", V, max_voxels)
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float32 or tuple(normals.shape) != (V, 3):
+        raise ValueError(f"track_plane_step: normals must be a [{V}, 3] float32 tensor, one per voxel id, got "
+                         f"{(tuple(normals.shape), normals.dtype) if isinstance(normals, torch.Tensor) else type(normals).__name__}")
+    skip = _packed_row("track_plane_step", "skip", skip, V, "voxels")
+    min_count = _superpoint_int(min_count, 1, 2 ** 31 - 1, "track_plane_step: min_count")
+    lead = _map_block("track_plane_step", block, max_voxels, max_pairs)
+    _chk(xyz, name="xyz")
+    _chk(normals, name="normals")
+    if not (xyz.device == block.device and normals.device == xyz.device and (bits is None or bits.device == xyz.device) and
+            (skip is None or skip.device == xyz.device)):
+        raise ValueError(f"track_plane_step: xyz is on {xyz.device}, the block on {block.device}; normals, bits and skip must be there too")
+    dev = xyz.device
+    L = _lib.load()
+    sums = torch.empty(PLANE_SUMS, dtype=torch.float64, device=dev)
+    nearest = torch.empty(M, dtype=torch.int32, device=dev) if return_nearest else None
+    ws = torch.empty(L.psam_scanmap_plane_workspace_bytes(M) // 8, dtype=torch.float64, device=dev)
+    P, pose_ptr = _pose_arg(words)
+    check(L.psam_scanmap_plane_step(*lead, V, normals.data_ptr(), _p(skip), min_count, reach, float(r2), xyz.data_ptr(), M, _p(bits), pose_ptr, _p(nearest),
+                                  sums.data_ptr(), ws.data_ptr(), ws.numel() * 8, _stream()), "psam_scanmap_plane_step")
+    return (sums, nearest) if return_nearest else sums
+
+
+# ------------------------------------------------------------------------------------------ scan map normals (csrc/map_normals.hip)
+MAP_NORMALS_MAX_REACH = 2        # PSAM_SCANMAP_NORMALS_MAX_REACH
+
+
+def map_normals(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, reach: int = 1, min_voxels: int = 5, skip: torch.Tensor = None,
+                min_count: int = 1, scatter: bool = False):
+    """One normal per voxel of a scan map (include/pointsam_hip.h: scan map normals) -> (count [V] int32, normal [V, 3] f32, curvature [V] f32), and
+    with scatter=True also the exact scatter matrix [V, 6] float64 (xx, xy, xz, yy, yz, zz).  The neighbourhood of a voxel is the allowed voxels
+    (count >= min_count, bit in `skip` clear: track_step's) in the (2 reach + 1)^3 cells around its own, reach 1 or 2; the scatter of their MEANS
+    (cloud()'s bits) is exact integer arithmetic, the solve and the sign rule are voxel_normals' without a viewpoint.  Below min_voxels, and for a
+    voxel that is not allowed itself, the normal is (0, 0, 0): track_plane_step does not use such a pair.  The block is only read; no workspace, no
+    host synchronisation."""
+    V = _map_count("map_normals", V, max_voxels)
+    reach = _superpoint_int(reach, 1, MAP_NORMALS_MAX_REACH, "map_normals: reach")
+    min_voxels = _superpoint_int(min_voxels, 1, 2 ** 31 - 1, "map_normals: min_voxels")
+    skip = _packed_row("map_normals", "skip", skip, V, "voxels")
+    min_count = _superpoint_int(min_count, 1, 2 ** 31 - 1, "map_normals: min_count")
+    lead = _map_block("map_normals", block, max_voxels, max_pairs)
+    if skip is not None and skip.device != block.device:
+        raise ValueError(f"map_normals: the block is on {block.device}; skip must be there too")
+    dev = block.device
+    L = _lib.load()
+    count = torch.empty(V, dtype=torch.int32, device=dev)
+    normal = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    curvature = torch.empty(V, dtype=torch.float32, device=dev)
+    S = torch.empty(V, 6, dtype=torch.float64, device=dev) if scatter else None
+    check(L.psam_scanmap_normals(*lead, V, _p(skip), min_count, reach, min_voxels, count.data_ptr(), _p(S), normal.data_ptr(), curvature.data_ptr(), _stream()),
+          "psam_scanmap_normals")
+    return (count, normal, curvature, S) if scatter else (count, normal, curvature)

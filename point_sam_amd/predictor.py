@@ -429,14 +429,15 @@ class PointSAMPredictor:
         return torch.where(ids >= 0, label.index_select(0, ids.clamp(min=0).long()), torch.full_like(ids, -1))
 
     @torch.no_grad()
-    def map_align(self, m, cfg, init=None, mask=None, occupied=None, min_count: int = 1):
+    def map_align(self, m, cfg, init=None, mask=None, occupied=None, min_count: int = 1, normals=None, plane=None):
         """The pose of the CURRENT scan against the scanmap.ScanMap `m` itself, by ICP on the map's own voxels (ScanMap.track) -> align.Alignment; its
         `pose` is what map_add and map_carve take.  The coordinates are the ones map_add would add (after set_scene the full-resolution points).
         Exactly m.track(those, cfg, init, mask, occupied, min_count): cfg an align.AlignConfig with a radius of at most 4 voxels, init the pose to
         refine (odometry, the previous scan's pose, align()'s frame-to-frame estimate), mask an optional packed row [ceil(M / 64)] int64 at the
-        scan's width, occupied None / True / a [V] bool tensor.  Frame to model: the error of one scan's pose does not enter the next one's."""
+        scan's width, occupied None / True / a [V] bool tensor.  normals (None, True or a [V, 3] tensor) and plane (an align.PlaneConfig) are
+        ScanMap.track's: point-to-plane against the map's own voxel normals.  Frame to model: the error of one scan's pose does not enter the next one's."""
         xyz, _ = self._map_scan(m, "map_align")
-        return m.track(xyz, cfg, init, mask, occupied, min_count)
+        return m.track(xyz, cfg, init, mask, occupied, min_count, normals, plane)
 
     @torch.no_grad()
     def map_nearest(self, m, pose=None, radius=None, min_votes: int = 1) -> torch.Tensor:

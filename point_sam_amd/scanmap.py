@@ -25,10 +25,18 @@ object that has seen the whole walk: align.icp's loop, where a step (track_step)
 mean position, cloud()'s bits -- by probing the map's own voxel table.  No cloud is read out and no index is built; the step sums ops.align_step's
 twenty words, so the solve and the loop are align.py's unchanged.
 
+Point to plane (csrc/map_normals.hip, track.hip): a room is floors, walls and table tops, and a scan slides along a plane of voxel means.  normals() gives
+every voxel a normal from the means of the voxels around it -- an exact integer scatter matrix, probed out of the map's own table -- and
+track(normals=True) minimises the distance to the pair's tangent plane instead: track_plane_step sums ops.align_plane_step's thirty-two words over
+track_step's pairs, and the loop and solve are align.icp's point-to-plane ones unchanged.  Normals are not kept: they describe the map at the time of
+the call, and the caller asks again after an add.
+
 Not built: removing or decaying voxels (occupied() is a read-out; a freed voxel keeps its id, sums and votes), rays from an origin outside
 [-1, 1]^3, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, pose-graph optimisation (track() places a scan against the map, it does not go back and
-move the scans already added), point-to-plane against the map (the map stores no normals), a global search against the map (track() refines an
-initial pose), a search that reaches more than 4 voxels from a query's own.  No default here has been
+move the scans already added), a global search against the map (track() refines an
+initial pose), a search that reaches more than 4 voxels from a query's own, a viewpoint sign for map normals (the sign is the largest component's),
+normals kept in the block and updated per add, a normal neighbourhood that reaches more than 2 cells, a switch for point-to-plane in the demo
+server.  No default here has been
 tuned on real scans or a trained checkpoint.  Beyond the voxel and pair capacities a map takes at most 2^31 - 1 accepted points in all (the bound that
 keeps counts and votes in int32 and every sum in one 64-bit word); that refusal is not exercised by any test.
 """
@@ -49,6 +57,13 @@ class AddResult:
     new_voxels: int
     accepted: int
     rejected: int
+
+
+@dataclass
+class MapNormals:
+    normal: torch.Tensor      # [V, 3] f32: unit, the largest component positive; (0, 0, 0) without enough neighbours
+    curvature: torch.Tensor   # [V] f32: l0 / (l0 + l1 + l2) of the neighbourhood's scatter matrix
+    count: torch.Tensor       # [V] int32: the voxels of the neighbourhood, the voxel itself among them; 0 for a voxel that is not allowed
 
 
 @dataclass
@@ -267,13 +282,49 @@ class ScanMap:
         block, max_voxels, max_pairs, V = self._filled("track_step")
         return ops.track_step(block, max_voxels, max_pairs, V, xyz, pose, radius, bits, skip, min_count, return_nearest, voxel_size=self.voxel_size)
 
+    def _skip(self, what: str, occupied, V: int):
+        """occupied (None, True or a [V] bool tensor) -> the packed row of the voxels that are NOT, or None."""
+        if occupied is None:
+            return None
+        if occupied is True:
+            occupied = self.occupied()
+        if occupied.dtype != torch.bool or tuple(occupied.shape) != (V,) or occupied.device != self.device:
+            raise ValueError(f"{what}: occupied must be [{V}] bool on {self.device}, got {tuple(occupied.shape)} {occupied.dtype} on {occupied.device}")
+        return ops.mask_pack((~occupied).to(torch.float32)[None].contiguous(), 0.5, 0.0)[0][0]
+
     @torch.no_grad()
-    def track(self, xyz: torch.Tensor, cfg, init=None, bits: torch.Tensor = None, occupied=None, min_count: int = 1):
+    def normals(self, reach: int = 1, min_voxels: int = 5, occupied=None, min_count: int = 1) -> MapNormals:
+        """One normal per voxel (ops.map_normals): the eigenvector of the smallest eigenvalue of the exact scatter matrix of the means of the voxels in
+        the (2 reach + 1)^3 cells around it, reach 1 or 2; (0, 0, 0) where fewer than min_voxels are there.  occupied (None, True or a [V] bool
+        tensor, as track()'s) and min_count say which voxels count: one that does not has no normal and enters no other's.  Nothing is kept: the
+        normals describe the map at the time of the call.  MapOverflow for a dead map, ValueError for an empty one.  No host read."""
+        if occupied is not None and occupied is not True and not isinstance(occupied, torch.Tensor):
+            raise TypeError(f"normals: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
+        block, max_voxels, max_pairs, V = self._filled("normals")
+        count, normal, curvature = ops.map_normals(block, max_voxels, max_pairs, V, reach, min_voxels, self._skip("normals", occupied, V), min_count)
+        return MapNormals(normal, curvature, count)
+
+    @torch.no_grad()
+    def track_plane_step(self, xyz: torch.Tensor, normals: torch.Tensor, pose=None, radius=None, bits: torch.Tensor = None, skip: torch.Tensor = None,
+                         min_count: int = 1, return_nearest: bool = False):
+        """One point-to-plane ICP step of a scan against the map (ops.track_plane_step): track_step's arguments and pairs, and normals [V, 3] f32, one
+        per voxel id (normals().normal) -> sums [32] float64 on the device, ops.align_plane_step's words.  MapOverflow for a dead map, ValueError
+        for an empty one.  No host read."""
+        block, max_voxels, max_pairs, V = self._filled("track_plane_step")
+        return ops.track_plane_step(block, max_voxels, max_pairs, V, xyz, normals, pose, radius, bits, skip, min_count, return_nearest,
+                                    voxel_size=self.voxel_size)
+
+    @torch.no_grad()
+    def track(self, xyz: torch.Tensor, cfg, init=None, bits: torch.Tensor = None, occupied=None, min_count: int = 1, normals=None, plane=None):
         """The pose of a scan against the map, by ICP -> align.Alignment; its `pose` maps the scan's frame to the map's: what add() and carve() take.
         Exactly align.icp(self, xyz, cfg, init, bits, step=...) with track_step as the step: cfg an align.AlignConfig whose radius is at most 4 voxels
         (ops.track_reach; ValueError before any launch), init the pose to refine (odometry, or the last scan's pose).  occupied: None, True
         (self.occupied()) or a [V] bool tensor: only those voxels are paired (a scan is not pulled towards ghosts); the mask is packed once.  One
-        160-byte host read per step."""
+        160-byte host read per step.
+        normals: None = point to point, as above.  True = point to plane on self.normals(occupied=occupied, min_count=min_count).normal, computed
+        once before the loop; a [V, 3] f32 tensor on the map's device is used as given (ValueError before any launch for anything else).  The run
+        is then align.icp's point-to-plane loop with track_plane_step as the step: one 256-byte host read per step, align.solve_plane, and
+        `plane` an align.PlaneConfig (None: the defaults; without normals a ValueError)."""
         from . import align as A
         if not isinstance(cfg, A.AlignConfig):
             raise TypeError(f"track: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
@@ -281,13 +332,25 @@ class ScanMap:
         if occupied is not None and occupied is not True and not isinstance(occupied, torch.Tensor):
             raise TypeError(f"track: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
         V = self._filled("track")[3]
-        skip = None
-        if occupied is not None:
-            if occupied is True:
-                occupied = self.occupied()
-            if occupied.dtype != torch.bool or tuple(occupied.shape) != (V,) or occupied.device != self.device:
-                raise ValueError(f"track: occupied must be [{V}] bool on {self.device}, got {tuple(occupied.shape)} {occupied.dtype} on {occupied.device}")
-            skip = ops.mask_pack((~occupied).to(torch.float32)[None].contiguous(), 0.5, 0.0)[0][0]
+        if normals is None:
+            if plane is not None:
+                raise ValueError("track: plane configures point-to-plane tracking and needs normals")
+        elif normals is not True and not (isinstance(normals, torch.Tensor) and normals.dtype == torch.float32 and tuple(normals.shape) == (V, 3) and
+                                          normals.device == self.device):
+            raise ValueError(f"track: normals must be None, True or a [{V}, 3] float32 tensor on {self.device}, got "
+                             f"{(tuple(normals.shape), normals.dtype, normals.device) if isinstance(normals, torch.Tensor) else repr(normals)}")
+        elif plane is not None and not isinstance(plane, A.PlaneConfig):
+            raise TypeError(f"track: plane must be an align.PlaneConfig or None, got {type(plane).__name__}")
+        if occupied is True:
+            occupied = self.occupied()                             # read once, for the normals and for the pairs
+        skip = self._skip("track", occupied, V)
+        if normals is not None:
+            if normals is True:
+                normals = self.normals(occupied=occupied, min_count=min_count).normal
+
+            def plane_step(m, points, nrm, pose, radius, row):
+                return m.track_plane_step(points, nrm, pose, radius, row, skip, min_count)
+            return A.icp(self, xyz, cfg, init, bits, step=plane_step, normals=normals.contiguous(), plane=plane)
 
         def step(m, points, pose, radius, row):
             return m.track_step(points, pose, radius, row, skip, min_count)

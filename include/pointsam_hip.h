@@ -1273,6 +1273,34 @@ int32_t psam_scanmap_plane_step(const void* map, size_t map_bytes, int32_t max_v
 int32_t psam_scanmap_normals(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, const uint64_t* skip, int32_t min_count,
                          int32_t reach, int32_t min_voxels, int32_t* count, double* scatter, float* normal, float* curvature, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- scan map relocalisation */
+
+/* The score of a global pose search against a scan map (ScanMap.track_score, ScanMap.relocalize): under each of P candidate poses, the number
+ * of queries that land on the map -- all P poses from one call.  The map block is only read; the call allocates nothing and does not synchronise
+ * with the host.
+ *
+ * map, map_bytes, max_voxels, max_pairs, V, skip, min_count, reach, r2, qry [M, 3]: psam_track_step's.  poses [P, 12] f32 in DEVICE memory, one
+ * pose per row, row-major 3 x 4, scan frame -> map frame; 0 < P <= 2^20.  The entry cannot look at them: the host validates them before the upload.
+ *     candidates        of query i under pose p: psam_track_step's, bit for bit -- the same posed coordinate, cell and acceptance test, the same
+ *                       (2 reach + 1)^3 cells (a cell off the grid is skipped; no cell is dropped by a geometric bound), v < V,
+ *                       count(v) >= min_count, the bit of v in skip clear, q = (dx dx + dy dy) + dz dz <= r2 in fp32 against the voxel's mean with
+ *                       the bits psam_map_cloud gives it, NaN false
+ *     counts [P] i32    counts[p] = the number of queries with at least one candidate under pose p
+ *                       == (int)psam_track_step's sums[0] under pose p with the same r2, reach, skip and min_count and no qry_bits.
+ *                       A query without a cell scores nothing; a pose that is not finite gives NaN coordinates, no cell and a count of 0
+ * counts is cleared on the stream first and then raised by integer atomic additions (one per wave and pose, below 2^28 in all): the words are a
+ * function of the inputs alone, the same from run to run.
+ * ws: psam_relocalize_workspace_bytes(V) = 16 V bytes (0 for V outside (0, 2^28]), 16-byte aligned: one float4 per voxel id, its mean, or NaN for
+ * a voxel that is no candidate by min_count or skip.  It is rebuilt by every call and means nothing afterwards.
+ * Every refusal comes before any launch and leaves counts untouched: a null map, qry, poses, counts or ws, M outside (0, 2^28], V outside
+ * (0, max_voxels], bad capacities, reach outside 1 .. 4, min_count < 1, r2 not finite and positive, P outside (0, 2^20]: -1; a misaligned pointer
+ * (map and ws 16 bytes; skip 8; qry, poses and counts 4): -2; a short map block or ws: -3. */
+#define PSAM_RELOCALIZE_POSES 4      /* poses per workgroup: a chunk of the grid (query tiles x pose chunks) */
+size_t psam_relocalize_workspace_bytes(int32_t V);
+int32_t psam_relocalize_score(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, const uint64_t* skip, int32_t min_count,
+                              int32_t reach, float r2, const float* qry, int32_t M, const float* poses, int32_t P, int32_t* counts, void* ws,
+                              size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

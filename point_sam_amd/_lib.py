@@ -199,6 +199,8 @@ SIGNATURES = {
     "psam_scanmap_plane_workspace_bytes": (size_t, [i32]),
     "psam_scanmap_plane_step": (i32, [ptr, size_t, i32, i32, i32, ptr, ptr, i32, i32, f32, ptr, i32, ptr, ptr, ptr, ptr, ptr, size_t, ptr]),
     "psam_scanmap_normals": (i32, [ptr, size_t, i32, i32, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]),
+    "psam_relocalize_workspace_bytes": (size_t, [i32]),
+    "psam_relocalize_score": (i32, [ptr, size_t, i32, i32, i32, ptr, i32, i32, f32, ptr, i32, ptr, i32, ptr, ptr, size_t, ptr]),
 }
 
 

@@ -67,6 +67,8 @@ SOURCES = [
     ("track.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # scan map normals: scanmap.hip's voxel mean and fixed point (csrc/map_block.h) and normals.hip's eigen-solve (csrc/normal_eigen.h), so the flags of both.
     ("map_normals.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # scan map relocalisation: track.hip's posed coordinate, cell, voxel mean and distance for P poses at once (csrc/map_block.h), so track.hip's flags.
+    ("track_score.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

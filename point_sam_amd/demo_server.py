@@ -25,7 +25,7 @@ POST /fuse_labels {labels, tau, overlap?, min_points?, min_votes?, consistent?} 
 instance labelling of that cloud (predictor.fuse_labels).
 POST /map/add {pose?, labels?} . POST /map {min_votes?} . POST /map/clear (not in the reference): the loaded cloud, under its pose, is added to the
 session's scan map (predictor.map_add, point_sam_amd/scanmap.py), with "track": {AlignConfig fields} after its pose was refined against the map
-(predictor.map_align); /map returns the map's voxels as a cloud with one voted label each.
+(predictor.map_align), and with "search": {SearchConfig fields} beside it after the scan was relocalised in the map without a starting pose; /map returns the map's voxels as a cloud with one voted label each.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -583,13 +583,17 @@ class DemoSession:
         (predictor.map_carve, "margin": cells, optional, default 1) and the answer gains {"rays", "hit_voxels", "missed_voxels", "crossed",
         "num_carves"}.  With "track": {align.AlignConfig fields} the pose is first refined against the map itself (predictor.map_align, the request's
         pose as its start; skipped while the map is empty), the scan is added and carved under the refined pose, and the answer gains {"pose": the 3 x 4
-        rows used, "pairs", "coverage", "rms", "converged", "reason"}.  A bad value or a full map is a 400."""
+        rows used, "pairs", "coverage", "rms", "converged", "reason"}.  With "search": {align.SearchConfig fields} beside "track" and WITHOUT "pose" (a
+        pose is the start, a search starts from its own candidates: both together are a 400) the scan is first relocalised in the map
+        (predictor.map_relocalize: a grid of poses scored on the map's voxels, the best refined by the same loop; skipped while the map is empty,
+        as the track is) and the answer gains "search": {poses, sample, chosen, candidates: [{pose_index, count, pairs, rms, converged}]}, as
+        /propagate returns it.  A bad value or a full map is a 400."""
         with self.lock:
             if self.pc_xyz is None:
                 raise ValueError("/map/add before a point cloud was set")
-            if not isinstance(data, dict) or set(data) - {"pose", "labels", "origin", "margin", "track"}:
+            if not isinstance(data, dict) or set(data) - {"pose", "labels", "origin", "margin", "track", "search"}:
                 raise ValueError('/map/add takes {"pose": rows (optional), "labels": [ints] (optional), "origin": [x, y, z] (optional), "margin": n (optional), '
-                                 '"track": {AlignConfig fields} (optional)}')
+                                 '"track": {AlignConfig fields} (optional), "search": {SearchConfig fields} (optional, beside "track", without "pose")}')
             from . import ops
             pose = data.get("pose")
             ops.transfer_pose(pose)
@@ -598,6 +602,17 @@ class DemoSession:
                 from .align import AlignConfig
                 track_cfg = AlignConfig.from_overrides(data["track"])      # a bad track field is a 400 before anything is touched
                 ops.track_reach(track_cfg.radius, self.map_voxel_size)
+            search_cfg = None
+            if "search" in data:
+                if track_cfg is None or pose is not None:
+                    raise ValueError('/map/add: "search" is valid only together with "track" and without "pose": a pose is the start, and a search '
+                                     'starts from its own candidates')
+                from .align import SearchConfig
+                search_cfg = SearchConfig.from_overrides(data["search"])   # a bad search field is a 400 before anything is touched
+                if search_cfg.radius is not None:
+                    ops.track_reach(search_cfg.radius, self.map_voxel_size)
+                    if search_cfg.radius > track_cfg.radius:
+                        raise ValueError(f'/map/add: the "search" radius {search_cfg.radius} exceeds the "track" radius {track_cfg.radius}')
             origin, margin = data.get("origin"), data.get("margin", 1)
             if "margin" in data and origin is None:
                 raise ValueError('"margin" belongs to a carve: give "origin" too')
@@ -628,7 +643,10 @@ class DemoSession:
                         self.scan_map = self.predictor.new_map(self.map_voxel_size, self.map_max_voxels)
                     found = None
                     if track_cfg is not None and self.scan_map.num_voxels > 0:      # an empty map has nothing to track against: the pose as given
-                        found = self._map_error(lambda: self.predictor.map_align(self.scan_map, track_cfg, pose))
+                        if search_cfg is None:
+                            found = self._map_error(lambda: self.predictor.map_align(self.scan_map, track_cfg, pose))
+                        else:
+                            found = self._map_error(lambda: self.predictor.map_relocalize(self.scan_map, track_cfg, search_cfg))
                         pose = found.pose.tolist()
                         if origin is not None:
                             ops.carve_origin(origin, pose, self.map_voxel_size)
@@ -648,6 +666,10 @@ class DemoSession:
                 else:
                     out.update(pose=pose, pairs=int(found.pairs), coverage=float(found.coverage), rms=found.rms if np.isfinite(found.rms) else None,
                                converged=bool(found.converged), reason=found.reason)
+                    if search_cfg is not None:
+                        rec = found.search
+                        out["search"] = dict(poses=rec.poses, sample=rec.sample, chosen=rec.chosen, candidates=[
+                            dict(c, rms=c["rms"] if np.isfinite(c["rms"]) else None) for c in rec.candidates])
             return out
 
     def map_get(self, data: dict) -> dict:

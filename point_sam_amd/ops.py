@@ -2772,6 +2772,46 @@ def track_plane_step(block: torch.Tensor, max_voxels: int, max_pairs: int, V: in
     return (sums, nearest) if return_nearest else sums
 
 
+# ------------------------------------------------------------------------------------------ scan map relocalisation (csrc/track_score.hip)
+TRACK_SCORE_POSES = 4            # PSAM_RELOCALIZE_POSES: the poses one workgroup of psam_relocalize_score takes a tile of queries through
+
+
+def track_score(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, xyz: torch.Tensor, poses, radius=None, skip: torch.Tensor = None,
+                min_count: int = 1, *, voxel_size):
+    """The score of a pose search against a scan map (include/pointsam_hip.h: scan map relocalisation): the map's block, capacities and V, xyz [M, 3]
+    f32 (the queries), poses -> counts [P] int32 on the device: under pose p, the queries with at least one map voxel within `radius` of
+    pose_p(query) -- exactly int(track_step(..., pose_p, radius, None, skip, min_count)[0]) for every p, from ONE call.  poses: align_score's -- [P, 3,
+    4] or [P, 4, 4] host numbers, every row checked as transfer_pose checks a pose; or a [P, 12] float32 tensor ON THE DEVICE, taken AS VALIDATED (a
+    row that is not finite scores 0).  radius, skip, min_count and voxel_size: track_step's.  1 <= P <= 2^20.  The workspace (one float4 per voxel
+    id) is allocated here.  No host synchronisation."""
+    xyz = _map_points("track_score", xyz, "xyz")
+    _, _, r2 = transfer_radius(voxel_size if radius is None else radius)
+    reach = track_reach(voxel_size if radius is None else radius, voxel_size)
+    M = xyz.shape[0]
+    V = _map_count("track_score", V, max_voxels)
+    skip = _packed_row("track_score", "skip", skip, V, "voxels")
+    min_count = _superpoint_int(min_count, 1, 2 ** 31 - 1, "track_score: min_count")
+    on_device = isinstance(poses, torch.Tensor) and poses.is_cuda and poses.dim() == 2
+    if on_device:
+        if poses.shape[1] != 12 or not 1 <= poses.shape[0] <= ALIGN_SCORE_MAX_POSES:
+            raise ValueError(f"track_score: device poses must be [P, 12] with 1 <= P <= 2^20, got {tuple(poses.shape)}")
+    else:
+        host = transfer_poses(poses)
+    lead = _map_block("track_score", block, max_voxels, max_pairs)
+    _chk(xyz, name="xyz")
+    words = _chk(poses, name="poses") if on_device else torch.from_numpy(host).to(xyz.device)
+    if not (xyz.device == block.device and words.device == xyz.device and (skip is None or skip.device == xyz.device)):
+        raise ValueError(f"track_score: xyz is on {xyz.device}, the block on {block.device}; poses and skip must be there too")
+    dev = xyz.device
+    L = _lib.load()
+    P = words.shape[0]
+    counts = torch.empty(P, dtype=torch.int32, device=dev)
+    ws = torch.empty(L.psam_relocalize_workspace_bytes(V) // 8, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    check(L.psam_relocalize_score(*lead, V, _p(skip), min_count, reach, float(r2), xyz.data_ptr(), M, words.data_ptr(), P, counts.data_ptr(), ws.data_ptr(),
+                                  ws.numel() * 8, _stream()), "psam_relocalize_score")
+    return counts
+
+
 # ------------------------------------------------------------------------------------------ scan map normals (csrc/map_normals.hip)
 MAP_NORMALS_MAX_REACH = 2        # PSAM_SCANMAP_NORMALS_MAX_REACH
 

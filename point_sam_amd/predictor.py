@@ -435,9 +435,22 @@ class PointSAMPredictor:
         Exactly m.track(those, cfg, init, mask, occupied, min_count): cfg an align.AlignConfig with a radius of at most 4 voxels, init the pose to
         refine (odometry, the previous scan's pose, align()'s frame-to-frame estimate), mask an optional packed row [ceil(M / 64)] int64 at the
         scan's width, occupied None / True / a [V] bool tensor.  normals (None, True or a [V, 3] tensor) and plane (an align.PlaneConfig) are
-        ScanMap.track's: point-to-plane against the map's own voxel normals.  Frame to model: the error of one scan's pose does not enter the next one's."""
+        ScanMap.track's: point-to-plane against the map's own voxel normals.  Frame to model: the error of one scan's pose does not enter the next one's.
+        (For a scan without a pose to refine: map_relocalize.)"""
         xyz, _ = self._map_scan(m, "map_align")
         return m.track(xyz, cfg, init, mask, occupied, min_count, normals, plane)
+
+    @torch.no_grad()
+    def map_relocalize(self, m, cfg, search, mask=None, occupied=None, min_count: int = 1, normals=None, plane=None):
+        """The pose of the CURRENT scan in the scanmap.ScanMap `m` WITHOUT a pose to refine (odometry dropped out, a second session, a scan from
+        elsewhere in the map) -> align.Alignment, its `search` the align.SearchRecord.  map_align's arguments with `search`, an align.SearchConfig,
+        in the place of `init`: exactly m.relocalize(the coordinates map_add would add, cfg, search, mask, occupied, min_count, normals, plane) -- a
+        grid of poses scored on the map's own voxels in one call, the best refined by map_align's loop."""
+        from . import align as A
+        if not isinstance(search, A.SearchConfig):
+            raise TypeError(f"map_relocalize: search must be an align.SearchConfig, got {type(search).__name__}")
+        xyz, _ = self._map_scan(m, "map_relocalize")
+        return m.relocalize(xyz, cfg, search, mask, occupied, min_count, normals, plane)
 
     @torch.no_grad()
     def map_nearest(self, m, pose=None, radius=None, min_votes: int = 1) -> torch.Tensor:

@@ -31,10 +31,17 @@ track(normals=True) minimises the distance to the pair's tangent plane instead: 
 track_step's pairs, and the loop and solve are align.icp's point-to-plane ones unchanged.  Normals are not kept: they describe the map at the time of
 the call, and the caller asks again after an add.
 
+Relocalisation (csrc/track_score.hip): track() refines a pose that is within a few voxels of the truth; a walk whose odometry dropped out, a second
+session in a room mapped yesterday or a scan that starts elsewhere in the map has none.  relocalize(xyz, cfg, SearchConfig) is align.search with the map in
+place of the index: track_score counts, for every pose of a grid at once, the sampled points that land within a radius of a pairable voxel's mean --
+exactly track_step's pair count under that pose, with the same occupied / min_count, so ghosts do not attract -- the best few are refined by the loop
+above and the refinement with the most pairs wins.  anchors() lists where a scan may land in a map larger than itself (the centres of the map's
+coarse cells), for SearchConfig(anchors=...).
+
 Not built: removing or decaying voxels (occupied() is a read-out; a freed voxel keeps its id, sums and votes), rays from an origin outside
 [-1, 1]^3, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, pose-graph optimisation (track() places a scan against the map, it does not go back and
-move the scans already added), a global search against the map (track() refines an
-initial pose), a search that reaches more than 4 voxels from a query's own, a viewpoint sign for map normals (the sign is the largest component's),
+move the scans already added), a multi-resolution or branch-and-bound search (the grid of relocalize() is scored pose by pose at one resolution),
+scoring on a coarser copy of the map, a search that reaches more than 4 voxels from a query's own, a viewpoint sign for map normals (the sign is the largest component's),
 normals kept in the block and updated per add, a normal neighbourhood that reaches more than 2 cells, a switch for point-to-plane in the demo
 server.  No default here has been
 tuned on real scans or a trained checkpoint.  Beyond the voxel and pair capacities a map takes at most 2^31 - 1 accepted points in all (the bound that
@@ -314,6 +321,39 @@ class ScanMap:
         return ops.track_plane_step(block, max_voxels, max_pairs, V, xyz, normals, pose, radius, bits, skip, min_count, return_nearest,
                                     voxel_size=self.voxel_size)
 
+    # -- relocalisation (csrc/track_score.hip) ----------------------------------------------------------------
+    @torch.no_grad()
+    def track_score(self, xyz: torch.Tensor, poses, radius=None, skip: torch.Tensor = None, min_count: int = 1) -> torch.Tensor:
+        """The score of a grid of poses (ops.track_score): xyz [M, 3] f32, poses [P, 3, 4] / [P, 4, 4] host numbers or a [P, 12] float32 device tensor
+        (ops.align_score's forms), scan frame -> map frame -> counts [P] int32 on the device: under pose p the points with at least one map voxel
+        within `radius` (None: the voxel size), int(track_step(xyz, pose_p, radius, None, skip, min_count)[0]) for every p from one call.
+        MapOverflow for a dead map, ValueError for an empty one.  No host read."""
+        block, max_voxels, max_pairs, V = self._filled("track_score")
+        return ops.track_score(block, max_voxels, max_pairs, V, xyz, poses, radius, skip, min_count, voxel_size=self.voxel_size)
+
+    def _pairable(self, what: str, occupied, min_count, V: int) -> torch.Tensor:
+        """[V] bool: the voxels track() may pair under `occupied` (None, True or a [V] bool tensor) and `min_count`."""
+        min_count = ops._superpoint_int(min_count, 1, 2 ** 31 - 1, f"{what}: min_count")
+        if occupied is not None and occupied is not True and not isinstance(occupied, torch.Tensor):
+            raise TypeError(f"{what}: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
+        if occupied is True:
+            occupied = self.occupied()
+        if occupied is not None and (occupied.dtype != torch.bool or tuple(occupied.shape) != (V,) or occupied.device != self.device):
+            raise ValueError(f"{what}: occupied must be [{V}] bool on {self.device}, got {tuple(occupied.shape)} {occupied.dtype} on {occupied.device}")
+        ok = self.counts() >= min_count
+        return ok if occupied is None else ok & occupied
+
+    @torch.no_grad()
+    def anchors(self, cells: int = 8, occupied=None, min_count: int = 1, min_voxels: int = 8):
+        """Where a scan may land in a map larger than itself -> [A, 3] float64 on the host, for align.SearchConfig(anchors=...): the pairable voxels
+        (occupied, min_count: track()'s) grouped by coarse cell -- each coordinate of the voxel's cell (keys(): cx | cy << 21 | cz << 42)
+        integer-divided by `cells` -- and per coarse cell with at least min_voxels of them the fp64 mean of their means (summed in id order), ordered
+        by coarse (cz, cy, cx).  Plain torch and one host read.  MapOverflow for a dead map, ValueError for an empty one or bad arguments."""
+        V = self._filled("anchors")[3]
+        _anchor_arguments(cells, min_voxels)
+        ok = self._pairable("anchors", occupied, min_count, V)
+        return anchors_from_voxels(self.keys(), self.cloud()[0], ok, cells, min_voxels)
+
     @torch.no_grad()
     def track(self, xyz: torch.Tensor, cfg, init=None, bits: torch.Tensor = None, occupied=None, min_count: int = 1, normals=None, plane=None):
         """The pose of a scan against the map, by ICP -> align.Alignment; its `pose` maps the scan's frame to the map's: what add() and carve() take.
@@ -325,33 +365,100 @@ class ScanMap:
         once before the loop; a [V, 3] f32 tensor on the map's device is used as given (ValueError before any launch for anything else).  The run
         is then align.icp's point-to-plane loop with track_plane_step as the step: one 256-byte host read per step, align.solve_plane, and
         `plane` an align.PlaneConfig (None: the defaults; without normals a ValueError)."""
+        return self._register("track", xyz, cfg, init, None, bits, occupied, min_count, normals, plane)
+
+    @torch.no_grad()
+    def relocalize(self, xyz: torch.Tensor, cfg, search, bits: torch.Tensor = None, occupied=None, min_count: int = 1, normals=None, plane=None):
+        """The pose of a scan against the map WITHOUT a pose to refine (odometry dropped out, a second session, a scan from elsewhere in the map)
+        -> align.Alignment, its `search` the align.SearchRecord.  track()'s arguments with `search`, an align.SearchConfig, in the place of `init`:
+        the search IS the start.  Exactly align.search with the map in place of the index -- its score is track_score at search.radius (None:
+        cfg.radius; at most cfg.radius, and both pass ops.track_reach before any launch), its refinement track()'s loop with the same skip,
+        min_count, normals and plane, its source centroid the fp64 mean of the pairable voxels' means.  On a map larger than the scan give
+        SearchConfig(anchors=self.anchors(...))."""
+        from . import align as A
+        if not isinstance(search, A.SearchConfig):
+            raise TypeError(f"relocalize: search must be an align.SearchConfig, got {type(search).__name__}")
+        return self._register("relocalize", xyz, cfg, None, search, bits, occupied, min_count, normals, plane)
+
+    def _register(self, what: str, xyz, cfg, init, search, bits, occupied, min_count, normals, plane):
+        """track (search None) and relocalize (init None): one set of checks, one pair of step closures, align.icp or align.search around them."""
         from . import align as A
         if not isinstance(cfg, A.AlignConfig):
-            raise TypeError(f"track: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
+            raise TypeError(f"{what}: cfg must be an align.AlignConfig, got {type(cfg).__name__}")
         ops.track_reach(cfg.radius, self.voxel_size)
+        if search is not None and search.radius is not None:
+            ops.track_reach(search.radius, self.voxel_size)
+            if search.radius > cfg.radius:
+                raise ValueError(f"{what}: the scoring radius {search.radius} exceeds the AlignConfig's {cfg.radius}")
         if occupied is not None and occupied is not True and not isinstance(occupied, torch.Tensor):
-            raise TypeError(f"track: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
-        V = self._filled("track")[3]
+            raise TypeError(f"{what}: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
+        V = self._filled(what)[3]
         if normals is None:
             if plane is not None:
-                raise ValueError("track: plane configures point-to-plane tracking and needs normals")
+                raise ValueError(f"{what}: plane configures point-to-plane tracking and needs normals")
         elif normals is not True and not (isinstance(normals, torch.Tensor) and normals.dtype == torch.float32 and tuple(normals.shape) == (V, 3) and
                                           normals.device == self.device):
-            raise ValueError(f"track: normals must be None, True or a [{V}, 3] float32 tensor on {self.device}, got "
+            raise ValueError(f"{what}: normals must be None, True or a [{V}, 3] float32 tensor on {self.device}, got "
                              f"{(tuple(normals.shape), normals.dtype, normals.device) if isinstance(normals, torch.Tensor) else repr(normals)}")
         elif plane is not None and not isinstance(plane, A.PlaneConfig):
-            raise TypeError(f"track: plane must be an align.PlaneConfig or None, got {type(plane).__name__}")
+            raise TypeError(f"{what}: plane must be an align.PlaneConfig or None, got {type(plane).__name__}")
         if occupied is True:
             occupied = self.occupied()                             # read once, for the normals and for the pairs
-        skip = self._skip("track", occupied, V)
+        skip = self._skip(what, occupied, V)
+        if search is not None:
+            sources = _SearchSources(self.cloud()[0][self._pairable(what, occupied, min_count, V)])
+
+            def score(_, points, poses, radius):
+                return self.track_score(points, poses, radius, skip, min_count)
         if normals is not None:
             if normals is True:
                 normals = self.normals(occupied=occupied, min_count=min_count).normal
 
-            def plane_step(m, points, nrm, pose, radius, row):
-                return m.track_plane_step(points, nrm, pose, radius, row, skip, min_count)
+            def plane_step(_, points, nrm, pose, radius, row):
+                return self.track_plane_step(points, nrm, pose, radius, row, skip, min_count)
+            if search is not None:
+                return A.search(sources, xyz, search, cfg, bits, score=score, step=plane_step, normals=normals.contiguous(), plane=plane)
             return A.icp(self, xyz, cfg, init, bits, step=plane_step, normals=normals.contiguous(), plane=plane)
 
-        def step(m, points, pose, radius, row):
-            return m.track_step(points, pose, radius, row, skip, min_count)
+        def step(_, points, pose, radius, row):
+            return self.track_step(points, pose, radius, row, skip, min_count)
+        if search is not None:
+            return A.search(sources, xyz, search, cfg, bits, score=score, step=step)
         return A.icp(self, xyz, cfg, init, bits, step=step)
+
+
+class _SearchSources:
+    """What align.search reads of its `index` when score and step are stand-ins: src_xyz, for the source centroid."""
+
+    def __init__(self, src_xyz: torch.Tensor):
+        self.src_xyz = src_xyz
+
+
+def _anchor_arguments(cells, min_voxels) -> None:
+    for name, v, hi in (("cells", cells, 1 << 21), ("min_voxels", min_voxels, 1 << 28)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f"anchors: {name} must be an integer in 1 .. {hi}, got {v!r}")
+
+
+def anchors_from_voxels(keys: torch.Tensor, xyz: torch.Tensor, ok: torch.Tensor, cells: int = 8, min_voxels: int = 8):
+    """ScanMap.anchors' arithmetic on any device: keys [V] int64 (cx | cy << 21 | cz << 42), xyz [V, 3] f32 the voxels' means, ok [V] bool the voxels
+    that count -> [A, 3] float64 numpy.  The coarse cell of a voxel is (cx // cells, cy // cells, cz // cells); a coarse cell with at least
+    min_voxels counted voxels gives one anchor, the fp64 sum of their means taken in id order, divided by their number; the anchors are ordered by
+    coarse (cz, cy, cx).  One host read: the counted voxels' means and coarse codes in one array."""
+    import numpy as np
+    _anchor_arguments(cells, min_voxels)
+    V = keys.shape[0]
+    if keys.dtype != torch.int64 or keys.dim() != 1 or tuple(xyz.shape) != (V, 3) or xyz.dtype != torch.float32 or tuple(ok.shape) != (V,) or \
+            ok.dtype != torch.bool:
+        raise ValueError("anchors: keys [V] int64, xyz [V, 3] float32 and ok [V] bool are needed")
+    low = (1 << 21) - 1
+    coarse = [torch.div((keys >> (21 * a)) & low, cells, rounding_mode="floor") for a in range(3)]
+    code = (coarse[2] << 42) | (coarse[1] << 21) | coarse[0]       # sorts as (cz, cy, cx)
+    rows = torch.cat([xyz.double(), code.view(torch.float64)[:, None]], 1)[ok].cpu().numpy()      # the code's bits ride along as a float64 word
+    if len(rows) == 0:
+        return np.zeros((0, 3))
+    _, inverse, count = np.unique(np.ascontiguousarray(rows[:, 3]).view(np.int64), return_inverse=True, return_counts=True)
+    inverse = inverse.reshape(-1)
+    total = np.stack([np.bincount(inverse, weights=rows[:, a], minlength=len(count)) for a in range(3)], 1)      # sequential: id order
+    keep = count >= min_voxels
+    return total[keep] / count[keep, None]

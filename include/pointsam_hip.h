@@ -250,7 +250,8 @@ int32_t psam_ln_stats_finalize(const float* stats, int32_t rows, int32_t segs, i
  * and its GELU (common.py:493-496) without the [rows, 512] fp32 activation.  x [rows, ldx] / w [512, ldw]: g8-packed operands of 128 columns with their row
  * scales; rowbias [rows / rowgroup, ldrb]: a bias row per group of rowgroup consecutive rows (the pooled half of conv2.0 with its bias); out [rows, ldo]
  * receives the packed rows scaled by out_scale[row] = the power of two that puts `bound` (>= max|gamma| sqrt(512) + max|beta|, which bounds every LayerNorm
- * output and its GELU) into [2^14, 2^15).  h1 == 512, rows % 64 == 0, rows < 2^31, rowgroup % 32 == 0; packed rows 32-byte, the fp32 vectors 16-byte aligned. */
+ * output and its GELU) into [2^14, 2^15).  h1 == 512, rows % 64 == 0, rows < 2^31, rowgroup % 32 == 0; packed rows 32-byte, the fp32 vectors 16-byte aligned.
+ * The caller guarantees rows % rowgroup == 0 (rows = groups x rowgroup): the entry does not check it, and rowbias is read as rows / rowgroup whole rows. */
 int32_t psam_linear128_ln_gelu_pack(const void* x, int64_t ldx, const float* x_scale, const void* w, int64_t ldw, const float* w_scale, const float* rowbias,
                                     int64_t ldrb, int32_t rowgroup, const float* gamma, const float* beta, float eps, float bound, int64_t rows, int32_t h1,
                                     void* out, int64_t ldo, float* out_scale, psam_stream_t stream);

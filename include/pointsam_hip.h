@@ -1302,6 +1302,57 @@ int32_t psam_relocalize_score(const void* map, size_t map_bytes, int32_t max_vox
                               int32_t reach, float r2, const float* qry, int32_t M, const float* poses, int32_t P, int32_t* counts, void* ws,
                               size_t ws_bytes, psam_stream_t stream);
 
+/* ---------------------------------------------------------------- scan map views */
+
+/* The scan map as a camera inside it sees it (ScanMap.view): one ray per pixel, walked through the map's own voxel table in exact integers, ends on
+ * the first voxel it meets.  The answer has the format of psam_view_splat's -- keys [height, width] u64, (bits(depth) << 32) | index, all ones where a
+ * pixel is empty -- with the VOXEL ID as the index, so psam_view_pick, psam_view_paint_ids and psam_view_paint_rows take it as it is, with N = V.
+ * Against point splats of psam_map_cloud it has no holes between voxels, nothing shows through a wall, and the voxels that every other reader leaves
+ * out (skip, min_count: psam_track_step's) are seen through.  The map block is only read; the call allocates nothing, does not synchronise with the
+ * host, and gives the same words from run to run: one thread owns one pixel and nothing is accumulated.
+ *
+ * map, map_bytes, max_voxels, max_pairs, V, skip, min_count: psam_track_step's.  inv_h: the value the map was cleared with (psam_map_clear); a
+ * block whose header holds another one, and a dead map (flags != 0), give all pixels empty.  pose, fx, fy, cx, cy, width, height, znear: the camera of
+ * psam_view_splat, its pose from the map's frame to the camera's.  eye: 3 floats in HOST memory, the camera's centre in the map's frame,
+ * e = -R^T t, which the caller computes in fp64 from the twelve pose words and rounds to fp32 once.
+ *     pairable voxel    v < V, count(v) >= min_count, the bit of v in skip clear (skip may be NULL)
+ *     eye cell          o_a = floorf((e_a - (-1)) * inv_h) with -1 <= e_a <= 1 and o_a in [0, 2^21): a map point's cell and acceptance test
+ *                       (psam_map_add's, colour apart).  An eye the map does not accept gives all pixels empty
+ *     grid              the cells 0 .. cmax on every axis, cmax = min((int)floorf(2 * inv_h), 2^21 - 1): the largest cell a coordinate of 1 can have
+ *     ray of (px, py)   fp32, every operation rounded on its own:
+ *                         a = ((float)px + 0.5f - cx) / fx;  b = ((float)py + 0.5f - cy) / fy
+ *                         d_k = (R[0][k] * a + R[1][k] * b) + R[2][k], k = 0, 1, 2        the camera's direction (a, b, 1) taken back by R^T
+ *                         m = max_k |d_k|; the pixel is empty unless every d_k is finite and m > 0
+ *                         N_k = (int)rintf((d_k / m) * 2097152.0f)                        the longest axis is exactly +-2^21
+ *                       The ray is psam_carve_scan's ray between cell centres from o to the cell o + N, which lies outside the grid: the walk of
+ *                       "scan map carving" with n_a = |N_a|, s_a = -1 where N_a < 0, tied axes stepping together; in its difference form
+ *                       D_ab = (2 k_a + 1) n_b - (2 k_b + 1) n_a stays below 2^44 in magnitude because the walk ends inside the grid (below)
+ *     end of the walk   the crossed cells are visited in order; o itself is not among them.  The walk ends at the first of
+ *                         (i)  a cell with a coordinate outside 0 .. cmax: the pixel is empty.  The grid and the segment are convex, so a ray never
+ *                              returns, and at most 3 (cmax + 1) cells are visited
+ *                         (ii) a cell that holds a pairable voxel v whose mean s (psam_map_cloud's bits) has the depth
+ *                              c = ((P[2][0] s_x + P[2][1] s_y) + P[2][2] s_z) + P[2][3] (psam_view_splat's) with c >= near and c < inf:
+ *                              key = ((u64)bits(c) << 32) | v
+ *                       A voxel that is not pairable, or whose mean lies in front of near, is passed through
+ * Every ray starts at the centre of the eye's cell: the picture is that of a camera moved by at most half a voxel.
+ * ws: psam_mapview_ws_bytes(inv_h) bytes (0 for an inv_h that is not finite and positive; at most 2.2 MB), 16-byte aligned: one bit per brick of
+ * (2^s)^3 cells, s = 3 while that gives at most 257 bricks per axis (voxels down to 2^-10) and the least larger s beyond; set, by a launch over the V
+ * voxel ids, where the brick holds a pairable voxel.  A cell whose brick bit is clear is stepped over without a look into the table: a lookup is
+ * skipped, never a step.  The bitmap is rebuilt by every call and means nothing afterwards.
+ * flags: 0, or for measurement PSAM_MAP_VIEW_NO_GATE (every cell is looked up; ws is not touched) and PSAM_MAP_VIEW_NO_LDS (the bitmap is read from
+ * global memory even where it would fit the workgroup's shared memory).  No flag changes a word of keys.
+ * stats: NULL, or 2 u64 words in DEVICE memory to which the call ADDS the cells its rays visited inside the grid and the table lookups they made.
+ * Every refusal comes before any launch and leaves keys untouched: a null map, pose, eye, keys or ws, bad capacities, V outside (0, max_voxels] (an
+ * empty map has no view), inv_h, fx, fy, near not finite and positive, cx, cy or a pose word not finite, width or height outside [1, 8192], an eye
+ * outside [-1, 1]^3 or NaN, min_count < 1, unknown flags: -1; a misaligned pointer (map and ws 16 bytes; skip, keys and stats 8): -2; a short map
+ * block or ws: -3. */
+#define PSAM_MAP_VIEW_NO_GATE 1
+#define PSAM_MAP_VIEW_NO_LDS 2
+size_t psam_mapview_ws_bytes(float inv_h);
+int32_t psam_mapview(const void* map, size_t map_bytes, int32_t max_voxels, int32_t max_pairs, int32_t V, float inv_h, const float* pose, float fx,
+                      float fy, float cx, float cy, int32_t width, int32_t height, float znear, const float* eye, const uint64_t* skip,
+                      int32_t min_count, int32_t flags, uint64_t* keys, uint64_t* stats, void* ws, size_t ws_bytes, psam_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,6 +201,8 @@ SIGNATURES = {
     "psam_scanmap_normals": (i32, [ptr, size_t, i32, i32, i32, ptr, i32, i32, i32, ptr, ptr, ptr, ptr, ptr]),
     "psam_relocalize_workspace_bytes": (size_t, [i32]),
     "psam_relocalize_score": (i32, [ptr, size_t, i32, i32, i32, ptr, i32, i32, f32, ptr, i32, ptr, i32, ptr, ptr, size_t, ptr]),
+    "psam_mapview_ws_bytes": (size_t, [f32]),
+    "psam_mapview": (i32, [ptr, size_t, i32, i32, i32, f32, ptr, f32, f32, f32, f32, i32, i32, f32, ptr, ptr, i32, i32, ptr, ptr, ptr, size_t, ptr]),
 }
 
 

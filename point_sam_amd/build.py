@@ -69,6 +69,9 @@ SOURCES = [
     ("map_normals.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     # scan map relocalisation: track.hip's posed coordinate, cell, voxel mean and distance for P poses at once (csrc/map_block.h), so track.hip's flags.
     ("track_score.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
+    # scan map views: carve.hip's integer walk from the eye's cell, scanmap.hip's voxel mean (csrc/map_block.h) and views.hip's depth
+    # (csrc/view_camera.h), so the flags of all three.
+    ("map_view.hip", ["-ffp-contract=off", "-fno-slp-vectorize"]),
     ("error.cpp", ["-x", "hip"]),
 ] + ([("experiments/gemm_f16x3q.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3s.hip", ["-I" + CSRC]), ("experiments/gemm_f16x3c.hip", ["-I" + CSRC]),
         ("experiments/twoway.hip", ["-I" + CSRC])] if EXPERIMENTS else [])

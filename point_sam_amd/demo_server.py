@@ -26,6 +26,8 @@ instance labelling of that cloud (predictor.fuse_labels).
 POST /map/add {pose?, labels?} . POST /map {min_votes?} . POST /map/clear (not in the reference): the loaded cloud, under its pose, is added to the
 session's scan map (predictor.map_add, point_sam_amd/scanmap.py), with "track": {AlignConfig fields} after its pose was refined against the map
 (predictor.map_align), and with "search": {SearchConfig fields} beside it after the scan was relocalised in the map without a starting pose; /map returns the map's voxels as a cloud with one voted label each.
+POST /map/view {camera, min_misses?, min_votes?} (not in the reference): the map as a camera inside it sees it, ray cast through its voxels
+(predictor.map_view): colour, voxel id, depth and voted label per pixel.
 Every path taken from a URL is resolved INSIDE its root directory (no `..`, no absolute paths, no symlink escape).
 
     python -m point_sam_amd.demo_server --config large --ckpt model.safetensors --models-dir demo/static/models
@@ -697,6 +699,37 @@ class DemoSession:
                 out["occupied"] = occupied.cpu().numpy().astype(bool).tolist()
             return out
 
+    def map_view(self, data: dict) -> dict:
+        """The session's scan map as a camera inside it sees it (predictor.map_view): {"camera": {...} as /view takes it, in the map's frame,
+        "min_misses": n (optional; voxels that ScanMap.occupied(n) votes free are seen through; without it nothing is), "min_votes": n (optional,
+        default 1)} -> {"width", "height", "rgb": height * width * 3 bytes as /view's (the voxels' mean colours, an empty pixel black), "index":
+        height * width little-endian int32 words, the voxel id per pixel, -1 = empty, "depth": height * width little-endian float32 words, +inf =
+        empty, "labels": height * width little-endian int32 words, the voxel's voted label, -1 = none; all base64}.  Before any /map/add, and for
+        a camera whose centre lies outside [-1, 1]^3: a 400."""
+        import base64
+        from . import ops
+        with self.lock:
+            if not isinstance(data, dict) or "camera" not in data or set(data) - {"camera", "min_misses", "min_votes"} or not isinstance(data["camera"], dict):
+                raise ValueError('/map/view takes {"camera": {...}, "min_misses": n (optional), "min_votes": n (optional)}')
+            min_misses, min_votes = data.get("min_misses"), data.get("min_votes", 1)
+            if min_misses is not None and (isinstance(min_misses, bool) or not isinstance(min_misses, int) or not 0 <= min_misses < 2 ** 31):
+                raise ValueError("min_misses must be an integer >= 0")
+            if isinstance(min_votes, bool) or not isinstance(min_votes, int) or not 1 <= min_votes < 2 ** 31:
+                raise ValueError("min_votes must be an integer >= 1")
+            camera = self._camera(data["camera"])
+            ops.map_view_eye(camera, self.map_voxel_size)          # a camera outside the map: a 400 before anything runs
+            if self.scan_map is None or self.scan_map.num_voxels == 0:
+                raise ValueError("/map/view before any /map/add: the map is empty")
+            m = self.scan_map
+            with torch.no_grad():
+                occupied = None if min_misses is None else self._map_error(lambda: m.occupied(min_misses))
+                view = self._map_error(lambda: self.predictor.map_view(m, camera, occupied))
+                labels = self._map_error(lambda: m.label_image(view, min_votes))
+                img = (view.colour(self._map_error(m.cloud)[1], 0.0).clamp(0, 1) * 255).round().to(torch.uint8)
+                index, depth = view.index.contiguous(), view.depth.contiguous()
+            b64 = lambda t: base64.b64encode(t.cpu().numpy().tobytes()).decode("ascii")
+            return {"width": camera.width, "height": camera.height, "rgb": b64(img), "index": b64(index), "depth": b64(depth), "labels": b64(labels)}
+
     def map_clear(self) -> dict:
         """Empties the session's scan map (a map that hit a capacity lives again)."""
         with self.lock:
@@ -813,6 +846,7 @@ def make_handler(session: DemoSession, allow_origin: str = "*"):
                       "/crop": lambda: session.set_crop(data), "/crop/clear": session.clear_crop,
                       "/instances": lambda: session.instances(data), "/superpoints": lambda: session.superpoints(data), "/crop/selection": lambda: session.crop_selection(data),
                       "/map/add": lambda: session.map_add(data), "/map": lambda: session.map_get(data), "/map/clear": session.map_clear,
+                      "/map/view": lambda: session.map_view(data),
                       "/clear": session.clear, "/next": session.next, "/save": session.save}
             fn = routes.get(self.path)
             if fn is None:

@@ -2841,3 +2841,65 @@ def map_normals(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, re
     check(L.psam_scanmap_normals(*lead, V, _p(skip), min_count, reach, min_voxels, count.data_ptr(), _p(S), normal.data_ptr(), curvature.data_ptr(), _stream()),
           "psam_scanmap_normals")
     return (count, normal, curvature, S) if scatter else (count, normal, curvature)
+
+
+# ------------------------------------------------------------------------------------------ scan map views (csrc/map_view.hip)
+MAP_VIEW_NO_GATE, MAP_VIEW_NO_LDS = 1, 2      # PSAM_MAP_VIEW_NO_GATE, PSAM_MAP_VIEW_NO_LDS: measurement switches, never a change of the result
+
+
+def _map_view_camera(camera, what: str):
+    from .views import Camera
+    if not isinstance(camera, Camera):
+        raise TypeError(f"{what}: camera must be a views.Camera, got {type(camera).__name__}")
+    return camera
+
+
+def map_view_eye(camera, voxel_size):
+    """camera (views.Camera, its pose from the map's frame to the camera's), the map's voxel size -> (eye [3] fp32, cell (three ints)): the camera's
+    centre e = -R^T t, computed in fp64 from the twelve fp32 pose words and rounded to fp32 once, and its cell by a map point's arithmetic in numpy
+    fp32, floor((e + 1) * inv_h) with -1 <= e <= 1, exactly as the device does it (carve_origin's rule).  ValueError for an eye the map does not
+    accept: rays from outside [-1, 1]^3 are not built.  Host only."""
+    import numpy as np
+    camera = _map_view_camera(camera, "map_view")
+    inv_h = map_inv_h(voxel_size)
+    w = np.asarray(camera.pose_words, dtype=np.float32).reshape(3, 4).astype(np.float64)
+    with np.errstate(all="ignore"):
+        eye = (-(w[:, :3].T @ w[:, 3])).astype(np.float32)
+        c = np.floor((eye - np.float32(-1)) * inv_h)
+        ok = (c >= 0) & (c < np.float32(1 << 21)) & (eye >= np.float32(-1)) & (eye <= np.float32(1))
+    if not ok.all():
+        raise ValueError(f"map_view: the camera's centre lies at {eye.tolist()} in the map's frame, outside [-1, 1]^3: it has no cell, so no ray can be cast")
+    return eye, tuple(int(v) for v in c)
+
+
+def map_view(block: torch.Tensor, max_voxels: int, max_pairs: int, V: int, camera, skip: torch.Tensor = None, min_count: int = 1, *, voxel_size,
+             flags: int = 0, stats: torch.Tensor = None) -> torch.Tensor:
+    """The scan map as `camera` sees it from inside (include/pointsam_hip.h: scan map views): the map's block, capacities and V, a views.Camera whose
+    pose runs from the map's frame to the camera's -> keys [height, width] int64 in view_splat's format, (bits(depth) << 32) | VOXEL ID, all ones
+    (-1) where the pixel's ray leaves the map without meeting a voxel: view_pick, view_paint_ids and view_paint_rows take them with N = V.  One ray
+    per pixel from the centre of the eye's cell, walked through the map's table in exact integers; the first pairable voxel (skip, min_count:
+    track_step's) whose mean lies at or behind `near` wins.  voxel_size: the size the map was cleared with.  flags: MAP_VIEW_NO_GATE /
+    MAP_VIEW_NO_LDS, for measurement; stats: None or [2] int64 on the device, to which the visited cells and the table lookups are added.  The
+    workspace (ops: psam_mapview_ws_bytes, at most 2.2 MB) is allocated here.  Every check comes before any device work; no host synchronisation."""
+    eye, _ = map_view_eye(camera, voxel_size)
+    inv_h = float(map_inv_h(voxel_size))
+    V = _map_count("map_view", V, max_voxels)
+    skip = _packed_row("map_view", "skip", skip, V, "voxels")
+    min_count = _superpoint_int(min_count, 1, 2 ** 31 - 1, "map_view: min_count")
+    flags = _superpoint_int(flags, 0, MAP_VIEW_NO_GATE | MAP_VIEW_NO_LDS, "map_view: flags")
+    if stats is not None and not (isinstance(stats, torch.Tensor) and stats.dtype == torch.int64 and tuple(stats.shape) == (2,)):
+        raise ValueError("map_view: stats must be None or a [2] int64 tensor")
+    P, cam = _view_camera(camera, "map_view")
+    lead = _map_block("map_view", block, max_voxels, max_pairs)
+    if stats is not None:
+        _chk(stats, torch.int64, "stats")
+    if (skip is not None and skip.device != block.device) or (stats is not None and stats.device != block.device):
+        raise ValueError(f"map_view: the block is on {block.device}; skip and stats must be there too")
+    dev = block.device
+    L = _lib.load()
+    keys = torch.empty(cam[6], cam[5], dtype=torch.int64, device=dev)
+    ws = torch.empty(L.psam_mapview_ws_bytes(inv_h) // 8 + 2, dtype=torch.int64, device=dev)      # torch allocations are at least 16-byte aligned
+    E = (ctypes.c_float * 3)(*eye.tolist())
+    check(L.psam_mapview(*lead, V, inv_h, *cam, ctypes.addressof(E), _p(skip), min_count, flags, keys.data_ptr(), _p(stats), ws.data_ptr(), ws.numel() * 8,
+                          _stream()), "psam_mapview")
+    return keys

@@ -453,6 +453,16 @@ class PointSAMPredictor:
         return m.relocalize(xyz, cfg, search, mask, occupied, min_count, normals, plane)
 
     @torch.no_grad()
+    def map_view(self, m, camera, occupied=True, min_count: int = 1):
+        """The scanmap.ScanMap `m` as `camera` (views.Camera, pose from the map's frame to the camera's, its centre inside [-1, 1]^3) sees it from
+        inside -> views.View over the map's voxel ids (ScanMap.view): ray cast through the map's voxels, so without the holes of render_view on
+        m.cloud().  occupied=True (the default here) leaves out what carving voted free; None shows every voxel.  Needs no cloud to be set."""
+        from .scanmap import ScanMap
+        if not isinstance(m, ScanMap):
+            raise TypeError(f"map_view: m must be a scanmap.ScanMap, got {type(m).__name__}")
+        return m.view(camera, occupied, min_count)
+
+    @torch.no_grad()
     def map_nearest(self, m, pose=None, radius=None, min_votes: int = 1) -> torch.Tensor:
         """map_lookup through the NEAREST voxel within `radius` (None: the voxel size) instead of the point's own: per point of the CURRENT scan the
         voted label of the map voxel whose mean lies nearest to the posed point -> [M] int32, -1 where no voxel is in reach or that voxel has no label

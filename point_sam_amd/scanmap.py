@@ -38,8 +38,14 @@ exactly track_step's pair count under that pose, with the same occupied / min_co
 above and the refinement with the most pairs wins.  anchors() lists where a scan may land in a map larger than itself (the centres of the map's
 coarse cells), for SearchConfig(anchors=...).
 
+Views (csrc/map_view.hip): view(camera) casts one ray per pixel from the camera's cell through the map's own table -- carve()'s exact integer walk,
+ended by the first pairable voxel instead of by a measured point -- and returns a views.View whose keys hold the VOXEL ID and the depth of its mean:
+the map drawn without the holes and the bleed-through of point splats of cloud(), with occupied / min_count honoured, and a predicted depth image.
+Every reader of a rendered scan's keys (ops.view_pick, ops.view_paint_ids, View.colour) takes it unchanged; label_image() is labels() per pixel.
+
 Not built: removing or decaying voxels (occupied() is a read-out; a freed voxel keeps its id, sums and votes), rays from an origin outside
-[-1, 1]^3, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, pose-graph optimisation (track() places a scan against the map, it does not go back and
+[-1, 1]^3 (carve()'s sensor and view()'s eye alike), a far limit for view(), sub-voxel rays from the true eye (every ray of a view starts at the centre
+of the eye's cell), shading a view by the map's normals, skipping whole empty bricks of a view's walk instead of only their lookups, TSDF surfaces, maps beyond [-1, 1]^3, soft votes, pose-graph optimisation (track() places a scan against the map, it does not go back and
 move the scans already added), a multi-resolution or branch-and-bound search (the grid of relocalize() is scored pose by pose at one resolution),
 scoring on a coarser copy of the map, a search that reaches more than 4 voxels from a query's own, a viewpoint sign for map normals (the sign is the largest component's),
 normals kept in the block and updated per add, a normal neighbourhood that reaches more than 2 cells, a switch for point-to-plane in the demo
@@ -379,6 +385,34 @@ class ScanMap:
         if not isinstance(search, A.SearchConfig):
             raise TypeError(f"relocalize: search must be an align.SearchConfig, got {type(search).__name__}")
         return self._register("relocalize", xyz, cfg, None, search, bits, occupied, min_count, normals, plane)
+
+    # -- views (csrc/map_view.hip) -----------------------------------------------------------------------------
+    @torch.no_grad()
+    def view(self, camera, occupied=None, min_count: int = 1):
+        """The map as `camera` (a views.Camera, its pose from the map's frame to the camera's) sees it from inside -> views.View with num_points =
+        num_voxels and splat = 0: its keys hold, per pixel, the depth and the ID of the first voxel the pixel's ray meets (ops.map_view), so
+        view.index is a voxel id per pixel and view.depth the predicted depth image; ops.view_pick, ops.view_paint_ids / _rows on bits(K), and
+        view.colour(cloud()[1]) take it as they take a rendered scan.  occupied (None, True or a [V] bool tensor) and min_count: track()'s -- a voxel
+        that is not pairable is seen through, so ghosts are not drawn.  Rays start at the centre of the eye's cell (at most half a voxel from the
+        true eye).  ValueError before any launch for a camera whose centre lies outside [-1, 1]^3 or an empty map, MapOverflow for a dead one.  No
+        host read (occupied=True reads the carve block on the device)."""
+        from .views import View
+        ops.map_view_eye(camera, self.voxel_size)
+        if occupied is not None and occupied is not True and not isinstance(occupied, torch.Tensor):
+            raise TypeError(f"view: occupied must be None, True or a [V] bool tensor, got {type(occupied).__name__}")
+        block, max_voxels, max_pairs, V = self._filled("view")
+        keys = ops.map_view(block, max_voxels, max_pairs, V, camera, self._skip("view", occupied, V), min_count, voxel_size=self.voxel_size)
+        return View(keys, camera, V, 0)
+
+    @torch.no_grad()
+    def label_image(self, view, min_votes: int = 1) -> torch.Tensor:
+        """view (ScanMap.view of this map as it is now) -> [height, width] int32: labels(min_votes)[0] at every pixel's voxel, -1 on an empty pixel
+        and on a voxel without a label of min_votes votes.  Plain torch."""
+        from .views import check_view
+        V = self._filled("label_image")[3]
+        idx = check_view(view, V, "label_image").index
+        label = self.labels(min_votes)[0]
+        return torch.where(idx >= 0, label.index_select(0, idx.reshape(-1).clamp_min(0).long()).reshape(idx.shape), torch.full_like(idx, -1)).contiguous()
 
     def _register(self, what: str, xyz, cfg, init, search, bits, occupied, min_count, normals, plane):
         """track (search None) and relocalize (init None): one set of checks, one pair of step closures, align.icp or align.search around them."""
